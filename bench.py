@@ -13,6 +13,11 @@ hi+lo pair = 22 significand bits, three MFMA products, fp32 accumulate; 1e-6 max
 the reference computes fp32, RDN.py:141, so a narrower mode is never the headline).  The single-product fp16 mode
 ("f16", 3.5e-4 max-abs, inside north_star's 1e-3 bar) is reported as `tolerance_mode`, beside `value`.
 
+The printed line stays under RESULT_LINE_MAX characters: it carries every top-level field and, of each object below, its
+own scalars; the whole object (notes, power trees, nested rooflines) is written to --detail, by default a new file in the
+temporary directory (named on the line as `detail`).  By default nothing is written to the working directory.
+--dump-outputs DIR writes the arrays the last timed step computed, so that two builds can be compared output for output.
+
 Extra objects on the JSON line:
   roofline     — dominant kernel (RDB 3x3 conv Cin->32, 70 % of FLOPs): algorithmic bytes per launch AT THE STORAGE
                  WIDTH OF THE TIMED MODE (f16x3: 4 B/element = the fp32 yardstick; f16: 2 B) / its mean duration
@@ -424,6 +429,73 @@ def timed_steps(fn, steps, sync_all):
     return dt, [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
 
 
+RESULT_LINE_MAX = 6000              # characters of the printed result line (inside the last 8 000 characters of stdout a driver keeps)
+
+
+def _scalars(d, max_str=128):
+    """One level of `d`: its numbers, flags and short strings (non-finite numbers as null); nested objects and prose left out."""
+    out = {}
+    for k, v in d.items():
+        if isinstance(v, float) and not math.isfinite(v):
+            out[k] = None
+        elif v is None or isinstance(v, (bool, int, float)) or (isinstance(v, str) and len(v) <= max_str):
+            out[k] = v
+    return out
+
+
+def result_line(line, detail_path=None):
+    """Write the whole result object to `detail_path` (None: a new file in the temporary directory — the working directory
+    may be read-only) and return the line to print: every top-level field of `line`, and of each object on it (config,
+    step_ms, roofline, power, train, ...) its own scalars — the notes, the power / power-bound trees and the nested rooflines
+    stay in the detail file, which the line names.  A detail file that cannot be written costs the line nothing but its
+    `detail` (null, the reason on stderr)."""
+    import tempfile
+    try:
+        if detail_path is None:
+            fd, detail_path = tempfile.mkstemp(prefix="bin_amd_bench_detail_", suffix=".json")
+            f = os.fdopen(fd, "w")
+        else:
+            f = open(detail_path, "w")
+        with f:
+            json.dump(line, f)
+        detail_path = os.path.abspath(detail_path)
+    except OSError as e:
+        print(f"bench.py: result detail not written: {e}", file=sys.stderr, flush=True)
+        detail_path = None
+    out = {}
+    for k, v in line.items():
+        if isinstance(v, dict):
+            out[k] = _scalars(v)
+        else:
+            out[k] = None if isinstance(v, float) and not math.isfinite(v) else v
+    out["detail"] = detail_path
+    return json.dumps(out, allow_nan=False)
+
+
+DUMP_BUDGET_BYTES = 48 << 20        # --dump-outputs: all arrays together stay below this
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: write each (name, tensor) of `arrays` as out_dir/<name>.npy — float64 tensors as float64, the rest as
+    float32.  A tensor larger than its even share of DUMP_BUDGET_BYTES is written as a fixed seeded sample of its flattened
+    elements (1-D, ascending flat index; the same indices on every run for the same element count), so the dumps of two
+    builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    index = {}
+    for name, t in arrays:
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = share // (8 if dtype == torch.float64 else 4)
+        if t.numel() > cap:
+            if t.numel() not in index:
+                pick = np.random.Generator(np.random.PCG64(seed)).choice(t.numel(), cap, replace=False)
+                index[t.numel()] = torch.from_numpy(np.sort(pick))
+            t = t.reshape(-1)[index[t.numel()].to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(dtype).cpu().numpy())
+
+
 def make_train_model(prec, bwd_prec, world, rank, B, zero_data=False, S=256):
     """The training model of --mode train (BASELINE config 3/4) with one synthetic batch fed; also used by tools/stall_hunt.py."""
     import tempfile
@@ -631,6 +703,11 @@ def train_bench(args, rank, world, dev, steps=None, warmup=None, standalone=True
     dt, step_ms = timed_steps(lambda i: m.optimize_parameters(warmup + i + 1), steps, sync_all)
     ops.check_status()                       # no activation / gradient left the fp16 storage range
     loss_value = float(m.loss.detach())
+    if standalone and rank == 0 and args.dump_outputs:
+        # the last timed step's results: its loss, the 14 generator outputs and the parameters Adam left behind
+        dump_outputs(args.dump_outputs, [("loss", m.loss.detach().double().reshape(1))] +
+                     [(f"Ft_p_{k:02d}", o) for k, o in enumerate(m.Ft_p)] +
+                     [("params", torch.cat([p.detach().reshape(-1) for p in m.netG.module.parameters()]))])
     # clock / package power of the same steps, sampled in a pass of its own (every rank runs it: collectives stay matched)
     counter = [warmup + steps]
 
@@ -727,7 +804,7 @@ def train_bench(args, rank, world, dev, steps=None, warmup=None, standalone=True
     if not standalone:
         return line
     if rank == 0:
-        print(json.dumps(line), flush=True)
+        print(result_line(line, args.detail), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -914,6 +991,14 @@ def main():
                          "binhip_set_variant, or tail=depth for binhip_set_tail_depth")
     ap.add_argument("--reference-schedule", action="store_true",
                     help="run the reference's literal 20 RDN calls + 12 cells instead of the exact 17 + 6")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy: the 14 outputs "
+                         "of the window (--mode train: the loss, the 14 outputs and the updated parameters); arrays over their "
+                         "share of 48 MiB as a fixed seeded sample")
+    ap.add_argument("--detail", metavar="PATH", default=None,
+                    help="the whole result object (every note, the power / power-bound trees, nested rooflines) goes to this "
+                         "file (default: a new file in the temporary directory); the printed line carries the headline and the "
+                         "scalars of each leg, and names the file")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1002,6 +1087,8 @@ def main():
             outs[0] = net(*frames, **kw_in)
         dt, step_ms = timed_steps(one_window, args.steps, sync_all)
         out = outs[0]
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, [(f"Ft_p_{k:02d}", o) for k, o in enumerate(out)])
         hip_out_path = alt_out_path = None
         if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.zero_data:
             # the timed window's outputs, kept for the cpu_baseline leg: the oracle it times there also checks them (hip_vs_oracle)
@@ -1172,7 +1259,7 @@ def main():
             for pth in (hip_out_path, alt_out_path):
                 if pth and os.path.exists(pth):
                     os.remove(pth)
-        print(json.dumps(line), flush=True)
+        print(result_line(line, args.detail), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -5,6 +5,10 @@ import os
 
 import numpy as np
 
+# HOME under which the option goldens of g7_host.json were recorded: parse() expands the "~" paths of OPTION_YML against
+# it, so the test and the generator both pin it (the suite runs under any user's HOME).
+OPTION_HOME = "/root"
+
 OPTION_YML = """\
 name: debug_host
 use_tb_logger: false

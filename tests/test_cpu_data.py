@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import REPO
-from host_fixtures import OPTION_YML, make_adobe_tree
+from host_fixtures import OPTION_HOME, OPTION_YML, make_adobe_tree
 
 G7 = json.load(open(os.path.join(REPO, "tests", "golden", "g7_host.json")))
 
@@ -139,6 +139,7 @@ def test_options_parse_matches_reference(tmp_path, monkeypatch):
     from bin_amd.options import options as option
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "")
+    monkeypatch.setenv("HOME", OPTION_HOME)
     yml = tmp_path / "o.yml"
     yml.write_text(OPTION_YML)
     assert _norm(option.parse(str(yml), is_train=True)) == G7["options_train"]

@@ -676,6 +676,80 @@ def test_bench_live_parity_object():
     json.dumps(d)
 
 
+def test_bench_result_line_is_bounded_and_names_the_whole_object(tmp_path):
+    """bench.result_line on a full inference line of the profiles (about 21 KB, every leg present) and on a training line: the
+    printed line stays under RESULT_LINE_MAX and is strict JSON, keeps every top-level scalar and the scalars of each leg, and
+    the detail file it names holds the whole object unchanged."""
+    import json
+    import bench
+    for name in ("r06_bench_f16x3_final_box2.json", "r06_bench_train.json"):
+        with open(os.path.join(REPO, "profiles", name)) as f:
+            full = json.load(f)
+        detail = str(tmp_path / (name + ".detail"))
+        s = bench.result_line(dict(full, nan_leg={"x": float("nan")}), detail)
+        assert "\n" not in s and len(s) <= bench.RESULT_LINE_MAX
+        line = json.loads(s, parse_constant=lambda c: pytest.fail(f"non-JSON constant {c}"))
+        with open(line["detail"]) as f:
+            assert json.load(f, parse_constant=lambda c: None) == dict(full, nan_leg={"x": None})
+        assert line["nan_leg"] == {"x": None}
+        for k, v in full.items():
+            if not isinstance(v, dict):
+                assert line[k] == v, k
+                continue
+            for kk, vv in v.items():                     # a leg: its numbers, flags and short strings; no nested objects, no prose
+                if vv is None or isinstance(vv, (bool, int, float)) or (isinstance(vv, str) and len(vv) <= 128):
+                    assert line[k][kk] == vv, (k, kk)
+                else:
+                    assert kk not in line[k], (k, kk)
+        assert line["step_ms"] == full["step_ms"] and "note" not in line["roofline"]
+        if "train" in full:
+            assert line["roofline"]["frac"] == full["roofline"]["frac"] and line["train"]["ms_per_step"] == full["train"]["ms_per_step"]
+
+
+def test_bench_result_line_never_needs_the_working_directory(tmp_path, monkeypatch):
+    """bench.py runs from trees it may not write: by default the detail file goes to the temporary directory, and a detail
+    file that cannot be written still leaves the result line (detail null), never an exception."""
+    import json
+    import bench
+    work, tmp = tmp_path / "work", tmp_path / "tmp"
+    work.mkdir()
+    tmp.mkdir()
+    monkeypatch.chdir(work)
+    monkeypatch.setenv("TMPDIR", str(tmp))
+    monkeypatch.setattr("tempfile.tempdir", None)
+    full = {"metric": "m", "value": 1.5, "roofline": {"frac": 0.5, "note": "n" * 300}}
+    line = json.loads(bench.result_line(full))
+    assert os.path.dirname(line["detail"]) == str(tmp) and os.listdir(work) == []
+    with open(line["detail"]) as f:
+        assert json.load(f) == full
+    line = json.loads(bench.result_line(full, str(tmp_path / "missing" / "d.json")))
+    assert line["detail"] is None and line["value"] == 1.5 and line["roofline"] == {"frac": 0.5}
+
+
+def test_bench_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """bench.dump_outputs: small arrays whole (float64 kept, the rest float32), large ones as the same seeded sample of their
+    flattened elements on every call, everything together under DUMP_BUDGET_BYTES."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    n = 3 * 768 * 1344
+    outs = [("big_%d" % k, torch.randperm(n, generator=g).float().view(1, 3, 768, 1344)) for k in range(14)]   # distinct values
+    small = [("loss", torch.tensor([0.25], dtype=torch.float64)), ("half", torch.rand(2, 3, generator=g).half())]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs + small)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n, _ in outs + small)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BUDGET_BYTES + 4096
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b) and a.dtype in (np.float32, np.float64)
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64 and np.load(tmp_path / "a" / "loss.npy")[0] == 0.25
+    assert np.array_equal(np.load(tmp_path / "a" / "half.npy"), dict(small)["half"].float().numpy())
+    a = np.load(tmp_path / "a" / "big_3.npy")
+    flat = outs[3][1].reshape(-1).numpy()
+    assert a.ndim == 1 and 0 < a.size < flat.size
+    assert np.isin(a, flat).all() and len(np.unique(a)) == a.size                  # distinct elements of the tensor
+
+
 def test_fused_upnet_weights_reproduce_the_two_layers():
     """rdn_plan.fused_upnet_weights: UPNet's two convolutions around the PixelShuffle (RDN.py:203-207, no activation) as one 5x5
     operator on 12 sub-pixel channels + the nine border variants — in float64 the composition equals F.conv2d / F.pixel_shuffle /

@@ -119,13 +119,36 @@ def test_stitch_on_the_device_matches_the_reference_fixture(tmp_path):
     assert abs(float(y.double().mean()) - float(g["mean"])) <= 1e-7
 
 
-def test_bench_line_carries_power_bound_harness_and_labelled_roofline():
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                        "--harness-frames", "7"], cwd=REPO, capture_output=True, text=True, timeout=900)
+def _strict_json(s):
+    def refuse(c):
+        raise ValueError(f"non-JSON constant {c}")
+    return json.loads(s, parse_constant=refuse)
+
+
+def bench_result(args, tmp_path, timeout):
+    """Run bench.py: its LAST stdout line is its one JSON result line, strict JSON of at most RESULT_LINE_MAX characters,
+    naming the detail file that holds the whole object.  Returns (printed line, whole object)."""
+    from bench import RESULT_LINE_MAX
+    detail = str(tmp_path / "bench_detail.json")
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args + ["--detail", detail], cwd=REPO,
+                       capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
-    assert len(lines) == 1
-    d = json.loads(lines[0])
+    out = r.stdout.strip().splitlines()
+    assert len([ln for ln in out if ln.startswith('{"metric"')]) == 1 and out[-1].startswith('{"metric"'), r.stdout[-1500:]
+    assert len(out[-1]) <= RESULT_LINE_MAX
+    line = _strict_json(out[-1])
+    assert line["detail"] == detail
+    with open(detail) as f:
+        d = json.load(f)
+    for k in ("metric", "value", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert line[k] == d[k], k
+    return line, d
+
+
+def test_bench_line_carries_power_bound_harness_and_labelled_roofline(tmp_path):
+    line, d = bench_result(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--harness-frames", "7"], tmp_path, 900)
+    assert line["steps"] == 3 and line["step_ms"]["steps"] == 3
+    assert line["roofline"]["frac"] == d["roofline"]["frac"] and line["harness"]["windows"] == d["harness"]["windows"]
     roof = d["roofline"]
     assert roof["bound"] in ("hbm", "mfma") and 0 < roof["frac"] <= 1.0
     assert roof["bound"] == ("mfma" if roof["arithmetic_intensity_flop_per_byte"] >= roof["ridge_flop_per_byte"] else "hbm")
@@ -149,13 +172,10 @@ def test_bench_line_carries_power_bound_harness_and_labelled_roofline():
     assert h["frames_per_s"] > 0 and h["gpu_only_frames_per_s"] > 0 and 0 < h["io_overlap_frac"] < 1.5
 
 
-def test_bench_power_bound_reading_is_computed_from_the_numbers_beside_it():
+def test_bench_power_bound_reading_is_computed_from_the_numbers_beside_it(tmp_path):
     """`power_bound` (bench.py): the device's own limiter residency, cycles = ms x clock for the real-data and the all-zero pass,
     and a `reading` that is one of four outcomes DERIVED from them — never a constant string."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
-                        "--no-extras"], cwd=REPO, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
-    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+    _, d = bench_result(["--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-extras"], tmp_path, 600)
     pw, pb = d["power"], d["power_bound"]
     assert pw["samples"] >= 5 and pw["clock_mhz"]["mean"] > 500
     assert "limiter" in pw and "source" in pw["limiter"]
