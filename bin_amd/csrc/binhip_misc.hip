@@ -529,9 +529,14 @@ grad_scale_final_kernel(const float* __restrict__ partials, int nb, float target
     m = sm[0];
     float s = 1.f;
     if (m > 0.f && isfinite(m)) {
-        int e = (int)floorf(log2f(target / m));
+        // e = floor(log2(target / m)), the largest e with m * 2^e <= target, exactly from the binary exponents (m = fm 2^em,
+        // target = ft 2^et, fm, ft in [0.5, 1)), so that m * scale <= target does not hang on the last-ulp rounding of
+        // log2f(target / m) when m sits a few ulps above a power of two.
+        int em, et;
+        const float fm = frexpf(m, &em), ft = frexpf(target, &et);
+        int e = et - em - (fm > ft ? 1 : 0);
         e = e > 40 ? 40 : (e < -40 ? -40 : e);
-        s = exp2f((float)e);
+        s = ldexpf(1.f, e);
     }
     sc[0] = s;
     sc[1] = 1.f / s;

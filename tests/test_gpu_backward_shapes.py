@@ -1,0 +1,448 @@
+"""-m gpu: the RDN backward at ragged shapes, batches and border-ring edges, against torch autograd of oracle/rdn_oracle.py in float64
+(canonical_weights(0)); the metric is max-abs error / max|ref| per tensor.  The older whole-RDN gradient checks all run at frame sizes
+that fall evenly on the tiles; these reach the fused UPNet's ring kernels at half-resolution sizes below 7, odd and with N > 1, the
+half-width last chunk of SFENet1 (k = 2, 3) in backward, the gradient scaling at its edges, and the per-op backward-data epilogues and the
+gather-form dense-block backward on partial tiles.  Every case prints its measured worst error.  Case table: tests/backward_cases.py."""
+import hashlib
+import zlib
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from backward_cases import (OP_SHAPES, RDN_BARS, RDN_CASES, RING_HALF_SIZES, RING_KINDS, SET_FOR_K, rdb_block_fwd_bwd, rel,
+                            restrict)
+
+pytestmark = pytest.mark.gpu
+
+F16X3_BAR = RDN_BARS["f16x3"]
+UPNET = ("UPNet.0.weight", "UPNet.0.bias", "UPNet.2.weight", "UPNet.2.bias")
+_ORACLE = {}            # (k, N, H, W, gout kinds) -> float64 gradients: the CPU cost is paid once per shape
+
+
+def _seed(*key):
+    return zlib.crc32(repr(key).encode())
+
+
+def _inputs(k, n, H, W):
+    """k frames in [0, 1) and a white-noise upstream gradient, fixed per shape."""
+    gen = torch.Generator().manual_seed(_seed(k, n, H, W))
+    ins = [torch.rand(n, 3, H, W, generator=gen) for _ in range(k)]
+    gout = torch.randn(n, 3, H, W, generator=gen) * 1e-3
+    return ins, gout
+
+
+# A ReLU whose float64 pre-activation lies within rounding of zero is a tie that any fp32-class computation (plain float32 torch
+# autograd of the oracle included) may decide either way; at ~1e6 ReLU units per call (22 x 38 frames, N = 3) about one such unit
+# is expected, and ONE flipped unit moves that conv's weight gradient by ~1 / sqrt(pixels) (measured 3e-3 .. 5e-2).  So the float64
+# reference takes the kernels' own mask at a tie, |z| <= TIE * max|z| of the layer, and everywhere else asserts that the kernels'
+# masks ARE float64's: a mask read from the wrong pixel, channel or image still fails.
+TIE = 1e-5
+
+
+def _saved_relu_masks(ws, dims, shape=(96, 12, 4, 32)):
+    """The ReLU masks the backward reads (saved post-ReLU hi plane > 0) of every dense-block conv of one training forward:
+    [D * C] bool tensors [N, G, h, w] in call order, from the saved workspace (binhip_rdn_workspace_layout)."""
+    from bin_amd import _lib as L
+    from bin_amd.range_stats import _layout, _view
+    n, H, W = dims[:3]
+    v = _layout(L.lib().binhip_rdn_workspace_layout, dims, L.RDN_LAYOUT_WORDS, shape)
+    G0, D, Cc, G = shape
+    c0, cg, cb = G0 // 16, G // 16, (G0 + Cc * G) // 16
+    P, blk = v[0], v[7]
+    masks = []
+    for d in range(D):
+        for c in range(Cc):
+            hi = _view(ws, blk + (d * cb + c0 + cg * c) * P, cg * P).view(cg, n, H // 2, W // 2, 16)
+            masks.append((hi.permute(1, 0, 4, 2, 3).reshape(n, cg * 16, H // 2, W // 2) > 0).cpu())
+    return masks
+
+
+def _oracle(canon_cpu, k, ins, gouts, masks, names=None):
+    """{name: float64 gradient} per upstream gradient in `gouts` (one forward, one backward each): parameters under their local names,
+    frames as in0 .. in{k-1}.  `masks`: the kernels' ReLU masks (see TIE).  `names`: the parameters to differentiate (default all)."""
+    from bin_amd.weights import rdn_param_shapes
+    from oracle import rdn_oracle as O
+    s = SET_FOR_K[k]
+    names = list(names or rdn_param_shapes(k))
+    W = {f"{s}.{n}": canon_cpu[f"{s}.{n}"].double().requires_grad_(n in names) for n in rdn_param_shapes(k)}
+    xs = [t.double().requires_grad_(True) for t in ins]
+    it = iter(masks)
+    ties = [0, 0]
+
+    def rdb_conv(x, w, b):                       # oracle.rdb_conv with the mask decided as above
+        z = F.conv2d(x, w, b, padding=1)
+        zd, mk = z.detach(), next(it)
+        own = zd > 0
+        tie = zd.abs() <= TIE * zd.abs().max()
+        off = int(((mk != own) & ~tie).sum())
+        assert off == 0, f"the kernels' ReLU mask differs from float64's at {off} units that are not ties"
+        ties[0] += int(tie.sum())
+        ties[1] += int((mk != own).sum())
+        return torch.cat((x, z * torch.where(tie, mk, own).to(z.dtype)), 1)
+    orig = O.rdb_conv
+    O.rdb_conv = rdb_conv
+    try:
+        out = O.rdn(xs, W, s)
+    finally:
+        O.rdb_conv = orig
+    assert next(it, None) is None
+    leaves = [W[f"{s}.{n}"] for n in names] + xs
+    res = []
+    for i, g in enumerate(gouts):
+        gr = torch.autograd.grad(out, leaves, g.double(), retain_graph=i + 1 < len(gouts))
+        res.append(dict(zip(names + [f"in{j}" for j in range(k)], gr)))
+    print(f"oracle k={k} {tuple(ins[0].shape)}: {ties[0]} ReLU ties, {ties[1]} decided otherwise than float64 by the kernels")
+    return res
+
+
+def _cached_oracle(key, canon_cpu, k, ins, gouts, masks, names=None):
+    key = key + (hashlib.sha1(b"".join(m.numpy().tobytes() for m in masks)).hexdigest(),)
+    if key not in _ORACLE:
+        _ORACLE[key] = _oracle(canon_cpu, k, ins, gouts, masks, names)
+    return _ORACLE[key]
+
+
+def _module(canon_cpu, k, mode):
+    from bin_amd.models.archs import RDN as A
+    from bin_amd.weights import rdn_param_shapes
+    cls = {2: A.RDN_residual_interp_2_input, 3: A.RDN_residual_interp_2_1_input, 5: A.RDN_residual_interp_4_1_input}[k]
+    mod = cls(G0=96, D=12)
+    mod.load_state_dict({n: canon_cpu[f"{SET_FOR_K[k]}.{n}"] for n in rdn_param_shapes(k)})
+    mod = mod.cuda()
+    mod.precision = "f16x3"
+    mod.backward_precision = "f16" if mode == "mixed" else None
+    return mod
+
+
+def _gpu_grads(mod, ins, gout, masks=None):
+    """{name: gradient} of one differentiable call: every parameter and every frame (all frames request a gradient).  `masks`: a list
+    that receives the call's saved ReLU masks."""
+    from bin_amd import ops
+
+    def hook(kind, module, dims, ws, info):
+        if kind == "forward" and masks is not None:
+            masks[:] = _saved_relu_masks(ws, dims)
+    mod.debug_hook = hook
+    xs = [t.cuda().requires_grad_(True) for t in ins]
+    mod(*xs).backward(gout.cuda())
+    torch.cuda.synchronize()
+    ops.check_status()
+    g = {n: p.grad.detach().cpu() for n, p in mod.named_parameters()}
+    g.update({f"in{i}": x.grad.cpu() for i, x in enumerate(xs)})
+    for p in mod.parameters():
+        p.grad = None
+    return g
+
+
+def _run(canon_cpu, k, mode, ins, gout, monkeypatch, masks=None):
+    """GPU gradients of a fresh module in `mode`, asserting that the UPNet path of that mode really ran."""
+    if mode == "two_layer":
+        monkeypatch.setenv("BIN_AMD_FUSED_UPNET_TRAIN", "0")
+    else:
+        monkeypatch.delenv("BIN_AMD_FUSED_UPNET_TRAIN", raising=False)
+    mod = _module(canon_cpu, k, mode)
+    g = _gpu_grads(mod, ins, gout, masks)
+    fused = mod.kernel_weights(3).fused_graph is not None
+    assert fused == (mode != "two_layer"), "the fused UPNet training path was (not) taken"
+    return g
+
+
+def _compare(got, ref, names, bar, label):
+    errs = {n: rel(got[n], ref[n]) for n in names}
+    worst = max(errs, key=errs.get)
+    print(f"{label}: worst relative error {errs[worst]:.2e} ({worst}; bar {bar:.0e})")
+    bad = {n: e for n, e in errs.items() if not e <= bar}
+    assert not bad, bad
+    return errs[worst]
+
+
+# ------------------------------------------------------------------------------------------------ 1. whole RDN at ragged shapes
+@pytest.mark.parametrize("tag", list(RDN_CASES))
+def test_rdn_backward_at_ragged_shapes_vs_float64(tag, canon_cpu, monkeypatch):
+    """All 132 parameter gradients and the gradients of every input frame of one RDN call (G0 = 96, D = 12) at a frame size that does not
+    fall on the tiles, in the fp32-class mode (fused UPNet), the mixed mode and the two-layer UPNet."""
+    k, n, H, W, mode = RDN_CASES[tag]
+    ins, gout = _inputs(k, n, H, W)
+    masks = []
+    got = _run(canon_cpu, k, mode, ins, gout, monkeypatch, masks)
+    ref, = _cached_oracle((k, n, H, W, "full"), canon_cpu, k, ins, [gout], masks)
+    assert len(got) == len(ref) == 132 + k
+    _compare(got, ref, list(ref), RDN_BARS[mode], f"{tag} k={k} N={n} {H}x{W} {mode}")
+
+
+# ------------------------------------------------------------------------------------------------ 2. upstream gradients that isolate the ring
+@pytest.mark.parametrize("kind", RING_KINDS)
+@pytest.mark.parametrize("hw", RING_HALF_SIZES, ids=[f"{h}x{w}" for h, w in RING_HALF_SIZES])
+def test_fused_upnet_backward_with_ring_isolating_gradients(hw, kind, canon_cpu, monkeypatch):
+    """The fused UPNet's backward splits dL/dO into the ring-zeroed part (ordinary 5x5 kernels on upnet_gsub_kernel's planes) and the
+    full-resolution border ring (upnet_ring_dgrad_kernel / upnet_ring_wgrad_kernel).  An upstream gradient on the ring only, on its four
+    corners only, or everywhere but the ring exercises each share alone: UPNet.0 / UPNet.2 and the frame gradients must match float64.
+    Sensitivity: the share under test must move the float64 UPNet.2 weight gradient of the whole gradient by >= 100x the bar, so a dropped
+    or mis-indexed share could not pass."""
+    h, w = hw
+    k, n, H, W = 2, 1, 2 * h, 2 * w
+    ins, g = _inputs(k, n, H, W)
+    gout = restrict(g, kind)
+    masks = []
+    got = _run(canon_cpu, k, "f16x3", ins, gout, monkeypatch, masks)
+    refs = _cached_oracle((k, n, H, W, RING_KINDS), canon_cpu, k, ins, [restrict(g, c) for c in RING_KINDS], masks, names=UPNET)
+    ref = dict(zip(RING_KINDS, refs))
+    names = list(UPNET) + [f"in{i}" for i in range(k)]
+    if not bool(gout.any()):                       # 1 x 1: every full-resolution pixel is ring, there is no interior
+        assert kind == "interior" and (h == 1 or w == 1)
+        assert all(bool((got[nm] == 0).all()) for nm in names)
+        print(f"ring {h}x{w} {kind}: empty, all gradients exactly zero")
+        return
+    worst = _compare(got, ref[kind], names, F16X3_BAR, f"ring {h}x{w} {kind}")
+    # the error the metric would report on the gradient of (this share + the rest) if this share were dropped
+    other = ref["ring" if kind == "interior" else "interior"]["UPNet.2.weight"]
+    mine = ref[kind]["UPNet.2.weight"]
+    share = float(mine.abs().max() / (mine + other).abs().max())
+    print(f"ring {h}x{w} {kind}: share of UPNet.2.weight {share:.2e} (needs >= {100 * F16X3_BAR:.0e}), worst {worst:.2e}")
+    assert share >= 100 * F16X3_BAR
+
+
+# ------------------------------------------------------------------------------------------------ 3. images of a batch stay apart
+BATCH_CASES = [(2, 14, 12, "full"), (2, 14, 12, "ring"), (3, 22, 38, "full"), (3, 22, 38, "ring")]
+
+
+@pytest.mark.parametrize("k,H,W,kind", BATCH_CASES, ids=[f"k{k}_{H}x{W}_{kd}" for k, H, W, kd in BATCH_CASES])
+def test_batch_images_do_not_leak_into_each_other(k, H, W, kind, canon_cpu, monkeypatch):
+    """N = 3 with an upstream gradient on image 1 only: the frame gradients of images 0 and 2 are exactly zero, and the parameter and
+    image-1 frame gradients equal those of an N = 1 call on image 1 (at the fp32-class bar: only the weight-gradient summation order
+    differs).  Catches leaks through the per-image ring partials (dwvar / dbvar) and through tiles that straddle images."""
+    ins, g = _inputs(k, 3, H, W)
+    g = restrict(g, "ring") if kind == "ring" else g
+    g[0].zero_()
+    g[2].zero_()
+    m3, m1 = [], []
+    got = _run(canon_cpu, k, "f16x3", ins, g, monkeypatch, m3)
+    one = _run(canon_cpu, k, "f16x3", [t[1:2] for t in ins], g[1:2], monkeypatch, m1)
+    assert all(torch.equal(a[1:2], b) for a, b in zip(m3, m1)), "image 1's forward differs between the N = 3 and N = 1 calls"
+    for i in range(k):
+        assert bool((got[f"in{i}"][0] == 0).all()) and bool((got[f"in{i}"][2] == 0).all()), f"frame {i}: gradient leaked into images 0 / 2"
+        got[f"in{i}"] = got[f"in{i}"][1:2]
+    _compare(got, one, list(one), F16X3_BAR, f"batch k={k} {H}x{W} {kind}: N=3 vs N=1")
+
+
+# ------------------------------------------------------------------------------------------------ 4. gradient scaling at its edges
+@pytest.mark.parametrize("mode", ["f16x3", "mixed", "two_layer"])
+def test_zero_upstream_gradient_gives_zero_gradients(mode, canon_cpu, monkeypatch):
+    """gout = 0 (max|g| = 0: the scale falls back to 1): every gradient is exactly zero and finite."""
+    k, n, H, W = 3, 2, 14, 12
+    ins, g = _inputs(k, n, H, W)
+    got = _run(canon_cpu, k, mode, ins, torch.zeros_like(g), monkeypatch)
+    bad = [nm for nm, t in got.items() if not (bool(torch.isfinite(t).all()) and bool((t == 0).all()))]
+    print(f"zero gout {mode}: {len(got)} gradients, {len(bad)} not exactly zero")
+    assert not bad, bad
+
+
+_SCALE_BASE = {}
+
+
+@pytest.mark.parametrize("e", [20, -20])
+@pytest.mark.parametrize("mode", ["f16x3", "mixed", "two_layer"])
+def test_power_of_two_scaled_upstream_gradient_scales_every_gradient_exactly(mode, e, canon_cpu, monkeypatch):
+    """gout * 2^e: the backward stores its gradient planes times a power-of-two scale chosen from max|gout|, so the planes are the same
+    bits and every gradient is the unscaled one times 2^e, bit for bit (fused ring kernels and the operator chain rule included)."""
+    k, n, H, W = 3, 2, 12, 14
+    ins, g = _inputs(k, n, H, W)
+    if mode not in _SCALE_BASE:
+        _SCALE_BASE[mode] = _run(canon_cpu, k, mode, ins, g, monkeypatch)
+    base = _SCALE_BASE[mode]
+    got = _run(canon_cpu, k, mode, ins, g * 2.0 ** e, monkeypatch)
+    bad = {nm: rel(t, base[nm] * 2.0 ** e) for nm, t in got.items() if not torch.equal(t, base[nm] * 2.0 ** e)}
+    print(f"gout * 2^{e} {mode}: {len(got) - len(bad)} / {len(got)} gradients bit-exact, worst {max(bad.values(), default=0.0):.2e}")
+    assert not bad, bad
+
+
+def _grad_planes_ref(g, nterms):
+    """(unclamped exponent, scale, planes) the scaled conversion must produce: e = floor(log2(16 / max|g|)) computed exactly,
+    scale = 2^clamp(e, -40, 40) (1 when max|g| is 0), planes = the unscaled conversion of g * scale."""
+    from bin_amd import ops
+    m = float(g.abs().max())
+    if m == 0.0:
+        return None, 1.0, ops.nchw_to_planes(g, nterms)
+    e = 0
+    while 2.0 ** (e + 1) * m <= 16.0:
+        e += 1
+    while 2.0 ** e * m > 16.0:
+        e -= 1
+    s = 2.0 ** max(-40, min(40, e))
+    return e, s, ops.nchw_to_planes(g * s, nterms)
+
+
+GRAD_PLANES_MAX = [("zero", 0.0), ("2^0", 1.0), ("2^4", 16.0), ("2^5", 32.0), ("2^-14", 2.0 ** -14), ("2^20", 2.0 ** 20),
+                   ("1ulp_above_2^0", 1.0 + 2.0 ** -23), ("3ulp_above_2^-10", 2.0 ** -10 * (1 + 3 * 2.0 ** -23)),
+                   ("1ulp_below_2^-10", 2.0 ** -10 * (1 - 2.0 ** -24)), ("1ulp_above_2^8", 2.0 ** 8 * (1 + 2.0 ** -23)),
+                   ("clamp_2^-50", 2.0 ** -50), ("clamp_2^50", 2.0 ** 50), ("2^-36", 2.0 ** -36), ("2^44", 2.0 ** 44)]
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag,m", GRAD_PLANES_MAX, ids=[t for t, _ in GRAD_PLANES_MAX])
+def test_grad_planes_scale_pair_and_planes(tag, m, nterms):
+    """ops.grad_planes (binhip_grad_scale + binhip_nchw_to_planes_scaled), which every backward starts with: the pair [scale, 1 / scale]
+    with scale = 2^floor(log2(16 / max|g|)) — max|g| * scale in (8, 16] — clamped to 2^+-40, 1 for an all-zero gradient; and the planes
+    equal the unscaled conversion of g * scale bit for bit, also when max|g| sits exactly at, or one ulp off, a power of two."""
+    from bin_amd import ops
+    gen = torch.Generator().manual_seed(_seed(tag))
+    n, c, h, w = 2, 3, 9, 13
+    g = (torch.rand(n, c, h, w, generator=gen) * 2 - 1) * 0.99 * m
+    g[1, 2, 4, 7] = -m                                               # max|g| exactly m, at a negative entry in image 1
+    g = g.float()
+    assert float(g.abs().max()) == m
+    gp, sc = ops.grad_planes(g.cuda(), nterms)
+    torch.cuda.synchronize()
+    ops.check_status()
+    e, s, want = _grad_planes_ref(g.cuda(), nterms)
+    got = sc.cpu().tolist()
+    print(f"grad_planes max|g| = {m!r} nterms={nterms}: scale pair {got}, expected [{s!r}, {1 / s!r}]")
+    assert got == [s, 1.0 / s]
+    if e is not None and -40 <= e <= 40:                             # inside the clamp: max|g| * scale lands in (8, 16]
+        assert 8.0 < m * s <= 16.0
+    assert torch.equal(gp.hi, want.hi)
+    if nterms == 3:
+        assert torch.equal(gp.lo, want.lo)
+    else:
+        assert gp.lo is None
+
+
+# ------------------------------------------------------------------------------------------------ 5. per-op backward at ragged tiles
+def _gq(t, nterms=3):
+    """(planes of t, what the kernels really read as fp64 NCHW: hi + lo)."""
+    from bin_amd import ops
+    p = ops.nchw_to_planes(t, nterms)
+    return p, ops.planes_to_nchw(p, t.shape[1]).double()
+
+
+@pytest.mark.parametrize("nhw", OP_SHAPES, ids=[f"{n}x{h}x{w}" for n, h, w in OP_SHAPES])
+def test_rdb_block_gather_backward_at_ragged_shapes_vs_float64(nhw, canon_gpu, canon_cpu):
+    """The dense block's forward and gather-form backward (tests/test_gpu_conv.py's golden test, op by op through the C ABI) at partial
+    tiles and N > 1 against float64 autograd of oracle.rdb."""
+    from oracle import rdn_oracle as O
+    n, h, w = nhw
+    gen = torch.Generator().manual_seed(_seed("rdb", nhw))
+    x = torch.rand(n, 96, h, w, generator=gen) - 0.3
+    gy = torch.rand(n, 96, h, w, generator=gen) - 0.5      # order 1, as the backward's scaled gradient planes (fp16 lo stays normal)
+    pre = "model1.RDBs.0."
+    Wd = {k: v.double().requires_grad_(True) for k, v in canon_cpu.items() if k.startswith(pre)}
+    xd = x.double().requires_grad_(True)
+    yd = O.rdb(xd, Wd, pre[:-1])
+    names = sorted(Wd)
+    grads = torch.autograd.grad(yd, [xd] + [Wd[k] for k in names], gy.double())
+    ref = {"gx": grads[0], **{k[len(pre):]: gr for k, gr in zip(names, grads[1:])}}
+    y, gx, got = rdb_block_fwd_bwd(x.cuda(), gy.cuda(), canon_gpu, 3, pre)
+    got = {k: v.cpu() for k, v in got.items()}
+    got["gx"] = gx.cpu()
+    ey = rel(y.cpu(), yd.detach())
+    print(f"rdb {nhw}: forward {ey:.2e}")
+    assert ey <= 2e-6
+    assert len(got) == len(ref) == 11
+    _compare(got, ref, list(ref), F16X3_BAR, f"rdb gather backward {nhw}")
+
+
+OP_BAR = 1e-5          # one fp32-class backward-data launch (hi/lo operands, fp32 accumulation): ~1e-6 measured at aligned tiles
+
+
+@pytest.mark.parametrize("k", [2, 3, 5], ids=["cin24", "cin36", "cin60"])
+@pytest.mark.parametrize("nhw", OP_SHAPES, ids=[f"{n}x{h}x{w}" for n, h, w in OP_SHAPES])
+def test_bwd_data_sfenet1_5x5_vs_conv_transpose(nhw, k, canon_gpu):
+    """SFENet1's backward-data (96 -> 12 k channels, 5x5): cin 24 / 36 are the layers whose forward uses the half-width last chunk."""
+    from bin_amd import ops
+    n, h, w = nhw
+    wt = canon_gpu[f"{SET_FOR_K[k]}.SFENet1.weight"]
+    cin = wt.shape[1]
+    assert cin == 12 * k
+    gen = torch.Generator().manual_seed(_seed("sfe", nhw, k))
+    gp, gq = _gq((torch.rand(n, 96, h, w, generator=gen) - 0.5).cuda())
+    got = ops.planes_to_nchw(ops.conv2d_bwd_data(gp, ops.DgradWeights(wt, nterms=3)), cin).double()
+    torch.cuda.synchronize()
+    ops.check_status()
+    ref = F.conv_transpose2d(gq, wt.double(), padding=2)
+    e = rel(got, ref)
+    print(f"bwd_data SFENet1 cin={cin} {nhw}: {e:.2e}")
+    assert e <= OP_BAR
+
+
+@pytest.mark.parametrize("nhw", OP_SHAPES, ids=[f"{n}x{h}x{w}" for n, h, w in OP_SHAPES])
+def test_bwd_data_lff_residual_and_mask_vs_float64(nhw, canon_gpu):
+    """The LFF 1x1 backward-data with its residual (first 6 chunks) and ReLU mask (chunks >= 12), as the plan issues it per dense block:
+    gcat = W^T gy ;  gcat[:, :96] += gy ;  gcat[:, 192:] *= (act[:, 192:] > 0)."""
+    from bin_amd import ops
+    n, h, w = nhw
+    wt = canon_gpu["model2.RDBs.3.LFF.weight"]
+    gen = torch.Generator().manual_seed(_seed("lff", nhw))
+    gp, gq = _gq((torch.rand(n, 96, h, w, generator=gen) - 0.5).cuda())
+    ap = ops.nchw_to_planes((torch.rand(n, 224, h, w, generator=gen) - 0.4).cuda(), 3)
+    out = ops.conv2d_bwd_data(gp, ops.DgradWeights(wt, nterms=3), res=gp, res_chunks=6, mask=ap, mask_from=12)
+    got = ops.planes_to_nchw(out, 224).double()
+    torch.cuda.synchronize()
+    ops.check_status()
+    ref = F.conv_transpose2d(gq, wt.double())
+    ref[:, :96] += gq
+    ref[:, 192:] *= (ops.planes_to_nchw(ops.CP(ap.hi, None, 224), 224)[:, 192:] > 0)      # the mask reads the hi plane
+    e = rel(got, ref)
+    print(f"bwd_data LFF res+mask {nhw}: {e:.2e}")
+    assert e <= OP_BAR
+    assert float(got[:, 192:][ref[:, 192:] == 0].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("nhw", OP_SHAPES, ids=[f"{n}x{h}x{w}" for n, h, w in OP_SHAPES])
+def test_bwd_data_accumulating_into_its_own_output_vs_float64(nhw, canon_gpu):
+    """`acc` aliasing the output (the plan's group-0 dgrad of every dense block but the last: GY[d] += L_0 + conv(...) in place), with a
+    residual on top: out = conv_transpose(gy) + res + out_before."""
+    from bin_amd import ops
+    n, h, w = nhw
+    wt = canon_gpu["model1.GFF.1.weight"]
+    gen = torch.Generator().manual_seed(_seed("acc", nhw))
+    gp, gq = _gq((torch.rand(n, 96, h, w, generator=gen) - 0.5).cuda())
+    rp, rq = _gq((torch.rand(n, 96, h, w, generator=gen) - 0.5).cuda())
+    op, oq = _gq((torch.rand(n, 96, h, w, generator=gen) - 0.5).cuda())
+    ops.conv2d_bwd_data(gp, ops.DgradWeights(wt, nterms=3), res=rp, acc=op, out=op)
+    got = ops.planes_to_nchw(op, 96).double()
+    torch.cuda.synchronize()
+    ops.check_status()
+    ref = F.conv_transpose2d(gq, wt.double(), padding=1) + rq + oq
+    e = rel(got, ref)
+    print(f"bwd_data acc in place {nhw}: {e:.2e}")
+    assert e <= OP_BAR
+
+
+@pytest.mark.parametrize("nhw", OP_SHAPES, ids=[f"{n}x{h}x{w}" for n, h, w in OP_SHAPES])
+def test_bwd_data_upnet2_inverse_pixelshuffle_vs_float64(nhw, canon_gpu):
+    """UPNet.2's backward-data (3 -> 64 channels at full resolution 2h x 2w) storing through the inverse PixelShuffle (y_unshuf = 4):
+    output chunk sub * 4 + c at h x w holds 64-channel chunk c of sub-pixel sub = 2 i + j."""
+    from bin_amd import ops
+    n, h, w = nhw
+    wt = canon_gpu["model3.UPNet.2.weight"]
+    gen = torch.Generator().manual_seed(_seed("up2", nhw))
+    gp, gq = _gq((torch.rand(n, 3, 2 * h, 2 * w, generator=gen) - 0.5).cuda())
+    out = ops.conv2d_bwd_data(gp, ops.DgradWeights(wt, nterms=3), y_unshuf=4)
+    assert tuple(out.hi.shape) == (16, n, h, w, 16)
+    got = ops.planes_to_nchw(out, 256).double()
+    torch.cuda.synchronize()
+    ops.check_status()
+    full = F.conv_transpose2d(gq, wt.double(), padding=1)                       # [n, 64, 2h, 2w]
+    ref = full.view(n, 64, h, 2, w, 2).permute(0, 3, 5, 1, 2, 4).reshape(n, 256, h, w)
+    e = rel(got, ref)
+    print(f"bwd_data UPNet.2 y_unshuf {nhw}: {e:.2e}")
+    assert e <= OP_BAR
+
+
+# ------------------------------------------------------------------------------------------------ 6. side stream
+@pytest.mark.parametrize("mode", ["f16x3", "mixed"])
+def test_weight_gradients_on_the_side_stream_are_bit_identical(mode, canon_cpu, monkeypatch):
+    """BIN_AMD_WGRAD_STREAM=0 / 1 (weight gradients on the main stream / on a side stream overlapping the backward-data chain) at a
+    ragged shape with N = 3: the same kernels in the same per-stream order, so every gradient is the same bits."""
+    k, n, H, W = 3, 3, 22, 38
+    ins, g = _inputs(k, n, H, W)
+    res = {}
+    for side in ("0", "1"):
+        monkeypatch.setenv("BIN_AMD_WGRAD_STREAM", side)
+        mod = _module(canon_cpu, k, mode)
+        assert mod.wgrad_side_stream == (side == "1")
+        res[side] = _gpu_grads(mod, ins, g)
+    diff = [nm for nm in res["0"] if not torch.equal(res["0"][nm], res["1"][nm])]
+    print(f"side stream {mode}: {len(res['0']) - len(diff)} / {len(res['0'])} gradients bit-identical")
+    assert not diff, diff

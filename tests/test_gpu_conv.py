@@ -234,52 +234,19 @@ def test_rdb_block_forward_and_gather_backward_golden(nterms, tol_y, tol_g, cano
     nterms = 1 (single fp16 product, the inference mode): ~1e-3 operand rounding in the forward flips ~0.3 % of the ReLU
     masks, which on this white-noise upstream gradient costs up to ~20 % on individual weight-gradient tensors (same
     bar as tests/test_gpu_train.py::test_rdn_backward_vs_oracle_autograd[f16]); training defaults to nterms = 3."""
-    from bin_amd import ops
+    from backward_cases import rdb_block_fwd_bwd
     g = load_golden("g2_rdb")
-    pre = "model1.RDBs.0."
     x = torch.from_numpy(g["x"]).cuda()
     gy = torch.from_numpy(g["gy"]).cuda()
-    n, _, h, w = x.shape
-    W = [canon_gpu[f"{pre}convs.{c}.conv.0.weight"] for c in range(4)]
-    Bc = [canon_gpu[f"{pre}convs.{c}.conv.0.bias"] for c in range(4)]
-    WL, BL = canon_gpu[pre + "LFF.weight"], canon_gpu[pre + "LFF.bias"]
-    cw = [ops.ConvWeights(W[c], Bc[c], nterms=nterms) for c in range(4)]
-    cwl = ops.ConvWeights(WL, BL, nterms=nterms)
-    # ---- forward (RDN.py:135-165): blk planes 0-5 = x, conv c writes planes 6+2c, 7+2c, the tail keeps o3 in 12, 13
-    blk = ops.CP.empty(14, n, h, w, nterms, x.device)
-    xin = ops.nchw_to_planes(x, nterms)
-    blk.hi[0:6].copy_(xin.hi)
-    if nterms == 3:
-        blk.lo[0:6].copy_(xin.lo)
-    for c in range(3):
-        ops.conv2d(blk, cw[c], relu=True, out=blk.sub(6 + 2 * c, 2), cin_chunks=6 + 2 * c)
-    y = ops.planes_to_nchw(ops.rdb_tail(blk, cw[3], cwl, store_o3=True), 96)
+    y, gx, grads = rdb_block_fwd_bwd(x, gy, canon_gpu, nterms)
     ref_y = torch.from_numpy(g["y"]).cuda()
     assert _rel(y, ref_y) <= tol_y
-    # ---- backward (autograd of the same lines), gather form
-    gyp = ops.nchw_to_planes(gy, nterms)
-    dWL, dbL = ops.conv2d_bwd_weight(blk, gyp, 96, 224, 1, nterms)
-    gcat = ops.conv2d_bwd_data(gyp, ops.DgradWeights(WL, nterms), res=gyp, res_chunks=6, mask=blk, mask_from=12)
-    assert gcat.hi.shape[0] == 14
-    grads = {}
-    gx = None
-    for c in (3, 2, 1, 0):
-        gyc = gcat.sub(6 + 2 * c, 2 * (4 - c))                     # stacked output gradients of convs c..3
-        grads[c] = ops.conv2d_bwd_weight(blk, gyc, 32, 96 + 32 * c, 3, nterms)
-        gw = ops.RdbGatherWeights(W, c, nterms)
-        if c > 0:
-            slot = gcat.sub(4 + 2 * c, 2)                          # conv c-1's output slot: G_{c-1} = relu'(L_c + sum dgrads)
-            ops.conv2d_bwd_data(gyc, gw, res=slot, mask=blk.sub(4 + 2 * c, 2), mask_from=0, out=slot)
-        else:
-            gx = ops.planes_to_nchw(ops.conv2d_bwd_data(gyc, gw, res=gcat.sub(0, 6)), 96)
-    torch.cuda.synchronize()
-    ops.check_status()
     assert _rel(gx, torch.from_numpy(g["gx"]).cuda()) <= tol_g, "block input gradient"
-    assert _rel(dWL, torch.from_numpy(g["g.LFF.weight"]).cuda()) <= tol_g
-    assert _rel(dbL, torch.from_numpy(g["g.LFF.bias"]).cuda()) <= tol_g
+    assert _rel(grads["LFF.weight"], torch.from_numpy(g["g.LFF.weight"]).cuda()) <= tol_g
+    assert _rel(grads["LFF.bias"], torch.from_numpy(g["g.LFF.bias"]).cuda()) <= tol_g
     for c in range(4):
-        assert _rel(grads[c][0], torch.from_numpy(g[f"g.convs.{c}.conv.0.weight"]).cuda()) <= tol_g, c
-        assert _rel(grads[c][1], torch.from_numpy(g[f"g.convs.{c}.conv.0.bias"]).cuda()) <= tol_g, c
+        assert _rel(grads[f"convs.{c}.conv.0.weight"], torch.from_numpy(g[f"g.convs.{c}.conv.0.weight"]).cuda()) <= tol_g, c
+        assert _rel(grads[f"convs.{c}.conv.0.bias"], torch.from_numpy(g[f"g.convs.{c}.conv.0.bias"]).cuda()) <= tol_g, c
 
 
 def test_concurrent_host_threads_share_the_library():
