@@ -146,13 +146,6 @@ _SIGNATURES = {
                                      C.c_size_t, C.c_void_p]),
 }
 
-# Entry points that exist only in BINHIP_TUNING side builds (tools/: variant sweeps, ablations) — never in the product
-# library, and not declared in include/binhip.h.  Bound when present.
-_TUNING_SIGNATURES = {
-    "binhip_set_variant": (C.c_int, [C.c_int, C.c_int]),
-    "binhip_set_tail_depth": (C.c_int, [C.c_int]),
-    "binhip_wgrad_set_debug": (C.c_int, [C.c_int]),
-}
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
@@ -168,7 +161,7 @@ def lib():
     """Load libbinhip.so (once).  Raises RuntimeError with the build hint when it is absent."""
     global _lib
     if _lib is None:
-        path = os.environ.get("BIN_AMD_LIB", LIB_PATH)      # developer knob: tools/ experiments load side builds
+        path = os.environ.get("BIN_AMD_LIB", LIB_PATH)      # developer knob: the timeline side build, another commit's library
         if not os.path.exists(path):
             raise RuntimeError(
                 f"bin_amd: HIP library {LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; "
@@ -178,16 +171,6 @@ def lib():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in _TUNING_SIGNATURES.items():
-            if hasattr(h, name):
-                fn = getattr(h, name)
-                fn.restype = res
-                fn.argtypes = args
-        # developer knob, tuning side builds only (the product library has no such entry point): pick the experimental
-        # weight-gradient kernels / ablations of binhip_wgrad.hip for a whole test or bench run
-        dbg = os.environ.get("BIN_AMD_WG_DEBUG")
-        if dbg and hasattr(h, "binhip_wgrad_set_debug"):
-            h.binhip_wgrad_set_debug(int(dbg, 0))
         _lib = h
     return _lib
 

@@ -14,7 +14,6 @@ LIB_PATH = os.path.join(CSRC, "libbinhip.so")
 
 
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
-TUNING_SYMBOLS = ("binhip_set_variant", "binhip_set_tail_depth", "binhip_wgrad_set_debug")
 
 
 def abi_symbols():
@@ -36,9 +35,9 @@ def _stale():
 def build_library(force=False, verbose=True, defines=(), out=None):
     """Compile every HIP source for gfx950 into bin_amd/csrc/libbinhip.so.
 
-    `defines` / `out`: side builds for tools/ (e.g. defines=("BINHIP_TUNING=1",), out="tools/_abl/libbinhip_tuning.so":
-    the kernel-variant / ablation switches, which the product library does not contain).  The sources are compiled in
-    parallel (one hipcc per file)."""
+    `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
+    per-workgroup time stamps, which the product library does not contain).  The sources are compiled in parallel (one
+    hipcc per file)."""
     lib_path = out or LIB_PATH
     if out is None and not force and not _stale():
         return LIB_PATH
@@ -61,8 +60,7 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     # Dynamic symbols = exactly the entry points include/binhip.h declares (sources are compiled -fvisibility=hidden; the
     # version script also makes the host-side kernel handles hipcc emits with default visibility local).
     vmap = os.path.join(objdir, "binhip_exports" + tag + ".map")
-    names = abi_symbols() + (list(TUNING_SYMBOLS) if any(d.startswith("BINHIP_TUNING") for d in defines) else []) + \
-        (["binhip_set_timeline"] if any(d.startswith("BINHIP_TIMELINE") for d in defines) else [])
+    names = abi_symbols() + (["binhip_set_timeline"] if any(d.startswith("BINHIP_TIMELINE") for d in defines) else [])
     with open(vmap, "w") as f:
         f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in names) + "  local: *;\n};\n")
     # -z defs: a kernel template the host pass silently failed to instantiate shows up as an undefined symbol HERE, not at dlopen
@@ -74,17 +72,6 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     return lib_path
 
 
-TUNING_LIB = os.path.join(os.path.dirname(HERE), "tools", "_abl", "libbinhip_tuning.so")
-
-
-def build_tuning_library(verbose=True):
-    """Side build with the kernel-variant / ablation switches (BINHIP_TUNING): load it with BIN_AMD_LIB=<path>."""
-    return build_library(force=True, verbose=verbose, defines=("BINHIP_TUNING=1",), out=TUNING_LIB)
-
-
 if __name__ == "__main__":
-    if "--tuning" in sys.argv:
-        print(build_tuning_library())
-    else:
-        build_library(force="--force" in sys.argv)
-        print(LIB_PATH)
+    build_library(force="--force" in sys.argv)
+    print(LIB_PATH)

@@ -40,37 +40,13 @@ struct ConvCfg {
     static constexpr int PS = NPL * KC * (NPJ + NWJ);    // DMA instructions per wave per full stage
     static_assert(NW == 4 || NW == 8 || NW == 16, "4, 8 or 16 waves per workgroup");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+    static_assert(NBUF >= 2, "ring of at least two stage buffers");
     static_assert(NBUF <= 2 || (NBUF - 2) * PS <= 63, "vmcnt immediate range");
 };
 
-// BINHIP_ABLATE (side builds only; 0 in the product): timing-only variants of the K-loop — 1 no MFMA (fragment loads
-// kept alive), 2 no fragment loads (MFMA on undefined registers), 3 no per-stage barrier, 4 no DMA instructions.
-// Results are garbage by construction (round-1 findings: profiles/r01_layer_variants.md).
-#ifndef BINHIP_ABLATE
-#define BINHIP_ABLATE 0
-#endif
-// runtime ablation switches exist in BINHIP_TUNING side builds only; in the product the tests fold to `false`
-#if BINHIP_TUNING
-#define BH_DBG(a, bit) ((a).dbg & (bit))
-#else
-#define BH_DBG(a, bit) false
-#endif
-__device__ __forceinline__ half8 lds_ld8(const char* p) {
-#if BINHIP_ABLATE == 2
-    half8 v;
-    asm volatile("" : "=v"(v));
-    return v;
-#else
-    return *reinterpret_cast<const half8*>(p);
-#endif
-}
+__device__ __forceinline__ half8 lds_ld8(const char* p) { return *reinterpret_cast<const half8*>(p); }
 __device__ __forceinline__ floatx16 mfma16(half8 a, half8 b, floatx16 c) {
-#if BINHIP_ABLATE == 1
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-#else
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-#endif
 }
 
 // Issue the LDS-DMA of K-stage `st` (KC chunks x NPL planes: input patch + weight slab) into buffer `buf`.
@@ -98,7 +74,7 @@ __device__ __forceinline__ void issue_stage(const ConvKArgs& a, char* smem, int 
 #pragma unroll
                 for (int j = 0; j < C::NPJ; ++j) {
                     const int i = wave + C::NW * j;
-                    const bool real = ((C::PP % C::NW == 0) || (i < C::PP)) && !BH_DBG(a, 2);
+                    const bool real = ((C::PP % C::NW == 0) || (i < C::PP));
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(real ? lds + i * 1024 : dummy), 16,
                                                              real ? voff[j] : 0x80000000u, 0, 0, 0);
                 }
@@ -109,7 +85,7 @@ __device__ __forceinline__ void issue_stage(const ConvKArgs& a, char* smem, int 
 #pragma unroll
                 for (int j = 0; j < C::NWJ; ++j) {
                     const int i = wave + C::NW * j;
-                    const bool real = ((C::WP % C::NW == 0) || (i < C::WP)) && !BH_DBG(a, 1);
+                    const bool real = ((C::WP % C::NW == 0) || (i < C::WP));
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(ws, (lds_void_t*)(real ? lds + (C::PP + i) * 1024 : dummy), 16,
                                                              real ? (unsigned)(lane * 16) : 0x80000000u,
                                                              real ? i * 1024 : 0, 0, 0);
@@ -209,7 +185,6 @@ conv_mfma_kernel(const ConvKArgs a, const float* __restrict__ bias) {
     const int n = lane & 31;     // pixel column (B/N index) and cout row (A/M index) of this lane
     const int kg = lane >> 5;    // which 8-channel half of the 16-channel chunk
 
-    if (BH_DBG(a, 16)) return;   // timing experiments: empty kernel (launch + boundary only)
     // 1-D grid of tiles x output-channel blocks, block index fastest: the workgroups that share an input patch are
     // neighbours on ONE XCD after the banding and fetch it into that L2 once (as a (tiles, blocks) grid every block was a
     // separate sweep: GFF.0's backward-data read its 214 MB gradient six times from HBM, profiles/r02_train_kernel_stats.md)
@@ -258,44 +233,29 @@ conv_mfma_kernel(const ConvKArgs a, const float* __restrict__ bias) {
     const int a_lane_off = n * 32 + ((kg ^ ((n >> 3) & 1)) << 4);
     const int b_lane_p = wn * R * C::PW + n;
 
-    if constexpr (NBUF >= 2) {
-        // ring of NBUF stage buffers; up to NBUF-1 stages of DMA in flight, counted waits, one barrier per stage
-        const int nfull = nchunks / KC;       // stages that issue the full C::PS instructions per wave
+    // ring of NBUF stage buffers; up to NBUF-1 stages of DMA in flight, counted waits, one barrier per stage
+    const int nfull = nchunks / KC;       // stages that issue the full C::PS instructions per wave
 #pragma unroll
-        for (int s0 = 0; s0 < NBUF - 1; ++s0)
-            if (s0 < nst && BINHIP_ABLATE != 4) issue_stage<C, KS, KC>(a, smem, s0, s0, wave, lane, z, voff, plane_elems, plane_bytes);
-        int cur = 0, nxt = NBUF - 1;
-        for (int st = 0; st < nst; ++st) {
-            // younger full-size stages still allowed in flight while stage st must have landed
-            int yf = nfull - 1 - st;
-            yf = yf < 0 ? 0 : (yf > NBUF - 2 ? NBUF - 2 : yf);
-            if (NBUF >= 4 && yf >= 2) wait_vmcnt<(NBUF >= 4 ? 2 : 0) * C::PS>();
-            else if (NBUF >= 3 && yf >= 1) wait_vmcnt<(NBUF >= 3 ? 1 : 0) * C::PS>();
-            else wait_vmcnt<0>();
-#if BINHIP_ABLATE != 3
-            __builtin_amdgcn_s_barrier();
-#endif
-            __builtin_amdgcn_sched_barrier(0);
-#if BINHIP_ABLATE != 4
-            if (st + NBUF - 1 < nst)
-                issue_stage<C, KS, KC>(a, smem, st + NBUF - 1, nxt, wave, lane, z, voff, plane_elems, plane_bytes);
-#endif
-            compute_stage<C, KS, MT, R, KC, NT>(smem, st, cur, nchunks, wm, a_lane_off, b_lane_p, kg, acc);
-            cur = (cur + 1 == NBUF) ? 0 : cur + 1;
-            nxt = (nxt + 1 == NBUF) ? 0 : nxt + 1;
-        }
-    } else {
-        for (int st = 0; st < nst; ++st) {
-            issue_stage<C, KS, KC>(a, smem, st, 0, wave, lane, z, voff, plane_elems, plane_bytes);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            compute_stage<C, KS, MT, R, KC, NT>(smem, st, 0, nchunks, wm, a_lane_off, b_lane_p, kg, acc);
-            __syncthreads();
-        }
+    for (int s0 = 0; s0 < NBUF - 1; ++s0)
+        if (s0 < nst) issue_stage<C, KS, KC>(a, smem, s0, s0, wave, lane, z, voff, plane_elems, plane_bytes);
+    int cur = 0, nxt = NBUF - 1;
+    for (int st = 0; st < nst; ++st) {
+        // younger full-size stages still allowed in flight while stage st must have landed
+        int yf = nfull - 1 - st;
+        yf = yf < 0 ? 0 : (yf > NBUF - 2 ? NBUF - 2 : yf);
+        if (NBUF >= 4 && yf >= 2) wait_vmcnt<(NBUF >= 4 ? 2 : 0) * C::PS>();
+        else if (NBUF >= 3 && yf >= 1) wait_vmcnt<(NBUF >= 3 ? 1 : 0) * C::PS>();
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        if (st + NBUF - 1 < nst)
+            issue_stage<C, KS, KC>(a, smem, st + NBUF - 1, nxt, wave, lane, z, voff, plane_elems, plane_bytes);
+        compute_stage<C, KS, MT, R, KC, NT>(smem, st, cur, nchunks, wm, a_lane_off, b_lane_p, kg, acc);
+        cur = (cur + 1 == NBUF) ? 0 : cur + 1;
+        nxt = (nxt + 1 == NBUF) ? 0 : nxt + 1;
     }
 
     // ---- epilogue (binhip_conv_common.h) ----------------------------------------------------------
-    if (BH_DBG(a, 8)) { if (acc[0][0][0] == 12345.f) a.y_hi[0] = (_Float16)1.f; return; }   // timing: no epilogue
     conv_epilogue<MT, R, NT, EPI, XTRA>(a, bias, acc, img, ty0 + wn * R, tx0, z * C::COUTB + wm * MT * 32, z == 0 && wm == 0, n, kg,
                                   plane_elems);
 }
@@ -335,16 +295,9 @@ struct BinhipProfiler {
 };
 namespace { constexpr size_t PROF_MAX_PAIRS = 16384; }
 
-#if BINHIP_TUNING
-static int g_x3_wide = 1;     // side builds: 0 = round-1 routing of the wide nterms = 3 3x3 layers (generic kernel, 64/96-row blocks)
-#define BH_X3_WIDE g_x3_wide
-#else
-#define BH_X3_WIDE 1
-#endif
-
 int bh_conv_cout_block(int ksize, int cout_pad, int nterms) {
     if (cout_pad <= 0 || cout_pad % 32) return -1;
-    if (ksize == 3 && nterms == 3 && BH_X3_WIDE) return 32;  // every fp32-class 3x3 conv: plane-split kernel, 32-row columns
+    if (ksize == 3 && nterms == 3) return 32;  // every fp32-class 3x3 conv: plane-split kernel, 32-row columns
     if (cout_pad == 256) return nterms == 3 ? 64 : 128;     // UPNet.0 (PixelShuffle epilogue)
     if (ksize == 5) return 32;
     if (ksize == 1 && cout_pad == 224) return 224;            // LFF backward-data: all 224 rows in one workgroup column
@@ -356,22 +309,10 @@ int bh_conv_cout_block(int ksize, int cout_pad, int nterms) {
 
 static int bh_dispatch_conv(const ConvKArgs& a, int k, int cp, int nt, int e, hipStream_t s);
 int bh_launch_conv_x3(const ConvKArgs& a, int cout_pad, int epilogue, hipStream_t s);   // binhip_conv_x3.hip
-int bh_launch_final_dot2(const ConvKArgs& a, int nterms, hipStream_t s);                 // binhip_conv_x3.hip
+int bh_launch_final_dot2(const ConvKArgs& a, hipStream_t s);                             // binhip_conv_x3.hip
 int bh_launch_conv_x3_k5(const ConvKArgs& a, int cout_pad, hipStream_t s);               // binhip_conv_x3.hip
 int bh_launch_conv_x3_k5_subpix(const ConvKArgs& a, hipStream_t s);                      // binhip_conv_x3.hip
 int bh_launch_final_m16(const ConvKArgs& a, hipStream_t s);                              // binhip_conv_x3.hip
-#ifndef BINHIP_LFFD_EPI
-#define BINHIP_LFFD_EPI 1     // 0 (side builds): the LFF backward-data tile on the generic extras grouping (rounds 2-3)
-#endif
-#ifndef BINHIP_FINAL_M16
-#define BINHIP_FINAL_M16 1    // 0 (side builds): UPNet.2 of the fp32-class mode on the 32-row tile of conv_x3_kernel (rounds 2-3)
-#endif
-#ifndef BINHIP_K5_PAIR
-#define BINHIP_K5_PAIR 1      // 0 (side builds): ignore BINHIP_CONV_HALF_LAST_CHUNK (SFENet1's last chunk on the plain 25-tap loop)
-#endif
-#ifndef BINHIP_K5_X3
-#define BINHIP_K5_X3 1        // 0 (side builds): the 5x5 layers of the fp32-class mode on the generic single-buffered kernel (rounds 1-3)
-#endif
 
 // validate a call and fill the kernel argument block (everything but the tile counts, which the launcher of the chosen
 // tile shape sets)
@@ -396,7 +337,7 @@ int bh_prepare_conv(const BhConvCall& c, ConvKArgs* out) {
     a.y_cpg = c.y_cpg; a.y_group_stride = c.y_group_stride;
     a.y_cpg_inv = c.y_cpg > 0 ? (unsigned)(((1u << 20) + c.y_cpg - 1) / c.y_cpg) : 0u;
     if (c.y_cpg > 128 || (c.y_cpg > 0 && d.cout_pad / 16 >= 4096)) return BINHIP_E_SHAPE;
-    a.half_last = ((d.reserved & BINHIP_CONV_HALF_LAST_CHUNK) && BINHIP_K5_PAIR) ? 1 : 0;
+    a.half_last = (d.reserved & BINHIP_CONV_HALF_LAST_CHUNK) ? 1 : 0;
     a.y_unshuf = c.y_unshuf;
     if (c.y_unshuf && (d.epilogue != BINHIP_EPI_PLANES || c.y_cpg > 0 || (d.H & 1) || (d.W & 1) || c.y_unshuf * 16 < d.cout))
         return BINHIP_E_SHAPE;
@@ -470,68 +411,29 @@ int bh_launch_conv(const BhConvCall& c, hipStream_t s) {
 }
 
 // Kernel configuration per layer class: the measured-best tile shapes on MI355X at the 720p working size
-// (profiles/r01_layer_variants.md, profiles/r02_*).  BINHIP_TUNING side builds (tools/) additionally compile the
-// alternatives below and the process-global switches that pick them; the product library has neither.
-enum { CLS_K3C32 = 0, CLS_K1C96 = 1, CLS_K3C96 = 2, CLS_SHUFFLE = 3, CLS_FINAL = 4, CLS_K5 = 5 };
-#if BINHIP_TUNING
-static int g_variant[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-static int g_xcd_remap = 1, g_dbg = 0, g_wt = 1;
-#define BH_VARIANT(cls) g_variant[cls]
-#else
-#define BH_VARIANT(cls) (-1)
-#endif
-
-// waves (= tile rows) of the wide backward-data 1x1 tiles (LFF: 224 rows, GFF.0: 192): 8 = one workgroup per CU, 4 = two
-// GFF.0 in the fp32-class mode (1x1, 1152 -> 96): rows per wave and waves of its tile (side builds; the product's 2 x 4 = 8 x 32 pixels)
-#ifndef BINHIP_GFF0_R
-#define BINHIP_GFF0_R 2
-#endif
-#ifndef BINHIP_GFF0_WN
-#define BINHIP_GFF0_WN 4
-#endif
-#ifndef BINHIP_K1_DGRAD_WN
-#define BINHIP_K1_DGRAD_WN 8
-#endif
-static int bh_dispatch_conv(const ConvKArgs& a0, int k, int cp, int nt, int e, hipStream_t s) {
+// (profiles/r01_layer_variants.md, profiles/r02_*).
+static int bh_dispatch_conv(const ConvKArgs& a, int k, int cp, int nt, int e, hipStream_t s) {
     const int P = BINHIP_EPI_PLANES, S = BINHIP_EPI_SHUFFLE, F = BINHIP_EPI_FINAL;
     const int cb = bh_conv_cout_block(k, cp, nt);
     if (cb <= 0 || cp % cb) return BINHIP_E_SHAPE;
-    ConvKArgs a = a0;
-#if BINHIP_TUNING
-    a.xcd_remap = g_xcd_remap;
-    a.dbg = g_dbg;
-    if (!g_wt) a.wt = 0;
-#endif
     if (e == BINHIP_EPI_FINAL_SUBPIX)                                                // the fused UPNet (shape checked in bh_prepare_conv)
         return nt == 3 ? bh_launch_conv_x3_k5_subpix(a, s) : launch_cfg<5, 1, 1, 2, 8, 1, 1, 2, BINHIP_EPI_FINAL_SUBPIX>(a, cp, s);
     // UPNet.2 (64 -> 3 + mean of the frames) in the single-product mode: three output channels as VALU dot products instead of
     // a 32-row MFMA tile (f16 720p window 33.02 -> 32.71 ms).  In the fp32-class mode the same kernel needs 648 dot2 per lane
-    // and chunk behind 112 scalar weight loads and measured 224 us against the MFMA kernel's 110 (profiles/r03_experiments.md):
-    // -DBINHIP_DOT2_X3=1 side builds only.
-#ifndef BINHIP_NO_DOT2        // (side builds: the round-2 MFMA path, for the A/B)
-#ifndef BINHIP_DOT2_X3
-#define BINHIP_DOT2_X3 0
-#endif
-    if (e == F && k == 3 && cp == 32 && a.cout <= 3 && (nt == 1 || BINHIP_DOT2_X3) && BH_VARIANT(CLS_FINAL) < 0)
-        return bh_launch_final_dot2(a, nt, s);
-#endif
+    // and chunk behind 112 scalar weight loads and measured 224 us against the MFMA kernel's 110 (profiles/r03_experiments.md).
+    if (e == F && k == 3 && cp == 32 && a.cout <= 3 && nt == 1)
+        return bh_launch_final_dot2(a, s);
     // UPNet.2 in the fp32-class mode: 16-row matrix tile over tap pairs (binhip_conv_x3.hip, round 4)
     // (its LDS-resident weight slab holds 40 taps = 4 input chunks, UPNet.2's 64 channels; a wider FINAL conv — only reachable
     //  through the per-op ABI — takes the 32-row tile below.  Round 5: the guard was `nchunks <= 5`, and 5 chunks silently
     //  multiplied taps 40-44 with zeros; found by tests/test_gpu_round5.py::test_final_m16_kernel_vs_float64[80-3])
-    if (e == F && k == 3 && cp == 32 && a.cout <= 3 && nt == 3 && a.nchunks <= 4 && BINHIP_FINAL_M16 && BH_VARIANT(CLS_FINAL) < 0)
+    if (e == F && k == 3 && cp == 32 && a.cout <= 3 && nt == 3 && a.nchunks <= 4)
         return bh_launch_final_m16(a, s);
     //                                   KS MT WM R WN KC NT NBUF EPI
     if (nt == 1) {
         if (e == F && k == 3 && cp == 32) return launch_cfg<3, 1, 1, 2, 8, 1, 1, 2, F>(a, cp, s);     // 8 waves, 16x32 tile
         if (e == S && k == 3 && cp == 256) return launch_cfg<3, 2, 2, 4, 4, 1, 1, 2, S>(a, cp, s);    // 8 waves, 16x32 tile, 128 rows
-        if (e == P && k == 3 && cb == 32) {
-#if BINHIP_TUNING
-            if (BH_VARIANT(CLS_K3C32) == 0) return launch_cfg<3, 1, 1, 4, 4, 1, 1, 2, P>(a, cp, s);    // 4 waves x 4 rows
-            if (BH_VARIANT(CLS_K3C32) == 12) return launch_cfg<3, 1, 1, 2, 16, 1, 1, 2, P>(a, cp, s);  // 16 waves, 32x32 tile
-#endif
-            return launch_cfg<3, 1, 1, 2, 8, 1, 1, 2, P>(a, cp, s);                                     // 8 waves x 2 rows, 16x32 tile
-        }
+        if (e == P && k == 3 && cb == 32)  return launch_cfg<3, 1, 1, 2, 8, 1, 1, 2, P>(a, cp, s);   // 8 waves x 2 rows, 16x32 tile
         if (e == P && k == 3 && cb == 64)  return launch_cfg<3, 2, 1, 2, 4, 1, 1, 2, P>(a, cp, s);
         if (e == P && k == 3 && cb == 96)  return launch_cfg<3, 3, 1, 2, 4, 1, 1, 2, P>(a, cp, s);
         if (e == P && k == 1 && cb == 224) return launch_cfg<1, 7, 1, 1, 8, 2, 1, 2, P>(a, cp, s);   // LFF dgrad, 8 waves x 1 row
@@ -544,14 +446,7 @@ static int bh_dispatch_conv(const ConvKArgs& a0, int k, int cp, int nt, int e, h
         }
         if (e == P && k == 5 && cb == 32)  return launch_cfg<5, 1, 1, 2, 8, 1, 1, 2, P>(a, cp, s);   // 8 waves, 16x32 tile
     } else {
-        if (k == 3 && cb == 32) {
-#if BINHIP_TUNING
-            // the generic both-planes-per-stage kernel (117 KB LDS, 157 VGPRs, 1 workgroup/CU): round-1 default
-            if (BH_VARIANT(e == F ? CLS_FINAL : CLS_K3C32) == 1 && e != S)
-                return e == F ? launch_cfg<3, 1, 1, 2, 8, 1, 3, 2, F>(a, cp, s) : launch_cfg<3, 1, 1, 2, 8, 1, 3, 2, P>(a, cp, s);
-#endif
-            return bh_launch_conv_x3(a, cp, e, s);      // plane-split stages, 2 workgroups/CU (binhip_conv_x3.hip)
-        }
+        if (k == 3 && cb == 32) return bh_launch_conv_x3(a, cp, e, s);   // plane-split stages, 2 workgroups/CU (binhip_conv_x3.hip)
         if (e == S && k == 3 && cp == 256) return launch_cfg<3, 1, 2, 4, 2, 1, 3, 2, S>(a, cp, s);
         if (e == P && k == 3 && cb == 64)  return launch_cfg<3, 2, 1, 2, 4, 1, 3, 2, P>(a, cp, s);
         if (e == P && k == 3 && cb == 96)  return launch_cfg<3, 3, 1, 1, 8, 1, 3, 2, P>(a, cp, s);   // 8 waves x 1 row: 168 vs 184 us
@@ -559,18 +454,17 @@ static int bh_dispatch_conv(const ConvKArgs& a0, int k, int cp, int nt, int e, h
             // bin_stage4's own pattern (residual gy on output chunks 0-5, ReLU mask from chunk 12, one output group): the
             // instantiation whose epilogue fetches its extras in two groups instead of four (binhip_conv_common.h)
             if (a.has_res && a.m_hi && !a.r2_hi && a.res_chunks == 6 && a.mask_from == 12 && a.y_cpg <= 0 && !a.y_unshuf &&
-                a.och_limit >= 14 && cp == 224 && BINHIP_LFFD_EPI)
-                return launch_cfg_x<1, 7, 1, 1, BINHIP_K1_DGRAD_WN, 1, 3, 2, BINHIP_EPI_PLANES_LFFD, true>(a, cp, s);
-            return launch_cfg<1, 7, 1, 1, BINHIP_K1_DGRAD_WN, 1, 3, 2, P>(a, cp, s);
+                a.och_limit >= 14 && cp == 224)
+                return launch_cfg_x<1, 7, 1, 1, 8, 1, 3, 2, BINHIP_EPI_PLANES_LFFD, true>(a, cp, s);
+            return launch_cfg<1, 7, 1, 1, 8, 1, 3, 2, P>(a, cp, s);
         }
-        if (e == P && k == 1 && cb == 192) return launch_cfg<1, 6, 1, 1, BINHIP_K1_DGRAD_WN, 1, 3, 2, P>(a, cp, s);   // GFF.0 dgrad
+        if (e == P && k == 1 && cb == 192) return launch_cfg<1, 6, 1, 1, 8, 1, 3, 2, P>(a, cp, s);   // GFF.0 dgrad
         if (e == P && k == 1 && cb == 32)  return launch_cfg<1, 1, 1, 4, 4, 2, 3, 2, P>(a, cp, s);
         if (e == P && k == 1 && cb == 96) {
-            if (a.nchunks >= 32) return launch_cfg<1, 3, 1, BINHIP_GFF0_R, BINHIP_GFF0_WN, 1, 3, 2, P>(a, cp, s);   // GFF.0
+            if (a.nchunks >= 32) return launch_cfg<1, 3, 1, 2, 4, 1, 3, 2, P>(a, cp, s);   // GFF.0, 2 x 4 = 8 x 32 pixels
             return launch_cfg<1, 3, 1, 1, 8, 1, 3, 2, P>(a, cp, s);    // LFF 90 vs 108 us
         }
-        if (e == P && k == 5 && cb == 32 && BINHIP_K5_X3) return bh_launch_conv_x3_k5(a, cp, s);   // plane-split stages, double-buffered
-        if (e == P && k == 5 && cb == 32)  return launch_cfg<5, 1, 1, 2, 8, 1, 3, 1, P>(a, cp, s);
+        if (e == P && k == 5 && cb == 32)  return bh_launch_conv_x3_k5(a, cp, s);   // plane-split stages, double-buffered
     }
     return BINHIP_E_SHAPE;
 }
@@ -849,18 +743,6 @@ int binhip_conv2d_bwd_data(const BinConvDesc* d, const void* gy_hi, const void* 
     for (int i = 0; i < 5; ++i) c.images[i] = nullptr;
     return bh_launch_conv(c, (hipStream_t)stream);
 }
-
-#if BINHIP_TUNING
-BINHIP_API int binhip_set_variant(int layer_class, int variant) {
-    if (layer_class == -1) { g_xcd_remap = variant; return 0; }
-    if (layer_class == -2) { g_dbg = variant; return 0; }
-    if (layer_class == -3) { g_wt = variant; return 0; }
-    if (layer_class == -4) { g_x3_wide = variant; return 0; }     // takes effect for weights relayouted afterwards
-    if (layer_class < 0 || layer_class >= 8) return BINHIP_E_ARG;
-    g_variant[layer_class] = variant;
-    return 0;
-}
-#endif
 
 #if BINHIP_TIMELINE
 // side builds only: `buf` = zeroed device memory holding a BhTlBuf with room for `cap` records, null = stamps off.

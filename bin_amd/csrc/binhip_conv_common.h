@@ -45,10 +45,10 @@ struct ConvKArgs {
     int tiles_x, tiles_y;
     int ncol;                 // plane-split kernel: output columns of 32 rows sharing a tile (1-D grid, column fastest)
     int relu, has_res, nimg, cout;
-    int xcd_remap;
+    int xcd_remap;            // always 1
     int wt;                   // write-through (sc1) output stores
     int och_limit;            // output chunks that exist at the destination (rows beyond are padding: not stored)
-    int dbg;                  // BINHIP_TUNING side builds only: ablation switches (timing experiments, results invalid)
+    int dbg;                  // unread (0); removing it would move every later offset of the block
     int res_chunks;           // residual r applies to output chunks < res_chunks
     int mask_from;            // mask applies to output chunks >= mask_from (when m_hi != null)
     int y_cpg;                // output chunk grouping (<=0: one group)

@@ -21,31 +21,8 @@
 // Neither was a 4-wave / 8x32-tile variant for grids that give each CU only one 16x32 workgroup (training crops,
 // 8 x 128x128 = 256 tiles): training step 176.0 vs 173.1 ms, 720p window 76.0 vs 72.2 ms (twice the weight DMA per pixel).
 #include "binhip_conv_common.h"
-#ifndef BINHIP_ABLATE
-#define BINHIP_ABLATE 0
-#endif
-// wave tile of the default instantiation: R output rows per wave, WN waves per workgroup (tile = R*WN x 32 pixels); side builds
-// (tools/) override it to measure other shapes
-#ifndef BINHIP_X3_R
-#define BINHIP_X3_R 2
-#endif
-#ifndef BINHIP_X3_WN
-#define BINHIP_X3_WN 8
-#endif
-// bit 0 (this kernel) / bit 1 (the fused tail, binhip_fused_x3.hip): wave priority falls with the tile's progress (s_setprio 3 .. 0
-// per quarter of the K loop), so of the two workgroups sharing a CU the one that lags issues first and they finish together
-// instead of one running alone at the end of the launch
-#ifndef BINHIP_X3_PRIO
-#define BINHIP_X3_PRIO 0
-#endif
-// 1 (product, round 6) = waves run their K loop at priority 2 and their epilogue at 0, so that a workgroup's epilogue VALU work does not
-// take issue slots from its CU partner's MFMAs: window -0.46 % (6 of 6 alternating pairs), training step -0.15 % (5 of 6); 0 = side builds
-#ifndef BINHIP_PROG_PRIO
-#define BINHIP_PROG_PRIO 1     // 0 = side builds without the progress-ordered priority of one-round launches
-#endif
-#ifndef BINHIP_EPI_PRIO
-#define BINHIP_EPI_PRIO 1
-#endif
+// wave tile of every instantiation: X3_R output rows per wave, X3_WN waves per workgroup (tile = 16 x 32 pixels)
+constexpr int X3_R = 2, X3_WN = 8;
 
 template <int KS, int R, int WN>
 struct X3Cfg {
@@ -66,10 +43,6 @@ struct X3Cfg {
     static_assert((KS == 3 ? 2 : 1) * LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
-// cache-policy bits of the patch DMA (side builds; 0 = default policy in the product): 2 = nt.  Measured in profiles/r06_experiments.md.
-#ifndef BINHIP_X3_PATCH_AUX
-#define BINHIP_X3_PATCH_AUX 0
-#endif
 template <class C>
 __device__ __forceinline__ void x3_issue_patch(const ConvKArgs& a, char* smem, int c, int pl, int buf, int wave,
                                                const unsigned* voff, long long plane_elems, unsigned plane_bytes) {
@@ -83,33 +56,8 @@ __device__ __forceinline__ void x3_issue_patch(const ConvKArgs& a, char* smem, i
 #pragma unroll
     for (int j = 0; j < C::NPJ; ++j) {
         const int i = wave + C::NW * j;
-        if (BINHIP_ABLATE != 4 && ((C::PP % C::NW == 0) || (i < C::PP)))
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(lds + i * 1024), 16, voff[j], 0, 0, BINHIP_X3_PATCH_AUX);
-    }
-}
-
-// piece j of the patch DMA alone (BINHIP_X3_SPREAD)
-template <class C>
-__device__ __forceinline__ void x3_issue_patch_piece(const ConvKArgs& a, char* smem, int c, int pl, int buf, int wave, int j,
-                                                     const unsigned* voff, long long plane_elems, unsigned plane_bytes) {
-    const _Float16* xb = pl ? a.x_lo : a.x_hi;
-    const long long coff = (a.cpg > 0) ? (long long)(c / a.cpg) * a.group_stride + (long long)(c % a.cpg) * plane_elems
-                                       : (long long)c * plane_elems;
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xb + coff), 0, plane_bytes, 0x00020000);
-    const int i = wave + C::NW * j;
-    if ((C::PP % C::NW == 0) || (i < C::PP))
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(smem + buf * C::PATCH_BYTES + i * 1024), 16, voff[j], 0, 0, 0);
-}
-template <class C, int KS>
-__device__ __forceinline__ void x3_issue_weights_piece(const ConvKArgs& a, char* smem, int c, int buf, int wave, int lane, int z, int j) {
-    const long long woff = ((long long)z * a.nchunks + c) * (KS * KS * 32 * 16);
-    const int i = wave + C::NW * j;
-    if (((2 * C::WP) % C::NW == 0) || (i < 2 * C::WP)) {
-        const bool lo = i >= C::WP;
-        const int t = lo ? i - C::WP : i;
-        __amdgpu_buffer_rsrc_t w = __builtin_amdgcn_make_buffer_rsrc((void*)((lo ? a.w_lo : a.w_hi) + woff), 0, KS * KS * 1024, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w, (lds_void_t*)(smem + 2 * C::PATCH_BYTES + buf * C::WBUF_BYTES + i * 1024), 16,
-                                                 (unsigned)(lane * 16), t * 1024, 0, 0);
+        if ((C::PP % C::NW == 0) || (i < C::PP))
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(lds + i * 1024), 16, voff[j], 0, 0, 0);
     }
 }
 
@@ -122,7 +70,7 @@ __device__ __forceinline__ void x3_issue_weights(const ConvKArgs& a, char* smem,
 #pragma unroll
     for (int j = 0; j < C::NWJ; ++j) {
         const int i = wave + C::NW * j;                  // piece: 0..WP-1 hi taps, WP..2WP-1 lo taps
-        if (BINHIP_ABLATE != 4 && (((2 * C::WP) % C::NW == 0) || (i < 2 * C::WP))) {
+        if (((2 * C::WP) % C::NW == 0) || (i < 2 * C::WP)) {
             const bool lo = i >= C::WP;
             const int t = lo ? i - C::WP : i;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(lo ? wl : wh, (lds_void_t*)(lds + i * 1024), 16,
@@ -131,42 +79,16 @@ __device__ __forceinline__ void x3_issue_weights(const ConvKArgs& a, char* smem,
     }
 }
 
-// BINHIP_ABLATE (side builds only, 0 in the product; results are garbage by construction): 1 = no MFMA (fragment loads kept
-// alive), 2 = no LDS fragment loads (MFMA on undefined registers), 4 = no LDS-DMA — used with tools/power_probe.py to split the
-// package power of the kernel into its matrix / LDS / DMA shares
-__device__ __forceinline__ half8 x3_ld8(const char* p) {
-#if BINHIP_ABLATE == 2
-    half8 v;
-    asm volatile("" : "=v"(v));
-    return v;
-#else
-    return *reinterpret_cast<const half8*>(p);
-#endif
-}
+__device__ __forceinline__ half8 x3_ld8(const char* p) { return *reinterpret_cast<const half8*>(p); }
 __device__ __forceinline__ floatx16 x3_mfma(half8 a, half8 b, floatx16 c) {
-#if BINHIP_ABLATE == 1
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-#else
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-#endif
 }
 
 // One sub-stage out of LDS.  HI: both weight planes against the hi patch (2 products); !HI: hi weights against the lo
 // patch.  Tap order dx-major: the R+KS-1 patch-row fragments of a tap column are fetched once and serve its KS taps;
 // weight fragments are fetched one tap ahead, the next column's patch rows at the column's first tap.
-// BINHIP_X3_SPREAD (side builds; 0 in the product): the DMA instructions of the next sub-stage go out one per tap BEHIND that tap's
-// MFMAs (`hook(step)`) instead of as a burst at the top of the sub-stage — a wave executes in order and a burst of
-// buffer_load ... lds sits at the head of its stream until the memory pipeline has taken all of it (binhip_wgrad.hip gained 5 %
-// from the same change); measured for this kernel in profiles/r06_experiments.md.
-#ifndef BINHIP_X3_SPREAD
-#define BINHIP_X3_SPREAD 0
-#endif
-struct X3NoHook { __device__ __forceinline__ void operator()(int) const {} };
-
-template <class C, int KS, int R, bool HI, class Hook = X3NoHook>
-__device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a_lane_off, int b_lane_off,
-                                           floatx16 (&acc)[R], Hook hook = Hook{}) {
+template <class C, int KS, int R, bool HI>
+__device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a_lane_off, int b_lane_off, floatx16 (&acc)[R]) {
     constexpr int NTAP = KS * KS;
     half8 B[2][R + KS - 1];
     half8 Ah[2], Al[2];
@@ -196,7 +118,6 @@ __device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a
 #pragma unroll
         for (int r = 0; r < R; ++r)
             acc[r] = x3_mfma(Ah[s & 1], B[dx & 1][r + dy], acc[r]);
-        hook(s);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -305,9 +226,9 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
     const int a_lane_off = n * 32 + ((kg ^ ((n >> 3) & 1)) << 4);
     const int b_lane_off = (kg * (C::PH * C::PW) + wave * R * C::PW + n) * 16;
 
-#if BINHIP_EPI_PRIO
-    __builtin_amdgcn_s_setprio(2);       // K loop above the CU partner's epilogue (profiles/r06_experiments.md)
-#endif
+    // K loop at priority 2, epilogue at 0: the epilogue's VALU work does not take issue slots from the CU partner's MFMAs
+    // (window -0.46 %, training step -0.15 %, profiles/r06_experiments.md)
+    __builtin_amdgcn_s_setprio(2);
     x3_issue_weights<C, KS>(a, smem, 0, 0, wave, lane, z);
     if constexpr (GATED) {
         if (gate.chunk <= 0 && gate.flags) {              // every input chunk is gated: wait before the first patch DMA
@@ -332,12 +253,12 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
     x3_issue_patch<C>(a, smem, 0, 0, 0, wave, voff, plane_elems, plane_bytes);
     for (int c = 0; c < nchunks; ++c) {
         const char* wb = smem + 2 * C::PATCH_BYTES + (c & 1) * C::WBUF_BYTES;
-        // Progress-ordered priority (round 3 side build, round 6 product for ONE-ROUND grids): of the two workgroups sharing a CU the
+        // Progress-ordered priority (ONE-ROUND grids): of the two workgroups sharing a CU the
         // one that lags issues first, so the pair finishes together instead of the younger one running alone at the end of the launch
         // (profiles/r06_wg_timeline.md).  Only when every workgroup of the launch is resident at once (`a.prog_prio`, set by the
         // launcher): in a multi-round grid a freshly started workgroup would outrank the ones about to free their slot — the
         // training step loses 0.6 % with it, the 720p window gains 0.7 %.
-        if ((BINHIP_X3_PRIO & 1) || a.prog_prio) {
+        if (a.prog_prio) {
             const int q = (4 * c) / nchunks;
             if (q == 0) __builtin_amdgcn_s_setprio(3);
             else if (q == 1) __builtin_amdgcn_s_setprio(2);
@@ -351,11 +272,8 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
 #if BINHIP_TIMELINE
         if (c == 0) BH_TL_STAMP(1);
 #endif
-        constexpr bool SPREAD = BINHIP_X3_SPREAD && KS == 3;
-        if constexpr (!SPREAD) {
-            x3_issue_patch<C>(a, smem, c, 1, 1, wave, voff, plane_elems, plane_bytes);
-            if (c + 1 < nchunks) x3_issue_weights<C, KS>(a, smem, c + 1, (c + 1) & 1, wave, lane, z);
-        }
+        x3_issue_patch<C>(a, smem, c, 1, 1, wave, voff, plane_elems, plane_bytes);
+        if (c + 1 < nchunks) x3_issue_weights<C, KS>(a, smem, c + 1, (c + 1) & 1, wave, lane, z);
         // GATED: one sub-stage before the first DMA of a gated chunk (the hi plane of chunk c + 1, issued in the lo sub-stage
         // below), lanes 0-8 of wave 0 fetch the flags of the 3 x 3 tile neighbourhood; the loads ride under this sub-stage's MFMAs
         unsigned gate_seen = gate.epoch;
@@ -374,13 +292,6 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
         if constexpr (KS == 5 && !XTRA) {
             if (pair) x3_compute_pair<C, KS, R, true>(smem, wb, n, kg, wave, acc[0]);
             else x3_compute<C, KS, R, true>(smem, wb, a_lane_off, b_lane_off, acc[0]);
-        } else if constexpr (SPREAD) {
-            // steps 0 .. NPJ-1: the lo patch plane, then NWJ steps: the next chunk's weights (9 taps: 6 of them carry a piece)
-            const bool more = c + 1 < nchunks;
-            x3_compute<C, KS, R, true>(smem, wb, a_lane_off, b_lane_off, acc[0], [&](int s) {
-                if (s < C::NPJ) x3_issue_patch_piece<C>(a, smem, c, 1, 1, wave, s, voff, plane_elems, plane_bytes);
-                else if (s < C::NPJ + C::NWJ && more) x3_issue_weights_piece<C, KS>(a, smem, c + 1, (c + 1) & 1, wave, lane, z, s - C::NPJ);
-            });
         } else {
             x3_compute<C, KS, R, true>(smem, wb, a_lane_off, b_lane_off, acc[0]);
         }
@@ -405,25 +316,16 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if constexpr (!SPREAD) {
-            if (c + 1 < nchunks) x3_issue_patch<C>(a, smem, c + 1, 0, 0, wave, voff, plane_elems, plane_bytes);
-        }
+        if (c + 1 < nchunks) x3_issue_patch<C>(a, smem, c + 1, 0, 0, wave, voff, plane_elems, plane_bytes);
         if constexpr (KS == 5 && !XTRA) {
             if (pair) x3_compute_pair<C, KS, R, false>(smem + C::PATCH_BYTES, wb, n, kg, wave, acc[0]);
             else x3_compute<C, KS, R, false>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0]);
-        } else if constexpr (SPREAD) {
-            const bool more = c + 1 < nchunks;
-            x3_compute<C, KS, R, false>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0], [&](int s) {
-                if (s < C::NPJ && more) x3_issue_patch_piece<C>(a, smem, c + 1, 0, 0, wave, s, voff, plane_elems, plane_bytes);
-            });
         } else {
             x3_compute<C, KS, R, false>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0]);
         }
     }
     BH_TL_STAMP(2);
-#if BINHIP_EPI_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     conv_epilogue<1, R, 3, EPI, XTRA>(a, bias, acc, img, ty0 + wave * R, tx0, z * 32, z == 0, n, kg, plane_elems);
     BH_TL_FINISH(a, (((img * a.tiles_y + ty) * a.tiles_x + tx) * a.ncol + z));
 }
@@ -532,7 +434,7 @@ static int launch_x3_x(const ConvKArgs& ka, int cout_pad, hipStream_t s) {
     a.ncol = cout_pad / 32;
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ncol));
     // progress-ordered wave priority: only for launches whose workgroups are all resident at once (two per CU), forward layers only
-    a.prog_prio = (BINHIP_PROG_PRIO && KS == 3 && !XTRA && (long long)grid.x <= 2ll * binhip_device_cus()) ? 1 : 0;
+    a.prog_prio = (KS == 3 && !XTRA && (long long)grid.x <= 2ll * binhip_device_cus()) ? 1 : 0;
 #if BINHIP_TIMELINE
     // kind: 1 = the dense-block conv (3x3, one 32-row column, plane epilogue, no extras), 3 = every other instantiation
     a.tl = bh_tl_reserve(grid.x, &a.tl_base);
@@ -554,14 +456,14 @@ static int launch_x3(const ConvKArgs& ka, int cout_pad, hipStream_t s) {
 // stores required), `flags` = 2 * T device words whose values differ from `epoch` (the caller zeroes them once per RDN call and
 // passes epoch = block index + 1).  Returns BINHIP_E_SHAPE when the kernel cannot keep two workgroups per CU resident.
 int bh_launch_rdb3_x3(const ConvKArgs* convs, unsigned* flags, unsigned epoch, int cus, hipStream_t s) {
-    using C = X3Cfg<3, BINHIP_X3_R, BINHIP_X3_WN>;
+    using C = X3Cfg<3, X3_R, X3_WN>;
     static std::atomic<unsigned long long> lds_set{0};
     static std::atomic<int> per_cu{-1};
-    if (int rc = bh_set_max_lds(&conv_x3_rdbs_kernel<BINHIP_X3_R, BINHIP_X3_WN>, C::LDS_BYTES, lds_set)) return rc;
+    if (int rc = bh_set_max_lds(&conv_x3_rdbs_kernel<X3_R, X3_WN>, C::LDS_BYTES, lds_set)) return rc;
     int occ = per_cu.load(std::memory_order_acquire);
     if (occ < 0) {             // co-residency of the whole grid is what makes the flag waits safe: ask the runtime once
         int n = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_x3_rdbs_kernel<BINHIP_X3_R, BINHIP_X3_WN>, 64 * C::NW,
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_x3_rdbs_kernel<X3_R, X3_WN>, 64 * C::NW,
                                                                     C::LDS_BYTES);
         if (e != hipSuccess) return (int)e;
         occ = n > 2 ? 2 : n;
@@ -587,8 +489,8 @@ int bh_launch_rdb3_x3(const ConvKArgs* convs, unsigned* flags, unsigned epoch, i
     a.flags = flags; a.epoch = epoch;
     const long long slots = (long long)occ * (cus > 0 ? cus : 256);
     const unsigned grid = (unsigned)(a.T < slots ? a.T : slots);
-    for (int p = 0; p < 3; ++p) a.conv[p].prog_prio = (BINHIP_PROG_PRIO && a.T <= slots) ? 1 : 0;     // one tile per workgroup and phase
-    conv_x3_rdbs_kernel<BINHIP_X3_R, BINHIP_X3_WN><<<dim3(grid), dim3(64 * C::NW), C::LDS_BYTES, s>>>(a, a.conv[0].bias, a.conv[1].bias,
+    for (int p = 0; p < 3; ++p) a.conv[p].prog_prio = (a.T <= slots) ? 1 : 0;     // one tile per workgroup and phase
+    conv_x3_rdbs_kernel<X3_R, X3_WN><<<dim3(grid), dim3(64 * C::NW), C::LDS_BYTES, s>>>(a, a.conv[0].bias, a.conv[1].bias,
                                                                                                    a.conv[2].bias);
     BH_CHECK_LAUNCH();
     return 0;
@@ -934,7 +836,7 @@ int bh_launch_final_m16(const ConvKArgs& ka, hipStream_t s) {
 }
 
 // FINAL epilogue with <= 3 output channels (UPNet.2), both precisions
-int bh_launch_final_dot2(const ConvKArgs& ka, int nterms, hipStream_t s) {
+int bh_launch_final_dot2(const ConvKArgs& ka, hipStream_t s) {
     using C = X3Cfg<3, 2, 4>;
     ConvKArgs a = ka;
     a.tiles_x = (a.W + 31) / 32;
@@ -942,9 +844,7 @@ int bh_launch_final_dot2(const ConvKArgs& ka, int nterms, hipStream_t s) {
     a.ncol = 1;
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N));
     const unsigned* wh = reinterpret_cast<const unsigned*>(a.w_hi);
-    const unsigned* wl = reinterpret_cast<const unsigned*>(nterms == 3 ? a.w_lo : a.w_hi);
-    if (nterms == 3) final_dot2_kernel<3><<<grid, dim3(256), 2 * C::PATCH_BYTES, s>>>(a, wh, wl);
-    else final_dot2_kernel<1><<<grid, dim3(256), 2 * C::PATCH_BYTES, s>>>(a, wh, wl);
+    final_dot2_kernel<1><<<grid, dim3(256), 2 * C::PATCH_BYTES, s>>>(a, wh, wh);
     BH_CHECK_LAUNCH();
     return 0;
 }
@@ -954,12 +854,12 @@ int bh_launch_final_dot2(const ConvKArgs& ka, int nterms, hipStream_t s) {
 // columns over the same tiles: the input patch is re-read per column, from L2)
 // SFENet1 (5x5, 12 n_inputs -> 96 as three 32-row columns) and its backward-data on the plane-split pipeline
 int bh_launch_conv_x3_k5(const ConvKArgs& a, int cout_pad, hipStream_t s) {
-    return launch_x3<5, BINHIP_X3_R, BINHIP_X3_WN, BINHIP_EPI_PLANES, 1>(a, cout_pad, s);
+    return launch_x3<5, X3_R, X3_WN, BINHIP_EPI_PLANES, 1>(a, cout_pad, s);
 }
 
 // the fused UPNet (BINHIP_PLAN_FUSED_UPNET): 5x5, G0 -> 12 sub-pixel channels at half resolution, fp32 NCHW full-resolution output
 int bh_launch_conv_x3_k5_subpix(const ConvKArgs& a, hipStream_t s) {
-    return launch_x3<5, BINHIP_X3_R, BINHIP_X3_WN, BINHIP_EPI_FINAL_SUBPIX, 0>(a, 32, s);
+    return launch_x3<5, X3_R, X3_WN, BINHIP_EPI_FINAL_SUBPIX, 0>(a, 32, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1061,9 +961,9 @@ int bh_launch_upnet_ring(const void* x_hi, const void* x_lo, const float* wvar, 
 
 int bh_launch_conv_x3(const ConvKArgs& a, int cout_pad, int epilogue, hipStream_t s) {
     if (epilogue == BINHIP_EPI_PLANES)
-        return cout_pad == 32 ? launch_x3<3, BINHIP_X3_R, BINHIP_X3_WN, BINHIP_EPI_PLANES, 0>(a, cout_pad, s)
-                              : launch_x3<3, BINHIP_X3_R, BINHIP_X3_WN, BINHIP_EPI_PLANES, 1>(a, cout_pad, s);
-    if (epilogue == BINHIP_EPI_SHUFFLE) return launch_x3<3, BINHIP_X3_R, BINHIP_X3_WN, BINHIP_EPI_SHUFFLE, 1>(a, cout_pad, s);
-    if (epilogue == BINHIP_EPI_FINAL) return launch_x3<3, BINHIP_X3_R, BINHIP_X3_WN, BINHIP_EPI_FINAL, 0>(a, cout_pad, s);
+        return cout_pad == 32 ? launch_x3<3, X3_R, X3_WN, BINHIP_EPI_PLANES, 0>(a, cout_pad, s)
+                              : launch_x3<3, X3_R, X3_WN, BINHIP_EPI_PLANES, 1>(a, cout_pad, s);
+    if (epilogue == BINHIP_EPI_SHUFFLE) return launch_x3<3, X3_R, X3_WN, BINHIP_EPI_SHUFFLE, 1>(a, cout_pad, s);
+    if (epilogue == BINHIP_EPI_FINAL) return launch_x3<3, X3_R, X3_WN, BINHIP_EPI_FINAL, 0>(a, cout_pad, s);
     return BINHIP_E_SHAPE;
 }

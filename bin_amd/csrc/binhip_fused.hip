@@ -350,10 +350,6 @@ static int launch_tail(const TailKArgs& a0, hipStream_t s) {
     return 0;
 }
 
-#if BINHIP_TUNING
-static int g_tail_depth = 0;   // 0 = default
-#endif
-
 extern "C" {
 
 int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* blk_hi, const void* blk_lo, const void* wc_hi,
@@ -377,21 +373,8 @@ int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* blk_hi, con
     a.N = N; a.H = H; a.W = W; a.tiles_x = a.tiles_y = 0; a.xcd_remap = 1;
     a.wt = (6 * plane * 2 < (1ll << 32) - 64) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
-    if (nterms == 1) {
-#if BINHIP_TUNING
-        if (g_tail_depth == 3) return launch_tail<1, 3>(a, s);
-        if (g_tail_depth == 4) return launch_tail<1, 4>(a, s);
-#endif
-        return launch_tail<1, 2>(a, s);     // ring depth 2: measured best on MI355X (56.7 vs 63 us at 384x672)
-    }
-#if BINHIP_TUNING
-    if (g_tail_depth == 1) return launch_tail<3, 2>(a, s);      // round-1 kernel: both planes per stage, 1 workgroup/CU
-#endif
+    if (nterms == 1) return launch_tail<1, 2>(a, s);             // ring depth 2: measured best on MI355X (56.7 vs 63 us at 384x672)
     return bh_launch_tail_x3(a, s);                              // plane-split stages, half-CU footprint (binhip_fused_x3.hip)
 }
-
-#if BINHIP_TUNING
-BINHIP_API int binhip_set_tail_depth(int depth) { g_tail_depth = depth; return 0; }
-#endif
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 // Same arithmetic as rdb_tail_kernel<3, 2> (binhip_fused.hip): o3 = relu(conv3x3(blk[0:192]) + b3);
 // y = LFF(cat(blk[0:192], o3)) + b + blk[0:96], with every 16-channel K-stage of conv #3 also feeding the LFF
 // accumulators (the 1x1's B operand is the conv's centre-tap fragment); the residual is a VALU add from that same
-// fragment (round 4; rounds 1-3: an identity MFMA) and o3 goes from the conv accumulators to the LFF's last two K-steps
+// fragment and o3 goes from the conv accumulators to the LFF's last two K-steps
 // through registers only (round 4; before: wave-private LDS tiles).
 // That kernel stages both precision planes per K-stage (141 KB of LDS) and its 8 waves hold 8 accumulator tiles + two
 // planes of fragments (~200 VGPRs): ONE workgroup owns a whole CU, so its DMA prologue, its o3 / output epilogues and
@@ -18,15 +18,6 @@
 // plane-split conv kernel from another stream — share a CU, each covering the other's waits.
 #include "binhip_fused.h"
 #include <type_traits>
-#ifndef BINHIP_X3_PRIO
-#define BINHIP_X3_PRIO 0      // bit 1: progress-ordered wave priority in this kernel (binhip_conv_x3.hip explains)
-#endif
-#ifndef BINHIP_EPI_PRIO
-#define BINHIP_EPI_PRIO 1        // K loop at wave priority 2, epilogues at 0: see binhip_conv_x3.hip
-#endif
-#ifndef BINHIP_TAIL_RES_MFMA
-#define BINHIP_TAIL_RES_MFMA 0   // side builds: 1 = the residual as an identity MFMA (rounds 1-3), for A/B runs
-#endif
 
 namespace {
 
@@ -150,15 +141,6 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
         h = ld8(wb + off);
         if constexpr (HI) l = ld8(wb + TX::WPL + off);
     };
-#if BINHIP_TAIL_RES_MFMA
-    // rounds 1-3: the residual as an identity MFMA (row m of A selects input channel k of the chunk when m == 16 HF + k)
-    half8 ident;
-    {
-        const int n = threadIdx.x & 31, kg = (threadIdx.x >> 5) & 1;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) ident[e] = (n == (RES & 1) * 16 + kg * 8 + e) ? (_Float16)1.0f : (_Float16)0.0f;
-    }
-#endif
     load_b(0, B[0]);
     load_a(0, Ah[0], Al[0]);
 #pragma unroll
@@ -169,7 +151,6 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
         if (s == 0) load_b(1, B[1]);
         if (s == 3) load_b(2, B[0]);                           // column 0's rows are dead after step 2
         __builtin_amdgcn_sched_barrier(0);
-#if !BINHIP_TAIL_RES_MFMA
         if constexpr (RES >= 0) {
             if (s == 0) {
 #pragma unroll
@@ -177,7 +158,6 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#endif
         if (!lff) {
             const int set = dx & 1;
             if constexpr (HI) {
@@ -189,15 +169,6 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
             for (int r = 0; r < R; ++r)
                 accc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[s & 1], B[set][r + k], accc[r], 0, 0, 0);
         } else {
-#if BINHIP_TAIL_RES_MFMA
-            if constexpr (RES >= 0) {
-                if (k == (RES >> 1)) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                        accl[k][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ident, B[1][r + 1], accl[k][r], 0, 0, 0);
-                }
-            }
-#endif
             if constexpr (HI) {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
@@ -260,9 +231,7 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
     const int a_lane_off = n * 32 + ((kg ^ ((n >> 3) & 1)) << 4);
     const int b_lane_off = (kg * (TX::PH * TX::PW) + wave * TX::R * TX::PW + n) * 16;
 
-#if BINHIP_EPI_PRIO
-    __builtin_amdgcn_s_setprio(2);
-#endif
+    __builtin_amdgcn_s_setprio(2);       // K loop above the CU partner's epilogue (binhip_conv_x3.hip)
     tx_issue_weights(a, smem, 0, 0, wave, lane);
     tx_issue_patch(a, smem, 0, 0, wave, voff, plane_elems, plane_bytes);
     // one 16-channel chunk = a hi and a lo sub-stage.  Chunks 0-5 (the block input) also carry the residual, with their index
@@ -271,15 +240,6 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
     auto chunk = [&](const int c, auto res_hi, auto res_lo) __attribute__((always_inline)) {
         constexpr int RH = decltype(res_hi)::value, RL = decltype(res_lo)::value;
         const char* wb = smem + TX::W_OFF + (c & 1) * TX::WBUF_BYTES;
-#if BINHIP_X3_PRIO & 2
-        {   // priority falls with progress (see binhip_conv_x3.hip): the workgroup that lags its CU neighbour issues first
-            const int q = (4 * c) / TX::NCHUNK;
-            if (q == 0) __builtin_amdgcn_s_setprio(3);
-            else if (q == 1) __builtin_amdgcn_s_setprio(2);
-            else if (q == 2) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
         // ---- hi sub-stage; meanwhile the lo plane and the next chunk's weights (last chunk: the o3 LFF weights) land
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
@@ -299,16 +259,6 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
         tx_compute<false, RL>(smem + TX::PATCH_BYTES, wb, a_lane_off, b_lane_off, accc, accl, carry);
     };
     using std::integral_constant;
-#if BINHIP_TAIL_RES_MFMA
-    // (identity-MFMA form: a sub-stage adds its OWN chunk's plane)
-    chunk(0, integral_constant<int, 0>{}, integral_constant<int, 0>{});
-    chunk(1, integral_constant<int, 1>{}, integral_constant<int, 1>{});
-    chunk(2, integral_constant<int, 2>{}, integral_constant<int, 2>{});
-    chunk(3, integral_constant<int, 3>{}, integral_constant<int, 3>{});
-    chunk(4, integral_constant<int, 4>{}, integral_constant<int, 4>{});
-    chunk(5, integral_constant<int, 5>{}, integral_constant<int, 5>{});
-    chunk(6, integral_constant<int, -1>{}, integral_constant<int, -1>{});
-#else
     // hi(c) adds the lo plane of chunk c - 1, lo(c) the hi plane of chunk c: each one sub-stage after it was read
     chunk(0, integral_constant<int, -1>{}, integral_constant<int, 0>{});
     chunk(1, integral_constant<int, 0>{}, integral_constant<int, 1>{});
@@ -317,16 +267,13 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
     chunk(4, integral_constant<int, 3>{}, integral_constant<int, 4>{});
     chunk(5, integral_constant<int, 4>{}, integral_constant<int, 5>{});
     chunk(6, integral_constant<int, 5>{}, integral_constant<int, -1>{});
-#endif
     for (int c = 7; c < TX::NCHUNK; ++c) chunk(c, integral_constant<int, -1>{}, integral_constant<int, -1>{});
     // every wave has finished reading the patch ring and weight buffer 1 (the o3 staging area); the o3 LFF weights landed
     wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
-#if BINHIP_EPI_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     // ---- conv #3 epilogue: bias + ReLU + hi/lo split; o3 never leaves the registers -------------------------------------
     // The accumulator tile gives lane (n, kg) channels 8g + 4kg + j; after the store epilogue's v_permlane32_swap of a
     // (g even, g odd) pair lane (n, kg) owns the full 16-byte slot kg of 16-channel group gp — channels 16gp + 8kg .. +7 of

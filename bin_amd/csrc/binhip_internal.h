@@ -4,12 +4,6 @@
 #include <stdint.h>
 #include "../../include/binhip.h"
 
-// BINHIP_TUNING (side builds for tools/: kernel-variant sweeps and ablations; 0 in the product): compiles the
-// alternative tile configurations and the process-global switches that select them.  The product library has neither.
-#ifndef BINHIP_TUNING
-#define BINHIP_TUNING 0
-#endif
-
 
 // Chunk-plane helpers -------------------------------------------------------------------------
 // CP tensor: fp16 [chunk][N][H][W][16]; plane_elems = N*H*W*16.
@@ -54,14 +48,10 @@ __device__ __forceinline__ _Float16 split_lo(float v, _Float16 hi) {
 // result is rounded once to f16, straight into its half of the packed dword: the same bits as the subtract-then-convert form for every
 // in-range value (tests/test_gpu_conv.py::test_packed_split_equals_the_scalar_split).  A saturated or NaN value gives lo = 0 instead of a
 // clamped remainder; such outputs raise at the host either way.
-#ifndef BINHIP_SPLIT_ASM
-#define BINHIP_SPLIT_ASM 1
-#endif
 // RELU (wave-uniform): the layer's ReLU rides on the clamp — the lower bound of the v_med3 becomes 0 (fmaxf costs a canonicalising
 // v_max on top of the v_max itself) — and a large NEGATIVE value is then not a saturation: the range test keeps the sign bit and
 // compares signed.
 __device__ __forceinline__ void split_pair(float a, float b, unsigned& sat, unsigned& hi2, unsigned& lo2, bool relu = false) {
-#if BINHIP_SPLIT_ASM
     const unsigned smask = relu ? 0xffffffffu : 0x7fffffffu;
     const float lb = relu ? 0.f : -BINHIP_F16_MAX;
     sat |= ((int)(__float_as_uint(a) & smask) > 0x477fe000) ? 1u : 0u;
@@ -73,13 +63,6 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned& sat, unsi
     asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(h), "v"(ac));
     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(h), "v"(bc));
     hi2 = h; lo2 = l;
-#else
-    if (relu) { a = fmaxf(a, 0.f); b = fmaxf(b, 0.f); }
-    union { _Float16 h[2]; unsigned u; } H, L;
-    H.h[0] = split_hi(a, sat); L.h[0] = split_lo(a, H.h[0]);
-    H.h[1] = split_hi(b, sat); L.h[1] = split_lo(b, H.h[1]);
-    hi2 = H.u; lo2 = L.u;
-#endif
 }
 
 // internal launcher used by both the per-op ABI and the RDN plan

@@ -16,30 +16,6 @@
 // fixed order (deterministic), un-scales and scatters to OIHW fp32.
 #include "binhip_internal.h"
 #include <utility>
-// 3x3 weight gradient, tile walk of a workgroup: 1 (default) = row-major tiles at stride PB; 0 = a contiguous range, DOWN a
-// 32-pixel column first, so that two of a tile's ten patch rows are still in L2 from the tile before: round 3 measured 583 ->
-// 494 MB of HBM-side traffic per launch and NO gain in time (140.9 vs 142.8 us, training step 132.5 vs 132.9 ms, same box) —
-// like the XCD mapping of round 2, the bytes are not what this kernel waits for.
-#ifndef BINHIP_WG3_STRIDE_WALK
-#define BINHIP_WG3_STRIDE_WALK 1
-#endif
-// 3x3 weight gradient, BINHIP_TUNING side builds only: 1 = wave owns an X row (wgrad3x3_xrow_kernel, the product's only form),
-// 0 = wave owns a gY row (wgrad3x3_db_kernel, round 2; tools/experiments/wgrad_experiments.inc)
-#ifndef BINHIP_WG3_XROW
-#define BINHIP_WG3_XROW 1
-#endif
-// ... and its prefetch DMA: 1 = spread over the multiply steps of a tile, 0 = one burst at the top of the tile (side builds)
-#ifndef BINHIP_WG3_SPREAD_DMA
-#define BINHIP_WG3_SPREAD_DMA 1
-#endif
-// ... the multiply steps (of 18) behind which the four (plane, chunk) groups go out: FIRST + k * STRIDE.  A group is needed at the
-// next tile's step 0, so a later step leaves its round trip less cover (steps 1 / 5 / 9 / 13: 17 / 13 / 9 / 5 steps)
-#ifndef BINHIP_WG3_DMA_FIRST
-#define BINHIP_WG3_DMA_FIRST 1
-#endif
-#ifndef BINHIP_WG3_DMA_STRIDE
-#define BINHIP_WG3_DMA_STRIDE 4
-#endif
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef short short4_ __attribute__((ext_vector_type(4)));
@@ -61,9 +37,9 @@ struct WgradKArgs {
     int tiles_x, tiles_y, ntiles;
     int PB, ncp, ncot;
     int ppg;      // 1x1 kernel: input-channel pairs per workgroup column (blockIdx.y)
-    int cgroups;  // rolling-row 3x3 kernel: channel-pair groups (blockIdx.y = cot * cgroups + group)
+    int cgroups;  // unused (1); kept with dbg: dropping both moves the kernels' register allocation
     int nz;       // generic / lean kernels: ncot * ndyg (1-D grid of PB * ncp * nz workgroups, see wg_block())
-    int dbg;      // ablation (timing experiments): 1 skip DMA, 2 skip MFMA/LDS reads, 4 skip the final reduction+store
+    int dbg;      // always 0; the kernels still test it (1 skip DMA, 2 skip MFMA/LDS reads, 4 skip the reduction+store)
 };
 
 template <int KS, int TR, int NT>
@@ -360,19 +336,8 @@ wgrad_mfma_kernel(const WgradKArgs a) {
 }
 
 
-constexpr int R3_SEG = 16;     // rolling-row kernel (side builds): pixel rows per column segment
-#if BINHIP_TUNING
-// round 1-3 kernels that the product does not dispatch (lean single-stage, wave = gY row, rolling rows): side builds only
-#include "../../tools/experiments/wgrad_experiments.inc"
-#endif
-
-// 3x3 layers, X-ROW form of the eight-wave kernel (round 3; the product's 3x3 weight gradient).  Its round-2 predecessor
-// (wgrad3x3_db_kernel, now in tools/experiments/wgrad_experiments.inc: eight waves, two LDS stages fed by LDS-DMA, transpose
-// reads issued from asm, chunk pairs 128 B apart against bank conflicts) gave wave w gY row w of the tile; it read, per K-step,
-// one gY fragment pair and NINE tap-shifted X fragments (rows w .. w + 2 of a 10-row halo patch): 20 fragments for 27 MFMAs —
-// fragment reads + DMA writes keep the LDS ~87 % busy, and the DMA prefetch measurably does not overlap with the multiply
-// (tools/bench_wgrad.py, 160 -> 32: MFMAs alone 104 us, + fragment reads 132, DMA alone 107, all together 210 = the SUM).
-// Here the tile is 8 X rows and the halo moves to the operand that needs no column shifts:
+// 3x3 layers: eight waves, X-ROW form (the tile is 8 X rows and the halo sits on the operand that needs no column shifts;
+// against a wave per gY row: -40 % LDS fragment reads for the same MFMAs, profiles/r03_experiments.md):
 //     dW[dy][dx] = sum_r sum_x X[r][x + dx - 1] * gY[r - dy + 1][x]
 // wave w owns X row r0 + w: three column-shifted X fragments per K-step, each used against the THREE gY rows r - dy + 1
 // (a 10-row gY patch, rows r0 - 1 .. r0 + 8, zero outside the image): 6 X + 6 gY = 12 fragments for the same 27 MFMAs
@@ -387,7 +352,7 @@ struct Wg3xCfg {
     static constexpr int XR = 8, GR = 10, PW = 34;
     static constexpr int XP = (XR * PW * 2 + 63) / 64;                   // 1-KiB DMA pieces of an X chunk patch (9)
     static constexpr int GP = GR;                                        // one piece = one 32-pixel gY row
-    static constexpr int XS = XP * 1024 + 128, GS = GP * 1024 + 128;     // chunk strides (bank offset as in Wg3Cfg)
+    static constexpr int XS = XP * 1024 + 128, GS = GP * 1024 + 128;     // chunk strides (+128 B: the pair's chunks on other banks)
     static constexpr int G0 = 2 * XS;
     static constexpr int PLANE = 2 * XS + 2 * GS;
     static constexpr int STAGE = NPL * PLANE;
@@ -410,15 +375,9 @@ __device__ __forceinline__ void wg3x_offsets(const WgradKArgs& a, int tile, int 
     using G = Wg3xCfg<NT>;
     const int H = a.H, W = a.W;
     int b = tile;
-#if BINHIP_WG3_STRIDE_WALK
     const int tx = b % a.tiles_x; b /= a.tiles_x;
     const int ty = b % a.tiles_y;
     const int img = b / a.tiles_y;
-#else
-    const int ty = b % a.tiles_y; b /= a.tiles_y;
-    const int tx = b % a.tiles_x;
-    const int img = b / a.tiles_x;
-#endif
     const int tx0 = tx * 32, ty0 = ty * G::XR;
     const int x0 = tx0 - 1;
     const long long row0 = (long long)img * H;
@@ -474,6 +433,7 @@ __device__ __forceinline__ void wg3x_issue_all(const WgradKArgs& a, char* stage,
     }
 }
 
+constexpr int WG3_DMA_FIRST = 1, WG3_DMA_STRIDE = 4;
 template <int NT>
 __global__ void __launch_bounds__(512)
 wgrad3x3_xrow_kernel(const WgradKArgs a) {
@@ -529,13 +489,9 @@ wgrad3x3_xrow_kernel(const WgradKArgs a) {
     for (int j = 0; j < G::NGJ; ++j)
         g_src[j] = ((wave + 8 * j) * W + g_px) * 32 + (((lane & 1) ^ ((g_px >> 3) & 1)) << 4);
 
-#if BINHIP_WG3_STRIDE_WALK
+    // row-major tiles at stride PB (a walk down 32-pixel columns saved HBM bytes and no time, profiles/r03_experiments.md)
     int tile = pb;
     const int tend = a.ntiles, tstep = a.PB;
-#else
-    int tile = (int)(((long long)pb * a.ntiles) / a.PB);
-    const int tend = (int)(((long long)(pb + 1) * a.ntiles) / a.PB), tstep = 1;
-#endif
     Wg3xTile<NT> to;
     if (tile < tend && !(a.dbg & 1)) {
         wg3x_offsets<NT>(a, tile, wave, x_py, x_px, x_src, g_px, g_src, to);
@@ -547,24 +503,18 @@ wgrad3x3_xrow_kernel(const WgradKArgs a) {
     for (; tile < tend; tile += tstep) {
         const int nxt = tile + tstep;
         // The next tile's DMA is NOT issued in one burst here: a wave executes in order, and a burst of buffer_load ... lds
-        // sits at the head of its instruction stream until the memory pipeline has accepted all of it — with one workgroup
-        // per CU nobody multiplies meanwhile, and prefetch and multiply ran one after the other (tools/bench_wgrad.py: DMA
-        // alone 110 us + MFMAs and reads alone 119 us = 214 us measured, 160 -> 32 channels).  One (plane, chunk) group of DMA
-        // instructions goes out behind the MFMAs of steps 1, 5, 9 and 13 instead.
+        // sits at the head of its instruction stream until the memory pipeline has accepted all of it, with nobody else on the
+        // CU to multiply meanwhile.  One (plane, chunk) group goes out behind the MFMAs of steps 1, 5, 9 and 13 instead
+        // (WG3_DMA_FIRST + k * WG3_DMA_STRIDE; a later step leaves its round trip less cover): 128-134 vs 136-138 us at 96
+        // channels, profiles/r03_experiments.md.
         const bool pre = nxt < tend && !(a.dbg & 1);
         if (pre) wg3x_offsets<NT>(a, nxt, wave, x_py, x_px, x_src, g_px, g_src, to);
         char* const stage_nxt = smem + (cur ^ 1) * G::STAGE;
-#if BINHIP_WG3_SPREAD_DMA == 0
-        if (pre) wg3x_issue_all<NT>(a, stage_nxt, cp, cot, wave, to, plane_elems, plane_bytes);
-#endif
         if (!(a.dbg & 2)) {
             const unsigned st = lds_addr(smem + cur * G::STAGE);
             TrFrag Bh[2], Bl[2], Ah[3], Al[3];
             auto load = [&](auto SC) {
                 constexpr int s = decltype(SC)::value, ks = s / NTAP, dy = (s % NTAP) / 3, dx = s % 3;
-#if BINHIP_TUNING
-                if (a.dbg & 8) return;                 // ablation: MFMAs on stale registers, no LDS fragment reads
-#endif
                 if constexpr (dx == 0) {
                     constexpr int bb = (ks * 3 + dy) & 1, off = ks * 512 + (2 - dy) * 1024;
                     tr_issue_pair<off>(Bh[bb], st + g_off, st + g_off + 128);
@@ -611,16 +561,14 @@ wgrad3x3_xrow_kernel(const WgradKArgs a) {
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t], 0, 0, 0);
                 }
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
-#if BINHIP_WG3_SPREAD_DMA
-                if constexpr (s >= BINHIP_WG3_DMA_FIRST && (s - BINHIP_WG3_DMA_FIRST) % BINHIP_WG3_DMA_STRIDE == 0 &&
-                              (s - BINHIP_WG3_DMA_FIRST) / BINHIP_WG3_DMA_STRIDE < (NT == 3 ? 4 : 2)) {
-                    constexpr int grp = (s - BINHIP_WG3_DMA_FIRST) / BINHIP_WG3_DMA_STRIDE;           // (plane, chunk) = (0,0) (0,1) (1,0) (1,1)
+                if constexpr (s >= WG3_DMA_FIRST && (s - WG3_DMA_FIRST) % WG3_DMA_STRIDE == 0 &&
+                              (s - WG3_DMA_FIRST) / WG3_DMA_STRIDE < (NT == 3 ? 4 : 2)) {
+                    constexpr int grp = (s - WG3_DMA_FIRST) / WG3_DMA_STRIDE;           // (plane, chunk) = (0,0) (0,1) (1,0) (1,1)
                     if (pre) wg3x_issue_part<NT>(a, stage_nxt, grp / 2, grp % 2, cp, cot, wave, to, plane_elems, plane_bytes);
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }, std::make_integer_sequence<int, NSTEP>{});
-        } else if (BINHIP_WG3_SPREAD_DMA && pre) {
+        } else if (pre) {
             wg3x_issue_all<NT>(a, stage_nxt, cp, cot, wave, to, plane_elems, plane_bytes);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -950,56 +898,10 @@ namespace {
 
 struct WgGeom { int ncp, ncot, ndyg, tr, ntap, tiles_x, tiles_y, ntiles, PB; size_t partial_floats, bias_floats; };
 
-#if BINHIP_TUNING
-// side builds only: ablation switches (1 skip DMA, 2 skip MFMA, 4 skip reduce/store; 3x3 kernel choice: 16 = the generic
-// double-buffered 4-wave kernel, 32 = the lean single-stage kernel at two workgroups per CU, bits 8..15 = its start stagger, 128 = the rolling-row kernel)
-int g_wg_dbg = 0;
-#define WG_DBG g_wg_dbg
-#else
-#define WG_DBG 0
-#endif
-#define WG3_LEAN ((WG_DBG & 32) != 0)
 bool use_w1(int ksize, int cout) { return ksize == 1 && cout <= 32 * W1_NCOT; }
 
-// rolling-row 3x3 kernel: channel pairs per workgroup (<= 6), tiles per wave, and whether its 32-bit chunk addressing fits
-struct R3Plan { int cgroups, ppg, tpw; };
-static inline R3Plan r3_plan(int ncp) {
-    R3Plan p;
-    p.cgroups = (ncp + 5) / 6;
-    p.ppg = (ncp + p.cgroups - 1) / p.cgroups;
-    p.tpw = (9 * p.ppg + 7) / 8;
-    return p;
-}
-// two-rows-per-stage variant: <= 4 pairs per workgroup, balanced groups
-static inline R3Plan r3_plan2(int ncp) {
-    R3Plan p;
-    p.cgroups = (ncp + 3) / 4;
-    p.ppg = (ncp + p.cgroups - 1) / p.cgroups;
-    p.tpw = (9 * p.ppg + 7) / 8;
-    return p;
-}
-static inline bool r3_usable(int ksize, int N, int H, int W, int cin_chunks, int x_cpg) {
-    return ksize == 3 && x_cpg == 0 && (unsigned long long)cin_chunks * N * H * W * 32ull < 0xfffffff0ull;
-}
-
-WgGeom wg_geom(int ksize, int N, int H, int W, int cin_chunks, int cout, int cus, int roll = 0) {
+WgGeom wg_geom(int ksize, int N, int H, int W, int cin_chunks, int cout, int cus) {
     WgGeom g;
-    if (roll) {
-        g.tr = 3; g.ndyg = 1; g.ntap = 9;
-        g.ncp = (cin_chunks + 1) / 2;
-        g.ncot = (cout + 31) / 32;
-        const R3Plan rp = (roll == 2) ? r3_plan2(g.ncp) : r3_plan(g.ncp);
-        g.tiles_x = (W + 31) / 32;
-        g.tiles_y = (H + R3_SEG - 1) / R3_SEG;              // column segments per image
-        g.ntiles = g.tiles_x * g.tiles_y * N;
-        int pb = (cus > 0 ? cus : 256) / (rp.cgroups * g.ncot);
-        if (pb < 1) pb = 1;
-        if (pb > g.ntiles) pb = g.ntiles;
-        g.PB = pb;
-        g.partial_floats = (size_t)g.ncp * g.ncot * pb * 9 * 1024;
-        g.bias_floats = (size_t)g.ncot * pb * 32;
-        return g;
-    }
     if (use_w1(ksize, cout)) {
         g.tr = 1; g.ndyg = 1; g.ntap = 1;
         g.ncp = (cin_chunks + 1) / 2;
@@ -1026,7 +928,7 @@ WgGeom wg_geom(int ksize, int N, int H, int W, int cin_chunks, int cout, int cus
     g.ntiles = g.tiles_x * g.tiles_y * N;
     const int groups = g.ncp * g.ncot * g.ndyg;
     // 3x3: one 8-wave workgroup per CU (two LDS stages); 5x5 / wide 1x1: the generic kernel, also one per CU
-    int pb = ((WG3_LEAN && ksize == 3 ? 2 : 1) * (cus > 0 ? cus : 256)) / groups;   // floor: no straggler in an extra round
+    int pb = (cus > 0 ? cus : 256) / groups;            // floor: no straggler in an extra round
     if (pb < 1) pb = 1;
     if (pb > g.ntiles) pb = g.ntiles;
     if (pb >= 8) pb &= ~7;                              // wg_block(): siblings of a pixel block share an XCD
@@ -1047,19 +949,6 @@ int launch_wg(const WgradKArgs& a, const WgGeom& g, hipStream_t s) {
     return 0;
 }
 
-#if BINHIP_TUNING
-template <int KS, int TR, int NT>
-int launch_wg_sb(const WgradKArgs& a, const WgGeom& g, hipStream_t s) {
-    using C = WgCfg<KS, TR, NT>;
-    constexpr int LDS = C::BUF_BYTES > 16384 ? C::BUF_BYTES : 16384;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&wgrad_mfma_sb_kernel<KS, TR, NT>, LDS, lds_set)) return rc;
-    dim3 grid((unsigned)(g.PB * g.ncp * g.ncot * g.ndyg));
-    wgrad_mfma_sb_kernel<KS, TR, NT><<<grid, dim3(256), LDS, s>>>(a);
-    BH_CHECK_LAUNCH();
-    return 0;
-}
-#endif
 
 template <int NT>
 int launch_wg3x(const WgradKArgs& a, const WgGeom& g, hipStream_t s) {
@@ -1070,60 +959,7 @@ int launch_wg3x(const WgradKArgs& a, const WgGeom& g, hipStream_t s) {
     return 0;
 }
 
-#if BINHIP_TUNING
-template <int NT>
-int launch_wg3(const WgradKArgs& a, const WgGeom& g, hipStream_t s) {
-    using C = WgCfg<3, 3, NT>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&wgrad3x3_db_kernel<NT>, Wg3Cfg<NT>::LDS_BYTES, lds_set)) return rc;
-    wgrad3x3_db_kernel<NT><<<dim3((unsigned)(g.PB * g.ncp * g.ncot * g.ndyg)), dim3(512), Wg3Cfg<NT>::LDS_BYTES, s>>>(a);
-    BH_CHECK_LAUNCH();
-    return 0;
-}
-#endif
 
-#if BINHIP_TUNING
-template <int NT, int TPW>
-int launch_r3_t(const WgradKArgs& a, const WgGeom& g, const R3Plan& rp, hipStream_t s) {
-    using R = R3Cfg<NT, TPW>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&wgrad3x3_roll_kernel<NT, TPW>, R::LDS_BYTES, lds_set)) return rc;
-    wgrad3x3_roll_kernel<NT, TPW><<<dim3((unsigned)g.PB, (unsigned)(rp.cgroups * g.ncot)), dim3(512), R::LDS_BYTES, s>>>(a);
-    BH_CHECK_LAUNCH();
-    return 0;
-}
-template <int NT, int TPW>
-int launch_r32_t(const WgradKArgs& a, const WgGeom& g, const R3Plan& rp, hipStream_t s) {
-    using R = R3Cfg2<NT, TPW>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&wgrad3x3_roll2_kernel<NT, TPW>, R::LDS_BYTES, lds_set)) return rc;
-    wgrad3x3_roll2_kernel<NT, TPW><<<dim3((unsigned)g.PB, (unsigned)(rp.cgroups * g.ncot)), dim3(512), R::LDS_BYTES, s>>>(a);
-    BH_CHECK_LAUNCH();
-    return 0;
-}
-template <int NT>
-int launch_r32(const WgradKArgs& a, const WgGeom& g, const R3Plan& rp, hipStream_t s) {
-    switch (rp.tpw) {
-        case 2: return launch_r32_t<NT, 2>(a, g, rp, s);
-        case 3: return launch_r32_t<NT, 3>(a, g, rp, s);
-        case 4: return launch_r32_t<NT, 4>(a, g, rp, s);
-        case 5: return launch_r32_t<NT, 5>(a, g, rp, s);
-    }
-    return BINHIP_E_SHAPE;
-}
-template <int NT>
-int launch_r3(const WgradKArgs& a, const WgGeom& g, const R3Plan& rp, hipStream_t s) {
-    switch (rp.tpw) {
-        case 2: return launch_r3_t<NT, 2>(a, g, rp, s);
-        case 3: return launch_r3_t<NT, 3>(a, g, rp, s);
-        case 4: return launch_r3_t<NT, 4>(a, g, rp, s);
-        case 5: return launch_r3_t<NT, 5>(a, g, rp, s);
-        case 6: return launch_r3_t<NT, 6>(a, g, rp, s);
-        case 7: return launch_r3_t<NT, 7>(a, g, rp, s);
-    }
-    return BINHIP_E_SHAPE;
-}
-#endif
 
 template <int NT, int PPW, int TR>
 int launch_w1(const WgradKArgs& a, const WgGeom& g, const W1Plan& wp, hipStream_t s) {
@@ -1145,21 +981,10 @@ int cus() {
 
 extern "C" {
 
-#if BINHIP_TUNING
-BINHIP_API int binhip_wgrad_set_debug(int flags) { g_wg_dbg = flags; return 0; }
-#endif
-
 size_t binhip_wgrad_workspace_bytes(int ksize, int N, int H, int W, int cin_chunks, int cout) {
     if (N <= 0 || H <= 0 || W <= 0 || cin_chunks <= 0 || cout <= 0) return 0;
     const WgGeom g = wg_geom(ksize, N, H, W, cin_chunks, cout, cus());
-    size_t fl = g.partial_floats + g.bias_floats;
-    if (BINHIP_TUNING && r3_usable(ksize, N, H, W, cin_chunks, 0)) {   // the rolling-row experiment keeps more partials
-        for (int roll = 1; roll <= 2; ++roll) {
-            const WgGeom r = wg_geom(ksize, N, H, W, cin_chunks, cout, cus(), roll);
-            if (r.partial_floats + r.bias_floats > fl) fl = r.partial_floats + r.bias_floats;
-        }
-    }
-    return fl * sizeof(float) + 256;
+    return (g.partial_floats + g.bias_floats) * sizeof(float) + 256;
 }
 
 }  // extern "C"
@@ -1177,9 +1002,7 @@ int bh_wgrad_partials(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
     if ((long long)d->N * d->H * d->W >= (1ll << 26)) return BINHIP_E_SHAPE;
     if (cin <= 0 || cin > d->cin_chunks * 16) return BINHIP_E_SHAPE;
     if (shuffle_perm && d->cout % 4) return BINHIP_E_SHAPE;
-    const bool r3ok = r3_usable(d->ksize, d->N, d->H, d->W, d->cin_chunks, d->x_cpg);
-    const int roll = ((WG_DBG & 64) && r3ok) ? 2 : ((WG_DBG & 128) && r3ok) ? 1 : 0;       // side builds only
-    const WgGeom g = wg_geom(d->ksize, d->N, d->H, d->W, d->cin_chunks, d->cout, cus(), roll);
+    const WgGeom g = wg_geom(d->ksize, d->N, d->H, d->W, d->cin_chunks, d->cout, cus());
     const size_t need = (g.partial_floats + g.bias_floats) * sizeof(float) + 256;
     if (workspace_bytes < need) return BINHIP_E_WORKSPACE;
     float* part = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
@@ -1192,7 +1015,7 @@ int bh_wgrad_partials(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
     a.cin_chunks = d->cin_chunks; a.cout_chunks = (d->cout + 15) / 16;
     a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.ntiles = g.ntiles;
     a.PB = g.PB; a.ncp = g.ncp; a.ncot = g.ncot; a.ppg = 0; a.nz = g.ncot * g.ndyg; a.cgroups = 1;
-    a.dbg = WG_DBG & 0xff0f;      // bits 8..15: start stagger of the lean kernel in units of s_sleep 16 (experiment)
+    a.dbg = 0;
     hipStream_t s = (hipStream_t)stream;
     int rc = BINHIP_E_SHAPE;
     if (use_w1(d->ksize, d->cout)) {
@@ -1201,28 +1024,6 @@ int bh_wgrad_partials(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
         rc = (d->nterms == 1)
             ? (wp.ppw == 2 ? launch_w1<1, 2, 1>(a, g, wp, s) : wp.tr == 2 ? launch_w1<1, 1, 2>(a, g, wp, s) : launch_w1<1, 1, 1>(a, g, wp, s))
             : (wp.ppw == 2 ? launch_w1<3, 2, 1>(a, g, wp, s) : wp.tr == 2 ? launch_w1<3, 1, 2>(a, g, wp, s) : launch_w1<3, 1, 1>(a, g, wp, s));
-#if BINHIP_TUNING
-    } else if (d->ksize == 3 && (WG_DBG & 16)) {    // side builds: the generic double-buffered 4-wave kernel for 3x3
-        rc = (d->nterms == 1) ? launch_wg<3, 3, 1>(a, g, s) : launch_wg<3, 3, 3>(a, g, s);
-    } else if (d->ksize == 3 && WG3_LEAN) {         // side builds: the lean single-stage kernel, two workgroups per CU
-        rc = (d->nterms == 1) ? launch_wg_sb<3, 3, 1>(a, g, s) : launch_wg_sb<3, 3, 3>(a, g, s);
-#endif
-#if BINHIP_TUNING
-    } else if (roll == 2) {                         // 3x3, rolling rows, two rows per stage (experiment)
-        const R3Plan rp = r3_plan2(g.ncp);
-        a.cgroups = rp.cgroups;
-        a.ppg = rp.ppg;
-        rc = (d->nterms == 1) ? launch_r32<1>(a, g, rp, s) : launch_r32<3>(a, g, rp, s);
-    } else if (roll) {                              // 3x3, rolling rows (experiment)
-        const R3Plan rp = r3_plan(g.ncp);
-        a.cgroups = rp.cgroups;
-        rc = (d->nterms == 1) ? launch_r3<1>(a, g, rp, s) : launch_r3<3>(a, g, rp, s);
-#endif
-#if BINHIP_TUNING
-    } else if (d->ksize == 3 && ((BINHIP_WG3_XROW != 0) == (((WG_DBG >> 16) & 1) != 0))) {
-        // side builds: the round-2 form, wave = gY row (debug bit 16, or -DBINHIP_WG3_XROW=0 to make it the side build's default)
-        rc = (d->nterms == 1) ? launch_wg3<1>(a, g, s) : launch_wg3<3>(a, g, s);
-#endif
     } else if (d->ksize == 3) {
         // eight waves, two LDS stages, one workgroup per CU; wave = X row
         rc = (d->nterms == 1) ? launch_wg3x<1>(a, g, s) : launch_wg3x<3>(a, g, s);

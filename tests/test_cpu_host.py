@@ -16,7 +16,7 @@ def T(a):
 
 
 # ------------------------------------------------------------------ C ABI
-def test_library_exports_every_header_symbol():
+def test_library_exports_every_header_symbol_and_no_tuning_setter():
     from bin_amd import _lib
     hdr = open(os.path.join(REPO, "include", "binhip.h")).read()
     declared = set(re.findall(r"\b(binhip_[a-z0-9_]+)\s*\(", hdr))
@@ -26,9 +26,9 @@ def test_library_exports_every_header_symbol():
         assert hasattr(lib, sym), f"libbinhip.so does not export {sym}"
     assert declared == set(_lib.exported_symbols()), declared ^ set(_lib.exported_symbols())
     assert _lib.lib().binhip_version() >= 400
-    # the product library has no process-global switches (SURVEY §8b "no globals except immutable tables"): the
-    # tuning / ablation setters exist only in BINHIP_TUNING side builds and are not declared in the public header
-    for sym in _lib._TUNING_SIGNATURES:
+    # the product library has no process-global switches (SURVEY §8b "no globals except immutable tables"): the retired
+    # tuning / ablation setters are neither exported nor declared in the public header
+    for sym in ("binhip_set_variant", "binhip_set_tail_depth", "binhip_wgrad_set_debug"):
         assert not hasattr(lib, sym), f"product libbinhip.so must not export {sym}"
         assert sym not in declared
     assert "binhip_profile_begin" not in declared and "set_variant" not in hdr
@@ -44,10 +44,10 @@ def test_library_exports_nothing_but_the_abi():
     assert dyn == set(build.abi_symbols()) == set(_lib.exported_symbols()), dyn ^ set(build.abi_symbols())
 
 
-def test_product_library_contains_only_dispatched_weight_gradient_kernels():
-    """The experimental weight-gradient kernels of rounds 1-3 (lean single-stage, wave = gY row, rolling rows) live in
-    tools/experiments/wgrad_experiments.inc and are compiled by `--tuning` side builds only: neither their host stubs nor
-    their device symbols are in the product .so, and the product source stays under 1 500 lines."""
+def test_product_library_and_tree_hold_only_dispatched_weight_gradient_kernels():
+    """The experimental weight-gradient kernels of rounds 1-3 (lean single-stage, wave = gY row, rolling rows) are retired:
+    neither their host stubs nor their device symbols are in the product .so, no side copy of them is kept in tools/, and the
+    product source stays under 1 150 lines."""
     from bin_amd import _lib
     blob = open(_lib.LIB_PATH, "rb").read()
     for name in (b"wgrad3x3_db_kernel", b"wgrad3x3_roll", b"wgrad_mfma_sb_kernel"):
@@ -55,8 +55,23 @@ def test_product_library_contains_only_dispatched_weight_gradient_kernels():
     for name in (b"wgrad3x3_xrow_kernel", b"wgrad1x1_kernel", b"wgrad_mfma_kernel", b"wgrad_reduce_kernel"):
         assert name in blob, name
     src = os.path.join(REPO, "bin_amd", "csrc", "binhip_wgrad.hip")
-    assert sum(1 for _ in open(src)) < 1500
-    assert os.path.exists(os.path.join(REPO, "tools", "experiments", "wgrad_experiments.inc"))
+    assert sum(1 for _ in open(src)) < 1150
+    assert not os.path.exists(os.path.join(REPO, "tools", "experiments"))
+
+
+def test_kernel_sources_have_no_compile_time_switches_but_the_timeline():
+    """The compile-time kernel-variant and ablation switches are retired: the sources hold only the product path.  The one
+    preprocessor switch left is the BINHIP_TIMELINE instrumentation build (tools/wg_timeline.py), plus the header's include
+    guard."""
+    csrc = os.path.join(REPO, "bin_amd", "csrc")
+    files = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
+    files += [os.path.join(REPO, "include", f) for f in os.listdir(os.path.join(REPO, "include"))]
+    names = set()
+    for path in files:
+        for line in open(path):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                names |= set(re.findall(r"\bBINHIP_\w+", line))
+    assert names == {"BINHIP_TIMELINE", "BINHIP_H"}, sorted(names)
 
 
 def test_bare_rdn_subnetwork_offers_the_direct_gradient_context():
@@ -94,7 +109,7 @@ def test_integration_doc_names_exist_in_the_header():
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
     macros = set(re.findall(r"#define\s+(BINHIP_\w+)", hdr)) | set(re.findall(r"\b(BINHIP_\w+)\s*=", hdr))
     macros |= set(re.findall(r"\b(BINHIP_\w+)\b", hdr))                      # enum members, too
-    side_build = {"BINHIP_TUNING", "BINHIP_E_"}                                # the -D switch of tools/ builds; a prefix in prose
+    side_build = {"BINHIP_TIMELINE", "BINHIP_E_"}                              # the -D switch of the timeline build; a prefix in prose
     for name in set(re.findall(r"\b(BINHIP_\w+)", doc)) - side_build:
         assert name in macros, f"INTEGRATION.md mentions {name}, which include/binhip.h does not define"
     entries = set(build.abi_symbols())

@@ -1,8 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer microbenchmark at the 720p working size (half-res 384x672): times each distinct layer class of the
-RDN forward with events on the launch stream and prints us / actual fp16 GB/s / TFLOP/s.  With the BINHIP_TUNING
-side build (`python -m bin_amd.build --tuning`, then BIN_AMD_LIB=tools/_abl/libbinhip_tuning.so) it also sweeps the
-kernel variants (binhip_set_variant) and reports the largest difference to the default variant's result."""
+RDN forward with events on the launch stream and prints us / actual fp16 GB/s / TFLOP/s."""
 import argparse
 import os
 import sys
@@ -36,7 +34,6 @@ def main():
     args = ap.parse_args()
     nt, n, h, w = args.nterms, args.n, args.h, args.w
     lib = L.lib()
-    tuning = hasattr(lib, "binhip_set_variant")
     dev = torch.device("cuda")
     g = torch.Generator(device="cpu").manual_seed(0)
     px = n * h * w
@@ -49,46 +46,46 @@ def main():
         wt = (torch.rand(cout, cin, ks, ks, generator=g) - 0.5) / (cin * ks * ks) ** 0.5
         return ops.ConvWeights(wt.to(dev), (torch.rand(cout, generator=g) - 0.5).to(dev), nterms=nt, shuffle=shuffle)
 
-    cases = []   # (class id, name, variants, fn factory, flops, bytes)
+    cases = []   # (class id, name, fn factory, flops, bytes)
     x224 = mk(224)
     res96 = mk(96)
     for cin in (96, 192):
         cw = wts(32, cin, 3)
         out = ops.CP.empty(2, n, h, w, nt, dev)
-        cases.append((0, f"RDB conv3x3 {cin}->32 +ReLU", [-1, 0, 12] if nt == 1 else [-1, 1],
+        cases.append((0, f"RDB conv3x3 {cin}->32 +ReLU",
                       (lambda cw=cw, cin=cin, out=out: ops.conv2d(x224, cw, relu=True, out=out, cin_chunks=cin // 16)),
-                      2 * 9 * cin * 32 * px, (cin + 32) * bpe * px, out))
+                      2 * 9 * cin * 32 * px, (cin + 32) * bpe * px))
     cw = wts(96, 224, 1)
     out96 = ops.CP.empty(6, n, h, w, nt, dev)
-    cases.append((1, "LFF 1x1 224->96 +res", [-1],
+    cases.append((1, "LFF 1x1 224->96 +res",
                   (lambda cw=cw: ops.conv2d(x224, cw, residual=res96, out=out96)), 2 * 224 * 96 * px,
-                  (224 + 96 + 96) * bpe * px, out96))
+                  (224 + 96 + 96) * bpe * px))
     x1152 = mk(1152)
     cwg = wts(96, 1152, 1)
     outg = ops.CP.empty(6, n, h, w, nt, dev)
-    cases.append((1, "GFF.0 1x1 1152->96", [-1],
-                  (lambda: ops.conv2d(x1152, cwg, out=outg)), 2 * 1152 * 96 * px, (1152 + 96) * bpe * px, outg))
+    cases.append((1, "GFF.0 1x1 1152->96",
+                  (lambda: ops.conv2d(x1152, cwg, out=outg)), 2 * 1152 * 96 * px, (1152 + 96) * bpe * px))
     cw3 = wts(96, 96, 3)
     out3 = ops.CP.empty(6, n, h, w, nt, dev)
-    cases.append((2, "3x3 96->96 +res", [-1],
+    cases.append((2, "3x3 96->96 +res",
                   (lambda: ops.conv2d(res96, cw3, residual=x224, out=out3)), 2 * 9 * 96 * 96 * px,
-                  (96 + 96 + 96) * bpe * px, out3))
+                  (96 + 96 + 96) * bpe * px))
     cwu = wts(256, 96, 3, shuffle=True)
     outu = ops.CP.empty(4, n, 2 * h, 2 * w, nt, dev)
-    cases.append((3, "UPNet.0 3x3 96->256 +shuffle", [-1],
+    cases.append((3, "UPNet.0 3x3 96->256 +shuffle",
                   (lambda: ops.conv2d(res96, cwu, out=outu, epilogue=L.EPI_SHUFFLE)), 2 * 9 * 96 * 256 * px,
-                  (96 + 256) * bpe * px, outu))
+                  (96 + 256) * bpe * px))
     xu = mk(64, 2 * h, 2 * w)
     cwf = wts(3, 64, 3)
     imgs = [torch.rand(n, 3, 2 * h, 2 * w, generator=g).to(dev) for _ in range(2)]
-    cases.append((4, "UPNet.2 3x3 64->3 +mean (final)", [-1] if nt == 1 else [-1, 1],
+    cases.append((4, "UPNet.2 3x3 64->3 +mean (final)",
                   (lambda: ops.conv2d(xu, cwf, epilogue=L.EPI_FINAL, images=imgs)), 2 * 9 * 64 * 3 * 4 * px,
-                  (64 * bpe + 3 * 4 * 3) * 4 * px, None))
+                  (64 * bpe + 3 * 4 * 3) * 4 * px))
     x48 = mk(48)
     cw5 = wts(96, 36, 5)
     out5 = ops.CP.empty(6, n, h, w, nt, dev)
-    cases.append((5, "SFENet1 5x5 36->96", [-1], (lambda: ops.conv2d(x48, cw5, out=out5, cin_chunks=3)),
-                  2 * 25 * 36 * 96 * px, (48 + 96) * bpe * px, out5))
+    cases.append((5, "SFENet1 5x5 36->96", (lambda: ops.conv2d(x48, cw5, out=out5, cin_chunks=3)),
+                  2 * 25 * 36 * 96 * px, (48 + 96) * bpe * px))
 
     # fused conv#3 + LFF vs the two separate kernels
     import ctypes as C
@@ -116,42 +113,13 @@ def main():
     print(f"fused conv3+LFF (+store o3):  {us:8.1f} us")
     us = time_fn(unfused)
     print(f"unfused conv3 ; LFF:          {us:8.1f} us")
-    if os.environ.get("WGRAD") and tuning:
-        # weight-gradient kernels at the training working size (8 x 128 x 128 half-res pixels)
-        nn_, hh_, ww_ = 8, 128, 128
-        gg = torch.Generator().manual_seed(1)
-        for (ks, cin, cout) in ((3, 96, 32), (3, 192, 32), (1, 224, 96), (3, 96, 96), (1, 1152, 96)):
-            xx = ops.nchw_to_planes(torch.rand(nn_, cin, hh_, ww_, generator=gg).to(dev), nt)
-            gy = ops.nchw_to_planes(torch.rand(nn_, cout, hh_, ww_, generator=gg).to(dev) - 0.5, nt)
-            f = (lambda xx=xx, gy=gy, ks=ks, cin=cin, cout=cout: ops.conv2d_bwd_weight(xx, gy, cout, cin, ks, nt))
-            for dbg, nm in ((0, "full"), (16, "full, 1 wg/CU double-buffered"), (1, "no DMA"), (2, "no MFMA"), (4, "no reduce/store"), (7, "nothing")):
-                lib.binhip_wgrad_set_debug(dbg)
-                us = time_fn(f, iters=10, warm=2)
-                print(f"wgrad k{ks} {cin}->{cout} nt={nt} {nm:16s}: {us:8.1f} us   {2*ks*ks*cin*cout*nn_*hh_*ww_*(3 if nt==3 else 1)/us/1e6:7.0f} TF-eq/s")
-            lib.binhip_wgrad_set_debug(0)
     want = {int(c) for c in args.classes.split(",")}
     print(f"nterms={nt} N={n} {h}x{w}")
-    for cls, name, variants, fn, flops, nbytes, outbuf in cases:
+    for cls, name, fn, flops, nbytes in cases:
         if cls not in want:
             continue
-        ref = None
-        for v in (variants if tuning else [-1]):
-            if tuning:
-                lib.binhip_set_variant(cls, v)
-            r = fn()
-            torch.cuda.synchronize()
-            if outbuf is not None:
-                cur = outbuf.hi.float() + (outbuf.lo.float() if outbuf.lo is not None else 0)
-            else:
-                cur = r.clone()
-            if ref is None:
-                ref = cur
-            diff = float((ref - cur).abs().max()) / max(float(ref.abs().max()), 1e-30)
-            us = time_fn(fn)
-            print(f"{name:34s} v{v}: {us:8.1f} us  {nbytes / us / 1e3:7.0f} GB/s(actual)  "
-                  f"{flops / us / 1e6:7.0f} TF/s  rel.diff to default {diff:.2e}")
-        if tuning:
-            lib.binhip_set_variant(cls, -1)
+        us = time_fn(fn)
+        print(f"{name:34s}: {us:8.1f} us  {nbytes / us / 1e3:7.0f} GB/s(actual)  {flops / us / 1e6:7.0f} TF/s")
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ limiter residency are sampled (bin_amd/utils/smi.py).
 
     python tools/launch_shape.py [--secs 4] [--th 16] [--kernels rdb,tail] [--rounds 0.5,1.0,1.3,1.5,2.0,3.0] [--zero]
 
-A tile is TH x 32 half-resolution pixels (dense-block conv: TH = 16 = 8 waves x 2 rows, BINHIP_X3_WN side builds change it;
+A tile is TH x 32 half-resolution pixels (dense-block conv: TH = 16 = 8 waves x 2 rows;
 fused tail: TH = 8); the CU holds two workgroups of either kernel, so one round = 512 tiles.  Only H varies (W = 672 = 21 tile
 columns, the 720p working width), so `rounds` is met to within one tile row.  Columns: launch time, the same per tile and per
 round-equivalent (512 tiles), shader clock (device mean and slowest XCD), socket watts, the share of firmware samples with the PPT
@@ -24,7 +24,7 @@ from bin_amd.utils.smi import Sampler  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--secs", type=float, default=4.0)
-ap.add_argument("--th", type=int, default=16, help="tile rows of the dense-block conv in the loaded library (BINHIP_X3_R * BINHIP_X3_WN)")
+ap.add_argument("--th", type=int, default=16, help="tile rows of the dense-block conv in the loaded library (X3_R * X3_WN)")
 ap.add_argument("--kernels", default="rdb,tail")
 ap.add_argument("--rounds", default="0.5,1.0,1.3,1.5,2.0,3.0")
 ap.add_argument("--zero", action="store_true")

@@ -1,5 +1,5 @@
 """Run ONE conv layer class a few times (for rocprofv3 --pmc / --kernel-trace passes on a single kernel).
-usage: pmc_one.py [rdb|tail|wgrad] [nterms] [cin] [variant]   (variant needs BIN_AMD_LIB=tools/_abl/libbinhip_tuning.so)"""
+usage: pmc_one.py [rdb|tail|wgrad] [nterms] [cin]"""
 import ctypes as C
 import os
 import sys
@@ -9,10 +9,7 @@ from bin_amd import _lib as L, ops
 which = sys.argv[1] if len(sys.argv) > 1 else "rdb"
 nt = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 cin = int(sys.argv[3]) if len(sys.argv) > 3 else 160
-variant = int(sys.argv[4]) if len(sys.argv) > 4 else -1
 lib = L.lib()
-if variant != -1:
-    lib.binhip_set_variant(0, variant)
 dev = torch.device("cuda")
 g = torch.Generator().manual_seed(0)
 n, h, w = 1, 384, 672

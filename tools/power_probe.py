@@ -1,6 +1,5 @@
 """Package power of ONE kernel under sustained load: loops the dense-block conv (f16x3, Cin = 160, 720p working size) for a
-few seconds while rocm-smi is sampled (tools/smi_watch.sh).  Run it against the product library and against
--DBINHIP_ABLATE=1|2|4 side builds (BIN_AMD_LIB) to split the power into matrix / LDS-read / LDS-DMA shares.
+few seconds while rocm-smi is sampled (tools/smi_watch.sh).
 usage: power_probe.py [seconds] [zero]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
