@@ -11,14 +11,20 @@ weak scaling), value = all ranks' windows / max-over-ranks time.
 The headline `value` is measured in the fp32-class precision mode "f16x3" (every activation / weight is an fp16
 hi+lo pair = 22 significand bits, three MFMA products, fp32 accumulate; 1e-6 max-abs vs the fp32 reference —
 the reference computes fp32, RDN.py:141, so a narrower mode is never the headline).  The single-product fp16 mode
-("f16", 3.5e-4 max-abs, inside north_star's 1e-3 bar) is reported as `tolerance_mode`, beside `value`.
+("f16", 3.5e-4 max-abs, inside north_star's 1e-3 bar) is reported as `tolerance_mode`, beside `value`, by a --full run.
 
 The printed line stays under RESULT_LINE_MAX characters: it carries every top-level field and, of each object below, its
 own scalars; the whole object (notes, power trees, nested rooflines) is written to --detail, by default a new file in the
 temporary directory (named on the line as `detail`).  By default nothing is written to the working directory.
 --dump-outputs DIR writes the arrays the last timed step computed, so that two builds can be compared output for output.
 
-Extra objects on the JSON line:
+A plain run (no --full) does only what the headline needs: set-up, --warmup untimed steps, the --steps timed steps, the
+--dump-outputs arrays, and the line (headline fields, `config`, `step_ms`).  --full adds the measurements below, each in
+passes of its own after the timed region (minutes: the CPU baseline alone takes about two); the --no-* options leave single
+legs out of a --full run.  In --mode train, --full adds that mode's `power`, `power_bound`, `roofline` and
+`mixed_mode`.
+
+Extra objects on the JSON line with --full:
   roofline     — dominant kernel (RDB 3x3 conv Cin->32, 70 % of FLOPs): algorithmic bytes per launch AT THE STORAGE
                  WIDTH OF THE TIMED MODE (f16x3: 4 B/element = the fp32 yardstick; f16: 2 B) / its mean duration
                  measured with HIP events on the launch stream; `traffic` from the committed per-precision PMC passes
@@ -694,8 +700,7 @@ def train_bench(args, rank, world, dev, steps=None, warmup=None, standalone=True
             dist.barrier()
         torch.cuda.synchronize()
 
-    from bin_amd import ops, _lib as L
-    from bin_amd.utils.smi import power_pass
+    from bin_amd import ops
     torch.cuda.reset_peak_memory_stats()
     for i in range(warmup):
         m.optimize_parameters(i + 1)
@@ -708,7 +713,55 @@ def train_bench(args, rank, world, dev, steps=None, warmup=None, standalone=True
         dump_outputs(args.dump_outputs, [("loss", m.loss.detach().double().reshape(1))] +
                      [(f"Ft_p_{k:02d}", o) for k, o in enumerate(m.Ft_p)] +
                      [("params", torch.cat([p.detach().reshape(-1) for p in m.netG.module.parameters()]))])
-    # clock / package power of the same steps, sampled in a pass of its own (every rank runs it: collectives stay matched)
+    dt = max_over_ranks(dt, dev, world)
+    line = {
+        "metric": "training samples/sec (256x256 crops, 6-frame windows)", "value": round(world * B * steps / dt, 4),
+        "unit": "samples/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": round(dt / steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": DTYPE[prec] + (" forward; single-product backward on the hi planes" if bwd_prec else ""),
+        "data": ("all-zero operands (diagnostic, INVALID as a result)" if args.zero_data else "synthetic"),
+        "loss": loss_value,
+        "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 1e9, 2),
+        "nccl_ranks": (dist.get_world_size() if dist.is_initialized() else 1),
+        "backend": (dist.get_backend() if dist.is_initialized() else None),
+        "step_ms": step_spread(step_ms),
+        "config": {"workload": f"Adobe240 training, 256x256 crops, batch {B} per GPU, Charbonnier x17, Adam, "
+                               f"DP flat gradient all-reduce (45.77 MB)", "precision": prec,
+                   "backward_precision": bwd_prec or prec}}
+    if args.full:
+        line.update(train_control_legs(args, m, batch, rank, world, dev, B, S, prec, bwd_prec, dt, steps, warmup, step_ms))
+    del m
+    torch.cuda.empty_cache()
+    if args.full and prec == "f16x3" and not bwd_prec and not args.zero_data and world == 1 and not args.no_extras:
+        # the supported reduced-precision training mode beside the headline (never instead of it): f16x3 forward, single-product
+        # backward — the counterpart of BASELINE config 4's "bf16" wording with a stated parity (profiles/r06_training_modes.md)
+        m2, _ = make_train_model("f16x3", "f16", world, rank, args.batch)
+        for i in range(2):
+            m2.optimize_parameters(i + 1)
+        torch.cuda.synchronize()
+        dt2, ms2 = timed_steps(lambda i: m2.optimize_parameters(3 + i), 4, torch.cuda.synchronize)
+        ops.check_status()
+        line["mixed_mode"] = {"value": round(B * 4 / dt2, 4), "unit": "samples/s", "ms_per_step": round(dt2 / 4 * 1e3, 2),
+                              "step_ms": step_spread(ms2), "config": {"precision": "f16x3", "backward_precision": "f16"},
+                              "parity": "loss and ReLU masks exact (f16x3 forward); parameter gradients ~2e-3 relative vs torch autograd of the "
+                                        "oracle (tests/test_gpu_train.py); converges like f16x3 (profiles/r06_training_modes.md)"}
+        del m2
+        torch.cuda.empty_cache()
+    if not standalone:
+        return line
+    if rank == 0:
+        print(result_line(line, args.detail), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def train_control_legs(args, m, batch, rank, world, dev, B, S, prec, bwd_prec, dt, steps, warmup, step_ms):
+    """--full: the training line's `power`, `power_bound` and `roofline`, in steps of their own after the timed ones (every rank
+    runs them: collectives stay matched).  `dt` = the timed steps' max-over-ranks time.  Zeroes the model's weights."""
+    from bin_amd import ops, _lib as L
+    from bin_amd.utils.smi import power_pass
+    # clock / package power of the same steps, sampled in a pass of its own
     counter = [warmup + steps]
 
     def one_step():
@@ -751,7 +804,6 @@ def train_bench(args, rank, world, dev, steps=None, warmup=None, standalone=True
                     kern = (kms.value / kn.value * 1e-3, kn.value)
                 else:
                     kern_overlapped = kms.value / kn.value * 1e-3
-    dt = max_over_ranks(dt, dev, world)
     # ---- zero-operand control: the SAME steps with all-zero batch and weights — identical launches
     # and instruction streams, idle datapaths.  Last thing this model does (its weights are gone afterwards).
     power_bound = None
@@ -766,48 +818,9 @@ def train_bench(args, rank, world, dev, steps=None, warmup=None, standalone=True
         zero = power_pass(one_step, dev, repetitions=5, sync=torch.cuda.synchronize)
         power_bound = power_bound_object(dt / steps * 1e3, power, zero, "training step")
         ops.check_status()
-    line = {
-        "metric": "training samples/sec (256x256 crops, 6-frame windows)", "value": round(world * B * steps / dt, 4),
-        "unit": "samples/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(dt / steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": DTYPE[prec] + (" forward; single-product backward on the hi planes" if bwd_prec else ""),
-        "data": ("all-zero operands (diagnostic, INVALID as a result)" if args.zero_data else "synthetic"),
-        "loss": loss_value,
-        "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 1e9, 2),
-        "nccl_ranks": (dist.get_world_size() if dist.is_initialized() else 1),
-        "backend": (dist.get_backend() if dist.is_initialized() else None),
-        "power": power,
-        "power_bound": power_bound,
-        "step_ms": step_spread(step_ms),
-        "roofline": {**train_roofline(B, S, dt / steps, prec, bwd_prec, kern, kern_overlapped), **clock_fields(dt / steps * 1e3, power),
-                     "step_ms": step_spread(step_ms)},
-        "config": {"workload": f"Adobe240 training, 256x256 crops, batch {B} per GPU, Charbonnier x17, Adam, "
-                               f"DP flat gradient all-reduce (45.77 MB)", "precision": prec,
-                   "backward_precision": bwd_prec or prec}}
-    del m
-    torch.cuda.empty_cache()
-    if prec == "f16x3" and not bwd_prec and not args.zero_data and world == 1 and not args.no_extras:
-        # the supported reduced-precision training mode beside the headline (never instead of it): f16x3 forward, single-product
-        # backward — the counterpart of BASELINE config 4's "bf16" wording with a stated parity (profiles/r06_training_modes.md)
-        m2, _ = make_train_model("f16x3", "f16", world, rank, args.batch)
-        for i in range(2):
-            m2.optimize_parameters(i + 1)
-        torch.cuda.synchronize()
-        dt2, ms2 = timed_steps(lambda i: m2.optimize_parameters(3 + i), 4, torch.cuda.synchronize)
-        ops.check_status()
-        line["mixed_mode"] = {"value": round(B * 4 / dt2, 4), "unit": "samples/s", "ms_per_step": round(dt2 / 4 * 1e3, 2),
-                              "step_ms": step_spread(ms2), "config": {"precision": "f16x3", "backward_precision": "f16"},
-                              "parity": "loss and ReLU masks exact (f16x3 forward); parameter gradients ~2e-3 relative vs torch autograd of the "
-                                        "oracle (tests/test_gpu_train.py); converges like f16x3 (profiles/r06_training_modes.md)"}
-        del m2
-        torch.cuda.empty_cache()
-    if not standalone:
-        return line
-    if rank == 0:
-        print(result_line(line, args.detail), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    return {"power": power, "power_bound": power_bound,
+            "roofline": {**train_roofline(B, S, dt / steps, prec, bwd_prec, kern, kern_overlapped), **clock_fields(dt / steps * 1e3, power),
+                         "step_ms": step_spread(step_ms)}}
 
 
 def fused_upnet_active():
@@ -962,17 +975,22 @@ def main():
     ap.add_argument("--precision", default=os.environ.get("BIN_AMD_BENCH_PRECISION", "f16x3"),
                     choices=["f16", "f16x3"],
                     help="f16x3 (default): fp32-class, the headline; f16: the tolerance mode (3.5e-4 vs the fp32 reference)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: roofline, power and "
+                         "zero-operand control, tolerance mode, streaming, training step, PNG harness, CPU baseline with the "
+                         "oracle check (--mode train: power, zero-operand control, roofline, mixed mode); off: the headline only")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the legs reported beside `value` (tolerance mode, streaming, training step)")
+                    help="with --full: skip the legs reported beside `value` (tolerance mode, streaming, training step)")
     ap.add_argument("--streams", type=int, default=None, help="concurrent RDN calls (HIP streams) in the forward")
     ap.add_argument("--four-calls", action="store_true",
                     help="A/B: force the four-call schedule (stage s of both windows batched along N; the default only for "
                          "small frames and training) for the 720p inference window")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its oracle check")
     ap.add_argument("--no-power", action="store_true",
-                    help="skip the power passes after the timed regions (clock / watts sampling, the zero-operand control)")
-    ap.add_argument("--no-harness", action="store_true", help="skip the PNG-in -> PNG-out folder leg")
-    ap.add_argument("--harness-frames", type=int, default=81, help="synthetic 720p PNG frames of the folder leg")
+                    help="with --full: skip the power passes after the timed regions (clock / watts sampling, the zero-operand "
+                         "control)")
+    ap.add_argument("--no-harness", action="store_true", help="with --full: skip the PNG-in -> PNG-out folder leg")
+    ap.add_argument("--harness-frames", type=int, default=81, help="synthetic 720p PNG frames of the folder leg (--full)")
     ap.add_argument("--calib", action="store_true",
                     help="also run one 256 MiB device copy (known HBM bytes) to calibrate rocprofv3 FETCH/WRITE_SIZE")
     ap.add_argument("--mode", default="infer", choices=["infer", "train"],
@@ -1090,14 +1108,14 @@ def main():
         if rank == 0 and args.dump_outputs:
             dump_outputs(args.dump_outputs, [(f"Ft_p_{k:02d}", o) for k, o in enumerate(out)])
         hip_out_path = alt_out_path = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.zero_data:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.zero_data:
             # the timed window's outputs, kept for the cpu_baseline leg: the oracle it times there also checks them (hip_vs_oracle)
             import tempfile
             fd, hip_out_path = tempfile.mkstemp(suffix=".pt", prefix="bin_amd_bench_out_")
             os.close(fd)
             torch.save([o.detach().float().cpu() for o in out], hip_out_path)
         # shader clock / package power of the same forwards, in a pass of its own right after the timed region
-        do_power = rank == 0 and not args.no_power
+        do_power = args.full and rank == 0 and not args.no_power
         power = power_pass(lambda: net(*frames, **kw_in), dev, min_seconds=1.0, sync=torch.cuda.synchronize) if do_power else None
         # ---- roofline leg: the dominant kernel's mean duration, HIP events on the launch stream.  With several
         # streams kernels of different RDN calls overlap and a per-kernel duration is not meaningful, so this pass
@@ -1106,7 +1124,7 @@ def main():
         ops.check_status()                    # nothing in the timed region left the fp16 storage range
         launches_per_step = (17 if net.reuse_schedule else 20) * 36
         prof_steps = min(args.steps, 5)
-        prof = rank == 0 and prof_steps * launches_per_step <= 16384
+        prof = args.full and rank == 0 and prof_steps * launches_per_step <= 16384
 
         def dominant_kernel_pass():
             """(summed ms, launches) of the dense-block conv class (3x3, 32 outputs, plane epilogue) over `prof_steps`
@@ -1130,7 +1148,7 @@ def main():
             return ms_.value, n_.value
 
         kern_ms, kern_n = dominant_kernel_pass() if prof else (0.0, 0)
-        extras = rank == 0 and not args.no_extras
+        extras = args.full and rank == 0 and not args.no_extras
         # ---- streaming leg (reported beside `value`, never instead of it): consecutive windows of
         # one clip, sliding by one frame, with the exact cross-window reuse -> 10 instead of 17 RDN calls per window (rounds 1-3: 13)
         stream_fps = None
@@ -1202,7 +1220,7 @@ def main():
 
     # ---- BASELINE config 3/4 on this GPU: one driver-timed training figure on the same line (N = 1 default run)
     train = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         try:
             train = train_bench(args, rank, world, dev, steps=4, warmup=2, standalone=False)
         except Exception as e:          # the headline must still print
@@ -1210,7 +1228,7 @@ def main():
 
     # ---- N1 end to end: PNG folder in -> PNG folder out through bin_amd.test, headline precision
     harness = None
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_harness and not args.zero_data:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not args.no_harness and not args.zero_data:
         try:
             matched = resident_clip_fps(net, frames, args.harness_frames) if net.reuse_schedule else None
             harness = harness_bench(args.precision, args.harness_frames, matched, steady_gpu_only_fps=stream_fps)
@@ -1241,20 +1259,23 @@ def main():
                        "parity": "max-abs <= 2e-5 (f16x3) vs the fp32 reference (tests/)" if prec == "f16x3"
                                  else "max-abs <= 1e-3 (f16) vs the fp32 reference (tests/)"},
             "step_ms": step_spread(step_ms),
-            "roofline": roof,
-            "power": power,
-            "power_bound": power_bound,
-            "harness": harness,
             "nccl_ranks": (dist.get_world_size() if world > 1 else 1),
             "backend": (dist.get_backend() if world > 1 else None),
-            "tolerance_mode" if other == "f16" else "fp32_class": alt,
-            "streaming": None if stream_fps is None else {
-                "value": round(stream_fps, 3), "unit": "interpolated frames/s",
-                "note": "consecutive windows of one clip (sliding by one frame) with exact cross-window reuse (the next window repeats 4 stage-1, 2 stage-2 and 1 stage-3 call of this one, none of which sees ConvLSTM state): 10 RDN calls per "
-                        "window instead of 17; same outputs bit for bit (tests/test_gpu_net.py); not the headline value"},
-            "train": train,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line.update({
+                "roofline": roof,
+                "power": power,
+                "power_bound": power_bound,
+                "harness": harness,
+                "tolerance_mode" if other == "f16" else "fp32_class": alt,
+                "streaming": None if stream_fps is None else {
+                    "value": round(stream_fps, 3), "unit": "interpolated frames/s",
+                    "note": "consecutive windows of one clip (sliding by one frame) with exact cross-window reuse (the next window repeats 4 stage-1, 2 stage-2 and 1 stage-3 call of this one, none of which sees ConvLSTM state): 10 RDN calls per "
+                            "window instead of 17; same outputs bit for bit (tests/test_gpu_net.py); not the headline value"},
+                "train": train,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(hip_outputs=hip_out_path, alt_outputs=alt_out_path)
             for pth in (hip_out_path, alt_out_path):
                 if pth and os.path.exists(pth):

@@ -239,7 +239,7 @@ def _bench_as_the_driver_launches_it(n, extra, port, tmp_path):
 
 
 def test_bench_two_ranks_inference_line_is_whole_job_throughput(tmp_path):
-    d = _bench_as_the_driver_launches_it(2, ["--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], 29631, tmp_path)
+    d = _bench_as_the_driver_launches_it(2, ["--full", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], 29631, tmp_path)
     assert d["n_gpus"] == 2 and d["nccl_ranks"] == 2 and d["backend"] == "gloo" and d["scaling"] == "weak"
     assert d["steps"] == 2 and d["warmup"] == 1
     assert abs(d["value"] - 2 * 2 / (d["ms_per_step"] * 2 * 1e-3)) < 1e-2 * d["value"]       # all ranks' windows / max time
@@ -247,7 +247,7 @@ def test_bench_two_ranks_inference_line_is_whole_job_throughput(tmp_path):
 
 
 def test_bench_two_ranks_training_line_reduces_gradients_across_ranks(tmp_path):
-    d = _bench_as_the_driver_launches_it(2, ["--mode", "train", "--batch", "1", "--steps", "2", "--warmup", "1"], 29633, tmp_path)
+    d = _bench_as_the_driver_launches_it(2, ["--full", "--mode", "train", "--batch", "1", "--steps", "2", "--warmup", "1"], 29633, tmp_path)
     assert d["n_gpus"] == 2 and d["nccl_ranks"] == 2 and d["backend"] == "gloo"
     assert abs(d["value"] - 2 * 1 * 2 / (d["ms_per_step"] * 2 * 1e-3)) < 1e-2 * d["value"]
     assert np.isfinite(d["loss"]) and d["roofline"]["dominant_kernel"]["launches"] > 0

@@ -146,7 +146,7 @@ def bench_result(args, tmp_path, timeout):
 
 
 def test_bench_line_carries_power_bound_harness_and_labelled_roofline(tmp_path):
-    line, d = bench_result(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--harness-frames", "7"], tmp_path, 900)
+    line, d = bench_result(["--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--harness-frames", "7"], tmp_path, 900)
     assert line["steps"] == 3 and line["step_ms"]["steps"] == 3
     assert line["roofline"]["frac"] == d["roofline"]["frac"] and line["harness"]["windows"] == d["harness"]["windows"]
     roof = d["roofline"]
@@ -175,7 +175,7 @@ def test_bench_line_carries_power_bound_harness_and_labelled_roofline(tmp_path):
 def test_bench_power_bound_reading_is_computed_from_the_numbers_beside_it(tmp_path):
     """`power_bound` (bench.py): the device's own limiter residency, cycles = ms x clock for the real-data and the all-zero pass,
     and a `reading` that is one of four outcomes DERIVED from them — never a constant string."""
-    _, d = bench_result(["--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-extras"], tmp_path, 600)
+    _, d = bench_result(["--full", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-extras"], tmp_path, 600)
     pw, pb = d["power"], d["power_bound"]
     assert pw["samples"] >= 5 and pw["clock_mhz"]["mean"] > 500
     assert "limiter" in pw and "source" in pw["limiter"]
@@ -203,6 +203,28 @@ def test_bench_power_bound_reading_is_computed_from_the_numbers_beside_it(tmp_pa
         assert pb["at_cap"] == (fr["ppt_power"] >= 0.5) and pb["at_cap_rule"].startswith("device:")
         assert all(0.0 <= v <= 1.0001 for v in fr.values())
     assert pb["power_cap_observed_w"] >= pb["power_w"]["data"] - 1e-6
+
+
+FULL_ONLY_LEGS = {"roofline", "power", "power_bound", "harness", "tolerance_mode", "fp32_class", "streaming", "train",
+                  "cpu_baseline", "mixed_mode"}
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full, bench.py sets up, warms up, times its steps, dumps the last step's outputs and prints the headline: no leg
+    that --full adds reaches the line (they run nowhere else), in either mode, and `value` is the rate of the timed steps."""
+    dump = tmp_path / "dump"
+    line, d = bench_result(["--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)], tmp_path, 600)
+    assert not FULL_ONLY_LEGS & set(d), sorted(d)
+    assert line["metric"] == "interpolated frames/sec at 1280x720" and line["unit"] == "interpolated frames/s"
+    assert line["higher_is_better"] is True and line["dtype"].startswith("f16x3")
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["step_ms"]["steps"] == 3
+    assert line["value"] == pytest.approx(1e3 / line["ms_per_step"], rel=1e-3)
+    assert sorted(os.listdir(dump)) == [f"Ft_p_{k:02d}.npy" for k in range(14)]
+    assert all(np.isfinite(np.load(dump / f)).all() for f in os.listdir(dump))
+    line, d = bench_result(["--mode", "train", "--batch", "1", "--steps", "2", "--warmup", "1"], tmp_path, 600)
+    assert not FULL_ONLY_LEGS & set(d), sorted(d)
+    assert line["metric"].startswith("training samples/sec") and line["steps"] == 2 and line["step_ms"]["steps"] == 2
+    assert line["value"] == pytest.approx(1e3 / line["ms_per_step"], rel=1e-2) and np.isfinite(line["loss"])
 
 
 def _blur_tree(root, clips=(("c0", 0, 5), ("c1", 40, 4)), hw=(72, 100)):

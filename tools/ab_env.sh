@@ -6,9 +6,9 @@ kv=$1; shift
 for rep in 1 2 3; do for v in default "$kv"; do
   echo -n "$v $rep: "
   if [ "$v" = default ]; then
-    timeout 400 python bench.py --no-cpu-baseline --no-extras "$@" 2>&1 | tail -1 | grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*' | head -2 | tr '\n' ' '
+    timeout 400 python bench.py "$@" 2>&1 | tail -1 | grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*' | head -2 | tr '\n' ' '
   else
-    env "$kv" timeout 400 python bench.py --no-cpu-baseline --no-extras "$@" 2>&1 | tail -1 | grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*' | head -2 | tr '\n' ' '
+    env "$kv" timeout 400 python bench.py "$@" 2>&1 | tail -1 | grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*' | head -2 | tr '\n' ' '
   fi
   echo
 done; done

@@ -1,13 +1,13 @@
 """Build the committed profile summaries of a round from what a `tools/gpu.sh` profile run left under gpurun_out/.
 
     gpurun --timeout 3000 -- bash tools/gpu.sh "tag r5p" \
-        "kt x3 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-power" \
-        "kt f16 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-power --precision f16" \
-        "env BIN_AMD_WGRAD_STREAM=0" "kt train --mode train --batch 8 --steps 2 --warmup 1 --no-power" \
-        "traffic wgrad3x3 --mode train --batch 8 --steps 1 --warmup 1 --no-power" "env BIN_AMD_WGRAD_STREAM=" \
-        "traffic f16x3 --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-power --calib" \
-        "traffic f16 --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-power --calib --precision f16" \
-        "sq rdb 3 160" "sq tail 3 192" "sq wgrad 3 160" "bench" "bench --mode train"
+        "kt x3 --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-power" \
+        "kt f16 --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-power --precision f16" \
+        "env BIN_AMD_WGRAD_STREAM=0" "kt train --full --mode train --batch 8 --steps 2 --warmup 1 --no-power" \
+        "traffic wgrad3x3 --full --mode train --batch 8 --steps 1 --warmup 1 --no-power" "env BIN_AMD_WGRAD_STREAM=" \
+        "traffic f16x3 --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-power --calib" \
+        "traffic f16 --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-power --calib --precision f16" \
+        "sq rdb 3 160" "sq tail 3 192" "sq wgrad 3 160" "bench --full" "bench --full --mode train"
     python tools/assemble_profiles.py --tag r5p --round 5
 
 Writes profiles/rNN_kernel_stats_720p.md, rNN_train_kernel_stats.md, rNN_pmc_traffic.md/.json, rNN_pmc_sq.md, rNN_bench_f16x3.json,
@@ -72,10 +72,10 @@ def main():
     gflop = roof["algorithmic_flop_per_launch"] * 3 / 1e9       # executed MFMA GFLOP of one launch (3 products)
     pb = b.get("power_bound") or {}
     with open(os.path.join(P, f"{R}_kernel_stats_720p.md"), "w") as f:
-        f.write(f"""# Round {a.round} — rocprofv3 --kernel-trace --stats of the default bench command (MI355X, 720p window, f16x3 headline)
+        f.write(f"""# Round {a.round} — rocprofv3 --kernel-trace --stats of the --full bench command (MI355X, 720p window, f16x3 headline)
 
 Command on the GPU box (`tools/gpu.sh "kt x3 ..."`, see the header of `tools/assemble_profiles.py`, which wrote this file):
-`export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/x3 -o kt -- python bench.py --steps 3
+`export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d <log dir>/prof/x3 -o kt -- python bench.py --full --steps 3
 --warmup 1 --no-cpu-baseline --no-extras --no-power` (default precision f16x3, default schedule = 1 stream, 17 RDN calls per window).  The run
 holds 8 forwards (1 warm-up + 3 timed + 1 + 3 of the serial roofline leg); per forward 612 dense-block conv launches (`{DOM_X3}`), 204
 fused tails, 34 wide 3x3 layers, 17 each of GFF.0, SFENet1 and the fused UPNet (`conv_x3_kernel<5, 2, 8, 4, 0, false>` + `upnet_ring_kernel`: round 6, one 5x5 convolution on 12 sub-pixel channels instead of UPNet.0 + UPNet.2).  bench.py's line in the same (profiled) run: {bp['value']} frames/s,
@@ -108,7 +108,7 @@ UPNet runs fused here too (`conv_mfma_kernel<5, 1, 1, 2, 8, 1, 1, 2, 4, false>` 
     with open(os.path.join(P, f"{R}_train_kernel_stats.md"), "w") as f:
         f.write(f"""# Round {a.round} — training step (BASELINE config 3/4: 8 x 256x256 crops per GPU, f16x3) kernel stats, MI355X
 
-`BIN_AMD_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --mode train --batch 8 --steps 2 --warmup 1 --no-power`
+`BIN_AMD_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --mode train --batch 8 --steps 2 --warmup 1 --no-power`
 (the side stream is off so that kernel durations do not include each other; written by `tools/assemble_profiles.py`).  Un-profiled on the
 same box (`{R}_bench_train.json`): **{bt['ms_per_step']} ms / step = {bt['value']} samples/s**, {(bt.get('power') or {}).get('power_from_energy_w')} W (energy counter) at
 {xcd(bt.get('power'))} MHz (per-XCD mean); the same steps on all-zero operands: {tpb.get('ms_zero')} ms at {xcd_z(tpb)} MHz (time ratio {tpb.get('ratio')},
@@ -126,8 +126,8 @@ schedule); bench.py's own event-timed average of the 192 dense-block launches pe
         f.write(f"""# Round {a.round} — HBM-side traffic per kernel launch (rocprofv3 PMC passes, MI355X)
 
 `tools/gpu.sh "traffic KEY ..."`: separate `rocprofv3 --pmc FETCH_SIZE --kernel-trace` and `--pmc WRITE_SIZE --kernel-trace` passes (no other trace
-domains) over `python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-power --calib [--precision f16]` and over
-`BIN_AMD_WGRAD_STREAM=0 python bench.py --mode train --batch 8 --steps 1 --warmup 1 --no-power`; traffic = 2 x FETCH_SIZE + WRITE_SIZE (KiB units;
+domains) over `python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-power --calib [--precision f16]` and over
+`BIN_AMD_WGRAD_STREAM=0 python bench.py --full --mode train --batch 8 --steps 1 --warmup 1 --no-power`; traffic = 2 x FETCH_SIZE + WRITE_SIZE (KiB units;
 FETCH_SIZE counts half of the bytes of wide streaming reads on gfx950 — checked in the same run on the three 256 MiB device copies `--calib`
 adds).  `bench.py` reads `{R}_pmc_traffic.json` for `roofline.traffic` (the entry of the precision it timed; `roofline.traffic_source` names the
 file) and for `train.roofline.dominant_kernel.traffic` (`wgrad3x3`).  Written by `tools/assemble_profiles.py`.

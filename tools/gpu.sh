@@ -72,7 +72,7 @@ for step in "$@"; do
       for rep in 1 2 3; do for v in product side; do
         if [ $v = product ]; then unset BIN_AMD_LIB; else export BIN_AMD_LIB=$side; fi
         echo -n "$v $rep: "
-        timeout 400 python bench.py --no-cpu-baseline --no-extras --steps 20 "$@" 2>&1 | tail -1 | grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*\|"avg_kernel_us": [0-9.]*' | head -3 | tr '\n' ' '; echo
+        timeout 400 python bench.py --full --no-cpu-baseline --no-extras --steps 20 "$@" 2>&1 | tail -1 | grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*\|"avg_kernel_us": [0-9.]*' | head -3 | tr '\n' ' '; echo
       done; done 2>&1 | tee -a gpurun_out/${TAG}_ab.log
       unset BIN_AMD_LIB ;;
     kt)
