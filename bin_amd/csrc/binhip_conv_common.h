@@ -313,17 +313,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, const float* _
 #pragma unroll
                                     for (int j = 0; j < 4; ++j) v[j] += (float)xrl[g][j];
                                 }
-                                if (a.relu) {
-#pragma unroll
-                                    for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-                                }
-                                if (kind == 2) {
+                                if (kind == 2) {      // (the mask and the ReLU commute: the ReLU rides on the clamp below)
 #pragma unroll
                                     for (int j = 0; j < 4; ++j) v[j] = ((float)xm[g][j] > 0.f) ? v[j] : 0.f;
                                 }
                                 if (ge == kg) o_slot = o - 4 * kg;
-                                split_pair(v[0], v[1], sat, hv[ge].u[0], lv[ge].u[0]);
-                                split_pair(v[2], v[3], sat, hv[ge].u[1], lv[ge].u[1]);
+                                split_pair(v[0], v[1], sat, hv[ge].u[0], lv[ge].u[0], a.relu);
+                                split_pair(v[2], v[3], sat, hv[ge].u[1], lv[ge].u[1], a.relu);
                             }
 #pragma unroll
                             for (int k = 0; k < 2; ++k) {
@@ -494,12 +490,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, const float* _
                                         }
                                     }
                                 }
-                                if constexpr (X) {               // (without extras the ReLU rides on split_pair's clamp)
-                                    if (a.relu) {
-#pragma unroll
-                                        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-                                    }
-                                }
+                                // the ReLU rides on split_pair's clamp (an fmaxf here would turn a NaN into 0 unflagged); it
+                                // commutes with the mask, which only ever selects v or 0
                                 if constexpr (X) {
                                     if (use_m && och >= a.mask_from && live) {
 #pragma unroll
@@ -510,7 +502,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, const float* _
                             // after the swap, lanes 0-31 own slot 0 (g even) and lanes 32-63 slot 1 (g odd) of pixel n:
                             // the slot start is this (g, kg=0) element offset
                             if (ge == kg) o_slot = o - 4 * kg;
-                            const bool fold_relu = !X && a.relu && (EPI != BINHIP_EPI_SHUFFLE);
+                            const bool fold_relu = a.relu && (EPI != BINHIP_EPI_SHUFFLE);
                             split_pair(v[0], v[1], sat, hv[ge].u[0], lv[ge].u[0], fold_relu);
                             split_pair(v[2], v[3], sat, hv[ge].u[1], lv[ge].u[1], fold_relu);
                         }

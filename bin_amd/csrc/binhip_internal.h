@@ -19,26 +19,29 @@ __device__ static inline int bh_chunks_dev(int C) { return (C + 15) / 16; }
 
 // fp16 storage range.  The reference computes in fp32 (RDN.py:141, no AMP), so a value beyond +-65504 is legal there;
 // here it cannot be stored in an fp16 hi plane.  Rather than let hi = inf, lo = -inf poison every later layer with NaN,
-// the epilogue saturates hi to +-65504 (lo then carries what it can of the rest) and raises bit 0 of the status word,
-// which the host checks (bin_amd/ops.py: RuntimeError "fp16 range exceeded").  Documented in include/binhip.h.
+// every plane store saturates: hi = +-65504 and lo = 0, so hi + lo is the clamped value; a NaN stores as the lower clamp
+// bound (-65504, or 0 on a ReLU layer) with lo = 0.  Either raises bit 0 of the status word, which the host checks
+// (bin_amd/ops.py: RuntimeError "fp16 range exceeded").  A NaN raises it on every path, ReLU layers included; a ReLU
+// negative or a masked gradient is stored as 0 and is not a saturation.  Documented in include/binhip.h.
 #define BINHIP_F16_MAX 65504.0f
 #define BINHIP_FLAG_SATURATED 1u
 
-// returns hi; sat |= (v left the range or is NaN).  The test is ONE integer compare on the magnitude bits (NaN and inf
-// patterns are above 65504's), OR-ed without short-circuit: a `sat = sat || ...` chain made hipcc keep every converted
-// value of the epilogue live (+86 VGPRs on the multi-tile kernels, one wave per SIMD less: GFF.0 253 -> 352 us)
+// returns hi; sat |= (v left the range or is NaN).  The test is ONE float compare on |v| that is true for NaN
+// (!(|v| <= 65504): the abs rides on the compare as a source modifier), OR-ed without short-circuit: a `sat = sat || ...`
+// chain made hipcc keep every converted value of the epilogue live (+86 VGPRs on the multi-tile kernels, one wave per SIMD
+// less: GFF.0 253 -> 352 us)
 __device__ __forceinline__ _Float16 split_hi(float v, unsigned& sat) {
-    sat |= ((__float_as_uint(v) & 0x7fffffffu) > 0x477fe000u) ? 1u : 0u;
+    sat |= !(fabsf(v) <= BINHIP_F16_MAX) ? 1u : 0u;
     // v_med3_f32 directly (round 4): fminf(fmaxf()) costs a canonicalising v_max per call on top of the med3 — two of the ~12 VALU
     // instructions per stored value, in epilogues that are instruction-issue-bound (GFF.0 backward-data: 3 583 instructions per pixel
     // row and wave for 48 stores).  Same results: in range the median is v; a NaN operand makes v_med3 return min3 = -65504, which is
     // what the fminf / fmaxf chain produced.
     return (_Float16)__builtin_amdgcn_fmed3f(v, -BINHIP_F16_MAX, BINHIP_F16_MAX);
 }
-// lo = v - hi, itself kept inside the fp16 range: in range it is |lo| <= ulp(hi)/2 and the clamp is the identity; after
-// a saturated hi the excess can be anything (or NaN), and an unclamped conversion would store inf / NaN after all
+// lo = clamp(v) - hi: in range it is v - hi (|lo| <= ulp(hi)/2, the clamp is the identity); after a saturated hi (or a NaN)
+// it is 0, the rule of split_pair below.  (The clamp is split_hi's own v_med3: the compiler shares it.)
 __device__ __forceinline__ _Float16 split_lo(float v, _Float16 hi) {
-    return (_Float16)__builtin_amdgcn_fmed3f(v - (float)hi, -BINHIP_F16_MAX, BINHIP_F16_MAX);
+    return (_Float16)(__builtin_amdgcn_fmed3f(v, -BINHIP_F16_MAX, BINHIP_F16_MAX) - (float)hi);
 }
 
 // Two values at once, packed (round 6).  The epilogues are VALU-bound — ~12 instructions per stored value, 192 values per lane in the
@@ -46,16 +49,16 @@ __device__ __forceinline__ _Float16 split_lo(float v, _Float16 hi) {
 // back, subtract, clamp, convert, pack.  Here: one v_med3 per value (the clamp of hi ALSO bounds lo: |vc - hi| <= 32), one
 // v_cvt_pk_f16_f32 per pair, and lo = vc - hi as ONE v_fma_mix{lo,hi}_f16 per value — an fp32 fma of (f16 hi) * -1.0 + vc whose exact
 // result is rounded once to f16, straight into its half of the packed dword: the same bits as the subtract-then-convert form for every
-// in-range value (tests/test_gpu_conv.py::test_packed_split_equals_the_scalar_split).  A saturated or NaN value gives lo = 0 instead of a
-// clamped remainder; such outputs raise at the host either way.
+// in-range value (tests/test_gpu_conv.py::test_packed_split_equals_the_scalar_split).  A saturated or NaN value gives lo = 0, as
+// split_lo does.
 // RELU (wave-uniform): the layer's ReLU rides on the clamp — the lower bound of the v_med3 becomes 0 (fmaxf costs a canonicalising
-// v_max on top of the v_max itself) — and a large NEGATIVE value is then not a saturation: the range test keeps the sign bit and
-// compares signed.
+// v_max on top of the v_max itself, and drops a NaN) — and a large NEGATIVE value is then not a saturation: the range test keeps the
+// sign bit, !(v <= 65504) instead of !(|v| <= 65504).  Both forms are true for a NaN of either sign (tests/test_gpu_fp16_range.py).
 __device__ __forceinline__ void split_pair(float a, float b, unsigned& sat, unsigned& hi2, unsigned& lo2, bool relu = false) {
     const unsigned smask = relu ? 0xffffffffu : 0x7fffffffu;
     const float lb = relu ? 0.f : -BINHIP_F16_MAX;
-    sat |= ((int)(__float_as_uint(a) & smask) > 0x477fe000) ? 1u : 0u;
-    sat |= ((int)(__float_as_uint(b) & smask) > 0x477fe000) ? 1u : 0u;
+    sat |= !(__uint_as_float(__float_as_uint(a) & smask) <= BINHIP_F16_MAX) ? 1u : 0u;
+    sat |= !(__uint_as_float(__float_as_uint(b) & smask) <= BINHIP_F16_MAX) ? 1u : 0u;
     const float ac = __builtin_amdgcn_fmed3f(a, lb, BINHIP_F16_MAX);
     const float bc = __builtin_amdgcn_fmed3f(b, lb, BINHIP_F16_MAX);
     unsigned h, l;

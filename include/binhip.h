@@ -19,10 +19,18 @@
  *   - nterms: 1 = fp16-input MFMA, fp32 accumulate (whole-net max-abs error ~3e-4 vs fp32);
  *             3 = fp16 hi/lo split, three MFMA products (error ~1e-6, fp32 class).
  *   - Dynamic range.  The reference computes in fp32 (RDN.py:141, no AMP); here every value stored
- *     between layers must fit the fp16 hi plane: |v| <= 65504.  Kernels SATURATE hi to +-65504
- *     (never inf/NaN from overflow; lo keeps what it can of the excess) and OR BINHIP_STATUS_SATURATED
- *     into the caller's device status word (`status`, may be NULL = not reported), so results that
- *     left the range are detectable instead of silently wrong; a NaN input raises the same bit.
+ *     between layers must fit the fp16 hi plane: |v| <= 65504.  Every plane store (packers, conv
+ *     epilogues, the fused dense-block tail, backward-data and gradient glue) SATURATES: a value
+ *     beyond +-65504 or +-inf stores hi = +-65504 and lo = 0, so hi + lo is the clamped value; a NaN
+ *     of either sign stores hi = -65504 (0 on a ReLU layer) and lo = 0.  Never inf/NaN.  Either case
+ *     ORs BINHIP_STATUS_SATURATED into the caller's device status word (`status`, may be NULL = not
+ *     reported), so results that left the range are detectable instead of silently wrong.  NaN raises
+ *     the bit on every path, ReLU layers included.  Not a saturation, and stored as 0 with the bit
+ *     clear, as the reference computes them: a ReLU of a value below -65504 (or -inf), and a gradient
+ *     behind a saved activation <= 0 (inf or NaN included).  FINAL outputs (BINHIP_EPI_FINAL*) are
+ *     fp32 and not clamped: 1e30, inf and NaN come out as computed, without the bit.  Weights outside
+ *     the fp16 range are NOT detected: binhip_weights_relayout* convert them without a clamp and have
+ *     no status word (a weight beyond 65504 becomes inf in its hi plane).
  *     Small magnitudes: nterms = 3 represents |v| >= 2^-24 * 2^-11 relative steps down to the fp16
  *     subnormal floor 6e-8 (absolute error <= 3e-8 per stored value); nterms = 1 flushes nothing but
  *     rounds to 11 bits, absolute error <= 3e-8 below 6.1e-5.  Backward gradient planes carry a

@@ -807,3 +807,78 @@ def test_rdn_config_case_table_keeps_its_coverage():
         check_shape(s)
         assert (H // 2) % 16 and (W // 2) % 32, "frames must leave partial 16 x 32 tiles at half resolution"
     assert {r for _, r, _, _ in BWD_DATA_OPS.values()} == {224, 256, 1152}
+
+
+def _saturating_sites():
+    """{(file, function): {kind: count}} of every split_hi( / split_pair( / atomicOr(..., BINHIP_FLAG_SATURATED) call in bin_amd/csrc/
+    (definitions excluded), attributed to the function that encloses it: the nearest line above that starts in column 0 with a name
+    followed by '(' (attribute and builtin names skipped)."""
+    csrc = os.path.join(REPO, "bin_amd", "csrc")
+    pats = {"split_hi": re.compile(r"\bsplit_hi\("), "split_pair": re.compile(r"\bsplit_pair\("),
+            "atomicOr": re.compile(r"\batomicOr\([^;]*BINHIP_FLAG_SATURATED")}
+    found = {}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        lines = open(os.path.join(csrc, f)).read().split("\n")
+        for i, line in enumerate(lines):
+            code = line.split("//")[0]
+            for kind, p in pats.items():
+                for _ in p.finditer(code):
+                    if re.match(r"^__device__", line):       # the helper's own definition
+                        continue
+                    fn = None
+                    for j in range(i, -1, -1):
+                        if re.match(r"^[A-Za-z_]", lines[j]):
+                            names = [n for n in re.findall(r"(\w+)\s*\(", lines[j].split("//")[0])
+                                     if not n.startswith("__") and n not in ("amdgpu_waves_per_eu",)]
+                            if names:
+                                fn = names[0]
+                                break
+                    key = (f, fn)
+                    found.setdefault(key, {}).setdefault(kind, 0)
+                    found[key][kind] += 1
+    return found
+
+
+def test_range_case_table_accounts_for_every_saturating_store():
+    """tests/range_cases.py names every store path of the fp16 range contract: the saturating calls per (file, function) in the sources
+    are exactly those its SITES list, every site is reached by cases that exist, every case reaches a site (or is the fp32 contrast
+    case), every path that runs in both precision modes carries both, and the table holds the conv tile variants, backward-data
+    variants, tail placements and whole-network cases the GPU suite relies on.  A new store path, or a case dropped from the table,
+    fails here."""
+    from range_cases import CASES, FP32_CASES, SITES
+    found = _saturating_sites()
+    listed = {k: {kind: n for kind, n in v.items() if kind != "cases"} for k, v in SITES.items()}
+    assert found == listed, f"saturating stores in bin_amd/csrc/ {found} != range_cases.SITES {listed}"
+    reached = set()
+    for site, v in SITES.items():
+        assert v["cases"], f"{site}: no case reaches it"
+        missing = [c for c in v["cases"] if c not in CASES]
+        assert not missing, f"{site}: cases {missing} are not in range_cases.CASES"
+        reached.update(v["cases"])
+    missing = [c for c in FP32_CASES if c not in CASES]
+    assert not missing, f"fp32 contrast cases {missing} are not in range_cases.CASES"
+    assert reached | set(FP32_CASES) == set(CASES), f"cases that reach no store site: {set(CASES) - reached - set(FP32_CASES)}"
+    modes = {}
+    for cid, c in CASES.items():
+        assert set(c["nterms"]) <= {1, 3} and c["entry"].startswith("binhip_") and c["variant"], cid
+        modes.setdefault(c.get("path", cid), set()).update(c["nterms"])
+    assert all(m == {1, 3} for m in modes.values()), {p: m for p, m in modes.items() if m != {1, 3}}
+    # what the GPU suite relies on, pinned independently of the table's own bookkeeping
+    conv = {(c["ks"], c["cout_pad"], c["relu"], c["residual"]) for c in CASES.values() if c["kind"] == "conv_fwd"}
+    want = {(ks, cp, relu, False) for ks in (1, 3) for cp in (32, 96, 224, 256) for relu in (0, 1)}
+    want |= {(5, cp, relu, False) for cp in (32, 96) for relu in (0, 1)} | {(3, 64, 1, False)}
+    want |= {(ks, 96, relu, True) for ks in (1, 3) for relu in (0, 1)}
+    assert conv == want, (conv ^ want)
+    bwd = {(c["res"], c["acc"], c["mask"], c["y_unshuf"], c["lffd"], c["nterms"]) for c in CASES.values() if c["kind"] == "bwd_data"}
+    assert bwd == {(False, False, False, False, False, (3, 1)), (True, False, False, False, False, (3, 1)),
+                   (False, True, False, False, False, (3, 1)), (True, False, True, False, False, (3, 1)),
+                   (False, False, False, True, False, (3, 1)), (True, False, True, False, True, (3,)),
+                   (True, False, True, False, True, (1,))}, bwd
+    assert {(c["store_o3"], c["where"]) for c in CASES.values() if c["kind"] == "rdb_tail"} == {(s, w) for s in (0, 1) for w in ("o3", "y")}
+    assert {(c["scale"] is None) for c in CASES.values() if c["kind"] == "nchw"} == {True, False}
+    assert {c["frames"] for c in CASES.values() if c["kind"] == "pack"} == {2, 3, 5}
+    kinds = [c["kind"] for c in CASES.values()]
+    for k in ("conv_shuffle", "conv_final", "rdn_fwd", "rdn_bwd", "glue", "status_null"):
+        assert kinds.count(k) == 1, k
