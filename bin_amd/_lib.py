@@ -68,6 +68,7 @@ class BinRelayoutItem(C.Structure):
 
 
 RELAYOUT_FWD, RELAYOUT_DGRAD, RELAYOUT_RDB_GATHER = 0, 1, 2
+SCORE_SSIM_G11, SCORE_SSIM_U7 = 1, 2   # BINHIP_SCORE_SSIM_* flags of binhip_image_score
 
 _SIGNATURES = {
     "binhip_version": (C.c_int, []),
@@ -144,6 +145,9 @@ _SIGNATURES = {
     "binhip_rdn_backward_workspace_layout": (C.c_int, [C.c_int] * 5 + [C.POINTER(BinRdnShape), C.POINTER(C.c_int64), C.c_int]),
     "binhip_rdn_forward": (C.c_int, [C.POINTER(BinRdnPlan), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
+    "binhip_image_score_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "binhip_image_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED

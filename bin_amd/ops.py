@@ -518,3 +518,46 @@ def pixel_unshuffle(x, r=2):
     y = torch.empty((n, c * r * r, h // r, w // r), dtype=torch.float32, device=x.device)
     L.check(L.lib().binhip_pixel_unshuffle_f32(_ptr(x), n, c, h, w, r, _ptr(y), _stream()), "pixel_unshuffle")
     return y
+
+
+# --------------------------------------------------------------------------------------------- evaluation metrics
+_G11_TAPS = None
+
+
+def image_scores(a_u8, b_u8, ssim=True):
+    """Scores of image pairs on the device (binhip_image_score; test.py:404-456, utils/util.py:201-251).  `a_u8`, `b_u8`: uint8
+    [H,W,3] or [n,H,W,3] device tensors (HWC, either channel order).  Returns a float64 device tensor [n,4] of
+    (sse, sad, ssim_g11, ssim_u7) per pair, launched on the current stream without a host sync: sse and sad are exact sums
+    (below 2^53, so float64 holds them exactly), ssim_g11 is util.calculate_ssim's SSIM, ssim_u7 the reference test.py's
+    (util.compare_ssim).  `ssim=False` computes only the sums; an SSIM the image is too small for is NaN (ssim_g11 below
+    11 x 11, as numpy's mean of an empty map), and below 7 x 7 an SSIM request raises.  util.score_row turns a row into
+    {psnr, mae, ssim, ssim_sk}."""
+    global _G11_TAPS
+    _need_cuda(a_u8, b_u8)
+    if a_u8.dtype != torch.uint8 or b_u8.dtype != torch.uint8 or a_u8.shape != b_u8.shape:
+        raise ValueError("image_scores: two uint8 tensors of one shape")
+    a = a_u8.unsqueeze(0) if a_u8.dim() == 3 else a_u8
+    b = b_u8.unsqueeze(0) if b_u8.dim() == 3 else b_u8
+    if a.dim() != 4 or a.shape[3] != 3:
+        raise ValueError(f"image_scores: [H,W,3] or [n,H,W,3] images, got {tuple(a_u8.shape)}")
+    a, b = a.contiguous(), b.contiguous()
+    n, h, w, _ = a.shape
+    flags = 0
+    if ssim:
+        flags = L.SCORE_SSIM_U7 | (L.SCORE_SSIM_G11 if min(h, w) >= 11 else 0)
+    if _G11_TAPS is None:
+        from .utils.util import _gauss_taps
+        _G11_TAPS = (C.c_double * 11)(*[float(v) for v in _gauss_taps()])
+    lib = L.lib()
+    with on_device(a):
+        nb = lib.binhip_image_score_workspace_bytes(n, h, w, flags)
+        if nb == 0:
+            raise RuntimeError(f"bin_amd: image_scores: unsupported shape {tuple(a.shape)} (SSIM needs 7 x 7 pixels)")
+        ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
+        raw = torch.empty((n, 4), dtype=torch.int64, device=a.device)          # BinImageScore {int64 sse, sad; double g11, u7}
+        L.check(lib.binhip_image_score(_ptr(a), _ptr(b), n, h, w, flags, _G11_TAPS, _ptr(ws), nb, _ptr(raw), _stream()),
+                "image_score")
+        out = torch.empty((n, 4), dtype=torch.float64, device=a.device)
+        out[:, :2] = raw[:, :2]
+        out[:, 2:] = raw[:, 2:].view(torch.float64)
+    return out

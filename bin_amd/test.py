@@ -35,7 +35,8 @@ from .utils import dist_util, util
 from .utils.util import AverageMeter
 
 OUT_KEYS = (13, 8, 12)         # interpolated, first deblurred, second deblurred (test.py:380-382)
-METRICS = ("interp_psnr", "interp_ssim", "interp_err", "deblur_psnr", "deblur_ssim", "blurry_psnr", "blurry_ssim")
+METRICS = ("interp_psnr", "interp_ssim", "interp_err", "deblur_psnr", "deblur_ssim", "blurry_psnr", "blurry_ssim",
+           "interp_ssim_sk", "deblur_ssim_sk", "blurry_ssim_sk")      # *_sk: test.py's SSIM (util.compare_ssim), --metrics device
 
 
 def parse_args(argv=None):
@@ -57,7 +58,10 @@ def parse_args(argv=None):
                    "RCCL on a GPU box; gloo lets several ranks share one device)")
     p.add_argument("--manifest", action="store_true", help="each rank also writes written.rank<R>.txt under the result "
                    "folder: the files IT saved (shard-ownership audit)")
-    p.add_argument("--ssim", action="store_true", help="also compute SSIM (host, ~0.2 s per 720p frame)")
+    p.add_argument("--ssim", action="store_true", help="--metrics host: also compute SSIM (numpy, seconds per 720p frame)")
+    p.add_argument("--metrics", choices=["host", "device"], default="host",
+                   help="where the scores are computed: host = numpy, as before; device = binhip_image_score on a stream of the "
+                   "writer thread, PSNR bit-identical, SSIM always on, plus the *_ssim_sk keys (test.py's skimage SSIM)")
     return p.parse_args(argv)
 
 
@@ -78,29 +82,74 @@ def output_names(frames, index):
 
 
 class _Sums:
-    """Thread-safe per-clip / total metric accumulators."""
+    """Thread-safe per-clip / total metric accumulators.  Values are kept per scored image (`tag`: its file name) and summed in
+    name order, so the sums do not depend on the order in which the writer threads finish."""
 
     def __init__(self):
         self.lock = threading.Lock()
-        self.total = {k: [0.0, 0] for k in METRICS}
-        self.clips = {}
+        self.values = {}                              # (clip, key) -> {tag: value}
 
-    def add(self, clip, key, value):
+    def add(self, clip, key, value, tag):
         with self.lock:
-            for d in (self.total, self.clips.setdefault(clip, {k: [0.0, 0] for k in METRICS})):
-                d[key][0] += float(value)
-                d[key][1] += 1
+            self.values.setdefault((clip, key), {})[tag] = float(value)
+
+    def _sum(self, clips):
+        out = {k: [0.0, 0] for k in METRICS}
+        for (clip, key), d in sorted(self.values.items()):
+            if clip in clips:
+                for _, v in sorted(d.items()):
+                    out[key][0] += v
+                    out[key][1] += 1
+        return out
+
+    @property
+    def total(self):
+        return self._sum({c for c, _ in self.values})
+
+    @property
+    def clips(self):
+        return {c: self._sum({c}) for c in sorted({c for c, _ in self.values})}
 
 
-def _score(sums, clip, kind, img_bgr, gt_path, want_ssim):
+def _score(sums, clip, kind, img_bgr, gt_path, want_ssim, tag):
     if gt_path is None or not os.path.exists(gt_path):
         return
     gt = data_util.imread_u8(gt_path)[:, :, :3]
-    sums.add(clip, kind + "_psnr", util.calculate_psnr(img_bgr, gt))
+    sums.add(clip, kind + "_psnr", util.calculate_psnr(img_bgr, gt), tag)
     if kind == "interp":
-        sums.add(clip, "interp_err", np.mean(np.abs(img_bgr.astype(np.float64) - gt.astype(np.float64))))
+        sums.add(clip, "interp_err", np.mean(np.abs(img_bgr.astype(np.float64) - gt.astype(np.float64))), tag)
     if want_ssim:
-        sums.add(clip, kind + "_ssim", util.calculate_ssim(img_bgr, gt))
+        sums.add(clip, kind + "_ssim", util.calculate_ssim(img_bgr, gt), tag)
+
+
+class _DeviceScorer:
+    """--metrics device: scores an image against its GT with ops.image_scores on a stream of the calling writer thread (one per
+    thread), never on the network's stream.  The GT is decoded on the thread as before; both images are uploaded from host
+    memory on that stream and 32 bytes per image come back."""
+
+    def __init__(self, dev):
+        self.dev, self.local = dev, threading.local()
+
+    def __call__(self, sums, clip, kind, img_bgr, gt_path, tag):
+        if gt_path is None or not os.path.exists(gt_path):
+            return
+        gt = data_util.imread_u8(gt_path)[:, :, :3]
+        if gt.shape != img_bgr.shape:
+            raise ValueError(f"{gt_path}: GT shape {gt.shape} != output shape {img_bgr.shape}")
+        with torch.cuda.device(self.dev):
+            stream = getattr(self.local, "stream", None)
+            if stream is None:
+                stream = self.local.stream = torch.cuda.Stream(device=self.dev)
+            with torch.cuda.stream(stream):
+                a = torch.from_numpy(np.ascontiguousarray(img_bgr)).to(self.dev, non_blocking=True)
+                b = torch.from_numpy(np.ascontiguousarray(gt)).to(self.dev, non_blocking=True)
+                row = ops.image_scores(a, b).cpu().numpy()[0]
+        r = util.score_row(row, img_bgr.size)
+        sums.add(clip, kind + "_psnr", r["psnr"], tag)
+        if kind == "interp":
+            sums.add(clip, "interp_err", r["mae"], tag)
+        sums.add(clip, kind + "_ssim", r["ssim"], tag)
+        sums.add(clip, kind + "_ssim_sk", r["ssim_sk"], tag)
 
 
 def main(argv=None, stats=None):
@@ -189,6 +238,13 @@ def main(argv=None, stats=None):
              opt["path"]["pretrain_model_G"], sum(p.numel() for p in netG.parameters() if p.requires_grad), world, reuse)
 
     sums = _Sums()
+    device_score = _DeviceScorer(dev) if args.metrics == "device" else None
+
+    def score(clip, kind, img_bgr, gt_path, tag):
+        if device_score is not None:
+            device_score(sums, clip, kind, img_bgr, gt_path, tag)
+        else:
+            _score(sums, clip, kind, img_bgr, gt_path, args.ssim, tag)
     copy_stream = torch.cuda.Stream(device=dev)
     decoded, frames_dev, stage1_cache, pending = {}, {}, {}, []
     geom = None                                        # (h, w, pads) of the current clip
@@ -253,10 +309,9 @@ def main(argv=None, stats=None):
             with written_lock:
                 written.append(os.path.join(clip, name))
         if mine or kind == "interp":               # the reference scores a deblurred frame when it writes it
-            _score(sums, clip, kind, img, args.gt_path and os.path.join(args.gt_path, clip, name), args.ssim)
+            score(clip, kind, img, args.gt_path and os.path.join(args.gt_path, clip, name), name)
         if blurry_path is not None and args.gt_path:
-            _score(sums, clip, "blurry", data_util.imread_u8(blurry_path)[:, :, :3],
-                   os.path.join(args.gt_path, clip, name), args.ssim)
+            score(clip, "blurry", data_util.imread_u8(blurry_path)[:, :, :3], os.path.join(args.gt_path, clip, name), name)
 
     written, written_lock = [], threading.Lock()       # files THIS rank saved (--manifest)
     stamps = []                                        # host time at which each window's work had been queued
@@ -361,7 +416,8 @@ def main(argv=None, stats=None):
             f.write("".join(sorted(w + "\n" for w in written)))
 
     # ---- combine the ranks' sums (one small all-reduce) and report like test.py:466-502
-    vec = torch.tensor([v for k in METRICS for v in sums.total[k]] + [end - begin, wall], dtype=torch.float64)
+    total = sums.total
+    vec = torch.tensor([v for k in METRICS for v in total[k]] + [end - begin, wall], dtype=torch.float64)
     if world > 1:
         import torch.distributed as dist
         if dist.get_backend() != "gloo":      # nccl reduces device tensors; gloo takes the host vector as it is
@@ -373,15 +429,18 @@ def main(argv=None, stats=None):
         vec = vec.cpu()
     if rank == 0:
         tot = {k: (vec[2 * i].item() / max(vec[2 * i + 1].item(), 1)) for i, k in enumerate(METRICS)}
+        counted = {k for i, k in enumerate(METRICS) if vec[2 * i + 1].item() > 0}
         n_win, wall = int(vec[-2].item()), vec[-1].item()
         if world == 1:
             for clip, d in sums.clips.items():
                 log.info("clip %s: " % clip + " ".join(f"{k} {d[k][0] / max(d[k][1], 1):.4f}" for k in METRICS if d[k][1]))
-        log.info("Avg. testset " + " ".join(f"{k} {tot[k]:.4f}" for k in METRICS))
+        # the keys of the host scores are always listed (as the reference does); the *_sk keys only when they were scored
+        log.info("Avg. testset " + " ".join(f"{k} {tot[k]:.4f}" for k in METRICS if k in counted or not k.endswith("_sk")))
         log.info("windows: %d  wall: %.2f s  -> %.2f interpolated frames/s (IO included); net+glue per window %.4f s",
                  n_win, wall, n_win / max(wall, 1e-9), timer.avg)
         if stats is not None:
-            stats.update(windows=n_win, wall=wall, net_s_per_window=timer.avg, stamps=[t - t_all for t in stamps], timeline=timeline)
+            stats.update(windows=n_win, wall=wall, net_s_per_window=timer.avg, stamps=[t - t_all for t in stamps], timeline=timeline,
+                         metrics={k: tot[k] for k in METRICS if k in counted})
     return 0
 
 

@@ -43,15 +43,26 @@ def tensor2img(tensor, out_type=np.uint8, min_max=(0, 1)):
 def calculate_psnr(img1, img2):
     """reference utils/util.py:201-208 (inputs in [0,255])."""
     mse = np.mean((img1.astype(np.float64) - img2.astype(np.float64)) ** 2)
+    return psnr_from_mse(mse)
+
+
+def psnr_from_mse(mse):
+    """The PSNR expression of calculate_psnr (inf at mse 0); shared with the device scores (score_row)."""
     if mse == 0:
         return float("inf")
     return 20 * math.log10(255.0 / math.sqrt(mse))
 
 
-def _gauss_window(size=11, sigma=1.5):
+def _gauss_taps(size=11, sigma=1.5):
+    """The 1-D Gaussian of calculate_ssim's window; the device SSIM (binhip_image_score) applies these same taps separably."""
     ax = np.arange(size, dtype=np.float64) - (size - 1) / 2.0
     k = np.exp(-(ax ** 2) / (2 * sigma ** 2))
     k /= k.sum()
+    return k
+
+
+def _gauss_window(size=11, sigma=1.5):
+    k = _gauss_taps(size, sigma)
     return np.outer(k, k)
 
 
@@ -86,6 +97,52 @@ def calculate_ssim(img1, img2):
         if img1.shape[2] == 1:
             return ssim(np.squeeze(img1), np.squeeze(img2))
     raise ValueError("Wrong input image dimensions.")
+
+
+def _box7(x):
+    """Exact 7x7 window sums of an integer image at the centres 3 .. H-4 x 3 .. W-4 (summed-area table in int64)."""
+    c = np.zeros((x.shape[0] + 1, x.shape[1] + 1), dtype=np.int64)
+    c[1:, 1:] = np.cumsum(np.cumsum(x.astype(np.int64), 0), 1)
+    return c[7:, 7:] - c[:-7, 7:] - c[7:, :-7] + c[:-7, :-7]
+
+
+def _ssim_u7(x, y):
+    np_ = 49.0
+    cov_norm = np_ / (np_ - 1.0)                     # use_sample_covariance=True
+    x, y = x.astype(np.int64), y.astype(np.int64)
+    ux, uy = _box7(x) / np_, _box7(y) / np_
+    uxx, uyy, uxy = _box7(x * x) / np_, _box7(y * y) / np_, _box7(x * y) / np_
+    vx = cov_norm * (uxx - ux * ux)
+    vy = cov_norm * (uyy - uy * uy)
+    vxy = cov_norm * (uxy - ux * uy)
+    R = 255                                          # data range of uint8
+    C1, C2 = (0.01 * R) ** 2, (0.03 * R) ** 2
+    A1, A2, B1, B2 = 2 * ux * uy + C1, 2 * vxy + C2, ux ** 2 + uy ** 2 + C1, vx + vy + C2
+    return ((A1 * A2) / (B1 * B2)).mean()
+
+
+def compare_ssim(img1, img2):
+    """SSIM as the reference's test.py scores it (test.py:31-36: use_default_ssim = 1 ->
+    skimage.measure.compare_ssim(img1, img2, multichannel=True) on uint8 images), restated in float64 numpy from skimage's
+    documented defaults, since skimage cannot be assumed to be installed to pin it: a 7x7 uniform window, K1 = 0.01,
+    K2 = 0.03, data range 255 (from the dtype), sample covariance (x 49/48), the 3-pixel border cropped from the SSIM map,
+    and for HWC images the mean of the per-channel means.  The window means come from exact integer sums / 49.  Needs
+    neither scipy nor skimage.  Host oracle of the device `ssim_u7` (binhip_image_score)."""
+    img1, img2 = np.asarray(img1), np.asarray(img2)
+    if img1.shape != img2.shape:
+        raise ValueError("Input images must have the same dimensions.")
+    if img1.ndim not in (2, 3) or min(img1.shape[:2]) < 7:
+        raise ValueError("compare_ssim: HW or HWC images of at least 7 x 7 pixels")
+    if img1.ndim == 2:
+        return float(_ssim_u7(img1, img2))
+    return float(np.mean([_ssim_u7(img1[..., c], img2[..., c]) for c in range(img1.shape[2])]))
+
+
+def score_row(row, numel):
+    """One row (sse, sad, ssim_g11, ssim_u7) of ops.image_scores for an image of `numel` values -> {psnr, mae, ssim, ssim_sk}.
+    sse and sad are exact sums, so psnr and mae are the bits calculate_psnr and np.mean(|a - b|) give on the host."""
+    sse, sad, g11, u7 = (float(v) for v in row)
+    return {"psnr": psnr_from_mse(sse / numel), "mae": sad / numel, "ssim": g11, "ssim_sk": u7}
 
 
 def pad_sizes(h, w):

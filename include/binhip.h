@@ -57,8 +57,8 @@ extern "C" {
 /* Interface version = what binhip_version() of a matching library returns (100 x round + revision); a binder checks
  * `binhip_version() == BINHIP_VERSION` after dlopen.  BINHIP_ABI_EXPORTS = number of BINHIP_API entry points below
  * (tests/test_cpu_host.py keeps it equal to the declarations and to `nm -D`). */
-#define BINHIP_VERSION 610
-#define BINHIP_ABI_EXPORTS 45
+#define BINHIP_VERSION 620
+#define BINHIP_ABI_EXPORTS 47
 
 #define BINHIP_E_ARG      (-1)   /* null pointer / bad enum */
 #define BINHIP_E_SHAPE    (-2)   /* unsupported shape */
@@ -418,6 +418,30 @@ BINHIP_API int binhip_rdn_backward_workspace_layout(int N, int H, int W, int n_i
                                          int64_t* out, int n_out);
 BINHIP_API int binhip_rdn_backward(const BinRdnBwdPlan* plan, const void* saved, size_t saved_bytes,
                         const float* gout, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- evaluation metrics (test.py:404-456, utils/util.py:201-251) ------------------------------------
+ * Scores n pairs of images a[i], b[i]: contiguous uint8 [n][H][W][3] (HWC; every metric is per channel, so BGR and RGB
+ * give the same result).  Per pair, out[i] (DEVICE memory, n entries) receives
+ *   sse, sad   sum over H W 3 values of (a - b)^2 and |a - b|: exact (PSNR = 20 log10(255 / sqrt(sse / (H W 3))))
+ *   ssim_g11   utils/util.py calculate_ssim: 11x11 Gaussian window, sigma 1.5, applied separably with the 11 taps
+ *              `g11_taps` (HOST pointer; the caller passes the taps its own oracle uses), mean of the valid
+ *              (H - 10) x (W - 10) map per channel, then the mean of the 3 channels.  fp64
+ *   ssim_u7    skimage compare_ssim(multichannel=True) defaults for uint8, which the reference's test.py uses: 7x7 uniform
+ *              window, K1 0.01, K2 0.03, data range 255, sample covariance (x 49/48), mean over the centres 3 .. H-4 x
+ *              3 .. W-4 per channel, then the mean of the 3 channels.  Window sums exact in int32, the rest fp64
+ * A field whose flag is not set is NaN.  `ws`: binhip_image_score_workspace_bytes() bytes (0 = bad shape or flag): one
+ * partial-sum slot per tile, summed in a fixed order by a second launch, so repeated calls give the same bits.
+ * Errors: BINHIP_E_ARG for a null pointer (g11_taps with BINHIP_SCORE_SSIM_G11 only) or an unknown flag; BINHIP_E_SHAPE for
+ * n, H or W <= 0 or > 65535, H or W < 11 with BINHIP_SCORE_SSIM_G11, < 7 with BINHIP_SCORE_SSIM_U7.                      */
+#define BINHIP_SCORE_SSIM_G11 1
+#define BINHIP_SCORE_SSIM_U7  2
+typedef struct BinImageScore {
+    int64_t sse, sad;
+    double ssim_g11, ssim_u7;
+} BinImageScore;
+BINHIP_API size_t binhip_image_score_workspace_bytes(int n, int H, int W, int flags);
+BINHIP_API int binhip_image_score(const uint8_t* a, const uint8_t* b, int n, int H, int W, int flags, const double* g11_taps,
+                       void* ws, size_t ws_bytes, BinImageScore* out, void* stream);
 
 /* ---- live kernel timing (bench.py roofline leg) --------------------------------------------------
  * An explicit host-side handle: every conv launch of a plan that carries it and whose (ksize,
