@@ -148,6 +148,8 @@ _SIGNATURES = {
     "binhip_image_score_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "binhip_image_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "binhip_gather_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
 }
 
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED

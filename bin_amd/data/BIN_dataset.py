@@ -54,19 +54,29 @@ def make_window_list(root, mode="train", split=100, shuffle=True):
     return windows[:keep], windows[keep:]
 
 
-def load_window(window, input_frame_size=(3, 128, 256), data_aug=True):
-    """Read the 17 frames of one window, with the reference's augmentation draws in its order: temporal order
-    (randint: 1 keeps it, 0 reverses; no aug => reversed, as in the reference), crop offsets (choice, choice),
-    horizontal flip (randint).  Returns ([B1..B11], [I1..I11], [I2..I10], key) as float32 HWC BGR crops."""
-    blurry, sharp, mid, key = window
-    if not (data_aug and random.randint(0, 1)):
-        blurry, sharp, mid = blurry[::-1], sharp[::-1], mid[::-1]
-    frames = [util.read_img(p) for p in list(blurry) + list(sharp) + list(mid)]
+def draw_window_aug(input_frame_size=(3, 128, 256), data_aug=True):
+    """The reference loader's augmentation draws for one window, in its order: temporal order (randint: 1 keeps it, 0
+    reverses; no aug => reversed, as in the reference), crop offsets (choice, choice), horizontal flip (randint).
+    Returns (reversed, y0, x0, flip).  load_window and the device-cache loader (device_cache.py) both draw through here."""
+    reverse = not (data_aug and random.randint(0, 1))
     _, ch, cw = input_frame_size
     y0 = random.choice(range(SRC_H - ch + 1))
     x0 = random.choice(range(SRC_W - cw + 1))
+    flip = bool(data_aug and random.randint(0, 1))
+    return reverse, y0, x0, flip
+
+
+def load_window(window, input_frame_size=(3, 128, 256), data_aug=True):
+    """Read the 17 frames of one window with the draws of draw_window_aug.  Returns ([B1..B11], [I1..I11], [I2..I10], key)
+    as float32 HWC BGR crops."""
+    blurry, sharp, mid, key = window
+    reverse, y0, x0, flip = draw_window_aug(input_frame_size, data_aug)
+    if reverse:
+        blurry, sharp, mid = blurry[::-1], sharp[::-1], mid[::-1]
+    frames = [util.read_img(p) for p in list(blurry) + list(sharp) + list(mid)]
+    _, ch, cw = input_frame_size
     frames = [f[y0:y0 + ch, x0:x0 + cw, :] for f in frames]
-    if data_aug and random.randint(0, 1):
+    if flip:
         frames = [np.fliplr(f) for f in frames]
     return frames[:6], frames[6:12], frames[12:], key
 

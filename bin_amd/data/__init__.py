@@ -26,6 +26,14 @@ def create_dataloader(dataset, dataset_opt, opt=None, sampler=None, vscode_debug
     if dataset_opt["phase"] != "train":
         return tud.DataLoader(dataset, batch_size=1, num_workers=0 if vscode_debug else 1, **common)
     batch, workers = _train_loader_shape(dataset_opt, opt)
+    if dataset_opt.get("device_cache"):
+        # bin_amd extension: batches cut out of a device-resident frame cache (data/device_cache.py); BIN windows only
+        from .BIN_dataset import BINDataset
+        if isinstance(dataset, BINDataset):
+            from .device_cache import create_device_loader
+            return create_device_loader(dataset, dataset_opt, batch, sampler)
+        logging.getLogger("base").warning("device_cache applies to mode BIN datasets only; [%s] uses the host loader",
+                                          type(dataset).__name__)
     return tud.DataLoader(dataset, batch_size=batch, sampler=sampler, drop_last=True,
                           num_workers=0 if vscode_debug else workers, **common)
 

@@ -1,0 +1,160 @@
+"""Training batches assembled on the GPU from a device-resident frame cache (bin_amd extension, opt-in with
+`datasets.train.device_cache: true`).
+
+The host loader (BIN_dataset.load_window) decodes the 17 whole PNGs of every sample, converts them to float32, crops them
+and collates them, and feed_data then copies the batch to the device.  Consecutive windows share most of their frames and
+every epoch revisits all of them.  Here every frame the training list touches is decoded ONCE into one uint8 arena on the
+device (DeviceFrameCache), and each batch is one binhip_gather_windows launch (ops.gather_windows): crop, flip, BGR -> RGB,
+/255 and the layout feed_data consumes.  The augmentation draws are the host loader's own (draw_window_aug), made in its
+order in the main process, so with the same `random` state a batch equals the host loader's batch at n_workers 0 bit for
+bit."""
+import concurrent.futures as cf
+import logging
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from .BIN_dataset import draw_window_aug
+from .util import imread_u8
+
+N_SLOTS = 17                     # 6 blurry + 6 sharp + 5 in-between sharp frames per window
+CHUNK_BYTES = 256 << 20          # host staging per pinned buffer while the arena fills
+
+
+def _frame_shape(path):
+    """(H, W, channels of imread_u8) from the file header, without decoding the pixels."""
+    from PIL import Image
+    with Image.open(path) as im:
+        w, h = im.size
+        return h, w, {"L": 1, "RGBA": 4}.get(im.mode, 3)
+
+
+def _default_threads():
+    return max(1, min(16, os.cpu_count() or 1))
+
+
+def window_slots(window, reverse):
+    """The 17 frame paths of a window in slot order ([B1..B11], [I1..I11], [I2..I10]), each group reversed when the
+    window's temporal order is (as load_window reverses them)."""
+    blurry, sharp, mid, _ = window
+    if reverse:
+        blurry, sharp, mid = blurry[::-1], sharp[::-1], mid[::-1]
+    return list(blurry) + list(sharp) + list(mid)
+
+
+class DeviceFrameCache:
+    """Every unique frame of `window_list` decoded once (imread_u8 on a thread pool) into one uint8 [n_frames, H, W, 3]
+    BGR arena on `device`.  Raises ValueError before allocating anything when the frames differ in size, a frame is not
+    colour (an RGBA frame keeps its first 3 channels, as read_img does), or the arena would exceed `max_gb` (10^9 bytes)."""
+
+    def __init__(self, window_list, device, max_gb=64, threads=None):
+        self.paths, self.index = [], {}
+        for win in window_list:
+            for p in window_slots(win, False):
+                if p not in self.index:
+                    self.index[p] = len(self.paths)
+                    self.paths.append(p)
+        if not self.paths:
+            raise ValueError("DeviceFrameCache: the window list is empty")
+        threads = threads or _default_threads()
+        with cf.ThreadPoolExecutor(threads) as pool:
+            shapes = list(pool.map(_frame_shape, self.paths))
+        h, w, _ = shapes[0]
+        for p, (fh, fw, c) in zip(self.paths, shapes):
+            if (fh, fw) != (h, w):
+                raise ValueError(f"DeviceFrameCache: frames differ in size: {self.paths[0]} is {h}x{w}, {p} is {fh}x{fw}")
+            if c < 3:
+                raise ValueError(f"DeviceFrameCache: {p} has {c} channel(s); the cache holds 3-channel colour frames")
+        self.shape = (len(self.paths), h, w, 3)
+        self.nbytes = len(self.paths) * h * w * 3
+        if self.nbytes > max_gb * 1e9:
+            raise ValueError(f"DeviceFrameCache: {len(self.paths)} frames of {h}x{w}x3 need {self.nbytes / 1e9:.2f} GB ({self.nbytes} bytes), "
+                             f"more than device_cache_max_gb = {max_gb}")
+        self.device = torch.device(device)
+        self.frames = torch.empty(self.shape, dtype=torch.uint8, device=self.device)
+        self._fill(threads)
+
+    def _fill(self, threads):
+        """Decode into two pinned buffers in turn; each chunk's copy to the arena overlaps the next chunk's decoding."""
+        n, h, w, _ = self.shape
+        per = max(1, min(n, CHUNK_BYTES // (h * w * 3)))
+        bufs = [torch.empty((per, h, w, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        done = [None, None]
+
+        def load(arg):
+            buf, j, path = arg
+            buf[j] = imread_u8(path)[:, :, :3]
+
+        with torch.cuda.device(self.device), cf.ThreadPoolExecutor(threads) as pool:
+            for k, start in enumerate(range(0, n, per)):
+                m = min(per, n - start)
+                buf = bufs[k % 2]
+                if done[k % 2] is not None:
+                    done[k % 2].synchronize()              # that buffer's previous copy has landed
+                list(pool.map(load, [(buf.numpy(), j, self.paths[start + j]) for j in range(m)]))
+                self.frames[start:start + m].copy_(buf[:m], non_blocking=True)
+                done[k % 2] = torch.cuda.Event()
+                done[k % 2].record()
+            torch.cuda.current_stream().synchronize()
+
+    def table(self, windows, draws):
+        """window_table of these windows against this arena."""
+        return window_table(windows, draws, self.index)
+
+
+def window_table(windows, draws, index):
+    """int32 [len(windows), 17 + 3] rows of binhip_gather_windows: the arena ids (`index`: path -> id) of each window's frames
+    in slot order, a reversed window's in reverse order, then y0, x0, flip.  `draws`: one (reverse, y0, x0, flip) per window
+    (draw_window_aug)."""
+    rows = np.empty((len(windows), N_SLOTS + 3), dtype=np.int32)
+    for r, (win, (reverse, y0, x0, flip)) in enumerate(zip(windows, draws)):
+        rows[r, :N_SLOTS] = [index[p] for p in window_slots(win, reverse)]
+        rows[r, N_SLOTS:] = (y0, x0, int(flip))
+    return rows
+
+
+class DeviceWindowLoader:
+    """The training DataLoader of a BINDataset, served from a DeviceFrameCache: `len` batches, each a dict
+    {"LQs", "GTenh", "GTinp", "key"} with device tensors [B, 6 | 6 | 5, 3, ch, cw] and the list of window keys.  As the
+    host loader: indices from `sampler` (DistIterSampler) or in order, the ragged last batch dropped, `batch` samples per
+    batch (data._train_loader_shape); the draws are made here, in the main process, in the order the host loader at
+    n_workers 0 makes them."""
+
+    def __init__(self, dataset, batch, sampler=None, device=None, max_gb=64, cache=None):
+        self.dataset, self.batch, self.sampler = dataset, int(batch), sampler
+        self.crop = tuple(dataset.input_frame_size)
+        self.cache = cache or DeviceFrameCache(dataset.all_paths, device, max_gb)
+
+    def __len__(self):
+        n = len(self.sampler) if self.sampler is not None else len(self.dataset)
+        return n // self.batch
+
+    def index_batches(self):
+        """The index lists of the batches, as the host loader's batch sampler yields them (drop_last)."""
+        it = iter(self.sampler) if self.sampler is not None else iter(range(len(self.dataset)))
+        while True:
+            idx = [i for _, i in zip(range(self.batch), it)]
+            if len(idx) < self.batch:
+                return
+            yield idx
+
+    def __iter__(self):
+        _, ch, cw = self.crop
+        for idx in self.index_batches():
+            windows = [self.dataset.all_paths[i] for i in idx]
+            draws = [draw_window_aug(self.crop) for _ in windows]
+            out = ops.gather_windows(self.cache.frames, self.cache.table(windows, draws), (ch, cw))
+            yield {"LQs": out[0:6].transpose(0, 1), "GTenh": out[6:12].transpose(0, 1), "GTinp": out[12:17].transpose(0, 1),
+                   "key": [w[3] for w in windows]}
+
+
+def create_device_loader(dataset, dataset_opt, batch, sampler=None):
+    """DeviceWindowLoader on the current device (each rank's own under torch.distributed)."""
+    device = torch.device("cuda", torch.cuda.current_device())
+    max_gb = dataset_opt.get("device_cache_max_gb") or 64
+    loader = DeviceWindowLoader(dataset, batch, sampler, device, max_gb)
+    logging.getLogger("base").info("Device frame cache: %d frames, %.2f GB on %s", loader.cache.shape[0],
+                                   loader.cache.nbytes / 1e9, device)
+    return loader

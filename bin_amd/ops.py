@@ -561,3 +561,43 @@ def image_scores(a_u8, b_u8, ssim=True):
         out[:, :2] = raw[:, :2]
         out[:, 2:] = raw[:, 2:].view(torch.float64)
     return out
+
+
+# --------------------------------------------------------------------------------------------- training data
+GATHER_MAX_SLOTS = 32        # n_slots limit of binhip_gather_windows
+
+
+def gather_windows(frames_u8, table_host, crop):
+    """Training crops cut out of a device-resident frame arena in one launch (binhip_gather_windows; the reference loader's
+    crop / np.fliplr / BGR -> RGB / read_img's /255 and feed_data's staging, data/BIN_dataset.py, models/bin_model.py).
+    `frames_u8`: uint8 [n_frames, H, W, 3] BGR device tensor; `table_host`: int32 [n, n_slots + 3] on the HOST, per sample the
+    frame ids in slot order then y0, x0, flip; `crop`: (ch, cw).  The table is checked here (the kernel only clamps), uploaded
+    through pinned memory without a host sync and the kernel launched on the current stream.  Returns fp32 [n_slots, n, 3, ch, cw]."""
+    import numpy as np
+    _need_cuda(frames_u8)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise ValueError(f"gather_windows: frames must be a contiguous uint8 [n_frames, H, W, 3] tensor, got "
+                         f"{frames_u8.dtype} {tuple(frames_u8.shape)}")
+    nf, h, w, _ = frames_u8.shape
+    ch, cw = (int(v) for v in crop)
+    tab = np.ascontiguousarray(table_host.numpy() if torch.is_tensor(table_host) else table_host, dtype=np.int32)
+    if tab.ndim != 2 or tab.shape[0] < 1 or not 1 <= tab.shape[1] - 3 <= GATHER_MAX_SLOTS:
+        raise ValueError(f"gather_windows: table must be [n, n_slots + 3] with 1 <= n_slots <= {GATHER_MAX_SLOTS}, "
+                         f"got {tab.shape}")
+    if not (0 < ch <= h and 0 < cw <= w):
+        raise ValueError(f"gather_windows: crop {ch}x{cw} does not fit {h}x{w} frames")
+    n, n_slots = tab.shape[0], tab.shape[1] - 3
+    ids, y0, x0, flip = tab[:, :n_slots], tab[:, n_slots], tab[:, n_slots + 1], tab[:, n_slots + 2]
+    if ids.min() < 0 or ids.max() >= nf:
+        raise ValueError(f"gather_windows: frame id outside [0, {nf})")
+    if y0.min() < 0 or y0.max() > h - ch or x0.min() < 0 or x0.max() > w - cw:
+        raise ValueError(f"gather_windows: crop offset outside the {h}x{w} frame for a {ch}x{cw} crop")
+    if ((flip != 0) & (flip != 1)).any():
+        raise ValueError("gather_windows: flip must be 0 or 1")
+    dev = frames_u8.device
+    with on_device(frames_u8):
+        table = torch.from_numpy(tab).pin_memory().to(dev, non_blocking=True)
+        out = torch.empty((n_slots, n, 3, ch, cw), dtype=torch.float32, device=dev)
+        L.check(L.lib().binhip_gather_windows(_ptr(frames_u8), nf, h, w, _ptr(table), n, n_slots, ch, cw, _ptr(out), _stream()),
+                "gather_windows")
+    return out

@@ -57,8 +57,8 @@ extern "C" {
 /* Interface version = what binhip_version() of a matching library returns (100 x round + revision); a binder checks
  * `binhip_version() == BINHIP_VERSION` after dlopen.  BINHIP_ABI_EXPORTS = number of BINHIP_API entry points below
  * (tests/test_cpu_host.py keeps it equal to the declarations and to `nm -D`). */
-#define BINHIP_VERSION 620
-#define BINHIP_ABI_EXPORTS 47
+#define BINHIP_VERSION 621
+#define BINHIP_ABI_EXPORTS 48
 
 #define BINHIP_E_ARG      (-1)   /* null pointer / bad enum */
 #define BINHIP_E_SHAPE    (-2)   /* unsupported shape */
@@ -442,6 +442,24 @@ typedef struct BinImageScore {
 BINHIP_API size_t binhip_image_score_workspace_bytes(int n, int H, int W, int flags);
 BINHIP_API int binhip_image_score(const uint8_t* a, const uint8_t* b, int n, int H, int W, int flags, const double* g11_taps,
                        void* ws, size_t ws_bytes, BinImageScore* out, void* stream);
+
+/* ---- training batches from a device-resident frame arena (data/BIN_dataset.py:30-54, 63-183, models/bin_model.py:147-202)
+ * The reference's loader reads the 17 frames of a window (6 blurry, 6 sharp, 5 in-between sharp), crops one (y0, x0) window
+ * of ch x cw from each, flips it horizontally or not, converts to fp32 RGB CHW / 255, and feed_data stages the batch on the
+ * device.  This call does all of that for n windows in one launch:
+ *   frames  uint8 [n_frames][H][W][3] BGR (HWC, what the loader's imread gives)
+ *   table   int32 [n][n_slots + 3] (DEVICE memory): per sample the frame ids in slot order (a temporally reversed window
+ *           is just its ids in reverse order), then y0, x0 and flip (0 / non-zero)
+ *   out     fp32 slot-major [n_slots][n][3][ch][cw]:
+ *           out[s][b][c][y][x] = (float)frames[id][y0 + y][flip ? x0 + cw - 1 - x : x0 + x][2 - c] / 255.f
+ *           with id = table[b][s] — read_img's astype(float32) / 255. (correctly rounded), crop, np.fliplr, BGR -> RGB, CHW,
+ *           bit for bit.
+ * Errors: BINHIP_E_ARG for a null pointer; BINHIP_E_SHAPE for n_frames, H, W, n, ch or cw <= 0, n_slots outside 1 .. 32, a
+ * crop larger than the frame (ch > H or cw > W) or more than 2^31 - 1 four-pixel output quads.  The table lives on the device
+ * and is not checked here (the caller validates it on the host); the kernel clamps every id to [0, n_frames), y0 to
+ * [0, H - ch] and x0 to [0, W - cw], so a bad row can never read outside the arena.                                        */
+BINHIP_API int binhip_gather_windows(const uint8_t* frames, int n_frames, int H, int W, const int32_t* table, int n, int n_slots,
+                          int ch, int cw, float* out, void* stream);
 
 /* ---- live kernel timing (bench.py roofline leg) --------------------------------------------------
  * An explicit host-side handle: every conv launch of a plan that carries it and whose (ksize,

@@ -1,0 +1,188 @@
+"""Training fed from the Adobe folder layout: host loader vs device frame cache (bin_amd/data/device_cache.py).
+
+Generates a synthetic Adobe tree of 352x640 PNG frames (tests/host_fixtures.make_adobe_tree) under a temporary directory and
+reports, as one JSON line:
+  host_loader      ms per batch of create_dataloader at n_workers 3 and 16: consumed and discarded, then with feed_data
+  device_loader    ms per batch of the device-cache loader (table, upload, one gather launch, synchronised)
+  train_step       optimize_parameters ms per step (f16x3, 8 x 256^2) fed by each loader and by a resident batch
+                   (--warmup steps, then --steps timed ones, each synchronised)
+  cache            build seconds and arena bytes
+  gather_kernel    device time per gather launch from events around --kernel-launches back-to-back launches, against
+                   the HBM bound (3 B read + 12 B written per output pixel at 6.3 TB/s)
+
+    python tools/bench_train_data.py                      # everything
+    python tools/bench_train_data.py --only kernel        # cache + gather launches only (for rocprofv3 --kernel-trace --stats)
+"""
+import argparse
+import json
+import os
+import random
+import shutil
+import sys
+import tempfile
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+HBM_BYTES_PER_S = 6.3e12
+CROP = 256
+
+
+def make_tree(root, clips, n_blur):
+    from host_fixtures import make_adobe_tree
+    # a clip of n blurry frames gives n - 5 windows (the first clip's list omits its last frame: one fewer)
+    spec = tuple((f"clip{c:02d}", 8 * c, n_blur) for c in range(clips))
+    return make_adobe_tree(root, clips=spec, hw=(352, 640))
+
+
+def dataset(root):
+    from bin_amd.data import create_dataset
+    random.seed(0)
+    return create_dataset({"mode": "BIN", "name": "train", "dataroot_GT": root, "dataroot_LQ": root,
+                           "LQ_size": [3, CROP, CROP], "data_type": "img", "phase": "train"})
+
+
+def host_loader(ds, batch, workers, ratio):
+    from bin_amd.data import create_dataloader
+    from bin_amd.data.data_sampler import DistIterSampler
+    sampler = DistIterSampler(ds, 1, 0, ratio)          # `ratio` passes over the windows without restarting the workers
+    loader = create_dataloader(ds, {"phase": "train", "batch_size": batch, "n_workers": workers},
+                               {"dist": False, "gpu_ids": [0]}, sampler)
+    if workers:
+        # fresh worker processes instead of forks of this one: they never touch the GPU, and a fork would inherit this
+        # process's open device handle.  Start-up is excluded from the timings (time_batches skips the first batches).
+        loader.multiprocessing_context = "spawn"
+    return loader
+
+
+def time_batches(it, n, per_batch=None, skip=2):
+    """ms per batch over n batches after `skip` untimed ones (worker start-up), each followed by per_batch(batch)."""
+    for _ in range(skip):
+        b = next(it)
+        if per_batch:
+            per_batch(b)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        b = next(it)
+        if per_batch:
+            per_batch(b)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / n
+
+
+def time_steps(model, it, steps, warmup):
+    """optimize_parameters ms per step; `it` None = the resident batch already fed."""
+    def one(k):
+        if it is not None:
+            model.feed_data(next(it))
+        model.optimize_parameters(k)
+        torch.cuda.synchronize()
+    for k in range(warmup):
+        one(k + 1)
+    t0 = time.perf_counter()
+    for k in range(steps):
+        one(warmup + k + 1)
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def forever(make):
+    while True:
+        yield from make()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clips", type=int, default=9)
+    ap.add_argument("--blurry", type=int, default=13, help="blurry frames per clip (n - 5 windows)")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--workers", type=int, nargs="+", default=[3, 16])
+    ap.add_argument("--loader-batches", type=int, default=24)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--kernel-launches", type=int, default=200)
+    ap.add_argument("--only", choices=["all", "kernel"], default="all")
+    args = ap.parse_args()
+    from bin_amd.data.device_cache import DeviceWindowLoader
+
+    dev = torch.device("cuda", 0)
+    tmp = tempfile.mkdtemp(prefix="bin_train_data_")
+    res = {"tool": "bench_train_data", "batch": args.batch, "crop": [CROP, CROP], "frame": [352, 640]}
+    try:
+        t = time.perf_counter()
+        root = make_tree(os.path.join(tmp, "adobe"), args.clips, args.blurry)
+        ds = dataset(root)
+        res["windows"], res["tree_s"] = len(ds), round(time.perf_counter() - t, 2)
+        print(f"tree: {len(ds)} windows in {res['tree_s']} s", file=sys.stderr, flush=True)
+
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        dl = DeviceWindowLoader(ds, args.batch, None, dev)
+        torch.cuda.synchronize()
+        res["cache"] = {"build_s": round(time.perf_counter() - t, 3), "bytes": dl.cache.nbytes, "frames": dl.cache.shape[0]}
+        print(f"cache: {res['cache']}", file=sys.stderr, flush=True)
+
+        # the gather kernel alone: one batch's table, launched back to back
+        from bin_amd import ops
+        from bin_amd.data.BIN_dataset import draw_window_aug
+        wins = [ds.all_paths[i] for i in range(args.batch)]
+        tab = dl.cache.table(wins, [draw_window_aug((3, CROP, CROP)) for _ in wins])
+        for _ in range(10):
+            ops.gather_windows(dl.cache.frames, tab, (CROP, CROP))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.kernel_launches):
+            ops.gather_windows(dl.cache.frames, tab, (CROP, CROP))
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / args.kernel_launches
+        nbytes = args.batch * 17 * CROP * CROP * (3 + 12)
+        res["gather_kernel"] = {"us_per_launch_events": round(us, 2), "bytes": nbytes,
+                                "hbm_bound_us": round(nbytes / HBM_BYTES_PER_S * 1e6, 2),
+                                "note": "event-timed launches include the pinned table upload and launch gaps; "
+                                        "rocprofv3 gives the kernel alone"}
+        res["device_loader_ms_per_batch"] = round(time_batches(forever(lambda: iter(dl)), args.loader_batches), 2)
+        print(f"device loader: {res['device_loader_ms_per_batch']} ms/batch", file=sys.stderr, flush=True)
+        if args.only == "kernel":
+            print(json.dumps(res))
+            return
+
+        import bench
+        model, _ = bench.make_train_model("f16x3", None, 1, 0, args.batch, S=CROP)
+        ratio = 1 + (args.loader_batches + 4) * args.batch // len(ds)
+        hl = {}
+        for w in args.workers:
+            row = {}
+            row["discard"] = round(time_batches(iter(host_loader(ds, args.batch, w, ratio)), args.loader_batches), 2)
+            row["feed_data"] = round(time_batches(iter(host_loader(ds, args.batch, w, ratio)), args.loader_batches,
+                                                  model.feed_data), 2)
+            hl[f"n_workers_{w}"] = row
+            print(f"host loader n_workers {w}: {row}", file=sys.stderr, flush=True)
+        res["host_loader_ms_per_batch"] = hl
+
+        ts = {}
+        steps_ratio = 1 + (args.steps + args.warmup + 4) * args.batch // len(ds)
+        for w in args.workers:
+            ts[f"host_n_workers_{w}"] = round(time_steps(model, iter(host_loader(ds, args.batch, w, steps_ratio)),
+                                                         args.steps, args.warmup), 2)
+            print(f"step fed by host loader ({w}): {ts[f'host_n_workers_{w}']} ms", file=sys.stderr, flush=True)
+        ts["device_cache"] = round(time_steps(model, forever(lambda: iter(dl)), args.steps, args.warmup), 2)
+        model.feed_data(next(iter(dl)))
+        ts["resident"] = round(time_steps(model, None, args.steps, args.warmup), 2)
+        print(f"step device-fed {ts['device_cache']} ms, resident {ts['resident']} ms", file=sys.stderr, flush=True)
+        res["train_step_ms"] = ts
+        res["device_vs_resident"] = round(ts["device_cache"] / ts["resident"], 4)
+        w0 = f"n_workers_{args.workers[0]}"
+        res["host_loader_vs_step"] = round(hl[w0]["feed_data"] / ts["resident"], 3)
+        print(json.dumps(res))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
