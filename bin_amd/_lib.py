@@ -150,6 +150,8 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "binhip_gather_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p]),
+    "binhip_gather_windows_blur": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 +
+                                   [C.c_void_p, C.c_void_p]),
 }
 
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED

@@ -7,7 +7,11 @@ every epoch revisits all of them.  Here every frame the training list touches is
 device (DeviceFrameCache), and each batch is one binhip_gather_windows launch (ops.gather_windows): crop, flip, BGR -> RGB,
 /255 and the layout feed_data consumes.  The augmentation draws are the host loader's own (draw_window_aug), made in its
 order in the main process, so with the same `random` state a batch equals the host loader's batch at n_workers 0 bit for
-bit."""
+bit.
+
+With the dataset option `blur_window` the arena holds sharp frames only, each clip's consecutively in file order, and the six
+blurry inputs of a window are averaged from them inside the launch (ops.gather_windows_blur), with the exposure of each
+sample in the table."""
 import concurrent.futures as cf
 import logging
 import os
@@ -16,10 +20,11 @@ import numpy as np
 import torch
 
 from .. import ops
-from .BIN_dataset import draw_window_aug
+from .BIN_dataset import blur_half_max, draw_blur_half, draw_window_aug, frame_number
 from .util import imread_u8
 
 N_SLOTS = 17                     # 6 blurry + 6 sharp + 5 in-between sharp frames per window
+N_BLUR = 6                       # the blurry slots come first
 CHUNK_BYTES = 256 << 20          # host staging per pinned buffer while the arena fills
 
 
@@ -47,15 +52,31 @@ def window_slots(window, reverse):
 class DeviceFrameCache:
     """Every unique frame of `window_list` decoded once (imread_u8 on a thread pool) into one uint8 [n_frames, H, W, 3]
     BGR arena on `device`.  Raises ValueError before allocating anything when the frames differ in size, a frame is not
-    colour (an RGBA frame keeps its first 3 channels, as read_img does), or the arena would exceed `max_gb` (10^9 bytes)."""
+    colour (an RGBA frame keeps its first 3 channels, as read_img does), or the arena would exceed `max_gb` (10^9 bytes).
+    `blur_half` (the largest half range h of the dataset's `blur_window`): the windows are make_sharp_window_list's, and the
+    arena holds per clip every sharp file from its first blurry centre - h to its last + h, consecutively in file order, so
+    frame id +- k is file number +- k; `clip_ranges` keeps each clip's [start, end) ids."""
 
-    def __init__(self, window_list, device, max_gb=64, threads=None):
-        self.paths, self.index = [], {}
-        for win in window_list:
-            for p in window_slots(win, False):
-                if p not in self.index:
-                    self.index[p] = len(self.paths)
-                    self.paths.append(p)
+    def __init__(self, window_list, device, max_gb=64, threads=None, blur_half=None):
+        self.paths, self.index, self.clip_ranges = [], {}, None
+        if blur_half is None:
+            for win in window_list:
+                for p in window_slots(win, False):
+                    if p not in self.index:
+                        self.index[p] = len(self.paths)
+                        self.paths.append(p)
+        else:
+            spans = {}                                       # clip folder -> [first, last] blurry centre of any window
+            for win in window_list:
+                d, a, b = os.path.dirname(win[0][0]), frame_number(win[0][0]), frame_number(win[0][-1])
+                lo, hi = spans.get(d, (a, b))
+                spans[d] = (min(lo, a), max(hi, b))
+            self.clip_ranges = np.empty((len(spans), 2), dtype=np.int64)
+            for c, (d, (lo, hi)) in enumerate(spans.items()):
+                clip = [os.path.join(d, str(k).zfill(5) + ".png") for k in range(lo - blur_half, hi + blur_half + 1)]
+                self.clip_ranges[c] = (len(self.paths), len(self.paths) + len(clip))
+                self.index.update((p, len(self.paths) + j) for j, p in enumerate(clip))
+                self.paths += clip
         if not self.paths:
             raise ValueError("DeviceFrameCache: the window list is empty")
         threads = threads or _default_threads()
@@ -99,19 +120,23 @@ class DeviceFrameCache:
                 done[k % 2].record()
             torch.cuda.current_stream().synchronize()
 
-    def table(self, windows, draws):
+    def table(self, windows, draws, halves=None):
         """window_table of these windows against this arena."""
-        return window_table(windows, draws, self.index)
+        return window_table(windows, draws, self.index, halves)
 
 
-def window_table(windows, draws, index):
+def window_table(windows, draws, index, halves=None):
     """int32 [len(windows), 17 + 3] rows of binhip_gather_windows: the arena ids (`index`: path -> id) of each window's frames
     in slot order, a reversed window's in reverse order, then y0, x0, flip.  `draws`: one (reverse, y0, x0, flip) per window
-    (draw_window_aug)."""
-    rows = np.empty((len(windows), N_SLOTS + 3), dtype=np.int32)
+    (draw_window_aug).  With `halves` (one half range h per window, draw_blur_half) the rows are binhip_gather_windows_blur's:
+    [len(windows), 17 + 4], h last, the blurry ids being those of the centre sharp frames."""
+    extra = 3 if halves is None else 4
+    rows = np.empty((len(windows), N_SLOTS + extra), dtype=np.int32)
     for r, (win, (reverse, y0, x0, flip)) in enumerate(zip(windows, draws)):
         rows[r, :N_SLOTS] = [index[p] for p in window_slots(win, reverse)]
-        rows[r, N_SLOTS:] = (y0, x0, int(flip))
+        rows[r, N_SLOTS:N_SLOTS + 3] = (y0, x0, int(flip))
+    if halves is not None:
+        rows[:, N_SLOTS + 3] = halves
     return rows
 
 
@@ -125,7 +150,9 @@ class DeviceWindowLoader:
     def __init__(self, dataset, batch, sampler=None, device=None, max_gb=64, cache=None):
         self.dataset, self.batch, self.sampler = dataset, int(batch), sampler
         self.crop = tuple(dataset.input_frame_size)
-        self.cache = cache or DeviceFrameCache(dataset.all_paths, device, max_gb)
+        self.blur_window = getattr(dataset, "blur_window", None)
+        blur_half = None if self.blur_window is None else blur_half_max(self.blur_window)
+        self.cache = cache or DeviceFrameCache(dataset.all_paths, device, max_gb, blur_half=blur_half)
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else len(self.dataset)
@@ -144,8 +171,13 @@ class DeviceWindowLoader:
         _, ch, cw = self.crop
         for idx in self.index_batches():
             windows = [self.dataset.all_paths[i] for i in idx]
-            draws = [draw_window_aug(self.crop) for _ in windows]
-            out = ops.gather_windows(self.cache.frames, self.cache.table(windows, draws), (ch, cw))
+            if self.blur_window is None:
+                draws = [draw_window_aug(self.crop) for _ in windows]
+                out = ops.gather_windows(self.cache.frames, self.cache.table(windows, draws), (ch, cw))
+            else:                                            # per sample: the four draws, then the exposure's (load_window's order)
+                both = [(draw_window_aug(self.crop), draw_blur_half(self.blur_window)) for _ in windows]
+                table = self.cache.table(windows, [d for d, _ in both], [h for _, h in both])
+                out = ops.gather_windows_blur(self.cache.frames, table, (ch, cw), N_BLUR, self.cache.clip_ranges)
             yield {"LQs": out[0:6].transpose(0, 1), "GTenh": out[6:12].transpose(0, 1), "GTinp": out[12:17].transpose(0, 1),
                    "key": [w[3] for w in windows]}
 

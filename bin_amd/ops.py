@@ -601,3 +601,59 @@ def gather_windows(frames_u8, table_host, crop):
         L.check(L.lib().binhip_gather_windows(_ptr(frames_u8), nf, h, w, _ptr(table), n, n_slots, ch, cw, _ptr(out), _stream()),
                 "gather_windows")
     return out
+
+
+GATHER_MAX_HALF = 16         # h limit of binhip_gather_windows_blur: exposures of 2h + 1 <= 33 sharp frames
+
+
+def gather_windows_blur(frames_u8, table_host, crop, n_blur, clip_ranges=None):
+    """gather_windows with the first `n_blur` slots synthesised as the reference's blurry frames: the truncated mean of the
+    2h + 1 arena frames around the slot's id (binhip_gather_windows_blur; the reference's
+    data_scripts/adobe240fps/create_dataset_blur_N_frames_average.py:116-134).  `table_host`: int32 [n, n_slots + 4] on the
+    HOST, a gather_windows row followed by the sample's h.  The arena must hold the sharp frames of a clip consecutively in
+    file order; `clip_ranges` (int [clips, 2], [start, end) arena ids per clip), when given, is checked against every blurry
+    range.  Checked here (the kernel only clamps): everything gather_windows checks, h in [0, 16], id - h .. id + h inside
+    the arena and inside one clip.  Returns fp32 [n_slots, n, 3, ch, cw]."""
+    import numpy as np
+    _need_cuda(frames_u8)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise ValueError(f"gather_windows_blur: frames must be a contiguous uint8 [n_frames, H, W, 3] tensor, got "
+                         f"{frames_u8.dtype} {tuple(frames_u8.shape)}")
+    nf, h, w, _ = frames_u8.shape
+    ch, cw = (int(v) for v in crop)
+    tab = np.ascontiguousarray(table_host.numpy() if torch.is_tensor(table_host) else table_host, dtype=np.int32)
+    if tab.ndim != 2 or tab.shape[0] < 1 or not 1 <= tab.shape[1] - 4 <= GATHER_MAX_SLOTS:
+        raise ValueError(f"gather_windows_blur: table must be [n, n_slots + 4] with 1 <= n_slots <= {GATHER_MAX_SLOTS}, "
+                         f"got {tab.shape}")
+    n, n_slots, n_blur = tab.shape[0], tab.shape[1] - 4, int(n_blur)
+    if not 0 <= n_blur <= n_slots:
+        raise ValueError(f"gather_windows_blur: n_blur {n_blur} outside [0, {n_slots}]")
+    if not (0 < ch <= h and 0 < cw <= w):
+        raise ValueError(f"gather_windows_blur: crop {ch}x{cw} does not fit {h}x{w} frames")
+    ids, y0, x0, flip, half = (tab[:, :n_slots], tab[:, n_slots], tab[:, n_slots + 1], tab[:, n_slots + 2],
+                               tab[:, n_slots + 3])
+    if ids.min() < 0 or ids.max() >= nf:
+        raise ValueError(f"gather_windows_blur: frame id outside [0, {nf})")
+    if y0.min() < 0 or y0.max() > h - ch or x0.min() < 0 or x0.max() > w - cw:
+        raise ValueError(f"gather_windows_blur: crop offset outside the {h}x{w} frame for a {ch}x{cw} crop")
+    if ((flip != 0) & (flip != 1)).any():
+        raise ValueError("gather_windows_blur: flip must be 0 or 1")
+    if half.min() < 0 or half.max() > GATHER_MAX_HALF:
+        raise ValueError(f"gather_windows_blur: h outside [0, {GATHER_MAX_HALF}]")
+    if n_blur:
+        lo, hi = ids[:, :n_blur] - half[:, None], ids[:, :n_blur] + half[:, None]
+        if lo.min() < 0 or hi.max() >= nf:
+            raise ValueError(f"gather_windows_blur: a blurry centre's id - h .. id + h leaves the arena [0, {nf})")
+        if clip_ranges is not None:
+            cr = np.asarray(clip_ranges, dtype=np.int64).reshape(-1, 2)
+            cr = cr[np.argsort(cr[:, 0])]
+            clip = np.searchsorted(cr[:, 0], lo, side="right") - 1         # the clip that holds the first frame of the range
+            if (clip < 0).any() or (hi >= cr[np.maximum(clip, 0), 1]).any():
+                raise ValueError("gather_windows_blur: a blurry centre's id - h .. id + h crosses a clip boundary")
+    dev = frames_u8.device
+    with on_device(frames_u8):
+        table = torch.from_numpy(tab).pin_memory().to(dev, non_blocking=True)
+        out = torch.empty((n_slots, n, 3, ch, cw), dtype=torch.float32, device=dev)
+        L.check(L.lib().binhip_gather_windows_blur(_ptr(frames_u8), nf, h, w, _ptr(table), n, n_slots, n_blur, ch, cw, _ptr(out),
+                                                   _stream()), "gather_windows_blur")
+    return out

@@ -57,8 +57,8 @@ extern "C" {
 /* Interface version = what binhip_version() of a matching library returns (100 x round + revision); a binder checks
  * `binhip_version() == BINHIP_VERSION` after dlopen.  BINHIP_ABI_EXPORTS = number of BINHIP_API entry points below
  * (tests/test_cpu_host.py keeps it equal to the declarations and to `nm -D`). */
-#define BINHIP_VERSION 621
-#define BINHIP_ABI_EXPORTS 48
+#define BINHIP_VERSION 622
+#define BINHIP_ABI_EXPORTS 49
 
 #define BINHIP_E_ARG      (-1)   /* null pointer / bad enum */
 #define BINHIP_E_SHAPE    (-2)   /* unsupported shape */
@@ -460,6 +460,27 @@ BINHIP_API int binhip_image_score(const uint8_t* a, const uint8_t* b, int n, int
  * [0, H - ch] and x0 to [0, W - cw], so a bad row can never read outside the arena.                                        */
 BINHIP_API int binhip_gather_windows(const uint8_t* frames, int n_frames, int H, int W, const int32_t* table, int n, int n_slots,
                           int ch, int cw, float* out, void* stream);
+
+/* ---- the same, with the blurry frames synthesised from the sharp ones (the reference's
+ * data_scripts/adobe240fps/create_dataset_blur_N_frames_average.py:116-134): a blurry frame is the truncated mean of the
+ * L = 2h + 1 consecutive sharp frames around its centre, so an arena that holds the sharp frames of every clip consecutively,
+ * in file order, needs no blurry frames at all and the exposure L is a per-sample value.
+ *   table   int32 [n][n_slots + 4] (DEVICE memory): the frame ids in slot order, then y0, x0, flip, then h (0 .. 16) of this
+ *           sample.  The first n_blur slots are blurry: their id is the CENTRE frame.  The mean is symmetric in time, so a
+ *           temporally reversed window is still just its ids in reverse order
+ *   out     as binhip_gather_windows; for a slot s < n_blur
+ *           out[s][b][c][y][x] = (float)(S / L) / 255.f   (integer quotient),
+ *           S = sum over k = id - h .. id + h of frames[k][y0 + y][flip ? x0 + cw - 1 - x : x0 + x][2 - c]
+ *           — the script's float32 sum / float(L) truncated to uint8 (equal to S / L for every S <= 255 L, L <= 33), then
+ *           read_img's / 255.: bit for bit what the host loader returns for the PNG the script would have written.  A slot
+ *           s >= n_blur, and a blurry slot with h = 0, is a plain copy; with n_blur = 0 the call equals binhip_gather_windows
+ *           on the same rows (without the h column) bit for bit.
+ * Errors: BINHIP_E_ARG for a null pointer; BINHIP_E_SHAPE for everything binhip_gather_windows rejects and for n_blur outside
+ * 0 .. n_slots.  The table is not checked here; the kernel clamps h to [0, 16] (and to (n_frames - 1) / 2), a blurry id to
+ * [h, n_frames - 1 - h], every other id to [0, n_frames), y0 to [0, H - ch] and x0 to [0, W - cw], so a bad row can never
+ * read outside the arena.  That the frames id - h .. id + h belong to one clip is the caller's business.                   */
+BINHIP_API int binhip_gather_windows_blur(const uint8_t* frames, int n_frames, int H, int W, const int32_t* table, int n, int n_slots,
+                               int n_blur, int ch, int cw, float* out, void* stream);
 
 /* ---- live kernel timing (bench.py roofline leg) --------------------------------------------------
  * An explicit host-side handle: every conv launch of a plan that carries it and whose (ksize,

@@ -12,6 +12,17 @@ reports, as one JSON line:
 
     python tools/bench_train_data.py                      # everything
     python tools/bench_train_data.py --only kernel        # cache + gather launches only (for rocprofv3 --kernel-trace --stats)
+
+--blur_window N is a run of its own (the default run stays what it is): a sharp-only tree (tests/blur_cases.make_sharp_tree,
+--clips clips of --sharp-files consecutive frames) whose blurry folders tools/make_blur_folder.py writes for window N, and
+  train_step       optimize_parameters ms per step fed by today's device-cache loader (blurry PNGs in the arena) and by the
+                   synthesising one (`blur_window: N`, sharp frames only), alternating, --rounds times each
+  cache            build seconds and arena bytes of both
+  gather_kernel    binhip_gather_windows_blur launches at the exposures --kernel-windows (default 1, N, 33) against the HBM
+                   bound counted without any cache reuse (3 L B read + 12 B written per blurry pixel, 15 B per other pixel)
+
+    python tools/bench_train_data.py --blur_window 11
+    python tools/bench_train_data.py --blur_window 11 --only kernel --kernel-windows 33    # for rocprofv3, one exposure per run
 """
 import argparse
 import json
@@ -96,6 +107,93 @@ def forever(make):
         yield from make()
 
 
+def blur_leg(args):
+    """The --blur_window run (module docstring)."""
+    import importlib.util
+    from blur_cases import make_sharp_tree
+    from bin_amd import ops
+    from bin_amd.data import create_dataset
+    from bin_amd.data.BIN_dataset import draw_window_aug
+    from bin_amd.data.device_cache import N_BLUR, DeviceFrameCache, DeviceWindowLoader
+    spec = importlib.util.spec_from_file_location("make_blur_folder", os.path.join(REPO, "tools", "make_blur_folder.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+
+    def blur_dataset(root, window):
+        random.seed(0)
+        opt = {"mode": "BIN", "name": "train", "dataroot_GT": root, "dataroot_LQ": root, "LQ_size": [3, CROP, CROP],
+               "data_type": "img", "phase": "train", "blur_window": window}
+        return create_dataset(opt)
+
+    N = args.blur_window
+    dev = torch.device("cuda", 0)
+    tmp = tempfile.mkdtemp(prefix="bin_train_data_")
+    res = {"tool": "bench_train_data", "leg": "blur_window", "blur_window": N, "batch": args.batch, "crop": [CROP, CROP],
+           "frame": [352, 640]}
+    try:
+        t = time.perf_counter()
+        root = make_sharp_tree(os.path.join(tmp, "adobe"), clips=tuple((f"clip{c:02d}", 1 + 8 * c, args.sharp_files)
+                                                                       for c in range(args.clips)))
+        tool.make_blur_folder(root, "train", N)
+        res["tree_s"] = round(time.perf_counter() - t, 2)
+        print(f"tree: {args.clips} clips of {args.sharp_files} sharp frames in {res['tree_s']} s", file=sys.stderr, flush=True)
+
+        # the kernel alone: an arena with room for h = 16, one batch's table per exposure, launched back to back
+        wide = blur_dataset(root, 33)
+        cache = DeviceFrameCache(wide.all_paths, dev, blur_half=16)
+        wins = [wide.all_paths[i] for i in range(args.batch)]
+        draws = [draw_window_aug((3, CROP, CROP)) for _ in wins]
+        rows = []
+        for L in args.kernel_windows or [1, N, 33]:
+            tab = cache.table(wins, draws, [L // 2] * len(wins))
+            for _ in range(10):
+                ops.gather_windows_blur(cache.frames, tab, (CROP, CROP), N_BLUR, cache.clip_ranges)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.kernel_launches):
+                ops.gather_windows_blur(cache.frames, tab, (CROP, CROP), N_BLUR, cache.clip_ranges)
+            e1.record()
+            torch.cuda.synchronize()
+            nbytes = args.batch * CROP * CROP * (N_BLUR * (3 * L + 12) + (17 - N_BLUR) * 15)
+            rows.append({"L": L, "us_per_launch_events": round(e0.elapsed_time(e1) * 1e3 / args.kernel_launches, 2),
+                         "bytes_no_reuse": nbytes, "hbm_bound_us": round(nbytes / HBM_BYTES_PER_S * 1e6, 2)})
+            print(f"gather_windows_blur {rows[-1]}", file=sys.stderr, flush=True)
+        res["gather_kernel"] = {"arena_bytes": cache.nbytes, "rows": rows,
+                                "note": "event-timed launches include the pinned table upload and launch gaps; "
+                                        "rocprofv3 gives the kernel alone"}
+        del cache
+        if args.only == "kernel":
+            print(json.dumps(res))
+            return
+
+        loaders, res["cache"] = {}, {}
+        for name, ds in (("device_cache", dataset(root)), ("device_cache_blur_window", blur_dataset(root, N))):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            loaders[name] = DeviceWindowLoader(ds, args.batch, None, dev)
+            torch.cuda.synchronize()
+            c = loaders[name].cache
+            res["cache"][name] = {"build_s": round(time.perf_counter() - t, 3), "bytes": c.nbytes, "frames": c.shape[0],
+                                  "windows": len(ds)}
+            print(f"cache {name}: {res['cache'][name]}", file=sys.stderr, flush=True)
+        res["device_loader_ms_per_batch"] = {k: round(time_batches(forever(lambda dl=dl: iter(dl)), args.loader_batches), 3)
+                                             for k, dl in loaders.items()}
+
+        import bench
+        model, _ = bench.make_train_model("f16x3", None, 1, 0, args.batch, S=CROP)
+        ts = {k: [] for k in loaders}
+        for r in range(args.rounds):                         # alternating: A B A B ...
+            for k, dl in loaders.items():
+                ts[k].append(round(time_steps(model, forever(lambda dl=dl: iter(dl)), args.steps, args.warmup if r == 0 else 2), 2))
+                print(f"round {r}: step fed by {k}: {ts[k][-1]} ms", file=sys.stderr, flush=True)
+        med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+        res["train_step_ms"] = {"rounds": ts, "median": med}
+        res["blur_vs_device_cache"] = round(med["device_cache_blur_window"] / med["device_cache"], 4)
+        print(json.dumps(res))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=9)
@@ -107,7 +205,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--kernel-launches", type=int, default=200)
     ap.add_argument("--only", choices=["all", "kernel"], default="all")
+    ap.add_argument("--blur_window", type=int, default=None, help="run the blur_window leg with this exposure instead")
+    ap.add_argument("--sharp-files", type=int, default=120, help="blur_window leg: consecutive sharp frames per clip")
+    ap.add_argument("--kernel-windows", type=int, nargs="+", default=None, help="blur_window leg: exposures of the kernel launches")
+    ap.add_argument("--rounds", type=int, default=3, help="blur_window leg: alternations of the two device-fed steps")
     args = ap.parse_args()
+    if args.blur_window is not None:
+        return blur_leg(args)
     from bin_amd.data.device_cache import DeviceWindowLoader
 
     dev = torch.device("cuda", 0)
