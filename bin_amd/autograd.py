@@ -253,8 +253,9 @@ class _ConvLstmFn(torch.autograd.Function):
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gcp = torch.empty_like(x) if (cp is not None and ctx.needs_input_grad[1]) else None
         ghp = torch.empty_like(x) if (hp is not None and ctx.needs_input_grad[2]) else None
-        dw = torch.zeros_like(w)
-        db = torch.zeros_like(b)
+        need_w = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]          # frozen gate weights: the weight pass is not launched
+        dw = torch.zeros_like(w) if need_w else None
+        db = torch.zeros_like(b) if need_w else None
         ws = workspace(lib.binhip_convlstm_bwd_workspace_bytes(n, hh, ww), dev, key="clstm")
         L.check(lib.binhip_convlstm_bwd(_ptr(x), _ptr(cp), _ptr(hp), _ptr(w), _ptr(b), ctx.fb, n, hh, ww, _ptr(gh),
                                         _ptr(gc), _ptr(ws), ws.numel(), _ptr(gx), _ptr(ghp), _ptr(gcp), _ptr(dw),
@@ -314,8 +315,11 @@ class _LstmGatesFn(torch.autograd.Function):
         gates, cp = ctx.saved_tensors
         if gh is None and gc is None:
             return None, None, None, None
-        dg, gcp = ops.lstm_gates_grad(gates, cp, gh, gc, ctx.fb, ctx.hidden, cp is not None and ctx.needs_input_grad[1])
-        return dg, gcp, None, None
+        # (the kernel reads fp32 NCHW: the same .float() the forward applied, and the gradient back in the gates' own dtype)
+        dg, gcp = ops.lstm_gates_grad(gates.float(), cp, gh, gc, ctx.fb, ctx.hidden, cp is not None and ctx.needs_input_grad[1])
+        if gcp is not None:
+            gcp = gcp.to(cp.dtype)
+        return dg.to(gates.dtype), gcp, None, None
 
 
 def convlstm_general(x, state, weight, bias, forget_bias, hidden):

@@ -92,7 +92,10 @@ class ConvLSTMCell(nn.Module):
                 return convlstm_general(input_, prev_state, self.Gates.weight, self.Gates.bias, self._forget_bias, self.hidden_size)
             with torch.no_grad():
                 return convlstm_general(input_, prev_state, self.Gates.weight, self.Gates.bias, self._forget_bias, self.hidden_size)
-        if torch.is_grad_enabled() and (input_.requires_grad or self.Gates.weight.requires_grad):
+        # differentiable when ANY differentiable argument wants a gradient: the input, the gate weight or bias, or the previous
+        # state alone (frozen weights behind a recurrent state that is being optimised / probed)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in
+                                           (input_, self.Gates.weight, self.Gates.bias, *(prev_state or ()))):
             from ...autograd import convlstm_apply
             return convlstm_apply(input_, prev_state, self.Gates.weight, self.Gates.bias, self._forget_bias)
         return ops.convlstm_cell(input_, prev_state, self.Gates.weight, self.Gates.bias, self._forget_bias)

@@ -15,7 +15,9 @@
  *   - Activations between layers live in "chunk planes" (CP): fp16 [C/16][N][H][W][16]
  *     (channels-last inside 16-channel chunks, one contiguous plane per chunk, so a dense block's
  *     concat is just "the next plane").  A CP tensor has a `hi` plane set and, in split precision
- *     (nterms == 3), a `lo` plane set with x ~= hi + lo to ~22 mantissa bits.
+ *     (nterms == 3), a `lo` plane set: hi = fp16(x), lo = fp16(x - hi), both round-to-nearest-even
+ *     with fp16 subnormals kept, hence |x - (hi + lo)| <= max(2^-23 |x|, 2^-25) for |x| <= 65504
+ *     (nterms == 1: |x - hi| <= max(2^-11 |x|, 2^-25)); the packers store exactly this pair.
  *   - nterms: 1 = fp16-input MFMA, fp32 accumulate (whole-net max-abs error ~3e-4 vs fp32);
  *             3 = fp16 hi/lo split, three MFMA products (error ~1e-6, fp32 class).
  *   - Dynamic range.  The reference computes in fp32 (RDN.py:141, no AMP); here every value stored

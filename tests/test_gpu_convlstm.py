@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import REPO, load_golden
+from lstm_cases import off1 as _off1      # (shared with test_gpu_small_kernels.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -111,16 +112,6 @@ def test_general_convlstm_conv_refuses_a_weight_changed_before_backward():
         w.mul_(0.5)                                                # what an optimizer step does
     with pytest.raises(RuntimeError, match="modified in place"):
         y.sum().backward()
-
-
-def _off1(t):
-    """A copy of `t` whose data pointer is 4 bytes past a 16-byte boundary (forces the one-pixel ConvLSTM kernels)."""
-    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
-    assert buf.data_ptr() % 16 == 0
-    v = buf[1:1 + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == 4
-    return v
 
 
 @pytest.mark.parametrize("with_state", [False, True])
