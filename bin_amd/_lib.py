@@ -68,7 +68,8 @@ class BinRelayoutItem(C.Structure):
 
 
 RELAYOUT_FWD, RELAYOUT_DGRAD, RELAYOUT_RDB_GATHER = 0, 1, 2
-SCORE_SSIM_G11, SCORE_SSIM_U7 = 1, 2   # BINHIP_SCORE_SSIM_* flags of binhip_image_score
+SCORE_SSIM_G11, SCORE_SSIM_U7 = 1, 2   # BINHIP_SCORE_SSIM_* flags of binhip_image_score / binhip_frame_score
+SCORE_MAX_PAIRS = 32                   # BINHIP_SCORE_MAX_PAIRS
 
 _SIGNATURES = {
     "binhip_version": (C.c_int, []),
@@ -148,6 +149,9 @@ _SIGNATURES = {
     "binhip_image_score_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "binhip_image_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "binhip_frame_score_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "binhip_frame_score": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "binhip_gather_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p]),
     "binhip_gather_windows_blur": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 +

@@ -3,7 +3,8 @@
 Loader policy, as there: the training loader never shuffles itself (order comes from the sampler or from the dataset's
 own shuffled window list), drops the ragged last batch, and — under torch.distributed — gives every rank
 batch_size // world_size samples with n_workers workers; single-process runs scale the workers by the number of GPUs
-listed in the options.  Every other phase is an in-order loader of single samples."""
+listed in the options.  Every other phase is an in-order loader of single samples (from the device frame cache too, when
+the phase's `device_cache` asks for it)."""
 import logging
 
 import torch
@@ -23,17 +24,20 @@ def _train_loader_shape(dataset_opt, opt):
 
 def create_dataloader(dataset, dataset_opt, opt=None, sampler=None, vscode_debug=False):
     common = dict(shuffle=False, pin_memory=torch.cuda.is_available())
-    if dataset_opt["phase"] != "train":
-        return tud.DataLoader(dataset, batch_size=1, num_workers=0 if vscode_debug else 1, **common)
-    batch, workers = _train_loader_shape(dataset_opt, opt)
+    train = dataset_opt["phase"] == "train"
+    batch, workers = _train_loader_shape(dataset_opt, opt) if train else (1, 1)
     if dataset_opt.get("device_cache"):
-        # bin_amd extension: batches cut out of a device-resident frame cache (data/device_cache.py); BIN windows only
+        # bin_amd extension: batches cut out of a device-resident frame cache (data/device_cache.py); BIN windows only.  Any
+        # other phase: single windows in order, nothing dropped; the loader (and with it the cache) is built once and
+        # iterated by every validation pass
         from .BIN_dataset import BINDataset
         if isinstance(dataset, BINDataset):
             from .device_cache import create_device_loader
-            return create_device_loader(dataset, dataset_opt, batch, sampler)
+            return create_device_loader(dataset, dataset_opt, batch, sampler if train else None)
         logging.getLogger("base").warning("device_cache applies to mode BIN datasets only; [%s] uses the host loader",
                                           type(dataset).__name__)
+    if not train:
+        return tud.DataLoader(dataset, batch_size=1, num_workers=0 if vscode_debug else 1, **common)
     return tud.DataLoader(dataset, batch_size=batch, sampler=sampler, drop_last=True,
                           num_workers=0 if vscode_debug else workers, **common)
 

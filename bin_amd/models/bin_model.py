@@ -485,18 +485,40 @@ class bin_model(BaseModel):
             a.reset()
             b.reset()
 
-    def compute_current_psnr_ssim(self, save=False, name=None, save_path=None):
+    def compute_current_psnr_ssim(self, save=False, name=None, save_path=None, metrics=None):
         """PSNR / SSIM of the 14 outputs vs GT through tensor2img (bin_model.py:564-589); save=True also writes
-        `rlt_<name>_<i>.png` / `gt_<name>_<i>.png` under save_path."""
+        `rlt_<name>_<i>.png` / `gt_<name>_<i>.png` under save_path.  `metrics` (bin_amd extension, the option
+        `train.val_metrics` that train.validate passes): None or "host" scores with numpy on frames copied to the host;
+        "device" scores sample 0 of the 14 fp32 outputs where they are with ONE ops.frame_scores call and copies the
+        [14, 4] result back, so no frame leaves the device unless save=True asks for the PNGs.  The PSNRs are the host
+        path's bit for bit, the SSIMs (the same 11x11 Gaussian SSIM) agree to 1e-9."""
         import os.path as osp
+        if metrics not in (None, "host", "device"):
+            raise ValueError(f"compute_current_psnr_ssim: metrics {metrics!r} is not one of host, device")
         num = self.get_info()
-        visuals = self.get_current_visuals()
+        device = metrics == "device"
         psnr, ssim = [], []
+        if device:
+            from .. import ops
+            _, gt_list = self.get_info(mode=1)
+            outs = [self.Ft_p[i] for i in range(num)]
+            if not all(t.is_cuda for t in outs + gt_list):
+                raise RuntimeError("bin_amd: train.val_metrics: device needs a CUDA model (the scores are computed by a HIP "
+                                   "kernel on the outputs where they are; there is no CPU path) - use val_metrics: host")
+            rows = ops.frame_scores([t.detach()[0].float() for t in outs], [t.detach()[0].float() for t in gt_list])
+            rows = rows.cpu().numpy()
+            numel = outs[0][0].numel()
+            psnr = [float(util.score_row(r, numel)["psnr"]) for r in rows]
+            ssim = [float(r[2]) for r in rows]
+            if not save:
+                return psnr, ssim
+        visuals = self.get_current_visuals()
         for i in range(num):
             rlt_img = util.tensor2img(visuals["rlt"][i])
             gt_img = util.tensor2img(visuals["GT"][i])
-            psnr.append(util.calculate_psnr(rlt_img, gt_img))
-            ssim.append(util.calculate_ssim(rlt_img, gt_img))
+            if not device:
+                psnr.append(util.calculate_psnr(rlt_img, gt_img))
+                ssim.append(util.calculate_ssim(rlt_img, gt_img))
             if save:
                 util.save_img(rlt_img, osp.join(save_path, "rlt_{}_{}.png".format(name, i)))
                 util.save_img(gt_img, osp.join(save_path, "gt_{}_{}.png".format(name, i)))

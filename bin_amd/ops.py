@@ -563,6 +563,60 @@ def image_scores(a_u8, b_u8, ssim=True):
     return out
 
 
+def frame_scores(xs, ys, ssim=True):
+    """The scores of image_scores straight from fp32 frames (binhip_frame_score; the validation loop of
+    models/bin_model.py:564-589).  `xs`, `ys`: equally long sequences of float32 device tensors [3,H,W] or [1,3,H,W] of one
+    H x W; pair i is (xs[i], ys[i]) and a tensor may appear in several pairs and on either side.  Every value is quantised
+    as util.tensor2img / frame_to_u8 do (clamp to [0, 1], x 255, round half to even; NaN -> 0) inside the kernel, which
+    writes no u8 image, and the pair is scored as image_scores scores the two images.  Returns a float64 device tensor
+    [n,4] of (sse, sad, ssim_g11, ssim_u7) with image_scores' conventions: current stream, no host sync, NaN for an SSIM
+    the frame is too small for, and below 7 x 7 an SSIM request raises.  Lists longer than BINHIP_SCORE_MAX_PAIRS take
+    several calls.  A non-contiguous tensor is copied."""
+    global _G11_TAPS
+    xs, ys = list(xs), list(ys)
+    if not xs or len(xs) != len(ys):
+        raise ValueError(f"frame_scores: two equally long, non-empty sequences of frames, got {len(xs)} and {len(ys)}")
+    _need_cuda(*xs, *ys)
+    shape = None
+    frames = []
+    for t in xs + ys:
+        if t.dtype != torch.float32:
+            raise ValueError(f"frame_scores: float32 frames, got {t.dtype}")
+        if not ((t.dim() == 3 and t.shape[0] == 3) or (t.dim() == 4 and tuple(t.shape[:2]) == (1, 3))):
+            raise ValueError(f"frame_scores: [3,H,W] or [1,3,H,W] frames, got {tuple(t.shape)}")
+        if shape is None:
+            shape = tuple(t.shape[-2:])
+        if tuple(t.shape[-2:]) != shape or t.device != xs[0].device:
+            raise ValueError(f"frame_scores: frames of one H x W on one device, got {tuple(t.shape)} next to {shape}")
+        frames.append(t.detach().contiguous())
+    h, w = shape
+    n = len(xs)
+    flags = 0
+    if ssim:
+        flags = L.SCORE_SSIM_U7 | (L.SCORE_SSIM_G11 if min(h, w) >= 11 else 0)
+    if _G11_TAPS is None:
+        from .utils.util import _gauss_taps
+        _G11_TAPS = (C.c_double * 11)(*[float(v) for v in _gauss_taps()])
+    lib = L.lib()
+    dev = xs[0].device
+    with on_device(xs[0]):
+        raw = torch.empty((n, 4), dtype=torch.int64, device=dev)               # BinImageScore {int64 sse, sad; double g11, u7}
+        for i0 in range(0, n, L.SCORE_MAX_PAIRS):
+            m = min(L.SCORE_MAX_PAIRS, n - i0)
+            nb = lib.binhip_frame_score_workspace_bytes(m, h, w, flags)
+            if nb == 0:
+                raise RuntimeError(f"bin_amd: frame_scores: unsupported frame size {h} x {w} (SSIM needs 7 x 7 pixels)")
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            px = (C.c_void_p * m)(*[frames[i0 + i].data_ptr() for i in range(m)])
+            py = (C.c_void_p * m)(*[frames[n + i0 + i].data_ptr() for i in range(m)])
+            L.check(lib.binhip_frame_score(px, py, m, h, w, flags, _G11_TAPS, _ptr(ws), nb, _ptr(raw[i0:i0 + m]), _stream()),
+                    "frame_score")
+        out = torch.empty((n, 4), dtype=torch.float64, device=dev)
+        out[:, :2] = raw[:, :2]
+        out[:, 2:] = raw[:, 2:].view(torch.float64)
+    return out
+
+
 # --------------------------------------------------------------------------------------------- training data
 GATHER_MAX_SLOTS = 32        # n_slots limit of binhip_gather_windows
 

@@ -19,9 +19,27 @@ def _ordered_loader():
     return Loader
 
 
+VAL_METRICS = ("host", "device")
+
+
+def val_metrics(opt):
+    """`train.val_metrics` (bin_amd extension): where train.validate scores the 14 outputs.  Absent or `host`: numpy on
+    frames copied to the host, as the reference does; `device`: ops.frame_scores on the fp32 outputs where they are.
+    Anything else raises."""
+    train = opt.get("train") if isinstance(opt, dict) else None
+    value = train.get("val_metrics") if isinstance(train, dict) else None
+    if value is None:
+        return "host"
+    if value not in VAL_METRICS:
+        raise ValueError(f"train.val_metrics: {value!r} is not one of {', '.join(VAL_METRICS)}")
+    return value
+
+
 def parse(opt_path, is_train=True):
     with open(opt_path) as f:
         opt = yaml.load(f, Loader=_ordered_loader())
+    if is_train:
+        val_metrics(opt)                     # a misspelt value stops the run here, not at the first validation pass
     if is_train and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the reference exports CUDA_VISIBLE_DEVICES from gpu_ids (torch on ROCm honours the same variable); under
         # a one-process-per-GPU launcher the launcher owns device visibility, so it is left alone there

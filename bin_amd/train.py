@@ -34,7 +34,9 @@ def init_dist(backend=None):
 
 
 def validate(model, loader, step, opt, log, max_batches=None):
-    """Mean loss and PSNR/SSIM of the 14 outputs over the validation windows (bin_model.py:427-589 meters)."""
+    """Mean loss and PSNR/SSIM of the 14 outputs over the validation windows (bin_model.py:427-589 meters).  The scores
+    come from numpy on the host or, with `train.val_metrics: device`, from one ops.frame_scores call per window."""
+    metrics = option.val_metrics(opt)
     model.val_loss_AverageMeter()
     model.val_AverageMeter_para()
     save_dir = os.path.join(opt["path"]["val_images"], str(step))
@@ -49,7 +51,8 @@ def validate(model, loader, step, opt, log, max_batches=None):
         save = i < int(opt["train"]["val_save_images"] or 0)
         if save:
             util.mkdir(save_dir)
-        psnr, ssim = model.compute_current_psnr_ssim(save=save, name=batch["key"][0], save_path=save_dir)
+        kw = {"metrics": metrics} if metrics != "host" else {}       # host: the reference's call, whatever wrapper `model` is
+        psnr, ssim = model.compute_current_psnr_ssim(save=save, name=batch["key"][0], save_path=save_dir, **kw)
         model.val_AverageMeter_para_update(psnr, ssim)
     _, psnr_dict, psnr_avg, ssim_avg, loss_avg = model.get_current_log(mode="val")
     log.info("<val iter:%8d> loss %.4e  psnr %.3f dB  ssim %.4f  interp(I7''') psnr %.3f dB", step, loss_avg, psnr_avg,

@@ -60,7 +60,7 @@ extern "C" {
  * `binhip_version() == BINHIP_VERSION` after dlopen.  BINHIP_ABI_EXPORTS = number of BINHIP_API entry points below
  * (tests/test_cpu_host.py keeps it equal to the declarations and to `nm -D`). */
 #define BINHIP_VERSION 622
-#define BINHIP_ABI_EXPORTS 49
+#define BINHIP_ABI_EXPORTS 51
 
 #define BINHIP_E_ARG      (-1)   /* null pointer / bad enum */
 #define BINHIP_E_SHAPE    (-2)   /* unsupported shape */
@@ -444,6 +444,25 @@ typedef struct BinImageScore {
 BINHIP_API size_t binhip_image_score_workspace_bytes(int n, int H, int W, int flags);
 BINHIP_API int binhip_image_score(const uint8_t* a, const uint8_t* b, int n, int H, int W, int flags, const double* g11_taps,
                        void* ws, size_t ws_bytes, BinImageScore* out, void* stream);
+
+/* ---- the same scores straight from fp32 frames (validation inside training: models/bin_model.py:564-589) ------------
+ * Scores n pairs of frames x[i], y[i].  `x`, `y`: HOST arrays of n DEVICE pointers, each one contiguous fp32 planar
+ * [3][H][W] frame (a network output, a ground-truth frame); the pointers travel to the kernel by value, so nothing is
+ * stacked or copied, and one frame may appear in several pairs and on either side.  Every value is first quantised with
+ * tensor2img's expression, exactly as binhip_frame_to_u8 does it: (uint8) rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.0f), so
+ * NaN -> 0, -inf -> 0, +inf -> 255; out[i] then holds the scores binhip_image_score gives for the two quantised images:
+ * sse and sad exact, ssim_g11 and ssim_u7 by the same formulas in fp64 (the 7x7 window sums exact in int32).  The
+ * quantised images live in on-chip tiles only; no u8 image is written to memory.  A field whose flag is not set is NaN.
+ * `ws`: binhip_frame_score_workspace_bytes() bytes (0 = bad shape or flag): one partial-sum slot per tile, summed in a
+ * fixed order by a second launch, so repeated calls give the same bits.  Neither allocates nor syncs; re-entrant on
+ * different streams.
+ * Errors: BINHIP_E_ARG for a null array, a null element, a null ws / out, missing g11_taps with BINHIP_SCORE_SSIM_G11
+ * or an unknown flag; BINHIP_E_SHAPE for n < 1 or > BINHIP_SCORE_MAX_PAIRS, H or W outside 1 .. 65535, < 11 with
+ * BINHIP_SCORE_SSIM_G11, < 7 with BINHIP_SCORE_SSIM_U7.                                                                 */
+#define BINHIP_SCORE_MAX_PAIRS 32
+BINHIP_API size_t binhip_frame_score_workspace_bytes(int n, int H, int W, int flags);
+BINHIP_API int binhip_frame_score(const float* const* x, const float* const* y, int n, int H, int W, int flags,
+                       const double* g11_taps, void* ws, size_t ws_bytes, BinImageScore* out, void* stream);
 
 /* ---- training batches from a device-resident frame arena (data/BIN_dataset.py:30-54, 63-183, models/bin_model.py:147-202)
  * The reference's loader reads the 17 frames of a window (6 blurry, 6 sharp, 5 in-between sharp), crops one (y0, x0) window
