@@ -100,43 +100,72 @@ class _RdnFn(torch.autograd.Function):
             raise RuntimeError(f"bin_amd: unsupported RDN shape N={n} H={h} W={w}")
         saved = torch.empty(nbytes, dtype=torch.uint8, device=frames[0].device)
         # the fused UPNet in training (round 6): forward = one 5x5 convolution + border ring, backward = BINHIP_BWD_FUSED_UPNET + the
-        # chain rule from the operator's gradient to UPNet.0 / UPNet.2 (rdn_plan.fused_upnet_weights under autograd)
+        # chain rule from the operator's gradient to UPNet.0 / UPNet.2 (rdn_plan.fused_upnet_operator under autograd).  Decided by the
+        # switches alone: the training operands are a set of their own, whatever inference calls built on this weight version
         fused = (bool(module.plan_flags & L.PLAN_FUSED_UPNET) and train_fused_upnet() and
-                 weights.ensure_fused_upnet(train=True) is not None and weights.fused_graph is not None)
+                 weights.ensure_fused_upnet(train=True) is not None)
         flags = module.plan_flags | L.PLAN_KEEP_ACTS | (L.PLAN_FUSED_UPNET_TRAIN if fused else 0)
         out = rdn_forward(weights, frames, ws=saved, flags=flags, profiler=module.profiler)
         ctx.fused_up = fused
         if module.debug_hook is not None:
-            module.debug_hook("forward", module, (n, h, w, n_frames, nterms), saved, {"shape": module.shape})
+            module.debug_hook("forward", module, (n, h, w, n_frames, nterms), saved, {"shape": module.shape, "fused_upnet": fused})
         ctx.module, ctx.nterms, ctx.n_frames = module, nterms, n_frames
         ctx.saved_ws = saved
+        # the backward uses the weight objects THIS forward used (backward-data weights, the fused operands and their graph), not
+        # whatever the module's one-entry cache holds by then: a call in another precision in between replaces that entry
+        ctx.weights = weights
         ctx.dims = (n, h, w)
         ctx.param_meta = [(tuple(a.shape), a.device) for a in args[n_frames:]]
         ctx.params = args[n_frames:]
-        # the backward-data weights are rebuilt from the CURRENT parameters: like torch's saved-tensor version check,
+        # the backward-data weights are laid out from the parameters on the first backward: like torch's saved-tensor version check,
         # refuse a backward after an in-place update of the weights this forward used (forward -> optimizer.step() ->
         # backward would otherwise silently mix old activations with new weights)
-        ctx.param_versions = [a._version for a in args[n_frames:]]
+        ctx.param_versions = [(a._version, a.data_ptr()) for a in args[n_frames:]]
         ctx.weights_gen = module._wgen
         # backward calls still owed to this weight set in the current step (the pyramid shares model1 / model2 / model3
         # between 4-5 / 3 / 2 calls): when the count returns to zero the set's gradients are complete and a data-parallel
         # reducer may start their all-reduce while the rest of the backward is still running (bin_model.FlatGradAllReduce)
         module._bwd_pending = getattr(module, "_bwd_pending", 0) + 1
+        ctx.owes_backward = True
         return out
 
     @staticmethod
     def backward(ctx, gout):
+        # every refusal is raised here on the host, ahead of binhip_rdn_backward, and leaves the module as a completed backward would
+        if ctx.saved_ws is None:
+            raise RuntimeError("bin_amd: the saved activations of this RDN call were released by an earlier backward through it (the "
+                               "forward's private workspace is freed as soon as its backward has run or was refused; "
+                               "retain_graph=True does not keep it): run the forward again")
+        try:
+            return _RdnFn._backward(ctx, gout)
+        except BaseException:
+            # this forward's backward will not happen: give back what it held and the backward call it owed to its weight set
+            ctx.saved_ws = ctx.weights = None
+            _RdnFn._settle(ctx)
+            raise
+
+    @staticmethod
+    def _settle(ctx):
+        """Take this call's owed backward off its weight set's count, once, on whichever exit of backward comes first."""
+        if ctx.owes_backward:
+            ctx.owes_backward = False
+            ctx.module._bwd_pending = getattr(ctx.module, "_bwd_pending", 1) - 1
+
+    @staticmethod
+    def _backward(ctx, gout):
         module, nterms, k = ctx.module, ctx.nterms, ctx.n_frames
         n, h, w = ctx.dims
+        if ctx.weights_gen != module._wgen or any((a._version, a.data_ptr()) != v for a, v in zip(ctx.params, ctx.param_versions)):
+            raise RuntimeError("bin_amd: a parameter of this RDN was modified in place between its forward and its backward "
+                               "(optimizer step, load_state_dict, broadcast, re-pointed storage ...): the gradient would be computed with "
+                               "weights the forward did not use")
         dev = gout.device
         gout = gout.contiguous().float()
         lib = L.lib()
-        if ctx.weights_gen != module._wgen or any(a._version != v for a, v in zip(ctx.params, ctx.param_versions)):
-            raise RuntimeError("bin_amd: a parameter of this RDN was modified in place between its forward and its backward "
-                               "(optimizer step, load_state_dict, broadcast ...): the gradient would be computed with "
-                               "weights the forward did not use")
+        weights = ctx.weights
+        fused = ctx.fused_up
         nt_bwd = 1 if (module.backward_precision == "f16" and nterms == 3) else nterms
-        dgw = module.kernel_weights(nterms).dgrad(module, nt_bwd)
+        dgw = weights.dgrad(module, nt_bwd, fused=fused)
         plan = L.BinRdnBwdPlan()
         plan.N, plan.H, plan.W, plan.n_inputs, plan.nterms = n, h, w, k, nt_bwd
         if nt_bwd != nterms:
@@ -163,7 +192,6 @@ class _RdnFn(torch.autograd.Function):
         for i in range(len(grads) // 2):
             plan.dw[i] = grads[2 * i].data_ptr()
             plan.db[i] = grads[2 * i + 1].data_ptr()
-        fused = getattr(ctx, "fused_up", False)
         if fused:
             nl, g0 = len(grads) // 2, module.shape[0]
             plan.reserved |= L.BWD_FUSED_UPNET
@@ -189,22 +217,22 @@ class _RdnFn(torch.autograd.Function):
                                             _ptr(ws), ws.numel(), _stream()), "rdn_backward")
         if module.debug_hook is not None:          # tools/fp16_headroom.py, tests: inspect the planes of this call
             module.debug_hook("backward", module, (n, h, w, k, nt_bwd), ws, {"input_grads": any(g is not None for g in gins),
-                                                                              "shape": module.shape})
-        ctx.saved_ws = None
+                                                                              "shape": module.shape, "fused_upnet": fused})
+        ctx.saved_ws = ctx.weights = None
         if fused:
             # dL/dW_eff -> dL/dW0, dL/db0, dL/dW2, dL/db2: the operators are a bilinear function of the two layers' parameters
             nl = len(grads) // 2
             dW = up_dwr.sum(0)                                                  # ring layout [9, 12, 25, G0]
             dB = up_dbr.sum(0)
             dW[4], dB[4] = up_dw4.reshape(12, g0, 25).permute(0, 2, 1), up_db4
-            leaves, Wr, Br = module.kernel_weights(nterms).fused_graph          # built by this weight version's forward
+            leaves, Wr, Br = weights.fused_graph                                # built by this call's own forward
             gup = torch.autograd.grad([Wr, Br], leaves, [dW, dB], retain_graph=True)
             for slot, g in zip((2 * (nl - 2), 2 * (nl - 2) + 1, 2 * (nl - 1), 2 * (nl - 1) + 1), gup):
                 if plan.reserved & L.BWD_ACCUMULATE:
                     grads[slot].add_(g.float())
                 else:
                     grads[slot].copy_(g.float())
-        module._bwd_pending = getattr(module, "_bwd_pending", 1) - 1
+        _RdnFn._settle(ctx)
         if module._bwd_pending == 0 and direct:
             cb = getattr(module, "_grads_ready_cb", None)
             if cb is not None:

@@ -215,8 +215,8 @@ int binhip_rdn_forward(const BinRdnPlan* p, const float* const* inputs, float* o
     if ((rc = conv(LG, 1, D * c0, G0, G0, P_, 0, h, ww, w.blk + (int64_t)cb * P, w.s_blk, c0, (int64_t)cb * P, w.g0, w.s_g, -1, 0))) return rc;
     // GFF.1 3x3, x += f__1 (RDN.py:200, 219)
     if ((rc = conv(LG + 1, 3, c0, G0, G0, P_, 0, h, ww, w.g0, w.s_g, 0, 0, w.g1, w.s_g, w.f1, w.s_f1))) return rc;
-    // UPNet as ONE 5x5 convolution G0 -> 12 sub-pixel channels (BINHIP_PLAN_FUSED_UPNET, include/binhip.h): inference only — training keeps
-    // the two layers, whose activations and separate weight gradients its backward needs
+    // UPNet as ONE 5x5 convolution G0 -> 12 sub-pixel channels (BINHIP_PLAN_FUSED_UPNET, include/binhip.h): inference, and a training
+    // forward (KEEP_ACTS) that also sets BINHIP_PLAN_FUSED_UPNET_TRAIN (backward: BINHIP_BWD_FUSED_UPNET); KEEP_ACTS alone keeps the two layers
     const bool fused_up = (p->reserved & BINHIP_PLAN_FUSED_UPNET) &&
                           (!(p->reserved & BINHIP_PLAN_KEEP_ACTS) || (p->reserved & BINHIP_PLAN_FUSED_UPNET_TRAIN)) &&
                           sh.L + 1 < BINHIP_RDN_MAX_LAYERS && p->w_hi[sh.L] && (nt == 1 || p->w_lo[sh.L]) && p->bias[sh.L] &&

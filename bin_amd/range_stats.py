@@ -53,9 +53,17 @@ def _stats(name, hi, lo=None, scale=1.0, cls=None, kind="activation"):
     return row
 
 
-def forward_stats(ws, dims, tag="", shape=(96, 12, 4, 32)):
+def _empty(name, cls, kind, scale=1.0):
+    """Row of a plane the call did not write (its bytes are whatever the allocator or an earlier call left there)."""
+    return {"tensor": name, "class": cls, "kind": kind, "elements": 0, "amax": 0.0, "min_nonzero": 0.0, "zero_share": 1.0,
+            "subnormal_share": 0.0, "scale": scale, "headroom": float("inf")}
+
+
+def forward_stats(ws, dims, tag="", shape=(96, 12, 4, 32), fused_upnet=False):
     """Rows for X0, F1, every dense block's input and its four conv outputs, G0, G1, U of ONE forward call whose
-    workspace `ws` was filled with BINHIP_PLAN_KEEP_ACTS (the training forward).  dims = (N, H, W, n_inputs, nterms)."""
+    workspace `ws` was filled with BINHIP_PLAN_KEEP_ACTS (the training forward).  dims = (N, H, W, n_inputs, nterms).
+    `fused_upnet`: the call ran UPNet as one 5x5 convolution (BINHIP_PLAN_FUSED_UPNET_TRAIN), which has no intermediate U: its
+    planes were never written and are reported as empty."""
     v = _layout(L.lib().binhip_rdn_workspace_layout, dims, L.RDN_LAYOUT_WORDS, shape)
     G0, D, Cc, G = shape
     c0, cg, cb = G0 // 16, G // 16, (G0 + Cc * G) // 16
@@ -80,14 +88,19 @@ def forward_stats(ws, dims, tag="", shape=(96, 12, 4, 32)):
                 add(f"RDB{d}.conv{c} out", o, cg * P, s_blk, "dense-block conv outputs (post-ReLU)")
     add("G0 = GFF.0", v[9], v[10], v[10])
     add("G1 = GFF.1 + F1", v[11], v[12], v[12])
-    add("U = UPNet.0 shuffled", v[13], v[14], v[14])
+    if fused_upnet:
+        rows.append(_empty(tag + "U = UPNet.0 shuffled", "U = UPNet.0 shuffled", "activation"))
+    else:
+        add("U = UPNet.0 shuffled", v[13], v[14], v[14])
     return rows
 
 
-def backward_stats(ws, dims, tag="", input_grads=True, shape=(96, 12, 4, 32)):
+def backward_stats(ws, dims, tag="", input_grads=True, shape=(96, 12, 4, 32), fused_upnet=False):
     """Rows for the gradient planes left in the backward workspace of ONE call (stored x its power-of-two scale).
     `input_grads=False`: the call produced no input-frame gradients (stage 1 of the pyramid reads the raw frames), so its
-    gX0 planes were never written and are reported as empty."""
+    gX0 planes were never written and are reported as empty.  `fused_upnet` (BINHIP_BWD_FUSED_UPNET): there is no gradient of an
+    intermediate U either — "g U" and "g U unshuffled" are empty, and "g out" is the ONE half-resolution chunk of sub-pixel gradients
+    (ring zeroed) that upnet_gsub_kernel writes at the start of its region, its lo plane right behind it."""
     v = _layout(L.lib().binhip_rdn_backward_workspace_layout, dims, L.RDN_BWD_LAYOUT_WORDS, shape)
     G0, D = shape[0], shape[1]
     c0 = G0 // 16
@@ -105,7 +118,13 @@ def backward_stats(ws, dims, tag="", input_grads=True, shape=(96, 12, 4, 32)):
 
     names = ("g out", "g U", "g U unshuffled", "g G1", "g G0", "g F1")
     for i, nm in enumerate(names):
-        add(nm, v[3 + 2 * i], v[4 + 2 * i], v[4 + 2 * i])
+        if fused_upnet and i == 0:
+            sub = dims[0] * (dims[1] // 2) * (dims[2] // 2) * 16
+            add(nm, v[3], sub, sub)
+        elif fused_upnet and i in (1, 2):
+            rows.append(_empty(tag + nm, nm, "gradient", scale))
+        else:
+            add(nm, v[3 + 2 * i], v[4 + 2 * i], v[4 + 2 * i])
     gy, s_gy = v[15], v[16]
     for d in range(D + 1):
         add("g SFENet2 out" if d == 0 else f"g RDB{d - 1} out", gy + d * c0 * P, c0 * P, s_gy, "g SFENet2 / dense-block outputs")
@@ -114,8 +133,7 @@ def backward_stats(ws, dims, tag="", input_grads=True, shape=(96, 12, 4, 32)):
     if input_grads:
         add("g X0", v[21], v[22], v[22])
     else:
-        rows.append({"tensor": tag + "g X0", "class": "g X0", "kind": "gradient", "elements": 0, "amax": 0.0, "min_nonzero": 0.0,
-                     "zero_share": 1.0, "subnormal_share": 0.0, "scale": scale, "headroom": float("inf")})
+        rows.append(_empty(tag + "g X0", "g X0", "gradient", scale))
     return rows
 
 
@@ -153,5 +171,6 @@ class Recorder:
         torch.cuda.synchronize()
         tag = f"{self.tag}{type(module).__name__[len('RDN_residual_interp_'):]} N={dims[0]} "
         shape = info.get("shape", (96, 12, 4, 32))
-        self.rows += (forward_stats(ws, dims, tag, shape) if kind == "forward"
-                      else backward_stats(ws, dims, tag, info.get("input_grads", True), shape))
+        fused = bool(info.get("fused_upnet", False))
+        self.rows += (forward_stats(ws, dims, tag, shape, fused) if kind == "forward"
+                      else backward_stats(ws, dims, tag, info.get("input_grads", True), shape, fused))

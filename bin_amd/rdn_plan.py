@@ -209,67 +209,76 @@ class RdnWeights:
         relayout_batch(items)
 
         self._dgrad = None
-        # the fused UPNet's operands (BINHIP_PLAN_FUSED_UPNET) are built on the first INFERENCE call of this weight version
-        # (ensure_fused_upnet): a training step rebuilds its RdnWeights every step and never needs them
-        self._up_src = tuple(params[f"{prefix}UPNet.{k}.{t}"] for k in (0, 2) for t in ("weight", "bias"))
+        # the fused UPNet's operands (BINHIP_PLAN_FUSED_UPNET) are built on first use for this weight version (ensure_fused_upnet), as
+        # TWO independent sets: `fused_up` for inference calls (float64 einsum, rounded once) and `fused_train` for differentiable calls
+        # (`fused_upnet_operator` in fp32 under autograd, with `fused_graph` for the chain rule back to UPNet.0 / UPNet.2).  Which set a
+        # call uses depends on the call alone, never on which kind of call touched this weight version first.
+        w0, _, w2, _ = src = tuple(params[f"{prefix}UPNet.{k}.{t}"] for k in (0, 2) for t in ("weight", "bias"))
+        fusable = tuple(w0.shape[2:]) == (3, 3) and w0.shape[0] == 256 and tuple(w2.shape) == (3, 64, 3, 3)
+        self._up_src = src if fusable else None          # None: this weight set's UPNet is not the 256 -> shuffle -> 3 one
         self.fused_up = None
         self.fused_w4 = None
+        self.fused_train = None
+        self.fused_train_w4 = None
         self.fused_graph = None
 
     def ensure_fused_upnet(self, train=False):
         """(ConvWeights of the [12][G0][5][5] interior operator, fp32 [9][12][25][G0] ring operators, fp32 [9][12] ring biases) or None when
-        this weight set's UPNet is not the 256 -> shuffle -> 3 one.  `train`: build them with `fused_upnet_operator` under autograd and
-        keep the graph (`fused_graph` = leaves, operators, biases): the backward maps the operators' gradients to UPNet.0 / UPNet.2."""
-        if self.fused_up is None and self._up_src is not None and train:
-            w0, b0, w2, b2 = self._up_src
-            if tuple(w0.shape[2:]) == (3, 3) and w0.shape[0] == 256 and tuple(w2.shape) == (3, 64, 3, 3):
+        this weight set's UPNet is not the 256 -> shuffle -> 3 one.  `train`: the set of the differentiable calls, built with
+        `fused_upnet_operator` under autograd, keeping the graph (`fused_graph` = leaves, operators, biases): the backward maps the
+        operators' gradients to UPNet.0 / UPNet.2.  Otherwise the inference set.  The two sets live side by side."""
+        if self._up_src is None:
+            return None
+        if train:
+            if self.fused_train is None:
                 with torch.enable_grad():
-                    leaves = [t.detach().float().requires_grad_() for t in (w0, b0, w2, b2)]
+                    leaves = [t.detach().float().requires_grad_() for t in self._up_src]
                     Wr, Br = fused_upnet_operator(*leaves)
                 self.fused_graph = (leaves, Wr, Br)
                 with torch.no_grad():
                     g0 = Wr.shape[3]
-                    self.fused_w4 = Wr[4].permute(0, 2, 1).reshape(12, g0, 5, 5).contiguous()
-                    main = ConvWeights(self.fused_w4, Br[4].detach().contiguous(), nterms=self.nterms)
-                    self.fused_up = (main, Wr.detach().contiguous(), Br.detach().contiguous())
-            self._up_src = None
-        if self.fused_up is None and self._up_src is not None:
+                    self.fused_train_w4 = Wr[4].permute(0, 2, 1).reshape(12, g0, 5, 5).contiguous()
+                    main = ConvWeights(self.fused_train_w4, Br[4].detach().contiguous(), nterms=self.nterms)
+                    self.fused_train = (main, Wr.detach().contiguous(), Br.detach().contiguous())
+            return self.fused_train
+        if self.fused_up is None:
             with torch.no_grad():
-                w0, b0, w2, b2 = self._up_src
-                if tuple(w0.shape[2:]) == (3, 3) and w0.shape[0] == 256 and tuple(w2.shape) == (3, 64, 3, 3):
-                    W, B = fused_upnet_weights(w0, b0, w2, b2)
-                    self.fused_w4 = W[4].float().contiguous()               # (RdnDgradWeights relayouts its transpose for the backward)
-                    main = ConvWeights(self.fused_w4, B[4].float().contiguous(), nterms=self.nterms)
-                    ring_w = W.permute(0, 1, 3, 4, 2).reshape(9, 12, 25, W.shape[2]).float().contiguous()
-                    self.fused_up = (main, ring_w, B.float().contiguous())
-            self._up_src = None
+                W, B = fused_upnet_weights(*self._up_src)
+                self.fused_w4 = W[4].float().contiguous()
+                main = ConvWeights(self.fused_w4, B[4].float().contiguous(), nterms=self.nterms)
+                ring_w = W.permute(0, 1, 3, 4, 2).reshape(9, 12, 25, W.shape[2]).float().contiguous()
+                self.fused_up = (main, ring_w, B.float().contiguous())
         return self.fused_up
 
-    def fill_plan(self, plan):
+    def fill_plan(self, plan, fused=None):
+        """`fused`: the fused UPNet's operands of THIS call (one of ensure_fused_upnet's two sets) for slots L, L + 1, or None."""
         plan.shape = c_shape(self.shape)
         for i, cw in enumerate(self.layers):
             plan.w_hi[i] = cw.w_hi.data_ptr()
             plan.w_lo[i] = cw.w_lo.data_ptr() if cw.w_lo is not None else None
             plan.bias[i] = cw.bias.data_ptr()
         n = len(self.layers)
-        if self.fused_up is not None:
-            main, ring_w, ring_b = self.fused_up
+        if fused is not None:
+            main, ring_w, ring_b = fused
             plan.w_hi[n], plan.bias[n] = main.w_hi.data_ptr(), main.bias.data_ptr()
             plan.w_lo[n] = main.w_lo.data_ptr() if main.w_lo is not None else None
             plan.w_hi[n + 1], plan.w_lo[n + 1], plan.bias[n + 1] = ring_w.data_ptr(), None, ring_b.data_ptr()
 
-    def dgrad(self, module, nterms=None):
+    def dgrad(self, module, nterms=None, fused=False):
         """Backward-data weights (transposed + flipped), built on first use for the same parameter version; `nterms`
-        other than the forward's for the single-product backward behind an f16x3 forward."""
+        other than the forward's for the single-product backward behind an f16x3 forward; `fused`: with the slots of
+        BINHIP_BWD_FUSED_UPNET (the training set of ensure_fused_upnet, which the forward of that backward built)."""
         nterms = self.nterms if nterms is None else nterms
         if self._dgrad is None:
             self._dgrad = {}
-        if nterms not in self._dgrad:
+        key = (nterms, bool(fused))
+        if key not in self._dgrad:
+            if fused and self.fused_train is None:
+                raise RuntimeError("bin_amd: backward of a fused-UPNet forward on weights that never built the training operands")
             with torch.no_grad():
-                self._dgrad[nterms] = RdnDgradWeights(dict(module.named_parameters()), self.n_inputs, nterms,
-                                                      shape=self.shape,
-                                                      fused=(self.fused_w4, self.fused_up[1]) if self.fused_up is not None else None)
-        return self._dgrad[nterms]
+                self._dgrad[key] = RdnDgradWeights(dict(module.named_parameters()), self.n_inputs, nterms, shape=self.shape,
+                                                   fused=(self.fused_train_w4, self.fused_train[1]) if fused else None)
+        return self._dgrad[key]
 
 
 class RdnDgradWeights:
@@ -389,8 +398,9 @@ def default_plan_flags():
     """Plan flags a freshly built RDN module starts with (its `plan_flags` attribute; tests pass BINHIP_PLAN_NO_FUSE /
     BINHIP_PLAN_RDB3 per call).  BIN_AMD_RDB3=1: convs 0-2 of every dense block as three phases of one launch."""
     flags = L.PLAN_RDB3 if _os.environ.get("BIN_AMD_RDB3", "0") == "1" else 0
-    # round 6: UPNet (conv3x3 -> PixelShuffle -> conv3x3, no activation in between) as ONE 5x5 convolution in inference (fp32-class
-    # mode; same function up to fp32 summation order, 3.4 x fewer multiply-adds).  BIN_AMD_FUSED_UPNET=0: the two layers, as in training
+    # round 6: UPNet (conv3x3 -> PixelShuffle -> conv3x3, no activation in between) as ONE 5x5 convolution, in inference and (unless
+    # BIN_AMD_FUSED_UPNET_TRAIN=0, autograd.train_fused_upnet) in training; same function up to fp32 summation order, 3.4 x fewer
+    # multiply-adds.  BIN_AMD_FUSED_UPNET=0: the two layers everywhere
     if _os.environ.get("BIN_AMD_FUSED_UPNET", "1") != "0":
         flags |= L.PLAN_FUSED_UPNET
     return flags
@@ -415,9 +425,13 @@ def _rdn_forward(weights, inputs, out, ws, flags, profiler):
     plan.reserved = int(flags or 0)
     plan.status = status_word(inputs[0].device).data_ptr()
     plan.profiler = profiler if profiler else None
-    if (plan.reserved & L.PLAN_FUSED_UPNET) and (not (plan.reserved & L.PLAN_KEEP_ACTS) or (plan.reserved & L.PLAN_FUSED_UPNET_TRAIN)):
-        weights.ensure_fused_upnet()
-    weights.fill_plan(plan)
+    fused = None
+    if plan.reserved & L.PLAN_FUSED_UPNET:
+        if plan.reserved & L.PLAN_FUSED_UPNET_TRAIN:
+            fused = weights.ensure_fused_upnet(train=True)
+        elif not (plan.reserved & L.PLAN_KEEP_ACTS):
+            fused = weights.ensure_fused_upnet()
+    weights.fill_plan(plan, fused)
     nbytes = lib.binhip_rdn_workspace_bytes(n, h, w, weights.n_inputs, weights.nterms, C.byref(plan.shape))
     if nbytes == 0:
         raise RuntimeError(f"bin_amd: unsupported RDN shape N={n} H={h} W={w} (H, W must be even)")

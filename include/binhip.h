@@ -295,7 +295,7 @@ BINHIP_API int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* 
 #define BINHIP_PLAN_RDB3      4   /* nterms = 3: convs 0-2 of each RDB as three phases of ONE launch */
                                   /* (static tile ownership + per-tile neighbour flags, no grid       */
                                   /* barrier; per-conv launches when the grid cannot be co-resident)  */
-#define BINHIP_PLAN_FUSED_UPNET 8 /* inference (not with KEEP_ACTS), both modes:  UPNet = conv3x3(G0 -> 256) -> PixelShuffle(2) ->   */
+#define BINHIP_PLAN_FUSED_UPNET 8 /* inference, or KEEP_ACTS with _FUSED_UPNET_TRAIN; both modes:  UPNet = conv3x3 -> PixelShuffle(2) -> */
                                   /* conv3x3(64 -> 3) (RDN.py:203-207) has no activation in between, so it IS one linear map:     */
                                   /* a 5x5 convolution G0 -> 12 at half resolution (W_eff = W2 * shuffle * W0, 3.4 x fewer MACs,  */
                                   /* no 256-channel intermediate).  The caller supplies it: slot L = 2 + D (C + 1) + 4 of         */
@@ -304,7 +304,7 @@ BINHIP_API int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* 
                                   /* v = 0 first row / column, 1 interior, 2 last): the one-pixel full-resolution border ring,     */
                                   /* where UPNet.2's zero padding of the INTERMEDIATE differs from padding the input, is           */
                                   /* recomputed exactly by a second small launch.  Same function as the two-layer form up to fp32  */
-                                  /* summation order; bin_amd/rdn_plan.py builds the operands (fused_upnet_weights).               */
+                                  /* summation order; bin_amd/rdn_plan.py builds the operands (RdnWeights.ensure_fused_upnet).     */
 #define BINHIP_PLAN_FUSED_UPNET_TRAIN 16 /* with KEEP_ACTS: the fused UPNet in the TRAINING forward too (needs the slots of          */
                                         /* BINHIP_PLAN_FUSED_UPNET); its backward is BINHIP_BWD_FUSED_UPNET                          */
 typedef struct BinRdnPlan {

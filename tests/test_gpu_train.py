@@ -280,6 +280,61 @@ def test_backward_refuses_weights_modified_after_forward(canon_cpu):
     assert mod.SFENet1.weight.grad is not None and torch.isfinite(mod.SFENet1.weight.grad).all()
 
 
+@pytest.mark.parametrize("route", ["repoint", "data_copy_invalidate"])
+def test_new_parameter_values_reach_the_next_forward(route, canon_cpu):
+    """Both ways of changing a parameter behind the version counters: re-pointing its storage (`p.data = p.data.clone()`, then new values —
+    the cache key holds every data_ptr, so no invalidate_kernel_weights() is needed) and `.data.copy_()` followed by
+    invalidate_kernel_weights().  The next inference and training calls equal a fresh module's with the new values, bit for bit; and a
+    forward from before a re-pointing refuses its backward like any other weight change."""
+    from bin_amd.models.archs import RDN as A
+    from bin_amd.weights import rdn_param_shapes
+    sd = {n: canon_cpu[f"model1.{n}"].clone() for n in rdn_param_shapes(2)}
+    changed = ("SFENet1.weight", "RDBs.5.convs.2.conv.0.bias", "UPNet.2.weight")
+    new = {n: (sd[n] * 1.25 if n in changed else sd[n]) for n in sd}
+    g = torch.Generator().manual_seed(3)
+    ins = [torch.rand(2, 3, 12, 14, generator=g).cuda() for _ in range(2)]
+    gout = torch.randn(2, 3, 12, 14, generator=g).cuda() * 1e-3
+
+    def both(mod):
+        with torch.no_grad():
+            inf = mod(*ins).clone()
+        xs = [t.clone().requires_grad_(True) for t in ins]
+        out = mod(*xs)
+        out.backward(gout)
+        grads = [p.grad.clone() for p in mod.parameters()] + [x.grad for x in xs]
+        for p in mod.parameters():
+            p.grad = None
+        return [inf, out.detach().clone()] + grads
+
+    def make(weights):
+        mod = A.RDN_residual_interp_2_input(G0=96, D=12)
+        mod.load_state_dict(weights)
+        return mod.cuda()
+    ref = both(make(new))
+    mod = make(sd)
+    old = both(mod)                                        # the kernel-side copies of the OLD values are cached now
+    assert not torch.equal(old[0], ref[0])
+    pending = mod(*[t.clone().requires_grad_(True) for t in ins])
+    named = dict(mod.named_parameters())
+    for n in changed:
+        if route == "repoint":
+            ptr = named[n].data_ptr()
+            named[n].data = named[n].data.clone()
+            assert named[n].data_ptr() != ptr
+            named[n].data.mul_(1.25)
+        else:
+            named[n].data.copy_(new[n])
+    if route != "repoint":
+        mod.invalidate_kernel_weights()
+    with pytest.raises(RuntimeError, match="modified in place"):
+        pending.backward(gout)
+    got = both(mod)
+    assert len(got) == len(ref) == 2 + 132 + 2
+    bad = [i for i, (a, b) in enumerate(zip(got, ref)) if not torch.equal(a, b)]
+    assert not bad, f"{route}: tensors {bad} differ from a fresh module's with the new values"
+    assert mod._bwd_pending == 0
+
+
 def _train_opt_r3(tmp_path, dist=False):
     return {"model": "bin", "gpu_ids": [0], "is_train": True, "dist": dist,
             "network_G": {"which_model_G": "bin_stage4", "nframes": 6, "version": 2, "precision": "f16x3"},
