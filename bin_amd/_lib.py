@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import LIB_PATH
+from .build import LIB_PATH, OPT_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -70,6 +70,14 @@ class BinRelayoutItem(C.Structure):
 RELAYOUT_FWD, RELAYOUT_DGRAD, RELAYOUT_RDB_GATHER = 0, 1, 2
 SCORE_SSIM_G11, SCORE_SSIM_U7 = 1, 2   # BINHIP_SCORE_SSIM_* flags of binhip_image_score / binhip_frame_score
 SCORE_MAX_PAIRS = 32                   # BINHIP_SCORE_MAX_PAIRS
+
+ADAM_MAX_TENSORS = 64                  # BINOPT_ADAM_MAX_TENSORS (include/binopt.h, libbinopt.so)
+
+
+class BinAdamTensor(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_int64),
+                ("step_size", C.c_float), ("inv_sqrt_bc2", C.c_float)]
+
 
 _SIGNATURES = {
     "binhip_version": (C.c_int, []),
@@ -158,6 +166,13 @@ _SIGNATURES = {
                                    [C.c_void_p, C.c_void_p]),
 }
 
+# libbinopt.so (include/binopt.h): the optimizer library, loaded on first use
+OPT_VERSION = 100                      # BINOPT_VERSION
+_OPT_SIGNATURES = {
+    "binopt_version": (C.c_int, []),
+    "binopt_adam_step": (C.c_int, [C.POINTER(BinAdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
@@ -185,6 +200,34 @@ def lib():
             fn.argtypes = args
         _lib = h
     return _lib
+
+
+_optlib = None
+
+
+def opt_exported_symbols():
+    """Names every include/binopt.h entry point must resolve to."""
+    return sorted(_OPT_SIGNATURES)
+
+
+def optlib():
+    """Load libbinopt.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _optlib
+    if _optlib is None:
+        path = OPT_LIB_PATH
+        if not os.path.exists(path):
+            raise RuntimeError(
+                f"bin_amd: HIP library {OPT_LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; "
+                f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
+        h = C.CDLL(path)
+        for name, (res, args) in _OPT_SIGNATURES.items():
+            fn = getattr(h, name)
+            fn.restype = res
+            fn.argtypes = args
+        if h.binopt_version() != OPT_VERSION:
+            raise RuntimeError(f"bin_amd: {path} is version {h.binopt_version()}, this binding is for {OPT_VERSION}")
+        _optlib = h
+    return _optlib
 
 
 def check(rc, what):

@@ -12,6 +12,10 @@ CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["binhip_conv.hip", "binhip_conv_x3.hip", "binhip_fused.hip", "binhip_fused_x3.hip", "binhip_wgrad.hip", "binhip_misc.hip", "binhip_plan.hip",
            "binhip_metrics.hip", "binhip_data.hip"]
 LIB_PATH = os.path.join(CSRC, "libbinhip.so")
+# the optimizer library (include/binopt.h): a shared object of its own, so that libbinhip.so's interface does not change with it
+OPT_SOURCES = ["binopt_adam.hip"]
+OPT_LIB_PATH = os.path.join(CSRC, "libbinopt.so")
+OPT_HEADER = os.path.join(os.path.dirname(HERE), "include", "binopt.h")
 
 
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
@@ -24,17 +28,25 @@ def abi_symbols():
         return re.findall(r"(?m)^BINHIP_API\s+[\w\s\*]+?\b(binhip_\w+)\s*\(", f.read())
 
 
+def opt_abi_symbols():
+    """The entry points include/binopt.h declares (every BINOPT_API declaration), in header order."""
+    import re
+    with open(OPT_HEADER) as f:
+        return re.findall(r"(?m)^BINOPT_API\s+[\w\s\*]+?\b(binopt_\w+)\s*\(", f.read())
+
+
 def _stale():
-    if not os.path.exists(LIB_PATH):
+    if not os.path.exists(LIB_PATH) or not os.path.exists(OPT_LIB_PATH):
         return True
-    t = os.path.getmtime(LIB_PATH)
+    t = min(os.path.getmtime(LIB_PATH), os.path.getmtime(OPT_LIB_PATH))
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    deps.append(os.path.join(os.path.dirname(HERE), "include", "binhip.h"))
+    deps += [os.path.join(os.path.dirname(HERE), "include", "binhip.h"), OPT_HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def build_library(force=False, verbose=True, defines=(), out=None):
-    """Compile every HIP source for gfx950 into bin_amd/csrc/libbinhip.so.
+    """Compile every HIP source for gfx950 into bin_amd/csrc/libbinhip.so (and, for the product build, the optimizer
+    library bin_amd/csrc/libbinopt.so beside it).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain).  The sources are compiled in parallel (one
@@ -46,15 +58,15 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     objdir = CSRC if out is None else os.path.dirname(os.path.abspath(out))
     os.makedirs(objdir, exist_ok=True)
     tag = "" if out is None else "." + os.path.splitext(os.path.basename(out))[0]
-    procs, objs = [], []
-    for src in SOURCES:
+    procs, objs, opt_objs = [], [], []
+    for src in SOURCES + (OPT_SOURCES if out is None else []):
         obj = os.path.join(objdir, src.replace(".hip", tag + ".o"))
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"] + [f"-D{d}" for d in defines] + \
               ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((cmd, subprocess.Popen(cmd)))
-        objs.append(obj)
+        (opt_objs if src in OPT_SOURCES else objs).append(obj)
     for cmd, p in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
@@ -70,6 +82,15 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
+    if out is None:                                  # libbinopt.so: the same recipe, its exports from include/binopt.h
+        vmap = os.path.join(objdir, "binhip_exports.binopt.map")
+        with open(vmap, "w") as f:
+            f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in opt_abi_symbols()) + "  local: *;\n};\n")
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", f"-Wl,--version-script={vmap}",
+               "-o", OPT_LIB_PATH] + opt_objs
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
     return lib_path
 
 

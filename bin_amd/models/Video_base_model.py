@@ -22,6 +22,7 @@ from . import lr_scheduler, networks
 from .base_model import BaseModel, _direct_param_grads
 from .bin_model import FlatGradAllReduce, SingleProcessParallel, _get
 from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
+from ..options.options import adam_class
 from ..utils import util
 
 logger = logging.getLogger("base")
@@ -77,8 +78,9 @@ class VideoBaseModel(BaseModel):
                       {"params": [p for n, p in trainable if "tsa_fusion" in n], "lr": train_opt["lr_G"]}]
         else:
             params = [p for _, p in trainable]
-        self.optimizer_G = torch.optim.Adam(params, lr=train_opt["lr_G"], weight_decay=_get(train_opt, "weight_decay_G", 0),
-                                            betas=(train_opt["beta1"], train_opt["beta2"]))
+        # train.optimizer (bin_amd extension): torch.optim.Adam unless the option says `hip` (bin_amd/optim.py)
+        self.optimizer_G = adam_class(opt)(params, lr=train_opt["lr_G"], weight_decay=_get(train_opt, "weight_decay_G", 0),
+                                           betas=(train_opt["beta1"], train_opt["beta2"]))
         self.optimizers.append(self.optimizer_G)
         scheme = train_opt["lr_scheme"]
         if scheme == "MultiStepLR":

@@ -20,6 +20,7 @@ from . import lr_scheduler
 from . import networks
 from .base_model import BaseModel, unwrap, _direct_param_grads
 from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
+from ..options.options import adam_class
 from ..utils import dist_util, util
 from ..utils.util import AverageMeter
 
@@ -267,8 +268,9 @@ class bin_model(BaseModel):
                                 {"params": [v for k, v in trainable if "tsa_fusion" in k], "lr": train_opt["lr_G"]}]
             else:
                 optim_params = [v for _, v in trainable]
-            self.optimizer_G = torch.optim.Adam(optim_params, lr=train_opt["lr_G"], weight_decay=wd_G,
-                                                betas=(train_opt["beta1"], train_opt["beta2"]))
+            # train.optimizer (bin_amd extension): torch.optim.Adam unless the option says `hip` (bin_amd/optim.py)
+            self.optimizer_G = adam_class(opt)(optim_params, lr=train_opt["lr_G"], weight_decay=wd_G,
+                                               betas=(train_opt["beta1"], train_opt["beta2"]))
             self.optimizers.append(self.optimizer_G)
 
             scheme = train_opt["lr_scheme"]

@@ -711,3 +711,52 @@ def gather_windows_blur(frames_u8, table_host, crop, n_blur, clip_ranges=None):
         L.check(L.lib().binhip_gather_windows_blur(_ptr(frames_u8), nf, h, w, _ptr(table), n, n_slots, n_blur, ch, cw, _ptr(out),
                                                    _stream()), "gather_windows_blur")
     return out
+
+
+# --------------------------------------------------------------------------------------------- optimizer
+def adam_rows(n):
+    """A host table of n BinAdamTensor rows for adam_step (bin_amd.optim.Adam keeps one per group and rewrites only what changed)."""
+    return (L.BinAdamTensor * max(n, 1))()
+
+
+def adam_row(table, i, p, g, m, v, step_size, inv_sqrt_bc2):
+    """Fill row i of an adam_rows table from four float32 device tensors of one size.  Raises on CPU tensors (there is no CPU
+    fallback), on another dtype and on non-contiguous tensors: the kernel walks numel consecutive floats from each pointer."""
+    _need_cuda(p, g, m, v)
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if t.dtype != torch.float32:
+            raise ValueError(f"adam_step: float32 tensors, got {t.dtype} for {name}")
+        if not t.is_contiguous():
+            raise ValueError(f"adam_step: contiguous tensors, got strides {tuple(t.stride())} of shape {tuple(t.shape)} for {name}")
+        if t.numel() != p.numel() or t.device != p.device:
+            raise ValueError(f"adam_step: {name} has {t.numel()} elements on {t.device}, p has {p.numel()} on {p.device}")
+    if p.numel() < 1:
+        raise ValueError("adam_step: empty tensor")
+    r = table[i]
+    r.p, r.g, r.m, r.v, r.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    r.step_size, r.inv_sqrt_bc2 = step_size, inv_sqrt_bc2
+
+
+def adam_launch(table, n, device, beta1, beta2, eps, weight_decay):
+    """binopt_adam_step over the first n rows of an adam_rows table, on `device`'s current stream."""
+    if n == 0:
+        return
+    with torch.cuda.device(device):
+        L.check(L.optlib().binopt_adam_step(table, n, beta1, beta2, eps, weight_decay, _stream()), "adam_step")
+
+
+def adam_step(rows, beta1, beta2, eps, weight_decay):
+    """One Adam update of every row in place (binopt_adam_step: one elementwise kernel over a by-value table of tensors,
+    BINOPT_ADAM_MAX_TENSORS rows per launch, current stream, no host sync).  `rows`: a sequence of
+    (p, g, m, v, step_size, inv_sqrt_bc2): float32 contiguous device tensors of one size each (views at any 4-byte offset are
+    fine) and the two bias-correction factors lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) of that tensor's step t.  p, m, v
+    are written through raw pointers: the caller bumps their version counters (torch.autograd.graph.increment_version).
+    Raises on CPU tensors (there is no CPU fallback), on non-float32 and on non-contiguous tensors."""
+    rows = list(rows)
+    table = adam_rows(len(rows))
+    for i, (p, g, m, v, step_size, inv_sqrt_bc2) in enumerate(rows):
+        adam_row(table, i, p, g, m, v, step_size, inv_sqrt_bc2)
+    if rows:
+        if any(r[0].device != rows[0][0].device for r in rows):
+            raise ValueError("adam_step: rows of one call live on one device")
+        adam_launch(table, len(rows), rows[0][0].device, beta1, beta2, eps, weight_decay)

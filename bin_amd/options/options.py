@@ -35,11 +35,37 @@ def val_metrics(opt):
     return value
 
 
+OPTIMIZERS = ("torch", "hip")
+
+
+def optimizer(opt):
+    """`train.optimizer` (bin_amd extension): which Adam the wrappers build.  Absent or `torch`: torch.optim.Adam, as the
+    reference does; `hip`: bin_amd.optim.Adam, the same update as one HIP multi-tensor kernel with torch's state format.
+    Anything else raises."""
+    train = opt.get("train") if isinstance(opt, dict) else None
+    value = train.get("optimizer") if isinstance(train, dict) else None
+    if value is None:
+        return "torch"
+    if value not in OPTIMIZERS:
+        raise ValueError(f"train.optimizer: {value!r} is not one of {', '.join(OPTIMIZERS)}")
+    return value
+
+
+def adam_class(opt):
+    """The Adam class `train.optimizer` names."""
+    if optimizer(opt) == "hip":
+        from ..optim import Adam
+        return Adam
+    import torch
+    return torch.optim.Adam
+
+
 def parse(opt_path, is_train=True):
     with open(opt_path) as f:
         opt = yaml.load(f, Loader=_ordered_loader())
     if is_train:
         val_metrics(opt)                     # a misspelt value stops the run here, not at the first validation pass
+        optimizer(opt)
     if is_train and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the reference exports CUDA_VISIBLE_DEVICES from gpu_ids (torch on ROCm honours the same variable); under
         # a one-process-per-GPU launcher the launcher owns device visibility, so it is left alone there
