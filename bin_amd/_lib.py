@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import LIB_PATH, OPT_LIB_PATH
+from .build import GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -77,6 +77,19 @@ ADAM_MAX_TENSORS = 64                  # BINOPT_ADAM_MAX_TENSORS (include/binopt
 class BinAdamTensor(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_int64),
                 ("step_size", C.c_float), ("inv_sqrt_bc2", C.c_float)]
+
+
+GRAD_MAX_TENSORS = 128                 # BINGRAD_MAX_TENSORS (include/bingrad.h, libbingrad.so)
+GRAD_FLAG_NONFINITE, GRAD_FLAG_STATUS = 1, 2   # BINGRAD_FLAG_*
+
+
+class BinGradTensor(C.Structure):
+    _fields_ = [("g", C.c_void_p), ("numel", C.c_int64)]
+
+
+class BinGradRecord(C.Structure):
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_float), ("coef", C.c_float), ("flags", C.c_int32), ("status", C.c_uint32),
+                ("reserved", C.c_int32 * 2)]
 
 
 _SIGNATURES = {
@@ -173,6 +186,16 @@ _OPT_SIGNATURES = {
     "binopt_adam_step": (C.c_int, [C.POINTER(BinAdamTensor), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
 }
 
+# libbingrad.so (include/bingrad.h): the gradient-guard library, loaded on first use
+GRAD_VERSION = 100                     # BINGRAD_VERSION
+_GRAD_SIGNATURES = {
+    "bingrad_version": (C.c_int, []),
+    "bingrad_norm_workspace_bytes": (C.c_int64, [C.POINTER(BinGradTensor), C.c_int]),
+    "bingrad_norm": (C.c_int, [C.POINTER(BinGradTensor), C.c_int, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "bingrad_scale": (C.c_int, [C.POINTER(BinGradTensor), C.c_int, C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
@@ -228,6 +251,34 @@ def optlib():
             raise RuntimeError(f"bin_amd: {path} is version {h.binopt_version()}, this binding is for {OPT_VERSION}")
         _optlib = h
     return _optlib
+
+
+_gradlib = None
+
+
+def grad_exported_symbols():
+    """Names every include/bingrad.h entry point must resolve to."""
+    return sorted(_GRAD_SIGNATURES)
+
+
+def gradlib():
+    """Load libbingrad.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _gradlib
+    if _gradlib is None:
+        path = GRAD_LIB_PATH
+        if not os.path.exists(path):
+            raise RuntimeError(
+                f"bin_amd: HIP library {GRAD_LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; "
+                f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
+        h = C.CDLL(path)
+        for name, (res, args) in _GRAD_SIGNATURES.items():
+            fn = getattr(h, name)
+            fn.restype = res
+            fn.argtypes = args
+        if h.bingrad_version() != GRAD_VERSION:
+            raise RuntimeError(f"bin_amd: {path} is version {h.bingrad_version()}, this binding is for {GRAD_VERSION}")
+        _gradlib = h
+    return _gradlib
 
 
 def check(rc, what):

@@ -22,7 +22,7 @@ from . import lr_scheduler, networks
 from .base_model import BaseModel, _direct_param_grads
 from .bin_model import FlatGradAllReduce, SingleProcessParallel, _get
 from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class
+from ..options.options import adam_class, grad_guard
 from ..utils import util
 
 logger = logging.getLogger("base")
@@ -50,6 +50,7 @@ class VideoBaseModel(BaseModel):
         self.grad_sync = FlatGradAllReduce(self.netG.parameters()) if opt["dist"] else None
         self.print_network()
         self.load()
+        self.grad_guard = None
         if not self.is_train:
             return
 
@@ -82,6 +83,8 @@ class VideoBaseModel(BaseModel):
         self.optimizer_G = adam_class(opt)(params, lr=train_opt["lr_G"], weight_decay=_get(train_opt, "weight_decay_G", 0),
                                            betas=(train_opt["beta1"], train_opt["beta2"]))
         self.optimizers.append(self.optimizer_G)
+        # train.grad_clip / train.skip_bad_steps (bin_amd extensions): one guard over both groups' parameters, None when both are off
+        self.grad_guard = grad_guard(opt, [p for _, p in trainable])
         scheme = train_opt["lr_scheme"]
         if scheme == "MultiStepLR":
             sched = lr_scheduler.MultiStepLR_Restart(
@@ -137,7 +140,8 @@ class VideoBaseModel(BaseModel):
             l_pix.backward()
         if self.grad_sync is not None:
             self.grad_sync()
-        self.optimizer_G.step()
+        if self.grad_guard is None or self.grad_guard.apply():     # a skipped step still counts as an iteration
+            self.optimizer_G.step()
         if parts is None:
             self.log_dict["l_pix"] = l_pix.item()
         else:

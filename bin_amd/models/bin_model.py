@@ -20,7 +20,7 @@ from . import lr_scheduler
 from . import networks
 from .base_model import BaseModel, unwrap, _direct_param_grads
 from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class
+from ..options.options import adam_class, grad_guard
 from ..utils import dist_util, util
 from ..utils.util import AverageMeter
 
@@ -238,6 +238,7 @@ class bin_model(BaseModel):
 
         self.print_network()
         self.load()
+        self.grad_guard = None
 
         if self.is_train:
             self.netG.train()
@@ -272,6 +273,8 @@ class bin_model(BaseModel):
             self.optimizer_G = adam_class(opt)(optim_params, lr=train_opt["lr_G"], weight_decay=wd_G,
                                                betas=(train_opt["beta1"], train_opt["beta2"]))
             self.optimizers.append(self.optimizer_G)
+            # train.grad_clip / train.skip_bad_steps (bin_amd extensions): a guard between backward and step, None when both are off
+            self.grad_guard = grad_guard(opt, [v for _, v in trainable])
 
             scheme = train_opt["lr_scheme"]
             if scheme == "MultiStepLR":
@@ -331,7 +334,10 @@ class bin_model(BaseModel):
             l_pix.backward()
         if self.grad_sync is not None:
             self.grad_sync()
-        self.optimizer_G.step()
+        # a skipped step (the guard found non-finite gradients or fp16 saturation) leaves the weights and the optimizer state as they
+        # were; it still counts as an iteration for the schedule and the logger, as a GradScaler skip does
+        if self.grad_guard is None or self.grad_guard.apply():
+            self.optimizer_G.step()
 
     def set_params_lr_zero(self):
         self.optimizers[0].param_groups[0]["lr"] = 0

@@ -760,3 +760,85 @@ def adam_step(rows, beta1, beta2, eps, weight_decay):
         if any(r[0].device != rows[0][0].device for r in rows):
             raise ValueError("adam_step: rows of one call live on one device")
         adam_launch(table, len(rows), rows[0][0].device, beta1, beta2, eps, weight_decay)
+
+
+# --------------------------------------------------------------------------------------------- gradient guard
+GRAD_RECORD_WORDS = 8          # BinGradRecord (include/bingrad.h) as int32 words: sumsq (2), norm, coef, flags, status, reserved (2)
+GRAD_FLAGS_WORD = 4            # ... the word a data-parallel caller all-reduces with MAX
+
+
+class GradRows:
+    """A host table of BinGradTensor rows over float32 device tensors of one device (grad_rows)."""
+    __slots__ = ("table", "n", "device", "workspace_bytes", "numel")
+
+    def __init__(self, table, n, device, workspace_bytes, numel):
+        self.table, self.n, self.device, self.workspace_bytes, self.numel = table, n, device, workspace_bytes, numel
+
+
+def grad_rows(grads):
+    """The host row table of grad_norm / grad_scale over `grads`: float32 contiguous device tensors of one device (views at any
+    4-byte offset are fine).  The caller keeps it while no pointer changed (bin_amd.optim.GradGuard does).  Raises on CPU tensors
+    (there is no CPU fallback), on another dtype and on non-contiguous or empty tensors."""
+    grads = list(grads)
+    _need_cuda(*grads)
+    table = (L.BinGradTensor * max(len(grads), 1))()
+    for i, g in enumerate(grads):
+        if g.dtype != torch.float32:
+            raise ValueError(f"grad_rows: float32 tensors, got {g.dtype}")
+        if not g.is_contiguous():
+            raise ValueError(f"grad_rows: contiguous tensors, got strides {tuple(g.stride())} of shape {tuple(g.shape)}")
+        if g.numel() < 1:
+            raise ValueError("grad_rows: empty tensor")
+        if g.device != grads[0].device:
+            raise ValueError("grad_rows: rows of one table live on one device")
+        table[i].g, table[i].numel = g.data_ptr(), g.numel()
+    nbytes = L.gradlib().bingrad_norm_workspace_bytes(table, len(grads))
+    if nbytes < 0:
+        L.check(int(nbytes), "grad_norm_workspace_bytes")
+    device = grads[0].device if grads else torch.device("cuda", torch.cuda.current_device())
+    return GradRows(table, len(grads), device, int(nbytes), sum(g.numel() for g in grads))
+
+
+def grad_record(device):
+    """A device BinGradRecord as 8 int32 words; word GRAD_FLAGS_WORD is `flags`."""
+    return torch.zeros(GRAD_RECORD_WORDS, dtype=torch.int32, device=device)
+
+
+def grad_record_read(words):
+    """A BinGradRecord from its 8 int32 words on the HOST (a CPU tensor or a numpy array) -> _lib.BinGradRecord."""
+    import numpy as np
+    raw = np.ascontiguousarray(words.numpy() if isinstance(words, torch.Tensor) else words, dtype=np.int32)
+    assert raw.size == GRAD_RECORD_WORDS
+    return L.BinGradRecord.from_buffer_copy(raw.tobytes())
+
+
+def grad_norm(rows, workspace, record, max_norm=0.0, status=None, status_mask=0):
+    """bingrad_norm over a grad_rows table on its device's current stream, no host sync: the global sum of squares in double (one
+    deterministic pass, no atomics), its root, the clip coefficient of torch.nn.utils.clip_grad_norm_ for `max_norm` (0 = off) and
+    the flags into `record` (grad_record).  `workspace`: the caller's device tensor of at least rows.workspace_bytes bytes;
+    `status`: None, or the device status word (status_word), which is read under `status_mask`, never written."""
+    _need_cuda(workspace, record, status)
+    if workspace.numel() * workspace.element_size() < rows.workspace_bytes or not workspace.is_contiguous():
+        raise ValueError(f"grad_norm: workspace of {workspace.numel() * workspace.element_size()} bytes, need {rows.workspace_bytes}")
+    if workspace.data_ptr() % 8:
+        raise ValueError("grad_norm: the workspace holds doubles: 8-byte aligned")
+    if record.dtype != torch.int32 or record.numel() != GRAD_RECORD_WORDS or not record.is_contiguous() or record.data_ptr() % 8:
+        raise ValueError("grad_norm: the record is 8 contiguous int32 words, 8-byte aligned (grad_record)")
+    if any(t is not None and t.device != rows.device for t in (workspace, record, status)):
+        raise ValueError("grad_norm: workspace, record and status word live on the rows' device")
+    with torch.cuda.device(rows.device):
+        L.check(L.gradlib().bingrad_norm(rows.table, rows.n, float(max_norm), _ptr(status), int(status_mask) & 0xFFFFFFFF, _ptr(workspace),
+                                         _ptr(record), _stream()), "grad_norm")
+
+
+def grad_scale(rows, record):
+    """bingrad_scale: g *= record.coef in place in fp32 on the rows' device's current stream; the kernel reads coef on the device and
+    writes nothing when it is exactly 1 (not clipped, or a non-finite norm: unlike torch.nn.utils.clip_grad_norm_, which turns a
+    gradient set with an inf norm into zeros and NaNs).  The gradients are written through raw pointers."""
+    _need_cuda(record)
+    if record.dtype != torch.int32 or record.numel() != GRAD_RECORD_WORDS or record.device != rows.device:
+        raise ValueError("grad_scale: the record grad_norm wrote (grad_record), on the rows' device")
+    if rows.n == 0:
+        return
+    with torch.cuda.device(rows.device):
+        L.check(L.gradlib().bingrad_scale(rows.table, rows.n, _ptr(record), _stream()), "grad_scale")

@@ -6,7 +6,13 @@ step-counter adds of torch's default `foreach` path on bin_stage4's 540 paramete
 The optimizer STATE is torch's, key for key and dtype for dtype (`step`: float32 scalar on the CPU; `exp_avg`, `exp_avg_sq`:
 like the parameter, created at the parameter's first gradient), and `param_groups` carry every key torch.optim.Adam keeps, so a
 `state_dict()` of either class loads into the other and `.state` checkpoint files interchange.  There is no CPU fallback:
-`step()` on CPU parameters raises."""
+`step()` on CPU parameters raises.
+
+`GradGuard` (`train.grad_clip`, `train.skip_bad_steps`) sits between the backward and either Adam class: the global gradient norm in
+one deterministic HIP pass with double accumulation (bingrad_norm), torch.nn.utils.clip_grad_norm_'s clip in place (bingrad_scale),
+and the decision to skip a step whose gradients are not finite or that saturated an fp16 plane, before Adam writes anything."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -112,3 +118,132 @@ class Adam(torch.optim.Optimizer):
         view["step_size"] = lr / (1.0 - beta1 ** t)
         view["inv_sqrt_bc2"] = 1.0 / np.sqrt(1.0 - beta2 ** t)
         ops.adam_launch(table, n, dev, beta1, beta2, eps, weight_decay)
+
+
+GradState = namedtuple("GradState", "norm coef flags skipped consecutive")
+
+
+class GradGuard:
+    """The guard between `backward()` (and the data-parallel reduce) and `optimizer.step()`.  It acts on `.grad` in place, as torch's
+    clipping does, so it works with torch.optim.Adam and with `Adam` above; parameters without a gradient are left out.
+
+    max_norm        0 = no clipping; > 0: the gradients are multiplied by min(1, max_norm / (norm + 1e-6)), the formula of
+                    torch.nn.utils.clip_grad_norm_, with the norm accumulated in double.  Unlike torch, a gradient set whose norm is
+                    not finite is left as it is (coef = 1).
+    skip_bad_steps  0 = `apply()` never synchronises the host and always returns True.  N > 0: `apply()` waits for the 32-byte record
+                    and returns False (skip the optimizer step) when the norm is not finite or the device status word reports fp16
+                    saturation; after more than N consecutive skipped steps it raises.  Under torch.distributed the flags are
+                    all-reduced (MAX) first: the status word is per rank, and the ranks must agree.
+    There is no CPU fallback: `apply()` on CPU gradients raises."""
+
+    def __init__(self, params, max_norm=0.0, skip_bad_steps=0, process_group=None):
+        max_norm = float(max_norm)
+        if not 0.0 <= max_norm < float("inf"):
+            raise ValueError(f"Invalid max_norm: {max_norm}")
+        if isinstance(skip_bad_steps, bool) or int(skip_bad_steps) != skip_bad_steps or skip_bad_steps < 0:
+            raise ValueError(f"Invalid skip_bad_steps: {skip_bad_steps!r}")
+        self.params = [p for p in params]
+        self.max_norm, self.skip_bad_steps, self.process_group = max_norm, int(skip_bad_steps), process_group
+        self.consecutive = 0          # skipped steps in a row
+        self.skipped_total = 0        # skipped steps since construction
+        self._rows = None             # (pointers, ops.GradRows): the host row table, reused while no pointer changed
+        self._workspace = self._record = self._host = self._event = None
+        self._pending = False         # the record of the last apply() has not been read from `_host` yet
+        self._last = GradState(0.0, 1.0, 0, False, 0)
+
+    # -------------------------------------------------------------------------------------------- the decision (host only)
+    @staticmethod
+    def cause(flags):
+        names = [n for bit, n in ((ops.L.GRAD_FLAG_NONFINITE, "non-finite gradient norm"), (ops.L.GRAD_FLAG_STATUS, "fp16 saturation"))
+                 if flags & bit]
+        return " and ".join(names)
+
+    def _judge(self, flags):
+        """Count a step with these (agreed) flags: True = take it, False = skip it; raises beyond `skip_bad_steps` in a row."""
+        if not flags:
+            self.consecutive = 0
+            return True
+        self.consecutive += 1
+        self.skipped_total += 1
+        if self.consecutive > self.skip_bad_steps:
+            raise RuntimeError(f"bin_amd: {self.cause(flags)} on {self.consecutive} consecutive training steps "
+                               f"(train.skip_bad_steps tolerates {self.skip_bad_steps}); the optimizer has not been stepped")
+        return False
+
+    def _agree(self, flags):
+        """All-reduce (MAX) the one-element int32 `flags` tensor over the process group when there is more than one rank."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(self.process_group) == 1:
+            return flags
+        if flags.is_cuda and dist.get_backend(self.process_group) == "gloo":          # as utils/dist_util.py stages device tensors
+            stream = torch.cuda.current_stream(flags.device)
+            host = torch.empty(flags.shape, dtype=flags.dtype, pin_memory=True)
+            host.copy_(flags, non_blocking=True)
+            stream.synchronize()
+            dist.all_reduce(host, op=dist.ReduceOp.MAX, group=self.process_group)
+            flags.copy_(host, non_blocking=True)
+            stream.synchronize()
+        else:
+            dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=self.process_group)
+        return flags
+
+    # -------------------------------------------------------------------------------------------- the step
+    @torch.no_grad()
+    def apply(self):
+        """Norm (and clip) of every present `.grad` on the current stream.  True: step the optimizer; False: skip this step."""
+        grads = [p.grad for p in self.params if p.grad is not None]
+        if not grads:
+            self._pending, self._last = False, GradState(0.0, 1.0, 0, False, self.consecutive)
+            return True
+        if not all(g.is_cuda for g in grads):
+            raise RuntimeError("bin_amd.optim.GradGuard: gradients must live on a HIP device (there is no CPU fallback; "
+                               "use torch.nn.utils.clip_grad_norm_)")
+        key = tuple(g.data_ptr() for g in grads) + tuple(g.numel() for g in grads)
+        if self._rows is None or self._rows[0] != key:
+            self._rows = (key, ops.grad_rows(grads))
+        rows = self._rows[1]
+        dev = rows.device
+        if self._record is None or self._record.device != dev:
+            self._record = ops.grad_record(dev)
+            self._host = torch.zeros(ops.GRAD_RECORD_WORDS, dtype=torch.int32).pin_memory()
+            self._event = torch.cuda.Event()
+            self._workspace = None
+        if self._workspace is None or self._workspace.numel() * 8 < rows.workspace_bytes:
+            self._workspace = torch.empty((rows.workspace_bytes + 7) // 8, dtype=torch.float64, device=dev)
+        skipping = self.skip_bad_steps > 0
+        word = ops.status_word(dev) if skipping else None
+        ops.grad_norm(rows, self._workspace, self._record, self.max_norm, word, ops.L.STATUS_SATURATED if skipping else 0)
+        stream = torch.cuda.current_stream(dev)
+        if skipping:
+            self._agree(self._record[ops.GRAD_FLAGS_WORD:ops.GRAD_FLAGS_WORD + 1])
+        with torch.cuda.device(dev):
+            self._host.copy_(self._record, non_blocking=True)
+            self._event.record(stream)
+        self._pending = True
+        if self.max_norm > 0:
+            ops.grad_scale(rows, self._record)               # queued before the host waits below
+            torch.autograd.graph.increment_version(grads)    # written through raw pointers
+        if not skipping:
+            return True
+        rec = self._read()
+        if rec.flags & ops.L.GRAD_FLAG_STATUS:
+            word.bitwise_and_(~ops.L.STATUS_SATURATED)       # this step is dealt with here: check_status need not raise for it
+        try:
+            return self._judge(rec.flags)
+        finally:                                             # also when _judge raises: `last` names the step that was refused
+            self._last = self._last._replace(skipped=bool(rec.flags), consecutive=self.consecutive)
+
+    def _read(self):
+        self._event.synchronize()                            # this stream's copy of the record, not the whole device
+        rec = ops.grad_record_read(self._host)
+        self._pending = False
+        self._last = GradState(float(rec.norm), float(rec.coef), int(rec.flags), False, self.consecutive)
+        return rec
+
+    @property
+    def last(self):
+        """(norm, coef, flags, skipped, consecutive) of the last `apply()`.  With skip_bad_steps == 0 this is where the record is
+        read (an event wait): ask where the host synchronises anyway."""
+        if self._pending:
+            self._read()
+        return self._last

@@ -60,12 +60,57 @@ def adam_class(opt):
     return torch.optim.Adam
 
 
+def _train_value(opt, key):
+    train = opt.get("train") if isinstance(opt, dict) else None
+    return train.get(key) if isinstance(train, dict) else None
+
+
+def grad_clip(opt):
+    """`train.grad_clip` (bin_amd extension): the max global L2 norm the gradients are clipped to before the optimizer step
+    (bin_amd.optim.GradGuard: the formula of torch.nn.utils.clip_grad_norm_ with the norm accumulated in double by a HIP kernel).
+    Absent, null or 0: off -> 0.0; a positive finite number: the max norm.  Anything else raises."""
+    value = _train_value(opt, "grad_clip")
+    if value is None:
+        return 0.0
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise ValueError(f"train.grad_clip: {value!r} is not a number (in YAML write 1.0e+3 or !!float 1e3, not 1e3)")
+    if not 0.0 <= float(value) < float("inf"):                # NaN fails both comparisons
+        raise ValueError(f"train.grad_clip: {value!r} is not a finite number >= 0")
+    return float(value)
+
+
+def skip_bad_steps(opt):
+    """`train.skip_bad_steps` (bin_amd extension): how many consecutive training steps may be skipped (optimizer not stepped, weights
+    untouched) because the gradient norm was not finite or an fp16 plane saturated, before the run stops.  Absent, null or 0: off -> 0
+    (the status word is checked after the step, as before); a positive int.  Anything else raises."""
+    value = _train_value(opt, "skip_bad_steps")
+    if value is None:
+        return 0
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f"train.skip_bad_steps: {value!r} is not an integer")
+    if value < 0:
+        raise ValueError(f"train.skip_bad_steps: {value!r} is negative")
+    return value
+
+
+def grad_guard(opt, params, process_group=None):
+    """The bin_amd.optim.GradGuard `train.grad_clip` / `train.skip_bad_steps` ask for over `params`, or None when both are off (then
+    nothing of it is imported, built or loaded)."""
+    clip, skip = grad_clip(opt), skip_bad_steps(opt)
+    if not clip and not skip:
+        return None
+    from ..optim import GradGuard
+    return GradGuard(params, max_norm=clip, skip_bad_steps=skip, process_group=process_group)
+
+
 def parse(opt_path, is_train=True):
     with open(opt_path) as f:
         opt = yaml.load(f, Loader=_ordered_loader())
     if is_train:
         val_metrics(opt)                     # a misspelt value stops the run here, not at the first validation pass
         optimizer(opt)
+        grad_clip(opt)
+        skip_bad_steps(opt)
     if is_train and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the reference exports CUDA_VISIBLE_DEVICES from gpu_ids (torch on ROCm honours the same variable); under
         # a one-process-per-GPU launcher the launcher owns device visibility, so it is left alone there

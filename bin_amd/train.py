@@ -175,9 +175,15 @@ def main(argv=None, model_factory=None, probe=None):
                 _, avg = model.get_current_log("train")
                 dt = time.time() - t_print
                 t_print = time.time()
-                log.info("<epoch:%3d, iter:%8d, lr:%.3e> loss %.4e (I7''' %.4e)  %.1f samples/s", epoch, step,
+                guard = getattr(model, "grad_guard", None)   # train.grad_clip / train.skip_bad_steps: the last step's gradient norm
+                extra = ""
+                if guard is not None:
+                    extra = "  gnorm %.3e" % guard.last.norm
+                    if guard.skip_bad_steps:
+                        extra += "  skipped %d" % guard.skipped_total
+                log.info("<epoch:%3d, iter:%8d, lr:%.3e> loss %.4e (I7''' %.4e)  %.1f samples/s%s", epoch, step,
                          model.get_current_learning_rate()[0], avg["Al"], avg["13"],
-                         print_freq * per_rank_batch * world / max(dt, 1e-9))
+                         print_freq * per_rank_batch * world / max(dt, 1e-9), extra)
                 model.train_AverageMeter_reset()
             if val_loader is not None and val_freq and step % val_freq == 0:
                 val_loss = 0.0
