@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH
+from .build import EMA_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -90,6 +90,13 @@ class BinGradTensor(C.Structure):
 class BinGradRecord(C.Structure):
     _fields_ = [("sumsq", C.c_double), ("norm", C.c_float), ("coef", C.c_float), ("flags", C.c_int32), ("status", C.c_uint32),
                 ("reserved", C.c_int32 * 2)]
+
+
+EMA_MAX_TENSORS = 136                  # BINEMA_MAX_TENSORS (include/binema.h, libbinema.so)
+
+
+class BinEmaTensor(C.Structure):
+    _fields_ = [("e", C.c_void_p), ("p", C.c_void_p), ("numel", C.c_int64)]
 
 
 _SIGNATURES = {
@@ -196,6 +203,13 @@ _GRAD_SIGNATURES = {
     "bingrad_scale": (C.c_int, [C.POINTER(BinGradTensor), C.c_int, C.c_void_p, C.c_void_p]),
 }
 
+# libbinema.so (include/binema.h): the weight-average library, loaded on first use
+EMA_VERSION = 100                      # BINEMA_VERSION
+_EMA_SIGNATURES = {
+    "binema_version": (C.c_int, []),
+    "binema_step": (C.c_int, [C.POINTER(BinEmaTensor), C.c_int, C.c_float, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
@@ -279,6 +293,34 @@ def gradlib():
             raise RuntimeError(f"bin_amd: {path} is version {h.bingrad_version()}, this binding is for {GRAD_VERSION}")
         _gradlib = h
     return _gradlib
+
+
+_emalib = None
+
+
+def ema_exported_symbols():
+    """Names every include/binema.h entry point must resolve to."""
+    return sorted(_EMA_SIGNATURES)
+
+
+def emalib():
+    """Load libbinema.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _emalib
+    if _emalib is None:
+        path = EMA_LIB_PATH
+        if not os.path.exists(path):
+            raise RuntimeError(
+                f"bin_amd: HIP library {EMA_LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; "
+                f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
+        h = C.CDLL(path)
+        for name, (res, args) in _EMA_SIGNATURES.items():
+            fn = getattr(h, name)
+            fn.restype = res
+            fn.argtypes = args
+        if h.binema_version() != EMA_VERSION:
+            raise RuntimeError(f"bin_amd: {path} is version {h.binema_version()}, this binding is for {EMA_VERSION}")
+        _emalib = h
+    return _emalib
 
 
 def check(rc, what):

@@ -21,6 +21,11 @@ OPT_HEADER = os.path.join(os.path.dirname(HERE), "include", "binopt.h")
 GRAD_SOURCES = ["bingrad_norm.hip"]
 GRAD_LIB_PATH = os.path.join(CSRC, "libbingrad.so")
 GRAD_HEADER = os.path.join(os.path.dirname(HERE), "include", "bingrad.h")
+# the weight-average library (include/binema.h): the exponential moving average of the weights (train.ema_decay); a fourth shared
+# object, for the same reason
+EMA_SOURCES = ["binema_step.hip"]
+EMA_LIB_PATH = os.path.join(CSRC, "libbinema.so")
+EMA_HEADER = os.path.join(os.path.dirname(HERE), "include", "binema.h")
 
 
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
@@ -47,19 +52,27 @@ def grad_abi_symbols():
         return re.findall(r"(?m)^BINGRAD_API\s+[\w\s\*]+?\b(bingrad_\w+)\s*\(", f.read())
 
 
+def ema_abi_symbols():
+    """The entry points include/binema.h declares (every BINEMA_API declaration), in header order."""
+    import re
+    with open(EMA_HEADER) as f:
+        return re.findall(r"(?m)^BINEMA_API\s+[\w\s\*]+?\b(binema_\w+)\s*\(", f.read())
+
+
 def _stale():
-    libs = (LIB_PATH, OPT_LIB_PATH, GRAD_LIB_PATH)
+    libs = (LIB_PATH, OPT_LIB_PATH, GRAD_LIB_PATH, EMA_LIB_PATH)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    deps += [os.path.join(os.path.dirname(HERE), "include", "binhip.h"), OPT_HEADER, GRAD_HEADER]
+    deps += [os.path.join(os.path.dirname(HERE), "include", "binhip.h"), OPT_HEADER, GRAD_HEADER, EMA_HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def build_library(force=False, verbose=True, defines=(), out=None):
     """Compile every HIP source for gfx950 into bin_amd/csrc/libbinhip.so (and, for the product build, the optimizer
-    library bin_amd/csrc/libbinopt.so and the gradient-guard library bin_amd/csrc/libbingrad.so beside it).
+    library bin_amd/csrc/libbinopt.so, the gradient-guard library bin_amd/csrc/libbingrad.so and the weight-average library
+    bin_amd/csrc/libbinema.so beside it).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain).  The sources are compiled in parallel (one
@@ -71,15 +84,15 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     objdir = CSRC if out is None else os.path.dirname(os.path.abspath(out))
     os.makedirs(objdir, exist_ok=True)
     tag = "" if out is None else "." + os.path.splitext(os.path.basename(out))[0]
-    procs, objs, opt_objs, grad_objs = [], [], [], []
-    for src in SOURCES + (OPT_SOURCES + GRAD_SOURCES if out is None else []):
+    procs, objs, opt_objs, grad_objs, ema_objs = [], [], [], [], []
+    for src in SOURCES + (OPT_SOURCES + GRAD_SOURCES + EMA_SOURCES if out is None else []):
         obj = os.path.join(objdir, src.replace(".hip", tag + ".o"))
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"] + [f"-D{d}" for d in defines] + \
               ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((cmd, subprocess.Popen(cmd)))
-        (opt_objs if src in OPT_SOURCES else grad_objs if src in GRAD_SOURCES else objs).append(obj)
+        (opt_objs if src in OPT_SOURCES else grad_objs if src in GRAD_SOURCES else ema_objs if src in EMA_SOURCES else objs).append(obj)
     for cmd, p in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
@@ -95,9 +108,10 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
-    # libbinopt.so, libbingrad.so: the same recipe, their exports from include/binopt.h and include/bingrad.h
+    # libbinopt.so, libbingrad.so, libbinema.so: the same recipe, their exports from include/binopt.h, bingrad.h and binema.h
     for name, symbols, path, lib_objs in ((("binopt", opt_abi_symbols(), OPT_LIB_PATH, opt_objs),
-                                           ("bingrad", grad_abi_symbols(), GRAD_LIB_PATH, grad_objs)) if out is None else ()):
+                                           ("bingrad", grad_abi_symbols(), GRAD_LIB_PATH, grad_objs),
+                                           ("binema", ema_abi_symbols(), EMA_LIB_PATH, ema_objs)) if out is None else ()):
         vmap = os.path.join(objdir, f"binhip_exports.{name}.map")
         with open(vmap, "w") as f:
             f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in symbols) + "  local: *;\n};\n")

@@ -22,7 +22,7 @@ from . import lr_scheduler, networks
 from .base_model import BaseModel, _direct_param_grads
 from .bin_model import FlatGradAllReduce, SingleProcessParallel, _get
 from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class, grad_guard
+from ..options.options import adam_class, grad_guard, weight_ema
 from ..utils import util
 
 logger = logging.getLogger("base")
@@ -85,6 +85,8 @@ class VideoBaseModel(BaseModel):
         self.optimizers.append(self.optimizer_G)
         # train.grad_clip / train.skip_bad_steps (bin_amd extensions): one guard over both groups' parameters, None when both are off
         self.grad_guard = grad_guard(opt, [p for _, p in trainable])
+        # train.ema_decay (bin_amd extension): the average of every generator weight, started from the loaded ones; None when off
+        self.weight_ema = weight_ema(opt, self.netG.module.parameters())
         scheme = train_opt["lr_scheme"]
         if scheme == "MultiStepLR":
             sched = lr_scheduler.MultiStepLR_Restart(
@@ -142,6 +144,8 @@ class VideoBaseModel(BaseModel):
             self.grad_sync()
         if self.grad_guard is None or self.grad_guard.apply():     # a skipped step still counts as an iteration
             self.optimizer_G.step()
+            if self.weight_ema is not None:        # only a step that was taken moves the average
+                self.weight_ema.update()
         if parts is None:
             self.log_dict["l_pix"] = l_pix.item()
         else:
@@ -215,3 +219,4 @@ class VideoBaseModel(BaseModel):
 
     def save(self, iter_label):
         self.save_network(self.netG, "G", iter_label)
+        self.save_ema(iter_label)                  # train.ema_decay: `{iter}_G_ema.pth` beside it

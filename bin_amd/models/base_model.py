@@ -6,6 +6,7 @@ Checkpoint formats are the reference's, so files interchange both ways:
   `{iter}_G.pth`   CPU state_dict of the unwrapped generator (1332 aliased keys for bin_stage4)
   `{iter}.state`   {"epoch", "iter", "schedulers": [...], "optimizers": [...]}
 """
+import logging
 import os
 from collections import OrderedDict
 
@@ -74,6 +75,7 @@ class BaseModel:
                 "(each rank takes gpu_ids = [LOCAL_RANK], batch_size is per process), or list a single id.")
         self.optimizers = []
         self.schedulers = []
+        self.weight_ema = None       # train.ema_decay: the wrapper builds a bin_amd.optim.WeightEMA after load()
 
     # ---- interface stubs the concrete wrapper overrides (kept for API parity) ----------------------
     def feed_data(self, data):
@@ -137,6 +139,28 @@ class BaseModel:
             if hasattr(mod, "invalidate_kernel_weights"):        # the relayouted kernel weights must be rebuilt
                 mod.invalidate_kernel_weights()
 
+    # ---- train.ema_decay (bin_amd extension): the averaged weights ---------------------------------------
+    def ema_scope(self):
+        """Context in which the generator holds the averaged weights (validation, saving); a no-op with `train.ema_decay` off."""
+        ema = getattr(self, "weight_ema", None)
+        return ema.applied(self.netG) if ema is not None else _NoCtx()
+
+    def save_ema(self, iter_label):
+        """`{iter}_G_ema.pth`: the averaged weights as an ordinary generator checkpoint (save_network under ema_scope), so
+        bin_amd.test, `pretrain_model_G` and the reference load it unchanged.  Nothing is written with the option off."""
+        if getattr(self, "weight_ema", None) is not None:
+            with self.ema_scope():
+                self.save_network(self.netG, "G_ema", iter_label)
+
+    def load_ema(self, load_path):
+        """The shadows from a `{iter}_G_ema.pth` file, by parameter name."""
+        loaded = clean_state_dict_keys(torch.load(load_path, map_location="cpu"), True)
+        names = [name for name, _ in unwrap(self.netG).named_parameters()]
+        missing = [name for name in names if name not in loaded]
+        if missing:
+            raise KeyError(f"{load_path}: no key {missing[0]!r} ({len(missing)} of {len(names)} parameters are missing)")
+        self.weight_ema.load_shadow([loaded[name] for name in names])
+
     def save_training_state(self, epoch, iter_step):
         """`{iter}.state` with everything needed to resume (reference base_model.py:105-114)."""
         state = {"epoch": epoch, "iter": iter_step,
@@ -152,3 +176,11 @@ class BaseModel:
             target.load_state_dict(state)
         for target, state in zip(self.schedulers, saved_sched):
             target.load_state_dict(state)
+        if getattr(self, "weight_ema", None) is not None:
+            # `.state` files do not carry the average: it is the `{iter}_G_ema.pth` beside the `{iter}_G.pth` check_resume named
+            path = self.opt["path"].get("pretrain_model_G_ema")
+            if path is not None and os.path.exists(path):
+                self.load_ema(path)
+            else:
+                logging.getLogger("base").warning(
+                    "train.ema_decay: no averaged weights [%s] to resume from; the average starts from the loaded weights.", path)

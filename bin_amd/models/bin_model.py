@@ -20,7 +20,7 @@ from . import lr_scheduler
 from . import networks
 from .base_model import BaseModel, unwrap, _direct_param_grads
 from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class, grad_guard
+from ..options.options import adam_class, grad_guard, weight_ema
 from ..utils import dist_util, util
 from ..utils.util import AverageMeter
 
@@ -275,6 +275,8 @@ class bin_model(BaseModel):
             self.optimizers.append(self.optimizer_G)
             # train.grad_clip / train.skip_bad_steps (bin_amd extensions): a guard between backward and step, None when both are off
             self.grad_guard = grad_guard(opt, [v for _, v in trainable])
+            # train.ema_decay (bin_amd extension): the average of every generator weight, started from the loaded ones; None when off
+            self.weight_ema = weight_ema(opt, unwrap(self.netG).parameters())
 
             scheme = train_opt["lr_scheme"]
             if scheme == "MultiStepLR":
@@ -338,6 +340,8 @@ class bin_model(BaseModel):
         # were; it still counts as an iteration for the schedule and the logger, as a GradScaler skip does
         if self.grad_guard is None or self.grad_guard.apply():
             self.optimizer_G.step()
+            if self.weight_ema is not None:        # only a step that was taken moves the average
+                self.weight_ema.update()
 
     def set_params_lr_zero(self):
         self.optimizers[0].param_groups[0]["lr"] = 0
@@ -548,6 +552,7 @@ class bin_model(BaseModel):
 
     def save(self, iter_label):
         self.save_network(self.netG, "G", iter_label)
+        self.save_ema(iter_label)                  # train.ema_decay: `{iter}_G_ema.pth` beside it
 
     @staticmethod
     def get_lr(optimizer):

@@ -842,3 +842,36 @@ def grad_scale(rows, record):
         return
     with torch.cuda.device(rows.device):
         L.check(L.gradlib().bingrad_scale(rows.table, rows.n, _ptr(record), _stream()), "grad_scale")
+
+
+# --------------------------------------------------------------------------------------------- weight average (EMA)
+def ema_rows(n):
+    """A host table of n BinEmaTensor rows for ema_launch (bin_amd.optim.WeightEMA keeps one per device while no pointer changed)."""
+    return (L.BinEmaTensor * max(n, 1))()
+
+
+def ema_row(table, i, e, p):
+    """Fill row i of an ema_rows table from two float32 device tensors of one size: e, the average, is written; p is only read.
+    Raises on CPU tensors (there is no CPU fallback), on another dtype and on non-contiguous tensors: the kernel walks numel
+    consecutive floats from each pointer (views at any 4-byte offset are fine)."""
+    _need_cuda(e, p)
+    for name, t in (("e", e), ("p", p)):
+        if t.dtype != torch.float32:
+            raise ValueError(f"ema_step: float32 tensors, got {t.dtype} for {name}")
+        if not t.is_contiguous():
+            raise ValueError(f"ema_step: contiguous tensors, got strides {tuple(t.stride())} of shape {tuple(t.shape)} for {name}")
+        if t.numel() != p.numel() or t.device != p.device:
+            raise ValueError(f"ema_step: {name} has {t.numel()} elements on {t.device}, p has {p.numel()} on {p.device}")
+    if p.numel() < 1:
+        raise ValueError("ema_step: empty tensor")
+    r = table[i]
+    r.e, r.p, r.numel = e.data_ptr(), p.data_ptr(), p.numel()
+
+
+def ema_launch(table, n, device, decay):
+    """binema_step over the first n rows of an ema_rows table, on `device`'s current stream, no host sync: e += (1 - decay) * (p - e)
+    in fp32, BINEMA_MAX_TENSORS rows per launch.  e is written through raw pointers: the caller bumps its version counters."""
+    if n == 0:
+        return
+    with torch.cuda.device(device):
+        L.check(L.emalib().binema_step(table, n, decay, _stream()), "ema_step")

@@ -10,7 +10,12 @@ like the parameter, created at the parameter's first gradient), and `param_group
 
 `GradGuard` (`train.grad_clip`, `train.skip_bad_steps`) sits between the backward and either Adam class: the global gradient norm in
 one deterministic HIP pass with double accumulation (bingrad_norm), torch.nn.utils.clip_grad_norm_'s clip in place (bingrad_scale),
-and the decision to skip a step whose gradients are not finite or that saturated an fp16 plane, before Adam writes anything."""
+and the decision to skip a step whose gradients are not finite or that saturated an fp16 plane, before Adam writes anything.
+
+`WeightEMA` (`train.ema_decay`) runs after the optimizer step: an exponential moving average of the weights in one flat fp32 buffer,
+updated by binema_step (the work split of the Adam kernel over a by-value table of {e, p, numel} rows), and a context that puts the
+averaged weights in place of the training ones for validation and saving without copying either."""
+import contextlib
 from collections import namedtuple
 
 import numpy as np
@@ -247,3 +252,126 @@ class GradGuard:
         if self._pending:
             self._read()
         return self._last
+
+
+class WeightEMA:
+    """An exponential moving average of `params` (`train.ema_decay`): after every optimizer step `update()` moves each shadow
+    towards its parameter, e += (1 - decay) * (p - e) in fp32, with one binema_step call per device on the current stream: no
+    allocation and no host synchronisation.  The shadows are views into ONE flat fp32 buffer on the parameters' device, each
+    starting on a 16-byte boundary (so every row takes the kernel's 16-byte path when its parameter does), initialised to the
+    parameters' current values; `shadow` lists them in parameter order.
+
+    `applied()` is the context in which the parameters hold the averaged values (validation, saving).  There is no CPU fallback:
+    `update()` on CPU parameters raises; building, `state_dict()` and `load_state_dict()` work anywhere."""
+
+    def __init__(self, params, decay):
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) < 1.0:   # NaN fails both
+            raise ValueError(f"Invalid decay: {decay!r} (0 <= decay < 1)")
+        self.decay = float(decay)
+        self.params = [p for p in params]
+        for p in self.params:
+            if p.dtype != torch.float32:
+                raise ValueError(f"bin_amd.optim.WeightEMA: float32 parameters, got {p.dtype}")
+        self._alloc()
+        self._tables = {}             # device -> (pointers, table, n): the host row table, reused while no pointer changed
+        self._held = None             # inside applied(): the training values' tensors, in parameter order
+
+    def _alloc(self):
+        """One flat buffer per device; a tensor's slice starts on a multiple of 4 floats from the (allocator-aligned) base."""
+        self._flat, self.shadow = {}, [None] * len(self.params)
+        by_dev = {}
+        for i, p in enumerate(self.params):
+            by_dev.setdefault(p.device, []).append(i)
+        with torch.no_grad():
+            for dev, idx in by_dev.items():
+                offsets, total = [], 0
+                for i in idx:
+                    offsets.append(total)
+                    total += (self.params[i].numel() + 3) // 4 * 4
+                flat = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
+                assert flat.data_ptr() % 16 == 0
+                for i, o in zip(idx, offsets):
+                    p = self.params[i]
+                    view = flat[o:o + p.numel()].view(p.shape)
+                    view.copy_(p.detach().contiguous())
+                    self.shadow[i] = view
+                self._flat[dev] = flat
+
+    @torch.no_grad()
+    def update(self):
+        """One averaging step of every shadow towards its parameter, on the current stream of each device."""
+        if self._held is not None:
+            raise RuntimeError("bin_amd.optim.WeightEMA: update() inside applied(): the parameters hold the averaged values")
+        by_dev = {}
+        for i, p in enumerate(self.params):
+            if not p.is_cuda:
+                raise RuntimeError("bin_amd.optim.WeightEMA: parameters must live on a HIP device (there is no CPU fallback; "
+                                   "leave `train.ema_decay` out)")
+            by_dev.setdefault(p.device, []).append(i)
+        for dev, idx in by_dev.items():
+            key = tuple(self.params[i].data_ptr() for i in idx) + tuple(self.shadow[i].data_ptr() for i in idx)
+            cached = self._tables.get(dev)
+            if cached is not None and cached[0] == key:
+                table = cached[1]
+            else:
+                table = ops.ema_rows(len(idx))
+                for r, i in enumerate(idx):
+                    ops.ema_row(table, r, self.shadow[i], self.params[i].detach())
+                self._tables[dev] = (key, table)
+            ops.ema_launch(table, len(idx), dev, self.decay)
+        # the kernel wrote through raw pointers: whatever keys on the shadows' version counters must see a new weight set
+        torch.autograd.graph.increment_version(self.shadow)
+
+    @contextlib.contextmanager
+    def applied(self, invalidate=()):
+        """Inside, the parameters hold the averaged values; on exit the training values again, bit for bit, at the same storage
+        addresses and with the same `_version` as before entry.  Each parameter's `.data` is exchanged with its shadow's, so nothing
+        is copied: inside, a parameter IS its shadow's memory (torch keeps the parameter's own version counter across the exchange),
+        and Adam's cached row table, FlatGradAllReduce's views and autograd's saved-tensor checks see nothing afterwards.
+        `invalidate`: the modules (or one module) whose `invalidate_kernel_weights()`, where they have it, is called on entry and
+        on exit, since the parameters' version counters do not tell the two weight sets apart.  Not re-entrant; entering it with a
+        forward outstanding is the caller's error."""
+        if self._held is not None:
+            raise RuntimeError("bin_amd.optim.WeightEMA: applied() is not re-entrant")
+        mods = list(invalidate.modules()) if isinstance(invalidate, torch.nn.Module) else \
+            [m for top in invalidate for m in top.modules()]
+        mods = [m for m in mods if hasattr(m, "invalidate_kernel_weights")]
+        for p, e in zip(self.params, self.shadow):
+            if p.shape != e.shape or p.device != e.device:
+                raise RuntimeError("bin_amd.optim.WeightEMA: a parameter changed shape or device since the shadows were made")
+        self._held = [p.data for p in self.params]
+        try:
+            for p, e in zip(self.params, self.shadow):
+                p.data = e
+            for m in mods:
+                m.invalidate_kernel_weights()
+            yield self
+        finally:
+            for p, d in zip(self.params, self._held):
+                p.data = d
+            self._held = None
+            for m in mods:
+                m.invalidate_kernel_weights()
+
+    def state_dict(self):
+        return {"decay": self.decay, "shadow": [e.detach().cpu().clone() for e in self.shadow]}
+
+    @torch.no_grad()
+    def load_shadow(self, tensors):
+        """Copy `tensors` (parameter order, any device) into the shadows.  A count or shape mismatch raises, naming the first."""
+        tensors = list(tensors)
+        if len(tensors) != len(self.shadow):
+            raise ValueError(f"bin_amd.optim.WeightEMA: {len(tensors)} shadow tensors for {len(self.shadow)} parameters")
+        for i, (e, t) in enumerate(zip(self.shadow, tensors)):
+            if tuple(t.shape) != tuple(e.shape):
+                raise ValueError(f"bin_amd.optim.WeightEMA: shadow {i} has shape {tuple(t.shape)}, parameter {i} has "
+                                 f"{tuple(e.shape)}")
+        for e, t in zip(self.shadow, tensors):
+            e.copy_(t)                                       # copy_ bumps the shadow's version counter
+
+    def load_state_dict(self, state):
+        self.load_shadow(state["shadow"])
+        decay = state["decay"]
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) < 1.0:
+            raise ValueError(f"Invalid decay: {decay!r} (0 <= decay < 1)")
+        self.decay = float(decay)

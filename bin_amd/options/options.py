@@ -103,6 +103,30 @@ def grad_guard(opt, params, process_group=None):
     return GradGuard(params, max_norm=clip, skip_bad_steps=skip, process_group=process_group)
 
 
+def ema_decay(opt):
+    """`train.ema_decay` (bin_amd extension): the decay of the exponential moving average of the generator weights that is
+    validated and saved beside the training weights (bin_amd.optim.WeightEMA: e += (1 - decay) * (p - e) after every optimizer step,
+    one HIP pass).  Absent, null or 0: off -> 0.0; a number in (0, 1): the decay.  Anything else raises."""
+    value = _train_value(opt, "ema_decay")
+    if value is None:
+        return 0.0
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise ValueError(f"train.ema_decay: {value!r} is not a number")
+    if not 0.0 <= float(value) < 1.0:                         # NaN fails both comparisons
+        raise ValueError(f"train.ema_decay: {value!r} is not a number >= 0 and < 1")
+    return float(value)
+
+
+def weight_ema(opt, params):
+    """The bin_amd.optim.WeightEMA `train.ema_decay` asks for over `params`, or None when it is off (then nothing of it is
+    imported, built or loaded)."""
+    decay = ema_decay(opt)
+    if not decay:
+        return None
+    from ..optim import WeightEMA
+    return WeightEMA(params, decay)
+
+
 def parse(opt_path, is_train=True):
     with open(opt_path) as f:
         opt = yaml.load(f, Loader=_ordered_loader())
@@ -111,6 +135,7 @@ def parse(opt_path, is_train=True):
         optimizer(opt)
         grad_clip(opt)
         skip_bad_steps(opt)
+        ema_decay(opt)
     if is_train and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the reference exports CUDA_VISIBLE_DEVICES from gpu_ids (torch on ROCm honours the same variable); under
         # a one-process-per-GPU launcher the launcher owns device visibility, so it is left alone there
@@ -189,6 +214,8 @@ def check_resume(opt, resume_iter):
         log.warning("pretrain_model path will be ignored when resuming training.")
     opt["path"]["pretrain_model_G"] = osp.join(opt["path"]["models"], f"{resume_iter}_G.pth")
     log.info("Set [pretrain_model_G] to " + opt["path"]["pretrain_model_G"])
+    # train.ema_decay: the averaged weights saved beside them; read after resume_training, only when the option is on
+    opt["path"]["pretrain_model_G_ema"] = osp.join(opt["path"]["models"], f"{resume_iter}_G_ema.pth")
     if "gan" in opt["model"]:
         opt["path"]["pretrain_model_D"] = osp.join(opt["path"]["models"], f"{resume_iter}_D.pth")
         log.info("Set [pretrain_model_D] to " + opt["path"]["pretrain_model_D"])

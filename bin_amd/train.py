@@ -9,6 +9,7 @@ One process per GPU; `datasets.train.batch_size` is the whole-job batch (// worl
 gradients are averaged with one flat RCCL all-reduce per step (bin_model.FlatGradAllReduce).  Iteration-oriented:
 the sampler enlarges an epoch `ratio` times so the loader is rebuilt rarely."""
 import argparse
+import contextlib
 import logging
 import math
 import os
@@ -37,6 +38,12 @@ def validate(model, loader, step, opt, log, max_batches=None):
     """Mean loss and PSNR/SSIM of the 14 outputs over the validation windows (bin_model.py:427-589 meters).  The scores
     come from numpy on the host or, with `train.val_metrics: device`, from one ops.frame_scores call per window."""
     metrics = option.val_metrics(opt)
+    ema = getattr(model, "weight_ema", None) is not None      # train.ema_decay: the averaged weights are the ones scored
+    with (model.ema_scope() if ema else contextlib.nullcontext()):
+        return _validate(model, loader, step, opt, log, max_batches, metrics, " ema" if ema else "")
+
+
+def _validate(model, loader, step, opt, log, max_batches, metrics, which):
     model.val_loss_AverageMeter()
     model.val_AverageMeter_para()
     save_dir = os.path.join(opt["path"]["val_images"], str(step))
@@ -55,7 +62,7 @@ def validate(model, loader, step, opt, log, max_batches=None):
         psnr, ssim = model.compute_current_psnr_ssim(save=save, name=batch["key"][0], save_path=save_dir, **kw)
         model.val_AverageMeter_para_update(psnr, ssim)
     _, psnr_dict, psnr_avg, ssim_avg, loss_avg = model.get_current_log(mode="val")
-    log.info("<val iter:%8d> loss %.4e  psnr %.3f dB  ssim %.4f  interp(I7''') psnr %.3f dB", step, loss_avg, psnr_avg,
+    log.info("<val%s iter:%8d> loss %.4e  psnr %.3f dB  ssim %.4f  interp(I7''') psnr %.3f dB", which, step, loss_avg, psnr_avg,
              ssim_avg, psnr_dict["Ap13"])
     return loss_avg
 
