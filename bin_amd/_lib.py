@@ -213,7 +213,24 @@ _EMA_SIGNATURES = {
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = None
+_lib = _optlib = _gradlib = _emalib = None
+
+
+def _load(path, built_path, signatures, version=None):
+    """dlopen `path` and type its entry points.  Raises RuntimeError with the build hint when it is absent, and when `version`
+    (the version entry point's name, the value this binding is for) does not match."""
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"bin_amd: HIP library {built_path} not built. Run `python -c 'import __graft_entry__ as g; "
+            f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
+    h = C.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(h, name)
+        fn.restype = res
+        fn.argtypes = args
+    if version is not None and getattr(h, version[0])() != version[1]:
+        raise RuntimeError(f"bin_amd: {path} is version {getattr(h, version[0])()}, this binding is for {version[1]}")
+    return h
 
 
 def exported_symbols():
@@ -224,22 +241,9 @@ def exported_symbols():
 def lib():
     """Load libbinhip.so (once).  Raises RuntimeError with the build hint when it is absent."""
     global _lib
-    if _lib is None:
-        path = os.environ.get("BIN_AMD_LIB", LIB_PATH)      # developer knob: the timeline side build, another commit's library
-        if not os.path.exists(path):
-            raise RuntimeError(
-                f"bin_amd: HIP library {LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; "
-                f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
-        h = C.CDLL(path)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
+    if _lib is None:                # BIN_AMD_LIB: developer knob: the timeline side build, another commit's library
+        _lib = _load(os.environ.get("BIN_AMD_LIB", LIB_PATH), LIB_PATH, _SIGNATURES)
     return _lib
-
-
-_optlib = None
 
 
 def opt_exported_symbols():
@@ -251,23 +255,8 @@ def optlib():
     """Load libbinopt.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
     global _optlib
     if _optlib is None:
-        path = OPT_LIB_PATH
-        if not os.path.exists(path):
-            raise RuntimeError(
-                f"bin_amd: HIP library {OPT_LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; "
-                f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
-        h = C.CDLL(path)
-        for name, (res, args) in _OPT_SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        if h.binopt_version() != OPT_VERSION:
-            raise RuntimeError(f"bin_amd: {path} is version {h.binopt_version()}, this binding is for {OPT_VERSION}")
-        _optlib = h
+        _optlib = _load(OPT_LIB_PATH, OPT_LIB_PATH, _OPT_SIGNATURES, ("binopt_version", OPT_VERSION))
     return _optlib
-
-
-_gradlib = None
 
 
 def grad_exported_symbols():
@@ -279,23 +268,8 @@ def gradlib():
     """Load libbingrad.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
     global _gradlib
     if _gradlib is None:
-        path = GRAD_LIB_PATH
-        if not os.path.exists(path):
-            raise RuntimeError(
-                f"bin_amd: HIP library {GRAD_LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; "
-                f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
-        h = C.CDLL(path)
-        for name, (res, args) in _GRAD_SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        if h.bingrad_version() != GRAD_VERSION:
-            raise RuntimeError(f"bin_amd: {path} is version {h.bingrad_version()}, this binding is for {GRAD_VERSION}")
-        _gradlib = h
+        _gradlib = _load(GRAD_LIB_PATH, GRAD_LIB_PATH, _GRAD_SIGNATURES, ("bingrad_version", GRAD_VERSION))
     return _gradlib
-
-
-_emalib = None
 
 
 def ema_exported_symbols():
@@ -307,19 +281,7 @@ def emalib():
     """Load libbinema.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
     global _emalib
     if _emalib is None:
-        path = EMA_LIB_PATH
-        if not os.path.exists(path):
-            raise RuntimeError(
-                f"bin_amd: HIP library {EMA_LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; "
-                f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
-        h = C.CDLL(path)
-        for name, (res, args) in _EMA_SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        if h.binema_version() != EMA_VERSION:
-            raise RuntimeError(f"bin_amd: {path} is version {h.binema_version()}, this binding is for {EMA_VERSION}")
-        _emalib = h
+        _emalib = _load(EMA_LIB_PATH, EMA_LIB_PATH, _EMA_SIGNATURES, ("binema_version", EMA_VERSION))
     return _emalib
 
 

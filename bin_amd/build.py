@@ -29,43 +29,45 @@ EMA_HEADER = os.path.join(os.path.dirname(HERE), "include", "binema.h")
 
 
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
+# (name, sources, header, path) of every shared object: what drives the compile, the version script and the link
+LIBRARIES = (("binhip", SOURCES, HEADER, LIB_PATH), ("binopt", OPT_SOURCES, OPT_HEADER, OPT_LIB_PATH),
+             ("bingrad", GRAD_SOURCES, GRAD_HEADER, GRAD_LIB_PATH), ("binema", EMA_SOURCES, EMA_HEADER, EMA_LIB_PATH))
+
+
+def _declared(header, macro, prefix):
+    """The entry points `header` declares (every `macro` declaration of a `prefix`_ name), in header order."""
+    import re
+    with open(header) as f:
+        return re.findall(rf"(?m)^{macro}\s+[\w\s\*]+?\b({prefix}_\w+)\s*\(", f.read())
 
 
 def abi_symbols():
     """The entry points include/binhip.h declares (every BINHIP_API declaration), in header order."""
-    import re
-    with open(HEADER) as f:
-        return re.findall(r"(?m)^BINHIP_API\s+[\w\s\*]+?\b(binhip_\w+)\s*\(", f.read())
+    return _declared(HEADER, "BINHIP_API", "binhip")
 
 
 def opt_abi_symbols():
     """The entry points include/binopt.h declares (every BINOPT_API declaration), in header order."""
-    import re
-    with open(OPT_HEADER) as f:
-        return re.findall(r"(?m)^BINOPT_API\s+[\w\s\*]+?\b(binopt_\w+)\s*\(", f.read())
+    return _declared(OPT_HEADER, "BINOPT_API", "binopt")
 
 
 def grad_abi_symbols():
     """The entry points include/bingrad.h declares (every BINGRAD_API declaration), in header order."""
-    import re
-    with open(GRAD_HEADER) as f:
-        return re.findall(r"(?m)^BINGRAD_API\s+[\w\s\*]+?\b(bingrad_\w+)\s*\(", f.read())
+    return _declared(GRAD_HEADER, "BINGRAD_API", "bingrad")
 
 
 def ema_abi_symbols():
     """The entry points include/binema.h declares (every BINEMA_API declaration), in header order."""
-    import re
-    with open(EMA_HEADER) as f:
-        return re.findall(r"(?m)^BINEMA_API\s+[\w\s\*]+?\b(binema_\w+)\s*\(", f.read())
+    return _declared(EMA_HEADER, "BINEMA_API", "binema")
 
 
 def _stale():
-    libs = (LIB_PATH, OPT_LIB_PATH, GRAD_LIB_PATH, EMA_LIB_PATH)
+    libs = [path for _, _, _, path in LIBRARIES]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    deps += [os.path.join(os.path.dirname(HERE), "include", "binhip.h"), OPT_HEADER, GRAD_HEADER, EMA_HEADER]
+    deps += [header for _, _, header, _ in LIBRARIES]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -75,52 +77,44 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     bin_amd/csrc/libbinema.so beside it).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
-    per-workgroup time stamps, which the product library does not contain).  The sources are compiled in parallel (one
-    hipcc per file)."""
-    lib_path = out or LIB_PATH
+    per-workgroup time stamps, which the product library does not contain): libbinhip.so alone, under another name.  The
+    sources are compiled in parallel (one hipcc per file)."""
     if out is None and not force and not _stale():
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = CSRC if out is None else os.path.dirname(os.path.abspath(out))
     os.makedirs(objdir, exist_ok=True)
     tag = "" if out is None else "." + os.path.splitext(os.path.basename(out))[0]
-    procs, objs, opt_objs, grad_objs, ema_objs = [], [], [], [], []
-    for src in SOURCES + (OPT_SOURCES + GRAD_SOURCES + EMA_SOURCES if out is None else []):
-        obj = os.path.join(objdir, src.replace(".hip", tag + ".o"))
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"] + [f"-D{d}" for d in defines] + \
-              ["-c", os.path.join(CSRC, src), "-o", obj]
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        procs.append((cmd, subprocess.Popen(cmd)))
-        (opt_objs if src in OPT_SOURCES else grad_objs if src in GRAD_SOURCES else ema_objs if src in EMA_SOURCES else objs).append(obj)
+    libraries = LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
+    procs, objs = [], {}
+    for name, sources, _, _ in libraries:
+        for src in sources:
+            obj = os.path.join(objdir, src.replace(".hip", tag + ".o"))
+            cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"] + [f"-D{d}" for d in defines] + \
+                  ["-c", os.path.join(CSRC, src), "-o", obj]
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            procs.append((cmd, subprocess.Popen(cmd)))
+            objs.setdefault(name, []).append(obj)
     for cmd, p in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
-    # Dynamic symbols = exactly the entry points include/binhip.h declares (sources are compiled -fvisibility=hidden; the
-    # version script also makes the host-side kernel handles hipcc emits with default visibility local).
-    vmap = os.path.join(objdir, "binhip_exports" + tag + ".map")
-    names = abi_symbols() + (["binhip_set_timeline"] if any(d.startswith("BINHIP_TIMELINE") for d in defines) else [])
-    with open(vmap, "w") as f:
-        f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in names) + "  local: *;\n};\n")
-    # -z defs: a kernel template the host pass silently failed to instantiate shows up as an undefined symbol HERE, not at dlopen
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", f"-Wl,--version-script={vmap}",
-           "-o", lib_path] + objs
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    # libbinopt.so, libbingrad.so, libbinema.so: the same recipe, their exports from include/binopt.h, bingrad.h and binema.h
-    for name, symbols, path, lib_objs in ((("binopt", opt_abi_symbols(), OPT_LIB_PATH, opt_objs),
-                                           ("bingrad", grad_abi_symbols(), GRAD_LIB_PATH, grad_objs),
-                                           ("binema", ema_abi_symbols(), EMA_LIB_PATH, ema_objs)) if out is None else ()):
-        vmap = os.path.join(objdir, f"binhip_exports.{name}.map")
+    for name, _, header, path in libraries:
+        # Dynamic symbols = exactly the entry points the library's header declares (sources are compiled -fvisibility=hidden; the
+        # version script also makes the host-side kernel handles hipcc emits with default visibility local).
+        vmap = os.path.join(objdir, "binhip_exports" + tag + ".map" if name == "binhip" else f"binhip_exports.{name}.map")
+        names = _declared(header, name.upper() + "_API", name)
+        if name == "binhip" and any(d.startswith("BINHIP_TIMELINE") for d in defines):
+            names.append("binhip_set_timeline")
         with open(vmap, "w") as f:
-            f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in symbols) + "  local: *;\n};\n")
+            f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in names) + "  local: *;\n};\n")
+        # -z defs: a kernel template the host pass silently failed to instantiate shows up as an undefined symbol HERE, not at dlopen
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", f"-Wl,--version-script={vmap}",
-               "-o", path] + lib_objs
+               "-o", path] + objs[name]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)
-    return lib_path
+    return out or LIB_PATH
 
 
 if __name__ == "__main__":

@@ -1,9 +1,9 @@
 // bingrad_norm.hip (libbingrad.so, include/bingrad.h) — the gradient guard of the training step: the global L2 norm of all
 // gradients, the clip coefficient of torch.nn.utils.clip_grad_norm_ and the in-place scale, for a whole parameter set in a handful
 // of launches and without a host round trip.
-// The rows travel BY VALUE (the idiom of adam_step_kernel, binopt_adam.hip): no device-side table, no copy, no allocation.
-//   grad_sumsq_kernel  a workgroup owns one GN_CHUNK-element chunk of one row; the table carries the first workgroup of every row and
-//                      a workgroup finds its row by a binary search over those (wave-uniform: loads from the kernel arguments).  Each
+// The rows travel BY VALUE and the work split is binhip_multi_tensor.h's: the table, the row search, the launch packing and the
+// two-path chunk walk (walk_chunk) live there; this file keeps the arithmetic, the reductions, the argument checks and the entry points.
+//   grad_sumsq_kernel  a workgroup owns one GN_CHUNK-element chunk of one row and finds its row by a binary search over the table.  Each
 //                      element is converted to double, squared (exact: 24 x 24 bits) and accumulated in double; the lanes' sums are
 //                      reduced within the wave by shuffles, across the waves through LDS, both in a fixed order, and lane 0 stores the
 //                      workgroup's sum to ITS slot of the workspace.  Nothing is accumulated across workgroups here, so the result does
@@ -11,14 +11,14 @@
 //   grad_final_kernel  one workgroup sums the slots in a fixed order (lane t takes slots t, t + 256, ...; then a tree through LDS),
 //                      reads the status word and writes the 32-byte record.
 //   grad_scale_kernel  the work split of the first kernel; reads coef from the record on the device, returns when it is exactly 1.0f,
-//                      otherwise g *= coef in fp32, everything a lane owns loaded before its first store ("Epilogues and
-//                      vmcnt").
+//                      otherwise g *= coef in fp32, everything a lane owns loaded before its first store.
 // A row whose pointer is 16-byte aligned moves 16 B per lane in every whole chunk; its last, partial chunk, and every row with a
 // misaligned pointer (the gradients of FlatGradAllReduce are views at any 4-byte offset), take 4 B per lane with clamped, unpredicated
 // loads.  HBM-bound: 4 B read per element for the norm, 8 B for a scale that clips.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/bingrad.h"
+#include "binhip_multi_tensor.h"
 
 #include <math.h>
 
@@ -29,92 +29,42 @@ constexpr int GN_CHUNK = GN_THREADS * GN_UNROLL * 4;             // 4096 element
 constexpr int GN_WAVES = GN_THREADS / 64;
 constexpr int64_t GN_MAX_BLOCKS = (1 << 24) - 1;                 // workgroups per launch: 256 x that many threads stay below 2^32 in a grid
 
-struct GradTable {
-    BinGradTensor row[BINGRAD_MAX_TENSORS];
-    int first_block[BINGRAD_MAX_TENSORS + 1];                    // row r owns workgroups first_block[r] .. first_block[r + 1] - 1
-    int n;
-};
+using GradTable = multi_tensor::RowTable<BinGradTensor, BINGRAD_MAX_TENSORS>;
+using GradLaunches = multi_tensor::Launches<GN_CHUNK, GN_MAX_BLOCKS>;
 // the launch's arguments travel in the kernel-argument segment: keep table + scalars well under 4 KB
 static_assert(sizeof(BinGradTensor) == 16, "BinGradTensor layout");
 static_assert(sizeof(BinGradRecord) == 32 && offsetof(BinGradRecord, flags) == 16, "BinGradRecord layout");
 static_assert(sizeof(GradTable) + 4 * sizeof(void*) <= 3072, "the table must fit the by-value argument limit");
-
-// the row of this workgroup: largest r with first_block[r] <= blockIdx.x  (first_block[0] = 0, first_block[n] = gridDim.x)
-__device__ __forceinline__ int find_row(const GradTable& tab) {
-    int lo = 0, hi = tab.n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tab.first_block[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+static_assert(BINGRAD_E_ARG == multi_tensor::E_ARG && BINGRAD_E_SHAPE == multi_tensor::E_SHAPE, "the shared checks return these");
 
 __device__ __forceinline__ double square_add(float x, double acc) {
     const double d = (double)x;
     return fma(d, d, acc);                                       // the product of two converted floats is exact in double
 }
 
-int64_t chunks_of(int64_t numel) { return (numel + GN_CHUNK - 1) / GN_CHUNK; }
+struct SquareAdd {                                               // walk_chunk's functor: what a lane past the end read is dropped by a select
+    double& acc;
+    __device__ __forceinline__ void operator()(float (&x)[1], bool valid) const { acc = valid ? square_add(x[0], acc) : acc; }
+};
+
+struct Scale {
+    float coef;
+    __device__ __forceinline__ void operator()(float (&x)[1], bool) const { x[0] *= coef; }
+};
 
 // -1 / -2 for a bad table, else the number of workgroups (= workspace slots) all rows take
 int64_t check_rows(const BinGradTensor* items, int n) {
-    if (n < 0 || (n > 0 && !items)) return BINGRAD_E_ARG;
-    int64_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!items[i].g || items[i].numel < 1) return BINGRAD_E_ARG;
-        if (chunks_of(items[i].numel) > GN_MAX_BLOCKS) return BINGRAD_E_SHAPE;
-        total += chunks_of(items[i].numel);
-    }
-    return total;
-}
-
-// rows [i, i + k) into `tab`, as many as one launch takes; returns k and the launch's workgroup count
-int fill_table(GradTable& tab, const BinGradTensor* items, int i, int n, int64_t& blocks) {
-    blocks = 0;
-    int k = 0;
-    for (; k < BINGRAD_MAX_TENSORS && i + k < n; ++k) {
-        const int64_t nb = chunks_of(items[i + k].numel);
-        if (blocks + nb > GN_MAX_BLOCKS) break;                       // the rest goes into the next launch
-        tab.row[k] = items[i + k];
-        tab.first_block[k] = (int)blocks;
-        blocks += nb;
-    }
-    for (int j = k; j <= BINGRAD_MAX_TENSORS; ++j) tab.first_block[j] = (int)blocks;
-    for (int j = k; j < BINGRAD_MAX_TENSORS; ++j) tab.row[j] = BinGradTensor{};
-    tab.n = k;
-    return k;
+    return GradLaunches::check_rows(items, n, [](const BinGradTensor& r) { return r.g != nullptr; });
 }
 }  // namespace
 
 __global__ void __launch_bounds__(GN_THREADS)
 grad_sumsq_kernel(const GradTable tab, double* __restrict__ slots) {
     const int row = find_row(tab);
-    const float* __restrict__ G = tab.row[row].g;
-    const int64_t numel = tab.row[row].numel;
     const int64_t base = (int64_t)((int)blockIdx.x - tab.first_block[row]) * GN_CHUNK;
     const int t = threadIdx.x;
     double acc = 0.0;
-    if ((((uintptr_t)G) & 15) == 0 && base + GN_CHUNK <= numel) { // a whole chunk of an aligned row: 16 B per lane, nothing predicated
-        float4 g[GN_UNROLL];
-#pragma unroll
-        for (int k = 0; k < GN_UNROLL; ++k) g[k] = *(const float4*)(G + base + 4 * (k * GN_THREADS + t));
-#pragma unroll
-        for (int k = 0; k < GN_UNROLL; ++k) {
-            acc = square_add(g[k].x, acc);
-            acc = square_add(g[k].y, acc);
-            acc = square_add(g[k].z, acc);
-            acc = square_add(g[k].w, acc);
-        }
-    } else {
-        // 4 B per lane, consecutive lanes on consecutive floats.  The loads are not predicated (a lane past the end re-reads the row's
-        // last element, numel >= 1), so all of them are in flight at once; what a lane past the end read is dropped by a select.
-        constexpr int U = GN_UNROLL * 4;
-        float g[U];
-#pragma unroll
-        for (int k = 0; k < U; ++k) g[k] = G[min(base + k * GN_THREADS + t, numel - 1)];
-#pragma unroll
-        for (int k = 0; k < U; ++k) acc = (base + k * GN_THREADS + t < numel) ? square_add(g[k], acc) : acc;
-    }
+    multi_tensor::walk_chunk<GN_THREADS, GN_UNROLL, 0>(tab.row[row].numel, base, SquareAdd{acc}, tab.row[row].g);   // nothing written
     // lanes of a wave: a shuffle tree, the same pairs every run
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
@@ -165,31 +115,8 @@ grad_scale_kernel(const GradTable tab, const BinGradRecord* __restrict__ record)
     const float coef = record->coef;                             // uniform over the grid
     if (coef == 1.0f) return;                                    // not clipped (or not finite): nothing is written
     const int row = find_row(tab);
-    float* __restrict__ G = tab.row[row].g;
-    const int64_t numel = tab.row[row].numel;
     const int64_t base = (int64_t)((int)blockIdx.x - tab.first_block[row]) * GN_CHUNK;
-    const int t = threadIdx.x;
-    if ((((uintptr_t)G) & 15) == 0 && base + GN_CHUNK <= numel) {
-        float4 g[GN_UNROLL];
-#pragma unroll
-        for (int k = 0; k < GN_UNROLL; ++k) g[k] = *(const float4*)(G + base + 4 * (k * GN_THREADS + t));
-#pragma unroll
-        for (int k = 0; k < GN_UNROLL; ++k) {
-            g[k].x *= coef; g[k].y *= coef; g[k].z *= coef; g[k].w *= coef;
-        }
-#pragma unroll
-        for (int k = 0; k < GN_UNROLL; ++k) *(float4*)(G + base + 4 * (k * GN_THREADS + t)) = g[k];
-    } else {
-        constexpr int U = GN_UNROLL * 4;
-        float g[U];
-#pragma unroll
-        for (int k = 0; k < U; ++k) g[k] = G[min(base + k * GN_THREADS + t, numel - 1)];
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            const int64_t e = base + k * GN_THREADS + t;
-            if (e < numel) G[e] = g[k] * coef;
-        }
-    }
+    multi_tensor::walk_chunk<GN_THREADS, GN_UNROLL, 0b1>(tab.row[row].numel, base, Scale{coef}, tab.row[row].g);   // g written
 }
 
 int bingrad_version(void) { return BINGRAD_VERSION; }
@@ -207,18 +134,12 @@ int bingrad_norm(const BinGradTensor* items, int n, float max_norm, const uint32
     if (!(max_norm >= 0.f) || !workspace || !record) return BINGRAD_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     double* slots = (double*)workspace;
-    int64_t slot = 0;
-    int i = 0;
-    while (i < n) {                                              // launches of at most BINGRAD_MAX_TENSORS rows, disjoint slots
-        GradTable tab;
-        int64_t blocks = 0;
-        const int k = fill_table(tab, items, i, n, blocks);
-        hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)blocks), dim3(GN_THREADS), 0, s, tab, slots + slot);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
+    int64_t slot = 0;                                            // launches of at most BINGRAD_MAX_TENSORS rows, disjoint slots
+    const int rc = GradLaunches::for_each_launch<GradTable>(items, n, [&](const GradTable& tab, unsigned blocks) {
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(GN_THREADS), 0, s, tab, slots + slot);
         slot += blocks;
-        i += k;
-    }
+    });
+    if (rc != 0) return rc;
     hipLaunchKernelGGL(grad_final_kernel, dim3(1), dim3(GN_THREADS), 0, s, (const double*)slots, slot, max_norm, status_word, status_mask,
                        record);
     const hipError_t e = hipGetLastError();
@@ -230,15 +151,7 @@ int bingrad_scale(const BinGradTensor* items, int n, const BinGradRecord* record
     if (total < 0) return (int)total;
     if (!record) return BINGRAD_E_ARG;
     hipStream_t s = (hipStream_t)stream;
-    int i = 0;
-    while (i < n) {
-        GradTable tab;
-        int64_t blocks = 0;
-        const int k = fill_table(tab, items, i, n, blocks);
-        hipLaunchKernelGGL(grad_scale_kernel, dim3((unsigned)blocks), dim3(GN_THREADS), 0, s, tab, record);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        i += k;
-    }
-    return 0;
+    return GradLaunches::for_each_launch<GradTable>(items, n, [&](const GradTable& tab, unsigned blocks) {
+        hipLaunchKernelGGL(grad_scale_kernel, dim3(blocks), dim3(GN_THREADS), 0, s, tab, record);
+    });
 }

@@ -714,6 +714,24 @@ def gather_windows_blur(frames_u8, table_host, crop, n_blur, clip_ranges=None):
 
 
 # --------------------------------------------------------------------------------------------- optimizer
+def _check_row_tensors(what, named_tensors):
+    """One row of a by-value table (adam_row, ema_row, grad_rows): float32 contiguous device tensors of one size on one device, not
+    empty.  `named_tensors`: (name, tensor) pairs; a name of None leaves the ` for <name>` out of the message.  The sizes are compared
+    with the tensor named p.  Raises on CPU tensors (there is no CPU fallback)."""
+    _need_cuda(*(t for _, t in named_tensors))
+    p = dict(named_tensors).get("p", named_tensors[0][1])
+    for name, t in named_tensors:
+        suffix = "" if name is None else f" for {name}"
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: float32 tensors, got {t.dtype}{suffix}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: contiguous tensors, got strides {tuple(t.stride())} of shape {tuple(t.shape)}{suffix}")
+        if t.numel() != p.numel() or t.device != p.device:
+            raise ValueError(f"{what}: {name} has {t.numel()} elements on {t.device}, p has {p.numel()} on {p.device}")
+    if p.numel() < 1:
+        raise ValueError(f"{what}: empty tensor")
+
+
 def adam_rows(n):
     """A host table of n BinAdamTensor rows for adam_step (bin_amd.optim.Adam keeps one per group and rewrites only what changed)."""
     return (L.BinAdamTensor * max(n, 1))()
@@ -722,16 +740,7 @@ def adam_rows(n):
 def adam_row(table, i, p, g, m, v, step_size, inv_sqrt_bc2):
     """Fill row i of an adam_rows table from four float32 device tensors of one size.  Raises on CPU tensors (there is no CPU
     fallback), on another dtype and on non-contiguous tensors: the kernel walks numel consecutive floats from each pointer."""
-    _need_cuda(p, g, m, v)
-    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
-        if t.dtype != torch.float32:
-            raise ValueError(f"adam_step: float32 tensors, got {t.dtype} for {name}")
-        if not t.is_contiguous():
-            raise ValueError(f"adam_step: contiguous tensors, got strides {tuple(t.stride())} of shape {tuple(t.shape)} for {name}")
-        if t.numel() != p.numel() or t.device != p.device:
-            raise ValueError(f"adam_step: {name} has {t.numel()} elements on {t.device}, p has {p.numel()} on {p.device}")
-    if p.numel() < 1:
-        raise ValueError("adam_step: empty tensor")
+    _check_row_tensors("adam_step", (("p", p), ("g", g), ("m", m), ("v", v)))
     r = table[i]
     r.p, r.g, r.m, r.v, r.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
     r.step_size, r.inv_sqrt_bc2 = step_size, inv_sqrt_bc2
@@ -783,12 +792,7 @@ def grad_rows(grads):
     _need_cuda(*grads)
     table = (L.BinGradTensor * max(len(grads), 1))()
     for i, g in enumerate(grads):
-        if g.dtype != torch.float32:
-            raise ValueError(f"grad_rows: float32 tensors, got {g.dtype}")
-        if not g.is_contiguous():
-            raise ValueError(f"grad_rows: contiguous tensors, got strides {tuple(g.stride())} of shape {tuple(g.shape)}")
-        if g.numel() < 1:
-            raise ValueError("grad_rows: empty tensor")
+        _check_row_tensors("grad_rows", ((None, g),))
         if g.device != grads[0].device:
             raise ValueError("grad_rows: rows of one table live on one device")
         table[i].g, table[i].numel = g.data_ptr(), g.numel()
@@ -854,16 +858,7 @@ def ema_row(table, i, e, p):
     """Fill row i of an ema_rows table from two float32 device tensors of one size: e, the average, is written; p is only read.
     Raises on CPU tensors (there is no CPU fallback), on another dtype and on non-contiguous tensors: the kernel walks numel
     consecutive floats from each pointer (views at any 4-byte offset are fine)."""
-    _need_cuda(e, p)
-    for name, t in (("e", e), ("p", p)):
-        if t.dtype != torch.float32:
-            raise ValueError(f"ema_step: float32 tensors, got {t.dtype} for {name}")
-        if not t.is_contiguous():
-            raise ValueError(f"ema_step: contiguous tensors, got strides {tuple(t.stride())} of shape {tuple(t.shape)} for {name}")
-        if t.numel() != p.numel() or t.device != p.device:
-            raise ValueError(f"ema_step: {name} has {t.numel()} elements on {t.device}, p has {p.numel()} on {p.device}")
-    if p.numel() < 1:
-        raise ValueError("ema_step: empty tensor")
+    _check_row_tensors("ema_step", (("e", e), ("p", p)))
     r = table[i]
     r.e, r.p, r.numel = e.data_ptr(), p.data_ptr(), p.numel()
 

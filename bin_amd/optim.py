@@ -28,6 +28,19 @@ _UNSUPPORTED = ("amsgrad", "maximize", "capturable", "differentiable")
 _ROW_DTYPE = np.dtype([("p", "u8"), ("g", "u8"), ("m", "u8"), ("v", "u8"), ("numel", "i8"), ("step_size", "f4"), ("inv_sqrt_bc2", "f4")])
 
 
+def _by_device(tensors):
+    """{device: the indices of `tensors` on it}: a library call takes the rows of one device."""
+    by_dev = {}
+    for i, t in enumerate(tensors):
+        by_dev.setdefault(t.device, []).append(i)
+    return by_dev
+
+
+def _reuse(cached, key, build):
+    """The (key, host row table) pair the three classes keep: `cached` while no pointer in `key` changed, else a table built anew."""
+    return cached if cached is not None and cached[0] == key else (key, build())
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
                  capturable=False, differentiable=False):
@@ -90,10 +103,7 @@ class Adam(torch.optim.Optimizer):
             ts = torch.stack(steps).tolist()
             beta1, beta2 = group["betas"]
             lr = float(group["lr"])
-            by_dev = {}
-            for i, p in enumerate(params):
-                by_dev.setdefault(p.device, []).append(i)
-            for dev, idx in by_dev.items():
+            for dev, idx in _by_device(params).items():
                 self._launch(gi, dev, idx, params, states, ts, lr, beta1, beta2, float(group["eps"]),
                              float(group["weight_decay"]))
             # the kernel wrote through raw pointers: the relayout cache key, the streaming memo and autograd's saved-tensor
@@ -103,20 +113,15 @@ class Adam(torch.optim.Optimizer):
 
     def _launch(self, gi, dev, idx, params, states, ts, lr, beta1, beta2, eps, weight_decay):
         n = len(idx)
-        ptrs = []
-        for i in idx:
-            p, s = params[i], states[i]
-            ptrs += [p.data_ptr(), p.grad.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()]
-        key = tuple(ptrs)
-        cached = self._tables.get((gi, dev))
-        if cached is not None and cached[0] == key:
-            table = cached[1]
-        else:
+        rows = [(params[i], params[i].grad, states[i]["exp_avg"], states[i]["exp_avg_sq"]) for i in idx]
+
+        def build():
             table = ops.adam_rows(n)
-            for r, i in enumerate(idx):
-                s = states[i]
-                ops.adam_row(table, r, params[i], params[i].grad, s["exp_avg"], s["exp_avg_sq"], 0.0, 0.0)
-            self._tables[(gi, dev)] = (key, table)
+            for r, row in enumerate(rows):
+                ops.adam_row(table, r, *row, 0.0, 0.0)
+            return table
+        self._tables[(gi, dev)] = _reuse(self._tables.get((gi, dev)), tuple(t.data_ptr() for row in rows for t in row), build)
+        table = self._tables[(gi, dev)][1]
         # the bias corrections in double, rounded once by the float fields of the rows; t may differ between parameters
         t = np.asarray([ts[i] for i in idx], dtype=np.float64)
         view = np.frombuffer(table, dtype=_ROW_DTYPE, count=n)
@@ -204,8 +209,7 @@ class GradGuard:
             raise RuntimeError("bin_amd.optim.GradGuard: gradients must live on a HIP device (there is no CPU fallback; "
                                "use torch.nn.utils.clip_grad_norm_)")
         key = tuple(g.data_ptr() for g in grads) + tuple(g.numel() for g in grads)
-        if self._rows is None or self._rows[0] != key:
-            self._rows = (key, ops.grad_rows(grads))
+        self._rows = _reuse(self._rows, key, lambda: ops.grad_rows(grads))
         rows = self._rows[1]
         dev = rows.device
         if self._record is None or self._record.device != dev:
@@ -273,17 +277,14 @@ class WeightEMA:
             if p.dtype != torch.float32:
                 raise ValueError(f"bin_amd.optim.WeightEMA: float32 parameters, got {p.dtype}")
         self._alloc()
-        self._tables = {}             # device -> (pointers, table, n): the host row table, reused while no pointer changed
+        self._tables = {}             # device -> (pointers, table): the host row table, reused while no pointer changed
         self._held = None             # inside applied(): the training values' tensors, in parameter order
 
     def _alloc(self):
         """One flat buffer per device; a tensor's slice starts on a multiple of 4 floats from the (allocator-aligned) base."""
         self._flat, self.shadow = {}, [None] * len(self.params)
-        by_dev = {}
-        for i, p in enumerate(self.params):
-            by_dev.setdefault(p.device, []).append(i)
         with torch.no_grad():
-            for dev, idx in by_dev.items():
+            for dev, idx in _by_device(self.params).items():
                 offsets, total = [], 0
                 for i in idx:
                     offsets.append(total)
@@ -302,23 +303,18 @@ class WeightEMA:
         """One averaging step of every shadow towards its parameter, on the current stream of each device."""
         if self._held is not None:
             raise RuntimeError("bin_amd.optim.WeightEMA: update() inside applied(): the parameters hold the averaged values")
-        by_dev = {}
-        for i, p in enumerate(self.params):
-            if not p.is_cuda:
-                raise RuntimeError("bin_amd.optim.WeightEMA: parameters must live on a HIP device (there is no CPU fallback; "
-                                   "leave `train.ema_decay` out)")
-            by_dev.setdefault(p.device, []).append(i)
-        for dev, idx in by_dev.items():
-            key = tuple(self.params[i].data_ptr() for i in idx) + tuple(self.shadow[i].data_ptr() for i in idx)
-            cached = self._tables.get(dev)
-            if cached is not None and cached[0] == key:
-                table = cached[1]
-            else:
+        if not all(p.is_cuda for p in self.params):
+            raise RuntimeError("bin_amd.optim.WeightEMA: parameters must live on a HIP device (there is no CPU fallback; "
+                               "leave `train.ema_decay` out)")
+        for dev, idx in _by_device(self.params).items():
+            def build():
                 table = ops.ema_rows(len(idx))
                 for r, i in enumerate(idx):
                     ops.ema_row(table, r, self.shadow[i], self.params[i].detach())
-                self._tables[dev] = (key, table)
-            ops.ema_launch(table, len(idx), dev, self.decay)
+                return table
+            key = tuple(self.params[i].data_ptr() for i in idx) + tuple(self.shadow[i].data_ptr() for i in idx)
+            self._tables[dev] = _reuse(self._tables.get(dev), key, build)
+            ops.ema_launch(self._tables[dev][1], len(idx), dev, self.decay)
         # the kernel wrote through raw pointers: whatever keys on the shadows' version counters must see a new weight set
         torch.autograd.graph.increment_version(self.shadow)
 

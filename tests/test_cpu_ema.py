@@ -199,13 +199,20 @@ def test_kernel_source_keeps_to_plain_cxx_without_atomics_allocation_or_sync():
     code = "\n".join(ln.split("//")[0] for ln in _source().splitlines())
     for word in ("atomic", "asm", "hipMalloc", "Synchronize", "hipMemcpy", "static int", "static double", "static float"):
         assert word not in code, word
-    # both data paths evaluate the one expression, and a path's loads all come before its first store
-    assert code.count("e + w * (p - e)") == 1 and code.count("ema_update(") == 1 + 4 + 1
-    fast = code[code.index("if (aligned &&"):code.index("} else {")]
-    slow = code[code.index("} else {"):code.index("int binema_version")]
-    assert fast.rindex("(const float4*)") < fast.index("*(float4*)(E + i) =")
-    assert slow.rindex("p[k] = P[i]") < slow.index("E[i] = e[k]")
-    assert "(float)(1.0 - shortest_decimal(decay))" in code
+    # both data paths evaluate the one expression, and a path's loads all come before its first store.  The expression is this
+    # file's, handed as one functor to the walk both paths share (binhip_multi_tensor.h), which only e is written back from
+    assert code.count("e + w * (p - e)") == 1 and code.count("ema_update(") == 1 + 1
+    assert code.count("walk_chunk<EM_THREADS, EM_UNROLL, 0b01>(") == 1 and "EmaElement{w}, r.e, r.p);" in code
+    walk = open(os.path.join(REPO, "bin_amd", "csrc", "binhip_multi_tensor.h")).read()
+    walk = "\n".join(ln.split("//")[0] for ln in walk[walk.index("void walk_chunk("):walk.index("inline double shortest_decimal")].splitlines())
+    for word in ("atomic", "asm", "hipMalloc", "Synchronize", "hipMemcpy", "static int", "static double", "static float"):
+        assert word not in walk, word
+    fast, slow = walk[walk.index("if ((low_bits & 15) == 0 &&"):walk.index("} else {")], walk[walk.index("} else {"):]
+    for path, load, call, store in ((fast, "*(const float4*)(ptr[j] +", "f(x[k], true);", "*(float4*)const_cast<float*>(ptr[j] +"),
+                                    (slow, "x[k][j] = ptr[j][e];", "f(x[k], base + k * THREADS + t < numel);", "const_cast<float*>(ptr[j])[e] = x[k][j];")):
+        assert path.count(load) == path.count(call) == path.count(store) == 1, "one load, one call of the functor, one store per path"
+        assert path.index(load) < path.index(call) < path.index(store)
+    assert "(float)(1.0 - multi_tensor::shortest_decimal(decay))" in code
 
 
 # ------------------------------------------------------------------------------------------------ the option

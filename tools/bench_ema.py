@@ -12,34 +12,13 @@ Without --leg, each leg runs as a child process under its own `timeout`, and not
 or step figure printed here is comparable across boxes: compare within one run.
 usage: python tools/bench_ema.py [--leg pass|train] [--samples 60] [--blocks 4] [--repeat 3] [--train_steps 10]"""
 import argparse
-import json
-import os
 import statistics
-import subprocess
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import bench_common as B
 
 LEG_TIMEOUT_S = {"pass": 240, "train": 420}
 BACK = 10
 DECAY = 0.999
-
-
-def _timed(fn, n):
-    """n calls of fn, each between a hipEvent pair on the current stream -> device ms per call."""
-    import torch
-    dev = []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        dev.append(e0.elapsed_time(e1))
-    return dev
 
 
 def leg_pass(args):
@@ -88,12 +67,8 @@ def leg_pass(args):
     for fn in legs.values():                                  # warm-up
         fn()
         fn()
-    ms = {k: [] for k in legs}
-    per_block = max(1, args.samples // args.blocks)
-    for _ in range(args.blocks):                              # alternating blocks
-        for k, fn in legs.items():
-            ms[k] += [v / BACK for v in _timed(fn, per_block)]
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    ms = {k: [v / BACK for v in dev] for k, dev in B.alternating_blocks(legs, args.blocks, max(1, args.samples // args.blocks))[0].items()}
+    med = B.medians(ms)
     nbytes = 12 * numel
     rate = {k: nbytes / (med[k] * 1e-3) / 1e12 for k in med}
     out = {"what": "ema_pass", "tensors": n, "elements": numel, "bytes_per_pass": nbytes, "launches_per_pass": launches,
@@ -112,51 +87,17 @@ def leg_pass(args):
     return out
 
 
-def _train_model(ema_decay):
-    """The training model of bench.py's training leg (8 x 256^2, f16x3) with `train.ema_decay` set or absent, one synthetic batch fed."""
-    import tempfile
-    import torch
-    from bin_amd.models import create_model
-    from bin_amd.weights import reference_state_dict
-    tmp = tempfile.mkdtemp()
-    opt = {"model": "bin", "gpu_ids": [0], "is_train": True, "dist": False,
-           "network_G": {"which_model_G": "bin_stage4", "nframes": 6, "version": 2, "precision": "f16x3", "backward_precision": None},
-           "path": {"pretrain_model_G": None, "strict_load": True, "models": tmp, "training_state": tmp},
-           "train": {"pixel_criterion": "cb", "pixel_weight": 1.0, "weight_decay_G": 0, "ft_tsa_only": None, "optimizer": "hip",
-                     "lr_G": 1e-4, "beta1": 0.9, "beta2": 0.99, "lr_scheme": "MultiStepLR", "lr_steps": [100000],
-                     "restarts": None, "restart_weights": None, "lr_gamma": 0.5, "clear_state": False}}
-    if ema_decay:
-        opt["train"]["ema_decay"] = ema_decay
-    m = create_model(opt)
-    m.netG.module.load_state_dict(reference_state_dict(0), strict=True)
-    g = torch.Generator().manual_seed(7)
-    B, S = 8, 256
-    m.feed_data({"LQs": torch.rand(B, 6, 3, S, S, generator=g), "GTenh": torch.rand(B, 6, 3, S, S, generator=g),
-                 "GTinp": torch.rand(B, 5, 3, S, S, generator=g)})
-    return m
-
-
 def leg_train(args):
     import torch
-    models = {"off": _train_model(None), "ema": _train_model(DECAY)}
+    models = {"off": B.train_model(), "ema": B.train_model(ema_decay=DECAY)}
     assert models["off"].weight_ema is None and type(models["ema"].weight_ema).__name__ == "WeightEMA"
-    n = {k: 0 for k in models}
-
-    def block(k, steps):
-        m = models[k]
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            n[k] += 1
-            m.optimize_parameters(n[k])
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / steps
-    for k in models:
-        block(k, 3)                                           # warm-up
+    n = {}
+    for m in models.values():
+        B.train_block(m, 3, n)                                # warm-up
     ms = {k: [] for k in models}
     for _ in range(args.repeat):                              # alternating
-        for k in models:
-            ms[k].append(block(k, args.train_steps))
+        for k, m in models.items():
+            ms[k].append(B.train_block(m, args.train_steps, n))
     losses = {k: float(models[k].loss.detach()) for k in models}
     med = {k: statistics.median(v) for k, v in ms.items()}
     return {"what": "training_step", "workload": "8 x 256^2 crops, f16x3, fwd + loss + bwd + Adam (hip)", "steps_per_block": args.train_steps,
@@ -175,20 +116,7 @@ def main():
     ap.add_argument("--train_steps", type=int, default=10)
     args = ap.parse_args()
     assert args.samples >= 50, "median of at least 50 samples"
-    if args.leg is None:
-        for leg, limit in LEG_TIMEOUT_S.items():              # each GPU step under its own time limit; stop at the first failure
-            cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--samples", str(args.samples),
-                   "--blocks", str(args.blocks), "--repeat", str(args.repeat), "--train_steps", str(args.train_steps)]
-            rc = subprocess.run(cmd, cwd=REPO).returncode
-            if rc != 0:
-                print(json.dumps({"what": "failed", "leg": leg, "exit_status": rc}), flush=True)
-                sys.exit(rc)
-        return
-    import torch
-    assert torch.cuda.is_available(), "bench_ema needs a GPU"
-    print(json.dumps({"what": "clock", "utc": time.strftime("%Y-%m-%d %H:%M:%S", time.gmtime()),
-                      "device": torch.cuda.get_device_name(0)}), flush=True)
-    print(json.dumps(leg_pass(args) if args.leg == "pass" else leg_train(args)), flush=True)
+    B.main(__file__, {"pass": leg_pass, "train": leg_train}, LEG_TIMEOUT_S, args, ("samples", "blocks", "repeat", "train_steps"))
 
 
 if __name__ == "__main__":

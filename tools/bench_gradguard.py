@@ -12,37 +12,11 @@ on bin_stage4's 540 gradients (11.44 M floats, 45.77 MB).  Needs no files on dis
 Without --leg, each leg runs as a child process under its own `timeout`, and nothing is started after a leg that failed.
 usage: python tools/bench_gradguard.py [--leg pass|train] [--steps 60] [--blocks 4] [--repeat 3] [--train_steps 10]"""
 import argparse
-import json
-import os
 import statistics
-import subprocess
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import bench_common as B
 
 LEG_TIMEOUT_S = {"pass": 240, "train": 500}
-
-
-def _timed(fn, n, before=None):
-    """n calls of fn, each between a hipEvent pair on the current stream with the stream idle before it (`before`, untimed, runs
-    first) -> (device ms per call, host ms per call)."""
-    import torch
-    dev, host = [], []
-    for _ in range(n):
-        if before is not None:
-            before()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        e0.record()
-        fn()
-        e1.record()
-        host.append((time.perf_counter() - t0) * 1e3)
-        e1.synchronize()
-        dev.append(e0.elapsed_time(e1))
-    return dev, host
 
 
 def leg_pass(args):
@@ -114,18 +88,11 @@ def leg_pass(args):
         restore()
         f()
     assert 0.49 < guard.last.coef < 0.51
-    ms = {k: [] for k in calls}
-    dev = {k: [] for k in host_calls}
-    host = {k: [] for k in host_calls}
-    per_block = max(1, args.steps // args.blocks)
-    for _ in range(args.blocks):                              # alternating blocks
-        for k, f in calls.items():
-            ms[k] += [v / BACK for v in _timed(f, per_block)[0]]
-        for k, f in host_calls.items():
-            d, h = _timed(f, per_block, before=restore)
-            dev[k] += d
-            host[k] += h
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    both, host = B.alternating_blocks({**calls, **host_calls}, args.blocks, max(1, args.steps // args.blocks),
+                                      before={k: restore for k in host_calls})
+    ms = {k: [v / BACK for v in both[k]] for k in calls}
+    dev = {k: both[k] for k in host_calls}
+    med = B.medians(ms)
     nbytes = 4 * numel
     out = {"what": "grad_guard_passes", "tensors": len(shapes), "elements": numel, "bytes": nbytes, "calls_timed_each": len(ms["copy"]),
            "blocks": args.blocks, "norm_of_the_test_gradients": norm}
@@ -147,49 +114,19 @@ def leg_pass(args):
     return out
 
 
-def _train_model(**train):
-    """The training model of bench.py's training leg (8 x 256^2, f16x3, `train.optimizer: hip`) with the given train options, one
-    synthetic batch fed."""
-    import tempfile
-    import torch
-    from bin_amd.models import create_model
-    from bin_amd.weights import reference_state_dict
-    tmp = tempfile.mkdtemp()
-    opt = {"model": "bin", "gpu_ids": [0], "is_train": True, "dist": False,
-           "network_G": {"which_model_G": "bin_stage4", "nframes": 6, "version": 2, "precision": "f16x3", "backward_precision": None},
-           "path": {"pretrain_model_G": None, "strict_load": True, "models": tmp, "training_state": tmp},
-           "train": {"pixel_criterion": "cb", "pixel_weight": 1.0, "weight_decay_G": 0, "ft_tsa_only": None, "optimizer": "hip",
-                     "lr_G": 1e-4, "beta1": 0.9, "beta2": 0.99, "lr_scheme": "MultiStepLR", "lr_steps": [100000],
-                     "restarts": None, "restart_weights": None, "lr_gamma": 0.5, "clear_state": False}}
-    opt["train"].update(train)
-    m = create_model(opt)
-    m.netG.module.load_state_dict(reference_state_dict(0), strict=True)
-    g = torch.Generator().manual_seed(7)
-    B, S = 8, 256
-    m.feed_data({"LQs": torch.rand(B, 6, 3, S, S, generator=g), "GTenh": torch.rand(B, 6, 3, S, S, generator=g),
-                 "GTinp": torch.rand(B, 5, 3, S, S, generator=g)})
-    return m
-
-
 def leg_train(args):
     import torch
     out = {"what": "training_step", "workload": "8 x 256^2 crops, f16x3, fwd + loss + bwd + guard + Adam (train.optimizer: hip)",
            "steps_per_block": args.train_steps, "pairs": args.repeat}
-    off = _train_model()
+    off = B.train_model()
     assert off.grad_guard is None
     n = {}
 
     def block(m, steps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            n[id(m)] = n.get(id(m), 0) + 1
-            m.optimize_parameters(n[id(m)])
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / steps
+        return B.train_block(m, steps, n)
     block(off, 3)                                             # warm-up
     for name, train in (("clip", {"grad_clip": 1.0}), ("skip", {"skip_bad_steps": 5})):
-        on = _train_model(**train)                            # two models alive at a time
+        on = B.train_model(**train)                            # two models alive at a time
         assert on.grad_guard is not None and (on.grad_guard.max_norm, on.grad_guard.skip_bad_steps) == (train.get("grad_clip", 0.0), train.get("skip_bad_steps", 0))
         block(on, 3)
         ms = {"on": [], "off": []}
@@ -219,20 +156,7 @@ def main():
     ap.add_argument("--train_steps", type=int, default=10)
     args = ap.parse_args()
     assert args.steps >= 50, "median of at least 50 calls"
-    if args.leg is None:
-        for leg, limit in LEG_TIMEOUT_S.items():              # each GPU step under its own time limit; stop at the first failure
-            cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--steps", str(args.steps),
-                   "--blocks", str(args.blocks), "--repeat", str(args.repeat), "--train_steps", str(args.train_steps)]
-            rc = subprocess.run(cmd, cwd=REPO).returncode
-            if rc != 0:
-                print(json.dumps({"what": "failed", "leg": leg, "exit_status": rc}), flush=True)
-                sys.exit(rc)
-        return
-    import torch
-    assert torch.cuda.is_available(), "bench_gradguard needs a GPU"
-    print(json.dumps({"what": "clock", "utc": time.strftime("%Y-%m-%d %H:%M:%S", time.gmtime()),
-                      "device": torch.cuda.get_device_name(0)}), flush=True)
-    print(json.dumps(leg_pass(args) if args.leg == "pass" else leg_train(args)), flush=True)
+    B.main(__file__, {"pass": leg_pass, "train": leg_train}, LEG_TIMEOUT_S, args, ("steps", "blocks", "repeat", "train_steps"))
 
 
 if __name__ == "__main__":

@@ -11,15 +11,9 @@ bin_amd.optim.Adam (binopt_adam_step, `train.optimizer: hip`).  Needs no files o
 Without --leg, each leg runs as a child process under its own `timeout`, and nothing is started after a leg that failed.
 usage: python tools/bench_optimizer.py [--leg step|train] [--steps 60] [--blocks 4] [--repeat 3] [--train_steps 10]"""
 import argparse
-import json
-import os
 import statistics
-import subprocess
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import bench_common as B
 
 LEG_TIMEOUT_S = {"step": 240, "train": 420}
 
@@ -32,23 +26,6 @@ def _params_and_grads(seed):
     for p in params:
         p.grad = (torch.randn(p.shape, generator=g) * 1e-3).cuda()
     return params
-
-
-def _timed(fn, n):
-    """n calls of fn, each between a hipEvent pair on the current stream -> (device ms per call, host ms per call)."""
-    import torch
-    dev, host = [], []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        e0.record()
-        fn()
-        e1.record()
-        host.append((time.perf_counter() - t0) * 1e3)
-        e1.synchronize()
-        dev.append(e0.elapsed_time(e1))
-    return dev, host
 
 
 def leg_step(args):
@@ -97,18 +74,11 @@ def leg_step(args):
             dst.copy_(src)
     kernel()
     kernel_one_row()
-    ms = {"torch": [], "hip": [], "copy": [], "kernel": [], "kernel_one_row": []}
-    host = {"torch": [], "hip": []}
-    per_block = max(1, args.steps // args.blocks)
-    for _ in range(args.blocks):                              # alternating blocks
-        for k, o in opts.items():
-            d, h = _timed(o.step, per_block)
-            ms[k] += d
-            host[k] += h
-        ms["kernel"] += [v / BACK for v in _timed(kernel, per_block)[0]]
-        ms["kernel_one_row"] += [v / BACK for v in _timed(kernel_one_row, per_block)[0]]
-        ms["copy"] += [v / BACK for v in _timed(copy, per_block)[0]]
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    calls = {"torch": opts["torch"].step, "hip": opts["hip"].step, "kernel": kernel, "kernel_one_row": kernel_one_row, "copy": copy}
+    ms, host = B.alternating_blocks(calls, args.blocks, max(1, args.steps // args.blocks))
+    for k in ("kernel", "kernel_one_row", "copy"):
+        ms[k] = [v / BACK for v in ms[k]]
+    med = B.medians(ms)
     nbytes = 28 * numel
     rate = {k: nbytes / (med[k] * 1e-3) / 1e12 for k in med}
     return {"what": "optimizer_step", "tensors": len(sets["hip"]), "elements": numel, "bytes_per_step": nbytes,
@@ -129,49 +99,17 @@ def leg_step(args):
                     "timed the same way"}
 
 
-def _train_model(optimizer):
-    """The training model of bench.py's training leg (8 x 256^2, f16x3) with `train.optimizer` set, one synthetic batch fed."""
-    import tempfile
-    import torch
-    from bin_amd.models import create_model
-    from bin_amd.weights import reference_state_dict
-    tmp = tempfile.mkdtemp()
-    opt = {"model": "bin", "gpu_ids": [0], "is_train": True, "dist": False,
-           "network_G": {"which_model_G": "bin_stage4", "nframes": 6, "version": 2, "precision": "f16x3", "backward_precision": None},
-           "path": {"pretrain_model_G": None, "strict_load": True, "models": tmp, "training_state": tmp},
-           "train": {"pixel_criterion": "cb", "pixel_weight": 1.0, "weight_decay_G": 0, "ft_tsa_only": None, "optimizer": optimizer,
-                     "lr_G": 1e-4, "beta1": 0.9, "beta2": 0.99, "lr_scheme": "MultiStepLR", "lr_steps": [100000],
-                     "restarts": None, "restart_weights": None, "lr_gamma": 0.5, "clear_state": False}}
-    m = create_model(opt)
-    m.netG.module.load_state_dict(reference_state_dict(0), strict=True)
-    g = torch.Generator().manual_seed(7)
-    B, S = 8, 256
-    m.feed_data({"LQs": torch.rand(B, 6, 3, S, S, generator=g), "GTenh": torch.rand(B, 6, 3, S, S, generator=g),
-                 "GTinp": torch.rand(B, 5, 3, S, S, generator=g)})
-    return m
-
-
 def leg_train(args):
     import torch
-    models = {k: _train_model(k) for k in ("torch", "hip")}
+    models = {k: B.train_model(optimizer=k) for k in ("torch", "hip")}
     assert type(models["hip"].optimizer_G).__module__ == "bin_amd.optim" and type(models["torch"].optimizer_G) is torch.optim.Adam
-    n = {k: 0 for k in models}
-
-    def block(k, steps):
-        m = models[k]
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            n[k] += 1
-            m.optimize_parameters(n[k])
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / steps
-    for k in models:
-        block(k, 3)                                           # warm-up
+    n = {}
+    for m in models.values():
+        B.train_block(m, 3, n)                                # warm-up
     ms = {k: [] for k in models}
     for _ in range(args.repeat):                              # alternating
-        for k in models:
-            ms[k].append(block(k, args.train_steps))
+        for k, m in models.items():
+            ms[k].append(B.train_block(m, args.train_steps, n))
     losses = {k: float(models[k].loss) for k in models}
     return {"what": "training_step", "workload": "8 x 256^2 crops, f16x3, fwd + loss + bwd + Adam", "steps_per_block": args.train_steps,
             "torch_ms_per_step": [round(v, 3) for v in ms["torch"]], "hip_ms_per_step": [round(v, 3) for v in ms["hip"]],
@@ -189,20 +127,7 @@ def main():
     ap.add_argument("--train_steps", type=int, default=10)
     args = ap.parse_args()
     assert args.steps >= 50, "median of at least 50 steps"
-    if args.leg is None:
-        for leg, limit in LEG_TIMEOUT_S.items():              # each GPU step under its own time limit; stop at the first failure
-            cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", leg, "--steps", str(args.steps),
-                   "--blocks", str(args.blocks), "--repeat", str(args.repeat), "--train_steps", str(args.train_steps)]
-            rc = subprocess.run(cmd, cwd=REPO).returncode
-            if rc != 0:
-                print(json.dumps({"what": "failed", "leg": leg, "exit_status": rc}), flush=True)
-                sys.exit(rc)
-        return
-    import torch
-    assert torch.cuda.is_available(), "bench_optimizer needs a GPU"
-    print(json.dumps({"what": "clock", "utc": time.strftime("%Y-%m-%d %H:%M:%S", time.gmtime()),
-                      "device": torch.cuda.get_device_name(0)}), flush=True)
-    print(json.dumps(leg_step(args) if args.leg == "step" else leg_train(args)), flush=True)
+    B.main(__file__, {"step": leg_step, "train": leg_train}, LEG_TIMEOUT_S, args, ("steps", "blocks", "repeat", "train_steps"))
 
 
 if __name__ == "__main__":
