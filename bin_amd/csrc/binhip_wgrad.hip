@@ -14,6 +14,7 @@
 // keeping all its taps' 32x32 accumulators in registers (K-split over the 4 waves by pixel row).  At the end the
 // 4 waves are reduced through LDS and ONE partial per block is written; a second kernel sums the PB partials in a
 // fixed order (deterministic), un-scales and scatters to OIHW fp32.
+// Tests: tests/wgrad_cases.py restates wg_geom() / w1_plan() and holds one case per kernel, variant and work-split property.
 #include "binhip_internal.h"
 #include <utility>
 
@@ -983,6 +984,7 @@ extern "C" {
 
 size_t binhip_wgrad_workspace_bytes(int ksize, int N, int H, int W, int cin_chunks, int cout) {
     if (N <= 0 || H <= 0 || W <= 0 || cin_chunks <= 0 || cout <= 0) return 0;
+    if (ksize != 1 && ksize != 3 && ksize != 5) return 0;      // as binhip_conv2d_bwd_weight; wg_geom() divides by the tap rows
     const WgGeom g = wg_geom(ksize, N, H, W, cin_chunks, cout, cus());
     return (g.partial_floats + g.bias_floats) * sizeof(float) + 256;
 }

@@ -422,21 +422,36 @@ def conv2d_bwd_data(gy, dw, res=None, res_chunks=0, acc=None, mask=None, mask_fr
     return out
 
 
-def conv2d_bwd_weight(x, gy, cout, cin, ks, nterms, inv_scale=None, shuffle=False):
-    """(dW [cout,cin,ks,ks], db [cout]) fp32 from saved input planes x and gradient planes gy."""
-    _, n, h, w, _ = x.hi.shape
+def conv2d_bwd_weight(x, gy, cout, cin, ks, nterms, inv_scale=None, shuffle=False, accumulate=False, x_cpg=0,
+                      x_group_stride=0, out=None, workspace=None):
+    """(dW [cout,cin,ks,ks], db [cout]) fp32 from saved input planes x and gradient planes gy.  `accumulate`: add to `out` instead of
+    overwriting it.  `x_cpg` / `x_group_stride` (fp16 elements): input chunk i lives in group i // x_cpg of x (BinConvDesc).  `out`: the
+    caller's contiguous fp32 (dw, db), views into larger buffers included.  `workspace`: the caller's uint8 buffer of at least
+    binhip_wgrad_workspace_bytes() bytes (a shorter one is the library's BINHIP_E_WORKSPACE)."""
+    n, h, w = gy.hi.shape[1:4]
     lib = L.lib()
     d = L.BinConvDesc()
     d.N, d.H, d.W, d.ksize = n, h, w, ks
     d.cin_chunks, d.cout, d.cout_pad, d.nterms = chunks(cin), cout, 0, nterms
-    d.epilogue, d.relu, d.x_cpg, d.x_group_stride, d.n_images = 0, 0, 0, 0, 0
+    d.epilogue, d.relu, d.x_cpg, d.x_group_stride, d.n_images = 0, 0, int(x_cpg), int(x_group_stride), 0
     dev = x.hi.device
-    ws = torch.empty(lib.binhip_wgrad_workspace_bytes(ks, n, h, w, chunks(cin), cout), dtype=torch.uint8, device=dev)
-    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=dev)
-    db = torch.empty((cout,), dtype=torch.float32, device=dev)
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(lib.binhip_wgrad_workspace_bytes(ks, n, h, w, chunks(cin), cout), dtype=torch.uint8, device=dev)
+    if out is None:
+        if accumulate:
+            raise ValueError("bin_amd: conv2d_bwd_weight(accumulate=True) needs out=(dw, db) to add to")
+        dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=dev)
+        db = torch.empty((cout,), dtype=torch.float32, device=dev)
+    else:
+        dw, db = out
+        _need_cuda(dw, db)
+        if (dw.dtype != torch.float32 or db.dtype != torch.float32 or tuple(dw.shape) != (cout, cin, ks, ks)
+                or tuple(db.shape) != (cout,) or not dw.is_contiguous() or not db.is_contiguous()):
+            raise ValueError("bin_amd: conv2d_bwd_weight out= must be contiguous fp32 (dw [cout,cin,ks,ks], db [cout])")
     L.check(lib.binhip_conv2d_bwd_weight(C.byref(d), _ptr(x.hi), _ptr(x.lo), _ptr(gy.hi), _ptr(gy.lo),
-                                         _ptr(inv_scale), _ptr(ws), ws.numel(), _ptr(dw), _ptr(db), cin,
-                                         1 if shuffle else 0, 0, _stream()), "conv2d_bwd_weight")
+                                         _ptr(inv_scale), _ptr(ws), ws.numel() * ws.element_size(), _ptr(dw), _ptr(db), cin,
+                                         1 if shuffle else 0, 1 if accumulate else 0, _stream()), "conv2d_bwd_weight")
     return dw, db
 
 

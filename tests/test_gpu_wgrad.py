@@ -1,4 +1,5 @@
-"""-m gpu: weight-gradient kernels (3x3 X-row, 5x5, 1x1 streaming, the batched reduction) and the conv backward-data/weight fixtures, against the reference's autograd outputs and float64."""
+"""-m gpu: weight-gradient kernels (3x3 X-row, 5x5, 1x1 streaming, the batched reduction) and the conv backward-data/weight fixtures, against the reference's autograd outputs and float64; and, over the case table of tests/wgrad_cases.py, exact integer and split-exact probes that both precisions must
+return bit for bit ("Weight-gradient kernels")."""
 import hashlib
 import os
 import socket
@@ -9,6 +10,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+import wgrad_cases as wc
 
 pytestmark = pytest.mark.gpu
 
@@ -109,6 +111,221 @@ def test_wgrad_1x1_ragged(nterms, cfg):
     assert _rel(db.cpu().double(), b.grad) <= TOL_BWD[nterms]
     dw2, db2 = ops.conv2d_bwd_weight(ops.nchw_to_planes(x.float().cuda(), nterms),
                                      ops.nchw_to_planes(gy.float().cuda(), nterms), cout, cin, 1, nterms)
+    assert torch.equal(dw, dw2) and torch.equal(db, db2), "fixed summation order"
+
+
+# ------------------------------------------------------------------------------------------------ the case table (tests/wgrad_cases.py)
+# Exact probes: operands whose products and partial sums are exact in fp16, in the MFMA and in fp32 (families A and B), so both precisions
+# must return the float64 reference BIT FOR BIT whatever the summation order; no tolerance anywhere but in the white-noise family C, which
+# keeps TOL_BWD.  Every test asserts the case's work-split property with the CU count of the device it runs on.
+SENTINEL = -7.25e7
+GUARD = 61                                # floats of sentinel on either side of dw / db: the views start off a 16-byte boundary
+
+
+def _case(tag):
+    """(case, geometry on this device) with every property of the case asserted, and the library's workspace size held to geometry()."""
+    from bin_amd import _lib as L
+    lib = L.lib()
+    c = wc.BY_TAG[tag]
+    g = wc.check_properties(c, lib.binhip_device_cus())
+    assert lib.binhip_wgrad_workspace_bytes(c.ks, c.N, c.H, c.W, wc.chunks(c.cin), c.cout) == g.workspace_bytes
+    return c, g
+
+
+def _planes(t, nterms):
+    from bin_amd import ops
+    return ops.nchw_to_planes(t.cuda(), nterms)
+
+
+def _exact(got, ref, what):
+    """torch.equal against the float64 reference, with the count and size of the differences in the message."""
+    got = got.detach().cpu().double()
+    if not torch.equal(got, ref):
+        bad = got != ref                                          # a NaN differs from everything
+        diff = (got - ref)[bad]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {ref.numel()} differ, largest |difference| {float(diff.abs().max())}, "
+                             f"first at {tuple(bad.nonzero()[0].tolist())}: got {float(got[bad][0])}, reference {float(ref[bad][0])}")
+
+
+def _guarded(shape):
+    """(view, whole buffer): a contiguous fp32 view of `shape` with GUARD sentinel floats on either side."""
+    n = int(np.prod(shape))
+    buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
+    return buf[GUARD:GUARD + n].view(shape), buf
+
+
+def _guards_intact(buf):
+    return bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[-GUARD:] == SENTINEL).all())
+
+
+def _nan_workspace(g, extra=0):
+    """A caller's workspace of exactly the needed size (+ extra), every byte of it a NaN pattern, 16 bytes into its allocation."""
+    ws = torch.full((g.workspace_bytes // 4 + 8 + (extra + 3) // 4,), float("nan"), dtype=torch.float32, device="cuda").view(torch.uint8)
+    return ws[16:16 + g.workspace_bytes + extra]
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.TAGS)
+def test_wgrad_integer_probe_is_bit_exact(tag, nterms):
+    """Family A over the whole table: dW and db are the float64 reference's integers, bit for bit, in both precisions."""
+    from bin_amd import ops
+    c, g = _case(tag)
+    x, gy = wc.family_a(c)
+    dw, db = ops.conv2d_bwd_weight(_planes(x, nterms), _planes(gy, nterms), c.cout, c.cin, c.ks, nterms)
+    rw, rb = wc.reference_a(tag)
+    _exact(dw, rw, f"{tag} dW ({g.kernel}, PB {g.PB}, {g.tiles_min}-{g.tiles_max} tiles per workgroup)")
+    _exact(db, rb, f"{tag} db")
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.SPLIT_TAGS)
+def test_wgrad_split_exact_probe_is_bit_exact(tag, nterms):
+    """Family B: the stored planes are hi = a, lo = b 2^-11, and the result is sum xh gh + xl gh + xh gl of those planes exactly (at
+    nterms = 1 the pure-hi part, an integer)."""
+    from bin_amd import ops
+    c, g = _case(tag)
+    x, gy, (xa, xb, ga, gb) = wc.family_b(c)
+    xp, gp = _planes(x, nterms), _planes(gy, nterms)
+    xh, gh = wc.planes_to_nchw(xp.hi, c.cin), wc.planes_to_nchw(gp.hi, c.cout)
+    assert torch.equal(xh, xa) and torch.equal(gh, ga), "hi planes"
+    if nterms == 3:
+        xl, gl = wc.planes_to_nchw(xp.lo, c.cin), wc.planes_to_nchw(gp.lo, c.cout)
+        assert torch.equal(xl, xb * 2.0 ** -11) and torch.equal(gl, gb * 2.0 ** -11), "lo planes"
+    else:
+        xl = gl = None
+    rw, rb = wc.split_reference(xh, xl, gh, gl, c.ks, nterms)
+    dw, db = ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms)
+    _exact(dw, rw, f"{tag} dW ({g.kernel})")
+    _exact(db, rb, f"{tag} db")
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.ARG_TAGS)
+def test_wgrad_accumulate_and_inv_scale_are_exact(tag, nterms):
+    """accumulate = 1 onto integer-filled dW / db gives the integer sum; inv_scale = 2^-3 and 2^5 scale the integers exactly."""
+    from bin_amd import ops
+    c, _ = _case(tag)
+    x, gy = wc.family_a(c)
+    xp, gp = _planes(x, nterms), _planes(gy, nterms)
+    rw, rb = wc.reference_a(tag)
+    gen = torch.Generator().manual_seed(77)
+    dw0 = torch.randint(-1000, 1001, rw.shape, generator=gen).float()
+    db0 = torch.randint(-1000, 1001, rb.shape, generator=gen).float()
+    dw, db = dw0.clone().cuda(), db0.clone().cuda()
+    out = ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms, accumulate=True, out=(dw, db))
+    assert out[0] is dw and out[1] is db
+    _exact(dw, rw + dw0.double(), f"{tag} accumulated dW")
+    _exact(db, rb + db0.double(), f"{tag} accumulated db")
+    for scale in (2.0 ** -3, 2.0 ** 5):
+        sc = torch.tensor([scale, 1.0 / scale], dtype=torch.float32, device="cuda")
+        sw, sb = ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms, inv_scale=sc[:1])
+        _exact(sw, rw * scale, f"{tag} dW x {scale}")
+        _exact(sb, rb * scale, f"{tag} db x {scale}")
+    ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms, inv_scale=sc[:1], accumulate=True, out=(dw, db))
+    _exact(dw, rw * 33 + dw0.double(), f"{tag} dW accumulated twice, the second time x 32")
+    _exact(db, rb * 33 + db0.double(), f"{tag} db accumulated twice")
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.SHUFFLE_TAGS)
+def test_wgrad_shuffle_perm_is_the_row_permutation(tag, nterms):
+    """shuffle_perm at cout 256: row co of the plain result lands at row (co % 64) * 4 + co // 64 (UPNet.0's PixelShuffle order)."""
+    from bin_amd import ops
+    c, _ = _case(tag)
+    x, gy = wc.family_a(c)
+    dw, db = ops.conv2d_bwd_weight(_planes(x, nterms), _planes(gy, nterms), c.cout, c.cin, c.ks, nterms, shuffle=True)
+    rw, rb = wc.reference_a(tag)
+    _exact(dw, wc.shuffle_rows(rw), f"{tag} shuffled dW")
+    _exact(db, wc.shuffle_rows(rb), f"{tag} shuffled db")
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.GROUP_TAGS)
+def test_wgrad_grouped_input_planes(tag, nterms):
+    """x_cpg = 6 with a group stride of 14 planes (GFF.0 reads planes 0 - 5 of each block buffer): input chunk i is plane
+    14 (i // 6) + i % 6 of a buffer whose other planes hold 1000.0.  Equal to the call on the gathered planes, and to the reference."""
+    from bin_amd import ops
+    c, _ = _case(tag)
+    x, gy = wc.family_a(c)
+    xp, gp = _planes(x, nterms), _planes(gy, nterms)
+    cc = wc.chunks(c.cin)
+    ngroups = (cc + 5) // 6
+    big_hi = torch.full((14 * ngroups,) + tuple(xp.hi.shape[1:]), 1000.0, dtype=torch.float16, device="cuda")
+    big_lo = torch.full_like(big_hi, 1000.0) if nterms == 3 else None
+    for i in range(cc):
+        big_hi[14 * (i // 6) + i % 6] = xp.hi[i]
+        if nterms == 3:
+            big_lo[14 * (i // 6) + i % 6] = xp.lo[i]
+    plane = xp.hi[0].numel()
+    dw, db = ops.conv2d_bwd_weight(ops.CP(big_hi, big_lo, c.cin), gp, c.cout, c.cin, c.ks, nterms, x_cpg=6, x_group_stride=14 * plane)
+    pw, pb = ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms)
+    assert torch.equal(dw, pw) and torch.equal(db, pb), "grouped planes != gathered planes"
+    rw, rb = wc.reference_a(tag)
+    _exact(dw, rw, f"{tag} dW from grouped planes")
+    _exact(db, rb, f"{tag} db from grouped planes")
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.TAGS)
+def test_wgrad_relies_on_no_memory_contents(tag, nterms):
+    """A caller's workspace full of NaN (and 16 bytes off its allocation), dW / db as views inside buffers of a sentinel: after a
+    non-accumulating call the results are exact and every sentinel stands, whatever cout leaves of the last 32- or 64-wide tile (35, 3,
+    12).  A workspace one byte short is refused and writes nothing."""
+    from bin_amd import ops
+    c, g = _case(tag)
+    x, gy = wc.family_a(c)
+    xp, gp = _planes(x, nterms), _planes(gy, nterms)
+    dw, dw_buf = _guarded((c.cout, c.cin, c.ks, c.ks))
+    db, db_buf = _guarded((c.cout,))
+    with pytest.raises(RuntimeError, match="workspace too small"):
+        ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms, out=(dw, db), workspace=_nan_workspace(g, -1))
+    assert bool((dw_buf == SENTINEL).all()) and bool((db_buf == SENTINEL).all())
+    ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms, out=(dw, db), workspace=_nan_workspace(g))
+    rw, rb = wc.reference_a(tag)
+    _exact(dw, rw, f"{tag} dW with a NaN workspace")
+    _exact(db, rb, f"{tag} db with a NaN workspace")
+    assert _guards_intact(dw_buf) and _guards_intact(db_buf), "sentinel around dW / db overwritten"
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.IMAGE_SUM_TAGS)
+def test_wgrad_batch_equals_the_sum_of_its_images(tag, nterms):
+    """The N-image call equals the exact sum of its N single-image calls (which split their tiles differently: another PB, other
+    rounds), accumulated by the kernel itself into one buffer."""
+    from bin_amd import ops
+    c, _ = _case(tag)
+    x, gy = wc.family_a(c)
+    dw, db = ops.conv2d_bwd_weight(_planes(x, nterms), _planes(gy, nterms), c.cout, c.cin, c.ks, nterms)
+    sw, sb = torch.zeros_like(dw), torch.zeros_like(db)
+    for i in range(c.N):
+        ops.conv2d_bwd_weight(_planes(x[i:i + 1], nterms), _planes(gy[i:i + 1], nterms), c.cout, c.cin, c.ks, nterms, accumulate=True,
+                              out=(sw, sb))
+    assert torch.equal(dw, sw) and torch.equal(db, sb)
+    rw, rb = wc.reference_a(tag)
+    _exact(sw, rw, f"{tag} dW summed over single images")
+
+
+_ratios = {}
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.TAGS)
+def test_wgrad_white_noise_vs_float64(tag, nterms):
+    """Family C over the whole table against float64 at TOL_BWD; two calls give the same bits (fixed summation order).  Prints the
+    largest error-to-bar ratio so far per kernel and precision."""
+    from bin_amd import ops
+    c, g = _case(tag)
+    x, gy = wc.family_c(c)
+    xp, gp = _planes(x, nterms), _planes(gy, nterms)
+    dw, db = ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms)
+    rw, rb = wc.reference_c(tag)
+    ew, eb = _rel(dw.cpu().double(), rw), _rel(db.cpu().double(), rb)
+    key = (g.kernel, nterms)
+    _ratios[key] = max(_ratios.get(key, 0.0), ew / TOL_BWD[nterms], eb / TOL_BWD[nterms])
+    print(f"wgrad family C {tag} nterms={nterms} {g.kernel}: dW {ew:.3g} db {eb:.3g} bar {TOL_BWD[nterms]:g}; "
+          f"largest error / bar of {g.kernel} so far {_ratios[key]:.3f}")
+    assert ew <= TOL_BWD[nterms] and eb <= TOL_BWD[nterms]
+    dw2, db2 = ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms)
     assert torch.equal(dw, dw2) and torch.equal(db, db2), "fixed summation order"
 
 
