@@ -741,9 +741,8 @@ int binhip_conv2d_bwd_data(const BinConvDesc* d, const void* gy_hi, const void* 
     c.y_cpg = y_cpg; c.y_group_stride = y_group_stride;
     c.y_unshuf = d->reserved > 0 ? d->reserved : 0;      // (BinConvDesc.reserved: the fused inverse PixelShuffle of the store)
     c.d.reserved = 0;
-    c.y_hi = gx_hi; c.y_lo = gx_lo; c.y_f32 = nullptr;
+    c.y_hi = gx_hi; c.y_lo = gx_lo;
     c.status = d->status;
-    for (int i = 0; i < 5; ++i) c.images[i] = nullptr;
     return bh_launch_conv(c, (hipStream_t)stream);
 }
 
@@ -834,7 +833,7 @@ int binhip_conv2d_fwd(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
     c.x_hi = x_hi; c.x_lo = x_lo; c.w_hi = w_hi; c.w_lo = w_lo; c.bias = bias;
     c.r_hi = res_hi; c.r_lo = res_lo; c.y_hi = y_hi; c.y_lo = y_lo; c.y_f32 = y_f32;
     c.status = d->status;
-    for (int i = 0; i < 5; ++i) c.images[i] = (images && i < d->n_images) ? images[i] : nullptr;
+    for (int i = 0; images && i < d->n_images && i < 5; ++i) c.images[i] = images[i];
     if (d->epilogue == BINHIP_EPI_FINAL && d->n_images > 0 && !images) return BINHIP_E_ARG;
     return bh_launch_conv(c, (hipStream_t)stream);
 }

@@ -68,12 +68,13 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned& sat, unsi
     hi2 = h; lo2 = l;
 }
 
-// internal launcher used by both the per-op ABI and the RDN plan
+// internal launcher used by both the per-op ABI and the RDN plan.  Every member starts as "absent" (null / zero): a call site
+// sets only what its call has
 struct BhConvCall {
-    BinConvDesc d;
-    const void *x_hi, *x_lo, *w_hi, *w_lo;
-    const float* bias;
-    const void *r_hi, *r_lo;
+    BinConvDesc d = {};
+    const void *x_hi = nullptr, *x_lo = nullptr, *w_hi = nullptr, *w_lo = nullptr;
+    const float* bias = nullptr;
+    const void *r_hi = nullptr, *r_lo = nullptr;     // residual
     const void *r2_hi = nullptr, *r2_lo = nullptr;   // second residual (may alias y: in-place accumulate)
     const void* m_hi = nullptr;                      // ReLU mask source planes (hi)
     int res_chunks = 0;                              // 0: residual applies to every chunk
@@ -81,9 +82,9 @@ struct BhConvCall {
     int y_cpg = 0;
     int64_t y_group_stride = 0;
     int y_unshuf = 0;                                // > 0: store through an inverse PixelShuffle(2), chunks per sub-position
-    void *y_hi, *y_lo;
-    float* y_f32;
-    const float* images[5];
+    void *y_hi = nullptr, *y_lo = nullptr;
+    float* y_f32 = nullptr;                          // FINAL epilogues: the fp32 output ...
+    const float* images[5] = {};                     // ... and the d.n_images frames averaged into it
     void* status = nullptr;                          // device status word (BINHIP_STATUS_*), may be null
     BinhipProfiler* prof = nullptr;                  // optional live-timing handle (binhip_profiler_create)
 };
