@@ -15,6 +15,19 @@
 // 4 waves are reduced through LDS and ONE partial per block is written; a second kernel sums the PB partials in a
 // fixed order (deterministic), un-scales and scatters to OIHW fp32.
 // Tests: tests/wgrad_cases.py restates wg_geom() / w1_plan() and holds one case per kernel, variant and work-split property.
+//
+// Three main kernels with three schedules (one-burst DMA and a K-split over 4 waves in wgrad_mfma_kernel, DMA spread over the multiply
+// steps and 8 waves in wgrad3x3_xrow_kernel, a streaming strip walk without K-split in wgrad1x1_kernel) over one core:
+//     helper                                   generic 5x5 / wide 1x1    3x3 X-row                     streaming 1x1
+//     tile_origin                              wg_issue                  wg3x_offsets                  issue
+//     x_chunk_rsrc / g_chunk_rsrc              wg_issue                  wg3x_issue_part               issue
+//     dma_lane / dma_offset                    wg_issue                  prologue / wg3x_offsets       prologue / issue
+//     tr_addr                                  tr_issue_at               xa, xb2, g_off                tr_off
+//     tr_issue (one address | two + immediate) tr_issue_at               load                          load
+//     tr_tie, tr_value                         K-step loop               step loop                     K-step loop
+//     acc_row                                  reduce_waves_to_partial   reduce_waves_to_partial       direct store
+//     reduce_waves_to_partial<NW>, pairwise    NW = 4                    NW = 8                        (no K-split: none)
+//     wg_block                                 workgroup id              workgroup id                  (2-D grid)
 #include "binhip_internal.h"
 #include <utility>
 
@@ -22,7 +35,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef short short4_ __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(3))) short4_ lds_short4_t;
 
 struct WgradKArgs {
     const _Float16* x_hi;
@@ -38,13 +50,12 @@ struct WgradKArgs {
     int tiles_x, tiles_y, ntiles;
     int PB, ncp, ncot;
     int ppg;      // 1x1 kernel: input-channel pairs per workgroup column (blockIdx.y)
-    int cgroups;  // unused (1); kept with dbg: dropping both moves the kernels' register allocation
     int nz;       // generic / lean kernels: ncot * ndyg (1-D grid of PB * ncp * nz workgroups, see wg_block())
-    int dbg;      // always 0; the kernels still test it (1 skip DMA, 2 skip MFMA/LDS reads, 4 skip the reduction+store)
 };
 
 template <int KS, int TR, int NT>
 struct WgCfg {
+    static constexpr int THREADS = 256;
     static constexpr int PAD = KS / 2;
     static constexpr int TH = 8;
     static constexpr int PH = TH + TR - 1;
@@ -57,131 +68,145 @@ struct WgCfg {
     static constexpr int NPL = (NT == 3) ? 2 : 1;
     static constexpr int BUF_BYTES = NPL * PLANE_BYTES;
     static constexpr int LDS_BYTES = (2 * BUF_BYTES > 16384) ? 2 * BUF_BYTES : 16384;
-    static constexpr int NXJ = (XP + 3) / 4, NGJ = GP / 4;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
-// fragment via two transpose reads: lane -> (channel col = lane&15 of chunk (lane>>4)&1, pixels p0 + 8*(lane>>5) + 0..7)
-__device__ __forceinline__ half8 tr_frag(const char* img, int chunk_bytes, int p0, int lane) {
-    const int t = lane & 15;
-    const int ch = (lane >> 4) & 1;
-    const int kg = lane >> 5;
-    const char* base = img + ch * chunk_bytes;
-    half8 r;
-#pragma unroll
-    for (int rd = 0; rd < 2; ++rd) {
-        const int p = p0 + kg * 8 + rd * 4 + (t >> 2);
-        const int off = p * 32 + (((((t & 3) >> 1)) ^ ((p >> 3) & 1)) << 4) + ((t & 1) << 3);
-        short4_ v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(base + off));
-        union { short4_ s; _Float16 h[4]; } u;
-        u.s = v;
-        r[rd * 4 + 0] = u.h[0]; r[rd * 4 + 1] = u.h[1]; r[rd * 4 + 2] = u.h[2]; r[rd * 4 + 3] = u.h[3];
-    }
-    return r;
+// ---- the core the three kernels share --------------------------------------------------------------------------------------------
+// pixel tile -> image and the tile's first row / column (tiles are TH rows x 32 columns, row-major within an image)
+struct TileOrigin { int img, ty0, tx0; };
+__device__ __forceinline__ TileOrigin tile_origin(const WgradKArgs& a, int tile, int TH) {
+    const int tx = tile % a.tiles_x, b = tile / a.tiles_x;
+    return {b / a.tiles_y, (b % a.tiles_y) * TH, tx * 32};
+}
+// byte offset of pixel (y, x) of image img in a chunk plane; y / x may be one halo step outside the image (the range check of
+// dma_offset() then decides), so this is a signed int (the entry point holds N * H * W below 2^26)
+__device__ __forceinline__ int pixel_byte(const WgradKArgs& a, int img, int y, int x) {
+    return (int)((((long long)img * a.H + y) * a.W + x) * 32);
 }
 
-// The same fragment with the reads issued from inline asm.  The compiler knows nothing about the alias classes of the
-// transpose-read builtin, so after an LDS-DMA (buffer_load ... lds) it protects every tr_frag() with s_waitcnt vmcnt(0) —
-// which serialises "prefetch the next stage" and "compute this one".  Asm reads are invisible to that pass; the price is
-// that the lgkmcnt wait is ours: tr_issue() ... tr_wait(...) on the SAME registers before their first use.
+// Buffer resource of one operand chunk plane (16 channels x all pixels) of precision plane pl (0 hi, 1 lo).  A chunk that does not
+// exist (odd chunk count, ragged cout) gets a resource of size 0: every load from it returns zeros.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t chunk_rsrc(const _Float16* plane0, long long elem_off, bool have, unsigned plane_bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(have ? plane0 + elem_off : plane0), 0, have ? plane_bytes : 0u, 0x00020000);
+}
+// X chunks may come in groups of x_cpg planes, x_group_stride elements apart (GFF.0 reads the first planes of each block buffer)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t x_chunk_rsrc(const WgradKArgs& a, int pl, int c, long long plane_elems, unsigned plane_bytes) {
+    const long long off = (a.x_cpg > 0) ? (long long)(c / a.x_cpg) * a.x_group_stride + (long long)(c % a.x_cpg) * plane_elems
+                                        : (long long)c * plane_elems;
+    return chunk_rsrc(pl ? a.x_lo : a.x_hi, off, c < a.cin_chunks, plane_bytes);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t g_chunk_rsrc(const WgradKArgs& a, int pl, int c, long long plane_elems, unsigned plane_bytes) {
+    return chunk_rsrc(pl ? a.g_lo : a.g_hi, (long long)c * plane_elems, c < a.cout_chunks, plane_bytes);
+}
+
+// Per-lane buffer offset of a 1-KiB DMA piece (64 lanes x 16 B = 32 pixels of one chunk).  Lane l of piece i carries 16-byte half
+// (q & 1) of pixel p = q >> 1, q = 64 i + l, of a patch PW pixels wide and npix pixels large, and fetches the half swizzled by bit 3
+// of p (so that the transpose reads below are conflict free).  dma_lane() is the tile-invariant part; dma_offset() adds the tile:
+// base = pixel_byte() of the patch's pixel (0, 0), which is image pixel (y0, x0); a pixel outside the image or the patch gets an
+// offset that fails the resource's range check and arrives as zeros.
+struct DmaLane { int py, px, src; };
+__device__ __forceinline__ DmaLane dma_lane(int piece, int lane, int PW, int npix, int W) {
+    const int q = piece * 64 + lane, p = q >> 1, py = p / PW, px = p - py * PW;
+    return {p < npix ? py : -(1 << 20), px, (py * W + px) * 32 + (((q & 1) ^ ((p >> 3) & 1)) << 4)};
+}
+__device__ __forceinline__ unsigned dma_offset(const DmaLane& d, int base, int y0, int x0, int H, int W) {
+    const bool ok = (unsigned)(y0 + d.py) < (unsigned)H && (unsigned)(x0 + d.px) < (unsigned)W;
+    return ok ? (unsigned)(base + d.src) : 0x80000000u;
+}
+
+// Fragments come from LDS by transpose reads issued from inline asm.  The compiler knows nothing about the alias classes of the
+// transpose-read builtin, so after an LDS-DMA (buffer_load ... lds) it protects every builtin read with s_waitcnt vmcnt(0) — which
+// serialises "prefetch the next stage" and "compute this one".  Asm reads are invisible to that pass; the price is that the lgkmcnt
+// wait is ours: tr_issue() ... s_waitcnt lgkmcnt ... tr_tie() on the SAME registers before their first use.
 typedef __attribute__((address_space(3))) const char lds_cchar_t;
 __device__ __forceinline__ unsigned lds_addr(const char* p) { return (unsigned)(size_t)(lds_cchar_t*)p; }
-// per-lane part of the address, valid for pixel offsets that are multiples of 16 (then (p >> 3) & 1 == lane >> 5)
-__device__ __forceinline__ unsigned tr_lane_off(int chunk_bytes, int lane) {
-    const int t = lane & 15, ch = (lane >> 4) & 1, kg = lane >> 5;
-    return (unsigned)(ch * chunk_bytes + (kg * 8 + (t >> 2)) * 32 + ((((t & 3) >> 1) ^ kg) << 4) + ((t & 1) << 3));
+// Byte offset, within a pair of chunk strips chunk_bytes apart, of the lane's 4-pixel read of the fragment that starts at pixel p0:
+// lane -> channel column lane & 15 of chunk (lane >> 4) & 1, pixels p0 + 8 (lane >> 5) + 0..3; lane t of a 16-lane group addresses
+// pixel t / 4, 8-byte piece t % 4, the 16-byte half un-swizzled by bit 3 of the pixel.  The read of pixels +4..7 is tr_addr(p0 + 4);
+// where p0 is a multiple of 8 that is the same address + 128.
+__device__ __forceinline__ unsigned tr_addr(int chunk_bytes, int p0, int lane) {
+    const int t = lane & 15, ch = (lane >> 4) & 1, p = p0 + (lane >> 5) * 8 + (t >> 2);
+    return (unsigned)(ch * chunk_bytes + p * 32 + ((((t & 3) >> 1) ^ ((p >> 3) & 1)) << 4) + ((t & 1) << 3));
 }
 struct TrFrag { short4_ a, b; };     // pixels +0..3 and +4..7 of the lane's channel
-__device__ __forceinline__ void tr_issue(TrFrag& f, unsigned addr) {      // addr = lds_addr(chunk strip) + lane part + p0 * 32
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.a) : "v"(addr));
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:128" : "=v"(f.b) : "v"(addr));
-}
-// (ordinary ds_read_b64 in place of the transpose reads, timing-only build: 209.8 vs 204.9 us — the transpose unit is free)
-#define WG_TR_OP "ds_read_b64_tr_b16"
+// (ordinary ds_read_b64 in place of the transpose read, timing-only build: 209.8 vs 204.9 us — the transpose unit is free)
 template <int OFF>
-__device__ __forceinline__ void tr_issue_pair(TrFrag& f, unsigned oa, unsigned ob) {      // two pre-computed addresses + immediate
-    asm volatile(WG_TR_OP " %0, %1 offset:%2" : "=v"(f.a) : "v"(oa), "n"(OFF));
-    asm volatile(WG_TR_OP " %0, %1 offset:%2" : "=v"(f.b) : "v"(ob), "n"(OFF));
+__device__ __forceinline__ void tr_read(short4_& dst, unsigned addr) {
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 }
-template <class F, int... S>
-__device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, S...>) {
-    (f(std::integral_constant<int, S>{}), ...);
-}
+// the two issue forms: one address for a fragment at a pixel offset that is a multiple of 8, or both reads' addresses + an immediate
+__device__ __forceinline__ void tr_issue(TrFrag& f, unsigned addr) { tr_read<0>(f.a, addr); tr_read<128>(f.b, addr); }
+template <int OFF>
+__device__ __forceinline__ void tr_issue(TrFrag& f, unsigned oa, unsigned ob) { tr_read<OFF>(f.a, oa); tr_read<OFF>(f.b, ob); }
 // general pixel offset (tap-shifted patches): both 4-pixel reads get their own swizzled address
 __device__ __forceinline__ void tr_issue_at(TrFrag& f, const char* img, int chunk_bytes, int p0, int lane) {
-    const int t = lane & 15, ch = (lane >> 4) & 1, kg = lane >> 5;
-    const unsigned base = lds_addr(img + ch * chunk_bytes) + ((t & 1) << 3);
-    const int pa = p0 + kg * 8 + (t >> 2), pb = pa + 4;
-    const unsigned oa = base + pa * 32 + ((((t & 3) >> 1) ^ ((pa >> 3) & 1)) << 4);
-    const unsigned ob = base + pb * 32 + ((((t & 3) >> 1) ^ ((pb >> 3) & 1)) << 4);
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.a) : "v"(oa));
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.b) : "v"(ob));
+    tr_issue<0>(f, lds_addr(img) + tr_addr(chunk_bytes, p0, lane), lds_addr(img) + tr_addr(chunk_bytes, p0 + 4, lane));
 }
-// after an `s_waitcnt lgkmcnt(0)` asm: re-defines the fragment's registers so that no use can be scheduled above the wait
+// after an `s_waitcnt lgkmcnt` asm: re-defines the fragment's registers so that no use can be scheduled above the wait
 __device__ __forceinline__ void tr_tie(TrFrag& f) { asm volatile("" : "+v"(f.a), "+v"(f.b)); }
 __device__ __forceinline__ half8 tr_value(const TrFrag& f) {
     union { struct { short4_ a, b; } s; half8 h; } u;
     u.s.a = f.a; u.s.b = f.b;
     return u.h;
 }
+template <class F, int... S>
+__device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, S...>) {
+    (f(std::integral_constant<int, S>{}), ...);
+}
 
+// element e of a lane's 32x32 accumulator -> row m of the tile (the column is lane & 31, hi = lane >> 5)
+__device__ __forceinline__ int acc_row(int e, int hi) { return (e & 3) + 8 * (e >> 2) + 4 * hi; }
+// p[0] + p[STRIDE] + ... (N terms) as a balanced tree: ((0 + 1) + (2 + 3)), (((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)))
+template <int N, int STRIDE>
+__device__ __forceinline__ float pairwise(const float* p) {
+    if constexpr (N == 1) return p[0];
+    else return pairwise<N / 2, STRIDE>(p) + pairwise<N / 2, STRIDE>(p + (N / 2) * STRIDE);
+}
+// K-split kernels: the NW waves' accumulators of one tap are summed through LDS (red: [NW][32 m][32 n]) in that fixed order and
+// the 32x32 partial tile goes to dst
+template <int NW>
+__device__ __forceinline__ void reduce_waves_to_partial(float* red, const floatx16& acc, int wave, int lane, float* dst) {
+    const int n = lane & 31, hi = lane >> 5, tid = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 16; ++e) red[wave * 1024 + acc_row(e, hi) * 32 + n] = acc[e];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 16 / NW; ++i) dst[tid + 64 * NW * i] = pairwise<NW, 1024>(red + tid + 64 * NW * i);
+}
+
+// generic kernel: DMA of one tile's X halo patches and gY tiles (both chunks of the pair, every plane) into stage buf, in one burst
 template <int KS, int TR, int NT, int NW = 4>
 __device__ __forceinline__ void wg_issue(const WgradKArgs& a, char* smem, int buf, int tile, int cp, int cot, int dy0,
                                          int wave, int lane, long long plane_elems, unsigned plane_bytes) {
     using C = WgCfg<KS, TR, NT>;
-    int b = tile;
-    const int tx = b % a.tiles_x; b /= a.tiles_x;
-    const int ty = b % a.tiles_y;
-    const int img = b / a.tiles_y;
-    const int tx0 = tx * 32, ty0 = ty * C::TH;
+    const TileOrigin o = tile_origin(a, tile, C::TH);
     const int H = a.H, W = a.W;
+    const int xy0 = o.ty0 + dy0 - C::PAD, xx0 = o.tx0 - C::PAD;
+    const int xbase = pixel_byte(a, o.img, xy0, xx0), gbase = pixel_byte(a, o.img, o.ty0, o.tx0);
 #pragma unroll
     for (int pl = 0; pl < C::NPL; ++pl) {
         char* pbase = smem + buf * C::BUF_BYTES + pl * C::PLANE_BYTES;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            // ---- X patch of input chunk 2*cp + h (zeros when the chunk does not exist)
-            const int c = 2 * cp + h;
-            const _Float16* xb = pl ? a.x_lo : a.x_hi;
-            const long long coff = (a.x_cpg > 0)
-                ? (long long)(c / a.x_cpg) * a.x_group_stride + (long long)(c % a.x_cpg) * plane_elems
-                : (long long)c * plane_elems;
-            const bool have = c < a.cin_chunks;
-            __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)(have ? xb + coff : xb), 0, have ? plane_bytes : 0u, 0x00020000);
+            // ---- X patch of input chunk 2*cp + h
+            const __amdgpu_buffer_rsrc_t rs = x_chunk_rsrc(a, pl, 2 * cp + h, plane_elems, plane_bytes);
             char* lds = pbase + h * C::XBYTES;
 #pragma unroll
             for (int j = 0; j < (C::XP + NW - 1) / NW; ++j) {
                 const int i = wave + NW * j;
-                if (i < C::XP) {
-                    const int q = i * 64 + lane;
-                    const int p = q >> 1, s = q & 1;
-                    const int py = p / C::PW, px = p - py * C::PW;
-                    const int gy = ty0 + py + dy0 - C::PAD, gx = tx0 + px - C::PAD;
-                    const int cg = s ^ ((p >> 3) & 1);
-                    const bool ok = (p < C::PH * C::PW) && gy >= 0 && gy < H && gx >= 0 && gx < W;
-                    const unsigned vo = ok ? (unsigned)((((long long)img * H + gy) * W + gx) * 32 + cg * 16) : 0x80000000u;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(lds + i * 1024), 16, vo, 0, 0, 0);
-                }
+                if (i >= C::XP) break;
+                const unsigned vo = dma_offset(dma_lane(i, lane, C::PW, C::PH * C::PW, W), xbase, xy0, xx0, H, W);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(lds + i * 1024), 16, vo, 0, 0, 0);
             }
             // ---- gY tile of output chunk 2*cot + h
-            const int gc = 2 * cot + h;
-            const bool haveg = gc < a.cout_chunks;
-            const _Float16* gb = pl ? a.g_lo : a.g_hi;
-            __amdgpu_buffer_rsrc_t gs = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)(haveg ? gb + (long long)gc * plane_elems : gb), 0, haveg ? plane_bytes : 0u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t gs = g_chunk_rsrc(a, pl, 2 * cot + h, plane_elems, plane_bytes);
             char* gl = pbase + 2 * C::XBYTES + h * C::GBYTES;
 #pragma unroll
             for (int j = 0; j < (C::GP + NW - 1) / NW; ++j) {
                 const int i = wave + NW * j;
                 if (C::GP % NW != 0 && i >= C::GP) break;
-                const int q = i * 64 + lane;
-                const int p = q >> 1, s = q & 1;
-                const int py = p >> 5, px = p & 31;
-                const int gy = ty0 + py, gx = tx0 + px;
-                const int cg = s ^ ((p >> 3) & 1);
-                const bool ok = gy < H && gx < W;
-                const unsigned vo = ok ? (unsigned)((((long long)img * H + gy) * W + gx) * 32 + cg * 16) : 0x80000000u;
+                const unsigned vo = dma_offset(dma_lane(i, lane, 32, C::TH * 32, W), gbase, o.ty0, o.tx0, H, W);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(gs, (lds_void_t*)(gl + i * 1024), 16, vo, 0, 0, 0);
             }
         }
@@ -211,7 +236,7 @@ __device__ __forceinline__ void wg_block(const WgradKArgs& a, int& pb, int& cp, 
 }
 
 template <int KS, int TR, int NT>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__((WgCfg<KS, TR, NT>::THREADS))
 wgrad_mfma_kernel(const WgradKArgs a) {
     using C = WgCfg<KS, TR, NT>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -240,14 +265,13 @@ wgrad_mfma_kernel(const WgradKArgs a) {
     for (int e = 0; e < 8; ++e) ones[e] = (_Float16)1.0f;
 
     int tile = pb;
-    if (tile < a.ntiles && !(a.dbg & 1)) wg_issue<KS, TR, NT>(a, smem, 0, tile, cp, cot, dy0, wave, lane, plane_elems, plane_bytes);
+    if (tile < a.ntiles) wg_issue<KS, TR, NT>(a, smem, 0, tile, cp, cot, dy0, wave, lane, plane_elems, plane_bytes);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int cur = 0;
     for (; tile < a.ntiles; tile += a.PB) {
         const int nxt = tile + a.PB;
-        if (nxt < a.ntiles && !(a.dbg & 1)) wg_issue<KS, TR, NT>(a, smem, cur ^ 1, nxt, cp, cot, dy0, wave, lane, plane_elems, plane_bytes);
-        if (a.dbg & 2) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); cur ^= 1; continue; }
+        if (nxt < a.ntiles) wg_issue<KS, TR, NT>(a, smem, cur ^ 1, nxt, cp, cot, dy0, wave, lane, plane_elems, plane_bytes);
         const char* xb = smem + cur * C::BUF_BYTES;
         const char* gb = xb + 2 * C::XBYTES;
         // 4 K-steps per wave and tile (2 rows x 2 half-rows of 16 pixels), software-pipelined: the transpose reads of
@@ -304,35 +328,19 @@ wgrad_mfma_kernel(const WgradKArgs a) {
         cur ^= 1;
     }
 
-    if (a.dbg & 4) { if (acc[0][0] == 12345.f) a.partial[0] = accb[0]; return; }
     // ---- reduce the 4 waves through LDS, one partial per block ----------------------------------
     float* red = reinterpret_cast<float*>(smem);          // [4 waves][32 m][32 n]
     const int n = lane & 31, hi = lane >> 5;
     const long long blk = ((long long)bz * a.ncp + cp) * a.PB + pb;
 #pragma unroll
-    for (int t = 0; t < C::NTAP; ++t) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int m = (e & 3) + 8 * (e >> 2) + 4 * hi;
-            red[wave * 1024 + m * 32 + n] = acc[t][e];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + 256 * i;
-            a.partial[(blk * C::NTAP + t) * 1024 + idx] =
-                (red[idx] + red[1024 + idx]) + (red[2048 + idx] + red[3072 + idx]);
-        }
-    }
+    for (int t = 0; t < C::NTAP; ++t) reduce_waves_to_partial<4>(red, acc[t], wave, lane, a.partial + (blk * C::NTAP + t) * 1024);
     if (do_bias) {
         __syncthreads();
         // bias: every row m of accb holds sum_k gY[k][n]; keep row 0 (e = 0 of the lanes with hi == 0)
         if (hi == 0) red[wave * 32 + n] = accb[0];
         __syncthreads();
         if (tid < 32)
-            a.partial_b[((long long)cot * a.PB + pb) * 32 + tid] =
-                (red[tid] + red[32 + tid]) + (red[64 + tid] + red[96 + tid]);
+            a.partial_b[((long long)cot * a.PB + pb) * 32 + tid] = pairwise<4, 32>(red + tid);
     }
 }
 
@@ -349,6 +357,7 @@ wgrad_mfma_kernel(const WgradKArgs a) {
 // fetched two steps after the last use of A[0][dx]), gY fragments alternate between two.
 template <int NT>
 struct Wg3xCfg {
+    static constexpr int THREADS = 512;
     static constexpr int NPL = (NT == 3) ? 2 : 1;
     static constexpr int XR = 8, GR = 10, PW = 34;
     static constexpr int XP = (XR * PW * 2 + 63) / 64;                   // 1-KiB DMA pieces of an X chunk patch (9)
@@ -367,56 +376,34 @@ struct Wg3xCfg {
 // (see the kernel): wg3x_offsets() = the per-lane buffer offsets of the tile (VALU only), wg3x_issue_part(PL, H) = the
 // buffer_load ... lds instructions of plane PL, chunk H of the pair (X pieces, then gY pieces).
 template <int NT>
+struct Wg3xLanes {                       // tile-invariant dma_lane() of the wave's X and gY pieces (wave, wave + 8)
+    DmaLane x[Wg3xCfg<NT>::NXJ], g[Wg3xCfg<NT>::NGJ];
+};
+template <int NT>
 struct Wg3xTile {
     unsigned xvo[Wg3xCfg<NT>::NXJ], gvo[Wg3xCfg<NT>::NGJ];
 };
 template <int NT>
-__device__ __forceinline__ void wg3x_offsets(const WgradKArgs& a, int tile, int wave, const int* x_py, const int* x_px,
-                                             const int* x_src, int g_px, const int* g_src, Wg3xTile<NT>& o) {
+__device__ __forceinline__ void wg3x_offsets(const WgradKArgs& a, int tile, const Wg3xLanes<NT>& l, Wg3xTile<NT>& o) {
     using G = Wg3xCfg<NT>;
-    const int H = a.H, W = a.W;
-    int b = tile;
-    const int tx = b % a.tiles_x; b /= a.tiles_x;
-    const int ty = b % a.tiles_y;
-    const int img = b / a.tiles_y;
-    const int tx0 = tx * 32, ty0 = ty * G::XR;
-    const int x0 = tx0 - 1;
-    const long long row0 = (long long)img * H;
-    const int xbase = (int)(((row0 + ty0) * W + x0) * 32);          // may be negative at the image border (then !ok)
-    const int gbase = (int)(((row0 + ty0 - 1) * W + tx0) * 32);
+    const TileOrigin t = tile_origin(a, tile, G::XR);
+    const int xbase = pixel_byte(a, t.img, t.ty0, t.tx0 - 1), gbase = pixel_byte(a, t.img, t.ty0 - 1, t.tx0);
 #pragma unroll
-    for (int j = 0; j < G::NXJ; ++j) {
-        const bool ok = (unsigned)(ty0 + x_py[j]) < (unsigned)H && (unsigned)(x0 + x_px[j]) < (unsigned)W;
-        o.xvo[j] = ok ? (unsigned)(xbase + x_src[j]) : 0x80000000u;
-    }
+    for (int j = 0; j < G::NXJ; ++j) o.xvo[j] = dma_offset(l.x[j], xbase, t.ty0, t.tx0 - 1, a.H, a.W);
 #pragma unroll
-    for (int j = 0; j < G::NGJ; ++j) {
-        const bool ok = (wave + 8 * j < G::GP) && (unsigned)(ty0 - 1 + wave + 8 * j) < (unsigned)H && (tx0 + g_px < W);
-        o.gvo[j] = ok ? (unsigned)(gbase + g_src[j]) : 0x80000000u;
-    }
+    for (int j = 0; j < G::NGJ; ++j) o.gvo[j] = dma_offset(l.g[j], gbase, t.ty0 - 1, t.tx0, a.H, a.W);
 }
 template <int NT>
 __device__ __forceinline__ void wg3x_issue_part(const WgradKArgs& a, char* stage, const int PL, const int HH, int cp, int cot,
                                                 int wave, const Wg3xTile<NT>& o, long long plane_elems, unsigned plane_bytes) {
     using G = Wg3xCfg<NT>;
-    const int c = 2 * cp + HH;
-    const _Float16* xb = PL ? a.x_lo : a.x_hi;
-    const long long coff = (a.x_cpg > 0)
-        ? (long long)(c / a.x_cpg) * a.x_group_stride + (long long)(c % a.x_cpg) * plane_elems
-        : (long long)c * plane_elems;
-    const bool have = c < a.cin_chunks;
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(have ? xb + coff : xb), 0,
-                                                                  have ? plane_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = x_chunk_rsrc(a, PL, 2 * cp + HH, plane_elems, plane_bytes);
     char* lds = stage + PL * G::PLANE + HH * G::XS;
 #pragma unroll
     for (int j = 0; j < G::NXJ; ++j)
         if (wave + 8 * j < G::XP)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(lds + (wave + 8 * j) * 1024), 16, o.xvo[j], 0, 0, 0);
-    const int gc = 2 * cot + HH;
-    const bool haveg = gc < a.cout_chunks;
-    const _Float16* gb = PL ? a.g_lo : a.g_hi;
-    __amdgpu_buffer_rsrc_t gs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(haveg ? gb + (long long)gc * plane_elems : gb), 0, haveg ? plane_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t gs = g_chunk_rsrc(a, PL, 2 * cot + HH, plane_elems, plane_bytes);
     char* ldg = stage + PL * G::PLANE + G::G0 + HH * G::GS;
 #pragma unroll
     for (int j = 0; j < G::NGJ; ++j)
@@ -436,7 +423,7 @@ __device__ __forceinline__ void wg3x_issue_all(const WgradKArgs& a, char* stage,
 
 constexpr int WG3_DMA_FIRST = 1, WG3_DMA_STRIDE = 4;
 template <int NT>
-__global__ void __launch_bounds__(512)
+__global__ void __launch_bounds__(Wg3xCfg<NT>::THREADS)
 wgrad3x3_xrow_kernel(const WgradKArgs a) {
     using G = Wg3xCfg<NT>;
     constexpr int NTAP = 9, NSTEP = 2 * NTAP;
@@ -462,40 +449,25 @@ wgrad3x3_xrow_kernel(const WgradKArgs a) {
 
     // ---- tile-invariant per-lane state: the two 4-pixel reads of the X fragment of column shift dx (K-step 0, hi plane)
     unsigned xa[3], xb2[3];
-    {
-        const int tt = lane & 15, ch = (lane >> 4) & 1, kg = lane >> 5;
 #pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const int p0 = wave * G::PW + dx;
-            const int pa = p0 + kg * 8 + (tt >> 2), pb4 = pa + 4;
-            const unsigned base = (unsigned)(ch * G::XS + ((tt & 1) << 3));
-            xa[dx] = base + pa * 32 + ((((tt & 3) >> 1) ^ ((pa >> 3) & 1)) << 4);
-            xb2[dx] = base + pb4 * 32 + ((((tt & 3) >> 1) ^ ((pb4 >> 3) & 1)) << 4);
-        }
+    for (int dx = 0; dx < 3; ++dx) {
+        xa[dx] = tr_addr(G::XS, wave * G::PW + dx, lane);
+        xb2[dx] = tr_addr(G::XS, wave * G::PW + dx + 4, lane);
     }
     // gY patch row `wave` (= image row r - 2); tap dy multiplies patch row wave + 2 - dy (an immediate)
-    const unsigned g_off = (unsigned)G::G0 + tr_lane_off(G::GS, lane) + wave * 32 * 32;
-    int x_py[G::NXJ], x_px[G::NXJ], x_src[G::NXJ], g_src[G::NGJ];
+    const unsigned g_off = (unsigned)G::G0 + tr_addr(G::GS, wave * 32, lane);
+    Wg3xLanes<NT> dl;
 #pragma unroll
-    for (int j = 0; j < G::NXJ; ++j) {
-        const int q = (wave + 8 * j) * 64 + lane;
-        const int p = q >> 1, sh = q & 1;
-        const bool in_patch = (wave + 8 * j < G::XP) && (p < G::XR * G::PW);
-        x_py[j] = in_patch ? p / G::PW : -(1 << 20);                       // out-of-patch lanes fail the range check
-        x_px[j] = p % G::PW;
-        x_src[j] = (x_py[j] * W + x_px[j]) * 32 + ((sh ^ ((p >> 3) & 1)) << 4);
-    }
-    const int g_px = lane >> 1;
+    for (int j = 0; j < G::NXJ; ++j) dl.x[j] = dma_lane(wave + 8 * j, lane, G::PW, G::XR * G::PW, W);
 #pragma unroll
-    for (int j = 0; j < G::NGJ; ++j)
-        g_src[j] = ((wave + 8 * j) * W + g_px) * 32 + (((lane & 1) ^ ((g_px >> 3) & 1)) << 4);
+    for (int j = 0; j < G::NGJ; ++j) dl.g[j] = dma_lane(wave + 8 * j, lane, 32, G::GP * 32, W);
 
     // row-major tiles at stride PB (a walk down 32-pixel columns saved HBM bytes and no time, profiles/r03_experiments.md)
     int tile = pb;
     const int tend = a.ntiles, tstep = a.PB;
     Wg3xTile<NT> to;
-    if (tile < tend && !(a.dbg & 1)) {
-        wg3x_offsets<NT>(a, tile, wave, x_py, x_px, x_src, g_px, g_src, to);
+    if (tile < tend) {
+        wg3x_offsets<NT>(a, tile, dl, to);
         wg3x_issue_all<NT>(a, smem, cp, cot, wave, to, plane_elems, plane_bytes);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -508,94 +480,76 @@ wgrad3x3_xrow_kernel(const WgradKArgs a) {
         // CU to multiply meanwhile.  One (plane, chunk) group goes out behind the MFMAs of steps 1, 5, 9 and 13 instead
         // (WG3_DMA_FIRST + k * WG3_DMA_STRIDE; a later step leaves its round trip less cover): 128-134 vs 136-138 us at 96
         // channels, profiles/r03_experiments.md.
-        const bool pre = nxt < tend && !(a.dbg & 1);
-        if (pre) wg3x_offsets<NT>(a, nxt, wave, x_py, x_px, x_src, g_px, g_src, to);
+        const bool pre = nxt < tend;
+        if (pre) wg3x_offsets<NT>(a, nxt, dl, to);
         char* const stage_nxt = smem + (cur ^ 1) * G::STAGE;
-        if (!(a.dbg & 2)) {
-            const unsigned st = lds_addr(smem + cur * G::STAGE);
-            TrFrag Bh[2], Bl[2], Ah[3], Al[3];
-            auto load = [&](auto SC) {
-                constexpr int s = decltype(SC)::value, ks = s / NTAP, dy = (s % NTAP) / 3, dx = s % 3;
-                if constexpr (dx == 0) {
-                    constexpr int bb = (ks * 3 + dy) & 1, off = ks * 512 + (2 - dy) * 1024;
-                    tr_issue_pair<off>(Bh[bb], st + g_off, st + g_off + 128);
-                    if constexpr (NT == 3) tr_issue_pair<off + G::PLANE>(Bl[bb], st + g_off, st + g_off + 128);
-                }
-                if constexpr (dy == 0) {
-                    tr_issue_pair<ks * 512>(Ah[dx], st + xa[dx], st + xb2[dx]);
-                    if constexpr (NT == 3) tr_issue_pair<ks * 512 + G::PLANE>(Al[dx], st + xa[dx], st + xb2[dx]);
-                }
-            };
-            load(std::integral_constant<int, 0>{});
-            load(std::integral_constant<int, 1>{});
-            static_for([&](auto SC) {
-                constexpr int s = decltype(SC)::value, ks = s / NTAP, dy = (s % NTAP) / 3, dx = s % 3, t = dy * 3 + dx;
-                constexpr int bb = (ks * 3 + dy) & 1;
-                // outstanding: the reads of steps s and s + 1, in issue order -> leave step s + 1's in flight
-                constexpr int s1 = s + 1;
-                constexpr int later = (s1 < NSTEP) ? NA * ((s1 % 3 == 0 ? 1 : 0) + ((s1 % NTAP) / 3 == 0 ? 1 : 0)) : 0;
-                asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(later) : "memory");
-                if constexpr (dy == 0) {
-                    tr_tie(Ah[dx]);
-                    if constexpr (NT == 3) tr_tie(Al[dx]);
-                }
-                if constexpr (dx == 0) {
-                    tr_tie(Bh[bb]);
-                    if constexpr (NT == 3) tr_tie(Bl[bb]);
-                }
-                if constexpr (s + 2 < NSTEP) load(std::integral_constant<int, s + 2>{});
-                __builtin_amdgcn_sched_barrier(0);
-                const half8 bh = tr_value(Bh[bb]);
-                half8 bl;
-                if constexpr (NT == 3) bl = tr_value(Bl[bb]);
-                if (dy == 1 && dx == 0 && do_bias) {           // patch row wave + 1 = the wave's own image row: once per gY row
+        const unsigned st = lds_addr(smem + cur * G::STAGE);
+        TrFrag Bh[2], Bl[2], Ah[3], Al[3];
+        auto load = [&](auto SC) {
+            constexpr int s = decltype(SC)::value, ks = s / NTAP, dy = (s % NTAP) / 3, dx = s % 3;
+            if constexpr (dx == 0) {
+                constexpr int bb = (ks * 3 + dy) & 1, off = ks * 512 + (2 - dy) * 1024;
+                tr_issue<off>(Bh[bb], st + g_off, st + g_off + 128);
+                if constexpr (NT == 3) tr_issue<off + G::PLANE>(Bl[bb], st + g_off, st + g_off + 128);
+            }
+            if constexpr (dy == 0) {
+                tr_issue<ks * 512>(Ah[dx], st + xa[dx], st + xb2[dx]);
+                if constexpr (NT == 3) tr_issue<ks * 512 + G::PLANE>(Al[dx], st + xa[dx], st + xb2[dx]);
+            }
+        };
+        load(std::integral_constant<int, 0>{});
+        load(std::integral_constant<int, 1>{});
+        static_for([&](auto SC) {
+            constexpr int s = decltype(SC)::value, ks = s / NTAP, dy = (s % NTAP) / 3, dx = s % 3, t = dy * 3 + dx;
+            constexpr int bb = (ks * 3 + dy) & 1;
+            // outstanding: the reads of steps s and s + 1, in issue order -> leave step s + 1's in flight
+            constexpr int s1 = s + 1;
+            constexpr int later = (s1 < NSTEP) ? NA * ((s1 % 3 == 0 ? 1 : 0) + ((s1 % NTAP) / 3 == 0 ? 1 : 0)) : 0;
+            asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(later) : "memory");
+            if constexpr (dy == 0) {
+                tr_tie(Ah[dx]);
+                if constexpr (NT == 3) tr_tie(Al[dx]);
+            }
+            if constexpr (dx == 0) {
+                tr_tie(Bh[bb]);
+                if constexpr (NT == 3) tr_tie(Bl[bb]);
+            }
+            if constexpr (s + 2 < NSTEP) load(std::integral_constant<int, s + 2>{});
+            __builtin_amdgcn_sched_barrier(0);
+            const half8 bh = tr_value(Bh[bb]);
+            half8 bl;
+            if constexpr (NT == 3) bl = tr_value(Bl[bb]);
+            if (dy == 1 && dx == 0 && do_bias) {           // patch row wave + 1 = the wave's own image row: once per gY row
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        bsum += (float)bh[e];
-                        if constexpr (NT == 3) bsum += (float)bl[e];
-                    }
+                for (int e = 0; e < 8; ++e) {
+                    bsum += (float)bh[e];
+                    if constexpr (NT == 3) bsum += (float)bl[e];
                 }
-                const half8 ah = tr_value(Ah[dx]);
-                if constexpr (NT == 3) {
-                    const half8 al = tr_value(Al[dx]);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t], 0, 0, 0);
-                }
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
-                if constexpr (s >= WG3_DMA_FIRST && (s - WG3_DMA_FIRST) % WG3_DMA_STRIDE == 0 &&
-                              (s - WG3_DMA_FIRST) / WG3_DMA_STRIDE < (NT == 3 ? 4 : 2)) {
-                    constexpr int grp = (s - WG3_DMA_FIRST) / WG3_DMA_STRIDE;           // (plane, chunk) = (0,0) (0,1) (1,0) (1,1)
-                    if (pre) wg3x_issue_part<NT>(a, stage_nxt, grp / 2, grp % 2, cp, cot, wave, to, plane_elems, plane_bytes);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }, std::make_integer_sequence<int, NSTEP>{});
-        } else if (pre) {
-            wg3x_issue_all<NT>(a, stage_nxt, cp, cot, wave, to, plane_elems, plane_bytes);
-        }
+            }
+            const half8 ah = tr_value(Ah[dx]);
+            if constexpr (NT == 3) {
+                const half8 al = tr_value(Al[dx]);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t], 0, 0, 0);
+            }
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
+            if constexpr (s >= WG3_DMA_FIRST && (s - WG3_DMA_FIRST) % WG3_DMA_STRIDE == 0 &&
+                          (s - WG3_DMA_FIRST) / WG3_DMA_STRIDE < (NT == 3 ? 4 : 2)) {
+                constexpr int grp = (s - WG3_DMA_FIRST) / WG3_DMA_STRIDE;           // (plane, chunk) = (0,0) (0,1) (1,0) (1,1)
+                if (pre) wg3x_issue_part<NT>(a, stage_nxt, grp / 2, grp % 2, cp, cot, wave, to, plane_elems, plane_bytes);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }, std::make_integer_sequence<int, NSTEP>{});
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         cur ^= 1;
     }
 
-    if (a.dbg & 4) { if (acc[0][0] == 12345.f) a.partial[0] = bsum; return; }
     // ---- the eight rows are summed through LDS in a fixed order: one partial per workgroup and tap
     float* red = reinterpret_cast<float*>(smem);          // [8 waves][32 m][32 n]
-    const int n = lane & 31, hi = lane >> 5;
     const long long blk = ((long long)bz * a.ncp + cp) * a.PB + pb;
 #pragma unroll
-    for (int t = 0; t < NTAP; ++t) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; ++e) red[wave * 1024 + ((e & 3) + 8 * (e >> 2) + 4 * hi) * 32 + n] = acc[t][e];
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = tid + 512 * i;
-            a.partial[(blk * NTAP + t) * 1024 + idx] =
-                ((red[idx] + red[1024 + idx]) + (red[2048 + idx] + red[3072 + idx])) +
-                ((red[4096 + idx] + red[5120 + idx]) + (red[6144 + idx] + red[7168 + idx]));
-        }
-    }
+    for (int t = 0; t < NTAP; ++t) reduce_waves_to_partial<8>(red, acc[t], wave, lane, a.partial + (blk * NTAP + t) * 1024);
     if (do_bias) {
         __syncthreads();
         red[tid] = bsum;                              // [wave][kg][co]
@@ -626,6 +580,10 @@ wgrad3x3_xrow_kernel(const WgradKArgs a) {
 //   * ncp > 8 (GFF.0: 36 pairs): PPW = 2 and ceil(ncp / 16) balanced groups (3 x 12), gY re-read once per group.
 // The last wave of group 0 also accumulates the bias gradient from the gY fragments it loads anyway.
 constexpr int W1_NW = 8, W1_NCOT = 3;
+struct W1Cfg {
+    static constexpr int THREADS = 64 * W1_NW;
+    static constexpr int LDS_BYTES = 160 * 1024;         // the opt-in limit; a launch asks for W1Plan::lds of it
+};
 
 struct W1Plan { int ppw, tr, cgroups, ppg; unsigned lds; };
 static inline W1Plan w1_plan(int ncp) {
@@ -641,7 +599,7 @@ static inline W1Plan w1_plan(int ncp) {
 }
 
 template <int NT, int PPW, int TR>
-__global__ void __launch_bounds__(64 * W1_NW)
+__global__ void __launch_bounds__(W1Cfg::THREADS)
 wgrad1x1_kernel(const WgradKArgs a) {
     constexpr int NPL = (NT == 3) ? 2 : 1;
     constexpr int CH = TR * 1024;                         // one chunk strip: TR rows x 32 px x 32 B
@@ -674,130 +632,96 @@ wgrad1x1_kernel(const WgradKArgs a) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-    // per-lane part of a DMA piece (one 32-pixel row of one chunk = 1 KiB): pixel lane/2, 16-byte half swizzled by pixel/8
-    const int lp = lane >> 1;
-    const unsigned lane_off = (unsigned)(lp * 32 + (((lane & 1) ^ ((lp >> 3) & 1)) << 4));
-    const unsigned tr_off = tr_lane_off(CH, lane);
+    const DmaLane dl = dma_lane(0, lane, 32, 32, a.W);     // a DMA piece = one 32-pixel row of one chunk
+    const unsigned tr_off = tr_addr(CH, 0, lane);
 
     auto issue = [&](int tile, int buf) {
-        int b = tile;
-        const int tx = b % a.tiles_x; b /= a.tiles_x;
-        const int ty = b % a.tiles_y;
-        const int img = b / a.tiles_y;
-        const int tx0 = tx * 32, ty0 = ty * TR;
-        const bool col_ok = tx0 + lp < a.W;
+        const TileOrigin o = tile_origin(a, tile, TR);
         char* stage = smem + buf * stage_bytes;
         for (int k = wave; k < nslots * TR; k += W1_NW) {
             const int slot = k / TR, r = k % TR;
-            const _Float16* src;
-            bool have;
+            __amdgpu_buffer_rsrc_t rs;
             if (slot < GSLOTS) {
-                const int pl = slot / (2 * W1_NCOT), c6 = slot % (2 * W1_NCOT);
-                have = c6 < a.cout_chunks;
-                src = (pl ? a.g_lo : a.g_hi) + (long long)c6 * plane_elems;
+                rs = g_chunk_rsrc(a, slot / (2 * W1_NCOT), slot % (2 * W1_NCOT), plane_elems, plane_bytes);
             } else {
                 const int xs = slot - GSLOTS;
                 const int pr = xs / (NPL * 2), rem = xs % (NPL * 2);
-                const int pl = rem >> 1, c = 2 * (cp0 + pr) + (rem & 1);
-                have = c < a.cin_chunks;
-                const long long coff = (a.x_cpg > 0)
-                    ? (long long)(c / a.x_cpg) * a.x_group_stride + (long long)(c % a.x_cpg) * plane_elems
-                    : (long long)c * plane_elems;
-                src = (pl ? a.x_lo : a.x_hi) + (have ? coff : 0);
+                rs = x_chunk_rsrc(a, rem >> 1, 2 * (cp0 + pr) + (rem & 1), plane_elems, plane_bytes);
             }
-            __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, have ? plane_bytes : 0u, 0x00020000);
-            const int gy = ty0 + r;
-            const bool ok = col_ok && gy < a.H;
-            const unsigned vo = ok ? (unsigned)((((long long)img * a.H + gy) * a.W + tx0) * 32) + lane_off : 0x80000000u;
+            const unsigned vo = dma_offset(dl, pixel_byte(a, o.img, o.ty0 + r, o.tx0), o.ty0 + r, o.tx0, a.H, a.W);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(stage + slot * CH + r * 1024), 16, vo, 0, 0, 0);
         }
     };
 
     int tile = pb;
     int buf = 0;
-    if (tile < a.ntiles && !(a.dbg & 1)) issue(tile, 0);
+    if (tile < a.ntiles) issue(tile, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (; tile < a.ntiles; tile += a.PB) {
-        if (tile + a.PB < a.ntiles && !(a.dbg & 1)) issue(tile + a.PB, buf ^ 1);
-        if (!(a.dbg & 2)) {
-            const unsigned gst = lds_addr(smem + buf * stage_bytes) + tr_off;
-            const unsigned xst = gst + GSLOTS * CH + wave * PPW * PAIR_BYTES;
-            // fragments of pixel step ks + 1 are in flight while step ks multiplies
-            TrFrag Bh[2][W1_NCOT], Bl[2][W1_NCOT], Ah[2][PPW], Al[2][PPW];
-            auto load = [&](int ks, int q) {
+        if (tile + a.PB < a.ntiles) issue(tile + a.PB, buf ^ 1);
+        const unsigned gst = lds_addr(smem + buf * stage_bytes) + tr_off;
+        const unsigned xst = gst + GSLOTS * CH + wave * PPW * PAIR_BYTES;
+        // fragments of pixel step ks + 1 are in flight while step ks multiplies
+        TrFrag Bh[2][W1_NCOT], Bl[2][W1_NCOT], Ah[2][PPW], Al[2][PPW];
+        auto load = [&](int ks, int q) {
 #pragma unroll
-                for (int j = 0; j < W1_NCOT; ++j) {
-                    tr_issue(Bh[q][j], gst + 2 * j * CH + ks * 512);
-                    if constexpr (NT == 3) tr_issue(Bl[q][j], gst + (2 * W1_NCOT + 2 * j) * CH + ks * 512);
-                }
+            for (int j = 0; j < W1_NCOT; ++j) {
+                tr_issue(Bh[q][j], gst + 2 * j * CH + ks * 512);
+                if constexpr (NT == 3) tr_issue(Bl[q][j], gst + (2 * W1_NCOT + 2 * j) * CH + ks * 512);
+            }
 #pragma unroll
-                for (int i = 0; i < PPW; ++i) {
-                    tr_issue(Ah[q][i], xst + i * PAIR_BYTES + ks * 512);
-                    if constexpr (NT == 3) tr_issue(Al[q][i], xst + i * PAIR_BYTES + 2 * CH + ks * 512);
-                }
-            };
-            load(0, 0);
+            for (int i = 0; i < PPW; ++i) {
+                tr_issue(Ah[q][i], xst + i * PAIR_BYTES + ks * 512);
+                if constexpr (NT == 3) tr_issue(Al[q][i], xst + i * PAIR_BYTES + 2 * CH + ks * 512);
+            }
+        };
+        load(0, 0);
 #pragma unroll
-            for (int ks = 0; ks < 2 * TR; ++ks) {
-                const int q = ks & 1;
-                // everything outstanding belongs to step ks; tie its registers to the wait so no use moves above it
-                if constexpr (NT == 3) {
-                    if constexpr (PPW == 2)
-                        asm volatile("s_waitcnt lgkmcnt(0)"
-                                     : "+v"(Bh[q][0].a), "+v"(Bh[q][0].b), "+v"(Bh[q][1].a), "+v"(Bh[q][1].b), "+v"(Bh[q][2].a),
-                                       "+v"(Bh[q][2].b), "+v"(Bl[q][0].a), "+v"(Bl[q][0].b), "+v"(Bl[q][1].a), "+v"(Bl[q][1].b),
-                                       "+v"(Bl[q][2].a), "+v"(Bl[q][2].b), "+v"(Ah[q][0].a), "+v"(Ah[q][0].b), "+v"(Al[q][0].a),
-                                       "+v"(Al[q][0].b), "+v"(Ah[q][PPW - 1].a), "+v"(Ah[q][PPW - 1].b), "+v"(Al[q][PPW - 1].a),
-                                       "+v"(Al[q][PPW - 1].b));
-                    else
-                        asm volatile("s_waitcnt lgkmcnt(0)"
-                                     : "+v"(Bh[q][0].a), "+v"(Bh[q][0].b), "+v"(Bh[q][1].a), "+v"(Bh[q][1].b), "+v"(Bh[q][2].a),
-                                       "+v"(Bh[q][2].b), "+v"(Bl[q][0].a), "+v"(Bl[q][0].b), "+v"(Bl[q][1].a), "+v"(Bl[q][1].b),
-                                       "+v"(Bl[q][2].a), "+v"(Bl[q][2].b), "+v"(Ah[q][0].a), "+v"(Ah[q][0].b), "+v"(Al[q][0].a),
-                                       "+v"(Al[q][0].b));
-                } else {
-                    if constexpr (PPW == 2)
-                        asm volatile("s_waitcnt lgkmcnt(0)"
-                                     : "+v"(Bh[q][0].a), "+v"(Bh[q][0].b), "+v"(Bh[q][1].a), "+v"(Bh[q][1].b), "+v"(Bh[q][2].a),
-                                       "+v"(Bh[q][2].b), "+v"(Ah[q][0].a), "+v"(Ah[q][0].b), "+v"(Ah[q][PPW - 1].a),
-                                       "+v"(Ah[q][PPW - 1].b));
-                    else
-                        asm volatile("s_waitcnt lgkmcnt(0)"
-                                     : "+v"(Bh[q][0].a), "+v"(Bh[q][0].b), "+v"(Bh[q][1].a), "+v"(Bh[q][1].b), "+v"(Bh[q][2].a),
-                                       "+v"(Bh[q][2].b), "+v"(Ah[q][0].a), "+v"(Ah[q][0].b));
-                }
-                if (ks + 1 < 2 * TR) load(ks + 1, q ^ 1);
-                __builtin_amdgcn_sched_barrier(0);
-                half8 bh[W1_NCOT], bl[W1_NCOT];
+        for (int ks = 0; ks < 2 * TR; ++ks) {
+            const int q = ks & 1;
+            // everything outstanding belongs to step ks; tie its registers to the wait so no use moves above it
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-                for (int j = 0; j < W1_NCOT; ++j) {
-                    bh[j] = tr_value(Bh[q][j]);
-                    if constexpr (NT == 3) bl[j] = tr_value(Bl[q][j]);
-                }
-                if (bias_wave) {
+            for (int j = 0; j < W1_NCOT; ++j) {
+                tr_tie(Bh[q][j]);
+                if constexpr (NT == 3) tr_tie(Bl[q][j]);
+            }
 #pragma unroll
-                    for (int j = 0; j < W1_NCOT; ++j)
+            for (int i = 0; i < PPW; ++i) {
+                tr_tie(Ah[q][i]);
+                if constexpr (NT == 3) tr_tie(Al[q][i]);
+            }
+            if (ks + 1 < 2 * TR) load(ks + 1, q ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+            half8 bh[W1_NCOT], bl[W1_NCOT];
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            bsum[j] += (float)bh[j][e];
-                            if constexpr (NT == 3) bsum[j] += (float)bl[j][e];
-                        }
-                }
+            for (int j = 0; j < W1_NCOT; ++j) {
+                bh[j] = tr_value(Bh[q][j]);
+                if constexpr (NT == 3) bl[j] = tr_value(Bl[q][j]);
+            }
+            if (bias_wave) {
 #pragma unroll
-                for (int i = 0; i < PPW; ++i) {
-                    if (!valid[i]) continue;
-                    const half8 ah = tr_value(Ah[q][i]);
-                    half8 al;
-                    if constexpr (NT == 3) al = tr_value(Al[q][i]);
+                for (int j = 0; j < W1_NCOT; ++j)
 #pragma unroll
-                    for (int j = 0; j < W1_NCOT; ++j) {
-                        if constexpr (NT == 3) {
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[j], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[j], acc[i][j], 0, 0, 0);
-                        }
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[j], acc[i][j], 0, 0, 0);
+                    for (int e = 0; e < 8; ++e) {
+                        bsum[j] += (float)bh[j][e];
+                        if constexpr (NT == 3) bsum[j] += (float)bl[j][e];
                     }
+            }
+#pragma unroll
+            for (int i = 0; i < PPW; ++i) {
+                if (!valid[i]) continue;
+                const half8 ah = tr_value(Ah[q][i]);
+                half8 al;
+                if constexpr (NT == 3) al = tr_value(Al[q][i]);
+#pragma unroll
+                for (int j = 0; j < W1_NCOT; ++j) {
+                    if constexpr (NT == 3) {
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[j], acc[i][j], 0, 0, 0);
+                    }
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[j], acc[i][j], 0, 0, 0);
                 }
             }
         }
@@ -806,7 +730,6 @@ wgrad1x1_kernel(const WgradKArgs a) {
         buf ^= 1;
     }
 
-    if (a.dbg & 4) { if (acc[0][0][0] == 12345.f) a.partial[0] = bsum[0]; return; }
     // ---- every accumulator tile is complete in its wave: straight to the partial buffer (layout of the generic kernel,
     // ntap = 1, z = co tile; 32 lanes = 32 consecutive floats)
     const int n = lane & 31, hi = lane >> 5;
@@ -819,7 +742,7 @@ wgrad1x1_kernel(const WgradKArgs a) {
             if (j >= a.ncot) continue;
             float* dst = a.partial + (((long long)j * a.ncp + cp) * a.PB + pb) * 1024 + n;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) dst[((e & 3) + 8 * (e >> 2) + 4 * hi) * 32] = acc[i][j][e];
+            for (int e = 0; e < 16; ++e) dst[acc_row(e, hi) * 32] = acc[i][j][e];
         }
     }
     if (bias_wave) {
@@ -903,73 +826,60 @@ bool use_w1(int ksize, int cout) { return ksize == 1 && cout <= 32 * W1_NCOT; }
 
 WgGeom wg_geom(int ksize, int N, int H, int W, int cin_chunks, int cout, int cus) {
     WgGeom g;
-    if (use_w1(ksize, cout)) {
-        g.tr = 1; g.ndyg = 1; g.ntap = 1;
-        g.ncp = (cin_chunks + 1) / 2;
-        g.ncot = (cout + 31) / 32;
-        const W1Plan wp = w1_plan(g.ncp);
-        g.tiles_x = (W + 31) / 32;
-        g.tiles_y = (H + wp.tr - 1) / wp.tr;
-        g.ntiles = g.tiles_x * g.tiles_y * N;
-        int pb = (cus > 0 ? cus : 256) / wp.cgroups;      // one workgroup per CU (the LDS is all staging buffer)
-        if (pb < 1) pb = 1;
-        if (pb > g.ntiles) pb = g.ntiles;
-        g.PB = pb;
-        g.partial_floats = (size_t)g.ncp * g.ncot * pb * 1024;
-        g.bias_floats = (size_t)g.ncot * pb * 32;
-        return g;
-    }
-    g.tr = (ksize == 5) ? 1 : ksize;
+    const bool w1 = use_w1(ksize, cout);
+    g.tr = (ksize == 5) ? 1 : ksize;                    // tap rows per workgroup: the 5x5 splits its rows over ndyg workgroups
     g.ndyg = ksize / g.tr;
     g.ntap = g.tr * ksize;
     g.ncp = (cin_chunks + 1) / 2;
     g.ncot = (cout + 31) / 32;
+    const W1Plan wp = w1_plan(g.ncp);
+    const int th = w1 ? wp.tr : 8;                      // tile rows
     g.tiles_x = (W + 31) / 32;
-    g.tiles_y = (H + 7) / 8;
+    g.tiles_y = (H + th - 1) / th;
     g.ntiles = g.tiles_x * g.tiles_y * N;
-    const int groups = g.ncp * g.ncot * g.ndyg;
-    // 3x3: one 8-wave workgroup per CU (two LDS stages); 5x5 / wide 1x1: the generic kernel, also one per CU
-    int pb = (cus > 0 ? cus : 256) / groups;            // floor: no straggler in an extra round
+    // One workgroup per CU in every kernel (3x3: two LDS stages of eight waves; streaming 1x1: the LDS is all staging buffer), so
+    // the pixel blocks are the CUs over the workgroups that walk the same tiles: the streaming kernel's columns, else every
+    // (cp, cot, dyg).  Floor: no straggler in an extra round.
+    const int blocks = g.ncp * g.ncot * g.ndyg;         // partial tiles (x ntap) per pixel block
+    int pb = (cus > 0 ? cus : 256) / (w1 ? wp.cgroups : blocks);
     if (pb < 1) pb = 1;
     if (pb > g.ntiles) pb = g.ntiles;
-    if (pb >= 8) pb &= ~7;                              // wg_block(): siblings of a pixel block share an XCD
+    if (!w1 && pb >= 8) pb &= ~7;                       // wg_block(): siblings of a pixel block share an XCD
     g.PB = pb;
-    g.partial_floats = (size_t)groups * pb * g.ntap * 1024;
+    g.partial_floats = (size_t)blocks * pb * g.ntap * 1024;
     g.bias_floats = (size_t)g.ncot * pb * 32;
     return g;
 }
 
-template <int KS, int TR, int NT>
-int launch_wg(const WgradKArgs& a, const WgGeom& g, hipStream_t s) {
-    using C = WgCfg<KS, TR, NT>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&wgrad_mfma_kernel<KS, TR, NT>, C::LDS_BYTES, lds_set)) return rc;
-    dim3 grid((unsigned)(g.PB * g.ncp * g.ncot * g.ndyg));
-    wgrad_mfma_kernel<KS, TR, NT><<<grid, dim3(256), C::LDS_BYTES, s>>>(a);
-    BH_CHECK_LAUNCH();
+size_t wg_workspace_bytes(const WgGeom& g) { return (g.partial_floats + g.bias_floats) * sizeof(float) + 256; }
+
+// the shape checks binhip_wgrad_workspace_bytes() and bh_wgrad_partials() share; wg_geom() divides by the tap rows
+int check_shape(int ksize, int N, int H, int W, int cin_chunks, int cout) {
+    if (ksize != 1 && ksize != 3 && ksize != 5) return BINHIP_E_SHAPE;
+    if (N <= 0 || H <= 0 || W <= 0 || cin_chunks <= 0 || cout <= 0) return BINHIP_E_SHAPE;
     return 0;
 }
 
-
+// one launch of a main kernel: block size and opt-in LDS limit from its config struct, `lds` bytes of it asked for
+template <class Cfg, void (*KERNEL)(WgradKArgs)>
+int launch(const WgradKArgs& a, dim3 grid, hipStream_t s, unsigned lds = Cfg::LDS_BYTES) {
+    static std::atomic<unsigned long long> lds_set{0};
+    if (int rc = bh_set_max_lds(KERNEL, Cfg::LDS_BYTES, lds_set)) return rc;
+    KERNEL<<<grid, dim3(Cfg::THREADS), lds, s>>>(a);
+    BH_CHECK_LAUNCH();
+    return 0;
+}
+template <int KS, int NT>
+int launch_generic(const WgradKArgs& a, dim3 grid, hipStream_t s) {
+    return launch<WgCfg<KS, 1, NT>, wgrad_mfma_kernel<KS, 1, NT>>(a, grid, s);
+}
 template <int NT>
-int launch_wg3x(const WgradKArgs& a, const WgGeom& g, hipStream_t s) {
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&wgrad3x3_xrow_kernel<NT>, Wg3xCfg<NT>::LDS_BYTES, lds_set)) return rc;
-    wgrad3x3_xrow_kernel<NT><<<dim3((unsigned)(g.PB * g.ncp * g.ncot * g.ndyg)), dim3(512), Wg3xCfg<NT>::LDS_BYTES, s>>>(a);
-    BH_CHECK_LAUNCH();
-    return 0;
-}
-
-
-
-template <int NT, int PPW, int TR>
 int launch_w1(const WgradKArgs& a, const WgGeom& g, const W1Plan& wp, hipStream_t s) {
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&wgrad1x1_kernel<NT, PPW, TR>, 160 * 1024, lds_set)) return rc;
-    const unsigned lds = (NT == 3) ? wp.lds : wp.lds / 2;
-    wgrad1x1_kernel<NT, PPW, TR><<<dim3((unsigned)g.PB, (unsigned)wp.cgroups), dim3(64 * W1_NW), lds < 16384 ? 16384 : lds, s>>>(a);
-    BH_CHECK_LAUNCH();
-    return 0;
+    const dim3 grid((unsigned)g.PB, (unsigned)wp.cgroups);
+    const unsigned want = (NT == 3) ? wp.lds : wp.lds / 2, lds = want < 16384 ? 16384 : want;
+    return wp.ppw == 2 ? launch<W1Cfg, wgrad1x1_kernel<NT, 2, 1>>(a, grid, s, lds)
+         : wp.tr == 2  ? launch<W1Cfg, wgrad1x1_kernel<NT, 1, 2>>(a, grid, s, lds)
+                       : launch<W1Cfg, wgrad1x1_kernel<NT, 1, 1>>(a, grid, s, lds);
 }
 
 // CU count of the current device (sizes the pixel-block split); looked up per call — no cached global
@@ -983,10 +893,8 @@ int cus() {
 extern "C" {
 
 size_t binhip_wgrad_workspace_bytes(int ksize, int N, int H, int W, int cin_chunks, int cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || cin_chunks <= 0 || cout <= 0) return 0;
-    if (ksize != 1 && ksize != 3 && ksize != 5) return 0;      // as binhip_conv2d_bwd_weight; wg_geom() divides by the tap rows
-    const WgGeom g = wg_geom(ksize, N, H, W, cin_chunks, cout, cus());
-    return (g.partial_floats + g.bias_floats) * sizeof(float) + 256;
+    if (check_shape(ksize, N, H, W, cin_chunks, cout)) return 0;
+    return wg_workspace_bytes(wg_geom(ksize, N, H, W, cin_chunks, cout, cus()));
 }
 
 }  // extern "C"
@@ -999,14 +907,12 @@ int bh_wgrad_partials(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
     if (!d || !x_hi || !gy_hi || !workspace || !dw_oihw) return BINHIP_E_ARG;
     if (d->nterms != 1 && d->nterms != 3) return BINHIP_E_ARG;
     if (d->nterms == 3 && (!x_lo || !gy_lo)) return BINHIP_E_ARG;
-    if (d->ksize != 1 && d->ksize != 3 && d->ksize != 5) return BINHIP_E_SHAPE;
-    if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->cin_chunks <= 0 || d->cout <= 0) return BINHIP_E_SHAPE;
+    if (int rc = check_shape(d->ksize, d->N, d->H, d->W, d->cin_chunks, d->cout)) return rc;
     if ((long long)d->N * d->H * d->W >= (1ll << 26)) return BINHIP_E_SHAPE;
     if (cin <= 0 || cin > d->cin_chunks * 16) return BINHIP_E_SHAPE;
     if (shuffle_perm && d->cout % 4) return BINHIP_E_SHAPE;
     const WgGeom g = wg_geom(d->ksize, d->N, d->H, d->W, d->cin_chunks, d->cout, cus());
-    const size_t need = (g.partial_floats + g.bias_floats) * sizeof(float) + 256;
-    if (workspace_bytes < need) return BINHIP_E_WORKSPACE;
+    if (workspace_bytes < wg_workspace_bytes(g)) return BINHIP_E_WORKSPACE;
     float* part = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     WgradKArgs a;
     a.x_hi = (const _Float16*)x_hi; a.x_lo = (const _Float16*)x_lo;
@@ -1016,23 +922,21 @@ int bh_wgrad_partials(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
     a.N = d->N; a.H = d->H; a.W = d->W;
     a.cin_chunks = d->cin_chunks; a.cout_chunks = (d->cout + 15) / 16;
     a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.ntiles = g.ntiles;
-    a.PB = g.PB; a.ncp = g.ncp; a.ncot = g.ncot; a.ppg = 0; a.nz = g.ncot * g.ndyg; a.cgroups = 1;
-    a.dbg = 0;
+    a.PB = g.PB; a.ncp = g.ncp; a.ncot = g.ncot; a.nz = g.ncot * g.ndyg;
     hipStream_t s = (hipStream_t)stream;
-    int rc = BINHIP_E_SHAPE;
+    const bool x3 = d->nterms == 3;
+    const dim3 grid((unsigned)(g.PB * g.ncp * g.ncot * g.ndyg));        // generic / 3x3: wg_block() unpacks the id
+    const W1Plan wp = w1_plan(g.ncp);
+    a.ppg = use_w1(d->ksize, d->cout) ? wp.ppg : 0;
+    int rc;
     if (use_w1(d->ksize, d->cout)) {
-        const W1Plan wp = w1_plan(g.ncp);
-        a.ppg = wp.ppg;
-        rc = (d->nterms == 1)
-            ? (wp.ppw == 2 ? launch_w1<1, 2, 1>(a, g, wp, s) : wp.tr == 2 ? launch_w1<1, 1, 2>(a, g, wp, s) : launch_w1<1, 1, 1>(a, g, wp, s))
-            : (wp.ppw == 2 ? launch_w1<3, 2, 1>(a, g, wp, s) : wp.tr == 2 ? launch_w1<3, 1, 2>(a, g, wp, s) : launch_w1<3, 1, 1>(a, g, wp, s));
-    } else if (d->ksize == 3) {
-        // eight waves, two LDS stages, one workgroup per CU; wave = X row
-        rc = (d->nterms == 1) ? launch_wg3x<1>(a, g, s) : launch_wg3x<3>(a, g, s);
+        rc = x3 ? launch_w1<3>(a, g, wp, s) : launch_w1<1>(a, g, wp, s);
+    } else if (d->ksize == 3) {                     // eight waves, two LDS stages, one workgroup per CU; wave = X row
+        rc = x3 ? launch<Wg3xCfg<3>, wgrad3x3_xrow_kernel<3>>(a, grid, s) : launch<Wg3xCfg<1>, wgrad3x3_xrow_kernel<1>>(a, grid, s);
     } else if (d->ksize == 1) {                     // 1x1 with more than 96 outputs (not on the bin_stage4 path)
-        rc = (d->nterms == 1) ? launch_wg<1, 1, 1>(a, g, s) : launch_wg<1, 1, 3>(a, g, s);
+        rc = x3 ? launch_generic<1, 3>(a, grid, s) : launch_generic<1, 1>(a, grid, s);
     } else {                                        // 5x5 (SFENet1)
-        rc = (d->nterms == 1) ? launch_wg<5, 1, 1>(a, g, s) : launch_wg<5, 1, 3>(a, g, s);
+        rc = x3 ? launch_generic<5, 3>(a, grid, s) : launch_generic<5, 1>(a, grid, s);
     }
     if (rc) return rc;
     out->partial = a.partial; out->partial_b = a.partial_b;

@@ -1,6 +1,8 @@
 """-m gpu: weight-gradient kernels (3x3 X-row, 5x5, 1x1 streaming, the batched reduction) and the conv backward-data/weight fixtures, against the reference's autograd outputs and float64; and, over the case table of tests/wgrad_cases.py, exact integer and split-exact probes that both precisions must
 return bit for bit ("Weight-gradient kernels")."""
+import functools
 import hashlib
+import json
 import os
 import socket
 import sys
@@ -9,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 import wgrad_cases as wc
 
 pytestmark = pytest.mark.gpu
@@ -327,6 +329,29 @@ def test_wgrad_white_noise_vs_float64(tag, nterms):
     assert ew <= TOL_BWD[nterms] and eb <= TOL_BWD[nterms]
     dw2, db2 = ops.conv2d_bwd_weight(xp, gp, c.cout, c.cin, c.ks, nterms)
     assert torch.equal(dw, dw2) and torch.equal(db, db2), "fixed summation order"
+
+
+@functools.lru_cache(maxsize=None)
+def _recorded_bits():
+    with open(os.path.join(GOLDEN, "wgrad_bits.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("nterms", [3, 1])
+@pytest.mark.parametrize("tag", wc.TAGS)
+def test_wgrad_white_noise_bits_are_the_recorded_ones(tag, nterms):
+    """Families A and B are exact in any summation order; this holds the order itself: dW and db of family C are, bit for bit, what
+    tests/golden/make_wgrad_bits.py recorded from the commit named in tests/golden/wgrad_bits.json.  PB and with it the order depend on
+    the CU count, so on a device with another CU count than the fixture's the test fails and says so."""
+    from bin_amd import _lib as L
+    rec = _recorded_bits()
+    cus = L.lib().binhip_device_cus()
+    assert cus == rec["cus"], (f"tests/golden/wgrad_bits.json was recorded on a device of {rec['cus']} CUs, this one has {cus}: another "
+                               f"pixel-block split, another summation order; record the fixture anew for this device")
+    key = f"{tag}/{nterms}"
+    assert key in rec["bits"], f"{key} is not in the fixture (left out as not reproducible: {rec['left_out']})"
+    got = wc.white_noise_bits(wc.BY_TAG[tag], nterms)
+    assert got == rec["bits"][key], f"{key}: the bits differ from those recorded from {rec['recorded_from']}"
 
 
 # ------------------------------------------------------------------------------------------------ live wgrad timing

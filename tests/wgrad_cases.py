@@ -260,6 +260,17 @@ def reference_c(tag):
     return reference(x, gy, c.ks)
 
 
+def white_noise_bits(case, nterms):
+    """{"dw", "db"}: sha256 of the bytes of the library's dW and db on family C (needs a GPU).  What tests/golden/make_wgrad_bits.py
+    records and test_wgrad_white_noise_bits_are_the_recorded_ones recomputes."""
+    import hashlib
+    from bin_amd import ops
+    x, gy = family_c(case)
+    dw, db = ops.conv2d_bwd_weight(ops.nchw_to_planes(x.cuda(), nterms), ops.nchw_to_planes(gy.cuda(), nterms), case.cout, case.cin,
+                                   case.ks, nterms)
+    return {"dw": hashlib.sha256(dw.cpu().numpy().tobytes()).hexdigest(), "db": hashlib.sha256(db.cpu().numpy().tobytes()).hexdigest()}
+
+
 def shuffle_rows(t):
     """The `cq` permutation of shuffle_perm: row co of the plain result lands at (co % cq) * 4 + co // cq, cq = cout / 4."""
     cout = t.shape[0]
