@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import EMA_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH
+from .build import EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -97,6 +97,18 @@ EMA_MAX_TENSORS = 136                  # BINEMA_MAX_TENSORS (include/binema.h, l
 
 class BinEmaTensor(C.Structure):
     _fields_ = [("e", C.c_void_p), ("p", C.c_void_p), ("numel", C.c_int64)]
+
+
+ENS_FLIP_W, ENS_FLIP_H = 1, 2          # BINENS_FLIP_* (include/binens.h, libbinens.so)
+ENS_MAX_ORIENT, ENS_MAX_SOURCES, ENS_MAX_SLOTS = 8, 6, 14   # BINENS_MAX_*
+
+
+class BinEnsOrient(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p * ENS_MAX_ORIENT), ("flip", C.c_uint8 * ENS_MAX_ORIENT), ("n_dst", C.c_int32)]
+
+
+class BinEnsMerge(C.Structure):
+    _fields_ = [("src", C.c_void_p * ENS_MAX_ORIENT), ("dst", C.c_void_p)]
 
 
 _SIGNATURES = {
@@ -210,10 +222,18 @@ _EMA_SIGNATURES = {
     "binema_step": (C.c_int, [C.POINTER(BinEmaTensor), C.c_int, C.c_float, C.c_void_p]),
 }
 
+# libbinens.so (include/binens.h): the self-ensemble library, loaded on first use
+ENS_VERSION = 100                      # BINENS_VERSION
+_ENS_SIGNATURES = {
+    "binens_version": (C.c_int, []),
+    "binens_orient": (C.c_int, [C.POINTER(BinEnsOrient), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "binens_merge": (C.c_int, [C.POINTER(BinEnsMerge), C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = _optlib = _gradlib = _emalib = None
+_lib = _optlib = _gradlib = _emalib = _enslib = None
 
 
 def _load(path, built_path, signatures, version=None):
@@ -283,6 +303,19 @@ def emalib():
     if _emalib is None:
         _emalib = _load(EMA_LIB_PATH, EMA_LIB_PATH, _EMA_SIGNATURES, ("binema_version", EMA_VERSION))
     return _emalib
+
+
+def ens_exported_symbols():
+    """Names every include/binens.h entry point must resolve to."""
+    return sorted(_ENS_SIGNATURES)
+
+
+def enslib():
+    """Load libbinens.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _enslib
+    if _enslib is None:
+        _enslib = _load(ENS_LIB_PATH, ENS_LIB_PATH, _ENS_SIGNATURES, ("binens_version", ENS_VERSION))
+    return _enslib
 
 
 def check(rc, what):

@@ -26,12 +26,18 @@ GRAD_HEADER = os.path.join(os.path.dirname(HERE), "include", "bingrad.h")
 EMA_SOURCES = ["binema_step.hip"]
 EMA_LIB_PATH = os.path.join(CSRC, "libbinema.so")
 EMA_HEADER = os.path.join(os.path.dirname(HERE), "include", "binema.h")
+# the self-ensemble library (include/binens.h): the orient and merge kernels of bin_amd/ensemble.py; a fifth shared object, for the
+# same reason
+ENS_SOURCES = ["binens.hip"]
+ENS_LIB_PATH = os.path.join(CSRC, "libbinens.so")
+ENS_HEADER = os.path.join(os.path.dirname(HERE), "include", "binens.h")
 
 
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
 # (name, sources, header, path) of every shared object: what drives the compile, the version script and the link
 LIBRARIES = (("binhip", SOURCES, HEADER, LIB_PATH), ("binopt", OPT_SOURCES, OPT_HEADER, OPT_LIB_PATH),
-             ("bingrad", GRAD_SOURCES, GRAD_HEADER, GRAD_LIB_PATH), ("binema", EMA_SOURCES, EMA_HEADER, EMA_LIB_PATH))
+             ("bingrad", GRAD_SOURCES, GRAD_HEADER, GRAD_LIB_PATH), ("binema", EMA_SOURCES, EMA_HEADER, EMA_LIB_PATH),
+             ("binens", ENS_SOURCES, ENS_HEADER, ENS_LIB_PATH))
 
 
 def _declared(header, macro, prefix):
@@ -61,6 +67,11 @@ def ema_abi_symbols():
     return _declared(EMA_HEADER, "BINEMA_API", "binema")
 
 
+def ens_abi_symbols():
+    """The entry points include/binens.h declares (every BINENS_API declaration), in header order."""
+    return _declared(ENS_HEADER, "BINENS_API", "binens")
+
+
 def _stale():
     libs = [path for _, _, _, path in LIBRARIES]
     if not all(os.path.exists(p) for p in libs):
@@ -73,8 +84,8 @@ def _stale():
 
 def build_library(force=False, verbose=True, defines=(), out=None):
     """Compile every HIP source for gfx950 into bin_amd/csrc/libbinhip.so (and, for the product build, the optimizer
-    library bin_amd/csrc/libbinopt.so, the gradient-guard library bin_amd/csrc/libbingrad.so and the weight-average library
-    bin_amd/csrc/libbinema.so beside it).
+    library bin_amd/csrc/libbinopt.so, the gradient-guard library bin_amd/csrc/libbingrad.so, the weight-average library
+    bin_amd/csrc/libbinema.so and the self-ensemble library bin_amd/csrc/libbinens.so beside it).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain): libbinhip.so alone, under another name.  The

@@ -21,7 +21,7 @@ def window_frame_ids(index, n_frames):
 
 
 @torch.no_grad()
-def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1):
+def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1, ensemble=None):
     """Run the test.py inner loop over a clip for this rank's share of its T-1 windows.
     `clip`: [T,H,W,3] uint8 BGR (what cv2.imread yields; decoded, padded and re-encoded ON THE DEVICE by the
     u8_to_frame / frame_to_u8 kernels, each padded frame cached because 5 of a window's 6 frames recur in the
@@ -33,8 +33,12 @@ def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1):
     batch > 1: that many consecutive windows go through the net as ONE forward along N.  A small frame does not fill
     the chip (a 320x320 window is 50 tiles per launch on 256 CUs): 8 windows per forward give 2.5x the windows/s at
     256x256 and 1.75x at 448x256 (tools/bench_small.py); per-image arithmetic is unchanged, so the images are
-    bit-identical to batch = 1.  Windows are independent (the net re-zeros its LSTM state per call)."""
+    bit-identical to batch = 1.  Windows are independent (the net re-zeros its LSTM state per call).
+    ensemble: a self-ensemble group (bin_amd/ensemble.py: letters of `hvt`, `flipx4`, `x8`); every image is then the mean of the
+    M = 2^k oriented forwards, the flips and the merge being two HIP launches.  With reuse_stage1 every orientation keeps its own
+    oriented frames and memo, so the 17 -> 10 RDN calls per window hold in each.  None / "" / "none": off, the path above."""
     from . import ops
+    from .ensemble import SelfEnsemble, parse_group
     dev = next(netG.parameters()).device
     is_u8 = clip.dtype == torch.uint8
     if is_u8:
@@ -58,6 +62,7 @@ def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1):
     inner = netG.module if hasattr(netG, "module") else netG
     batch = max(1, int(batch))
     stage1_cache = {} if (reuse_stage1 and batch == 1 and getattr(inner, "reuse_schedule", False)) else None
+    ens = SelfEnsemble(netG, ensemble) if parse_group(ensemble) else None
     for first in range(begin, end, batch):
         idx = list(range(first, min(first + batch, end)))
         ids = [window_frame_ids(i, T) for i in idx]
@@ -67,7 +72,11 @@ def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1):
             inputs = [frame(i) for i in ids[0]]
         else:
             inputs = [torch.cat([frame(w_ids[k]) for w_ids in ids], 0) for k in range(6)]
-        if stage1_cache is not None:
+        if ens is not None and len(idx) == 1:
+            Ft_p = ens.window(ids[0], inputs, slots=(13, 8, 12), reuse=stage1_cache is not None)
+        elif ens is not None:
+            Ft_p = ens(inputs, slots=(13, 8, 12))
+        elif stage1_cache is not None:
             Ft_p = netG(*inputs, stage1_cache=stage1_cache)
         else:
             Ft_p = netG(*inputs)

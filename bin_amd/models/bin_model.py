@@ -372,10 +372,26 @@ class bin_model(BaseModel):
     def test(self):
         self.netG.eval()
         with torch.no_grad():
-            Ft_p = self.netG(self.B1, self.B3, self.B5, self.B7, self.B9, self.B11)
+            ens = self.self_ensemble()
+            if ens is not None:                    # train.val_self_ensemble: all 14 outputs as the mean over the group's orientations
+                Ft_p = tuple(ens((self.B1, self.B3, self.B5, self.B7, self.B9, self.B11)))
+            else:
+                Ft_p = self.netG(self.B1, self.B3, self.B5, self.B7, self.B9, self.B11)
         self.netG.train()
         self.Ft_p = Ft_p
         return Ft_p
+
+    def self_ensemble(self):
+        """The bin_amd.ensemble.SelfEnsemble `train.val_self_ensemble` asks for (built on first use), or None when it is off."""
+        from ..options.options import val_self_ensemble
+        group = val_self_ensemble(self.opt)
+        if not group:
+            return None
+        ens = getattr(self, "_self_ensemble", None)
+        if ens is None or ens.group != group or ens.netG is not self.netG:
+            from ..ensemble import SelfEnsemble
+            ens = self._self_ensemble = SelfEnsemble(self.netG, group)
+        return ens
 
     def forward(self):
         Ft_p = self.netG(self.B1, self.B3, self.B5, self.B7, self.B9, self.B11)

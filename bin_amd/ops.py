@@ -885,3 +885,80 @@ def ema_launch(table, n, device, decay):
         return
     with torch.cuda.device(device):
         L.check(L.emalib().binema_step(table, n, decay, _stream()), "ema_step")
+
+
+# --------------------------------------------------------------------------------------------- self-ensemble (orient / merge)
+def _ens_geometry(what, tensors):
+    """(planes, H, W) shared by `tensors`: float32 contiguous device tensors [..., H, W] of one shape on one device.  Raises on CPU
+    tensors (there is no CPU fallback), on another dtype and on non-contiguous tensors: the kernels walk planes*H*W consecutive
+    floats from each pointer (batch slices and views at any 4-byte offset are fine)."""
+    _need_cuda(*tensors)
+    first = tensors[0]
+    if first.dim() < 2:
+        raise ValueError(f"{what}: tensors of at least two dimensions [..., H, W], got shape {tuple(first.shape)}")
+    for t in tensors:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: float32 tensors, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: contiguous tensors, got strides {tuple(t.stride())} of shape {tuple(t.shape)}")
+        if t.shape != first.shape or t.device != first.device:
+            raise ValueError(f"{what}: tensors of one shape on one device, got {tuple(t.shape)} on {t.device} beside "
+                             f"{tuple(first.shape)} on {first.device}")
+    h, w = first.shape[-2:]
+    return first.numel() // max(h * w, 1), h, w
+
+
+def ens_orient(frames, dsts, flips):
+    """binens_orient, one launch, current stream, no host sync: for every frame i (at most BINENS_MAX_SOURCES) and every j,
+    dsts[i][j] becomes frames[i] with flips[i][j] (an OR of _lib.ENS_FLIP_W / ENS_FLIP_H) applied per plane.  `dsts` is None, or
+    per frame a list whose entries are tensors of the frame's shape (batch slices are fine) or None; what is None is allocated.
+    Returns the destinations as a list of lists.  The frames are only read."""
+    frames = list(frames)
+    flips = [list(f) for f in flips]
+    dsts = [[None] * len(f) for f in flips] if dsts is None else [list(d) for d in dsts]
+    if len(dsts) != len(frames) or len(flips) != len(frames) or any(len(d) != len(f) for d, f in zip(dsts, flips)):
+        raise ValueError("ens_orient: one list of destinations and one list of flips per frame, of equal lengths")
+    if not frames:
+        return dsts
+    _need_cuda(*frames)
+    dsts = [[torch.empty_like(x, memory_format=torch.contiguous_format) if d is None else d for d in ds] for x, ds in zip(frames, dsts)]
+    planes, h, w = _ens_geometry("ens_orient", frames + [d for ds in dsts for d in ds])
+    table = (L.BinEnsOrient * len(frames))()
+    for it, x, ds, fs in zip(table, frames, dsts, flips):
+        if len(ds) > L.ENS_MAX_ORIENT:
+            raise ValueError(f"ens_orient: at most {L.ENS_MAX_ORIENT} destinations per frame, got {len(ds)}")
+        it.src, it.n_dst = x.data_ptr(), len(ds)
+        for j, (d, f) in enumerate(zip(ds, fs)):
+            it.dst[j], it.flip[j] = d.data_ptr(), int(f)
+    with on_device(frames[0]):
+        L.check(L.enslib().binens_orient(table, len(frames), planes, h, w, _stream()), "ens_orient")
+    return dsts
+
+
+def ens_merge(srcs_per_slot, flip_of, out=None):
+    """binens_merge, one launch, current stream, no host sync: for every slot (at most BINENS_MAX_SLOTS) the mean of its M = len(flip_of)
+    sources, source o un-flipped by flip_of[o] on the fly, summed as the balanced pairwise tree over o (include/binens.h) and scaled
+    by the exact 1/M.  Returns one FRESH tensor per slot (or fills `out`, a list of tensors of the sources' shape): the sources are
+    often outputs the network's memo shares with later forwards, and are only read."""
+    srcs = [list(s) for s in srcs_per_slot]
+    flip_of = [int(f) for f in flip_of]
+    m = len(flip_of)
+    if any(len(s) != m for s in srcs):
+        raise ValueError(f"ens_merge: {m} flips, so {m} sources per slot")
+    if not srcs:
+        return []
+    _need_cuda(*[t for s in srcs for t in s])
+    outs = [torch.empty_like(s[0], memory_format=torch.contiguous_format) for s in srcs] if out is None else list(out)
+    if len(outs) != len(srcs):
+        raise ValueError("ens_merge: one output per slot")
+    planes, h, w = _ens_geometry("ens_merge", [t for s in srcs for t in s] + outs)
+    if m > L.ENS_MAX_ORIENT:
+        raise ValueError(f"ens_merge: at most {L.ENS_MAX_ORIENT} sources per slot, got {m}")
+    table = (L.BinEnsMerge * len(srcs))()
+    for it, s, o in zip(table, srcs, outs):
+        it.dst = o.data_ptr()
+        for k, t in enumerate(s):
+            it.src[k] = t.data_ptr()
+    with on_device(outs[0]):
+        L.check(L.enslib().binens_merge(table, len(srcs), m, (C.c_uint8 * max(m, 1))(*flip_of), planes, h, w, _stream()), "ens_merge")
+    return outs

@@ -127,6 +127,17 @@ def weight_ema(opt, params):
     return WeightEMA(params, decay)
 
 
+def val_self_ensemble(opt):
+    """`train.val_self_ensemble` (bin_amd extension): the self-ensemble group validation runs the generator under
+    (bin_amd/ensemble.py: letters of `hvt`, `flipx4`, `x8`).  Absent, null, "" or `none`: off -> ""; otherwise the group's canonical
+    spelling.  Anything else raises."""
+    from ..ensemble import parse_group
+    try:
+        return parse_group(_train_value(opt, "val_self_ensemble"))
+    except ValueError as e:
+        raise ValueError(f"train.val_self_ensemble: {e}") from None
+
+
 def parse(opt_path, is_train=True):
     with open(opt_path) as f:
         opt = yaml.load(f, Loader=_ordered_loader())
@@ -136,6 +147,7 @@ def parse(opt_path, is_train=True):
         grad_clip(opt)
         skip_bad_steps(opt)
         ema_decay(opt)
+        val_self_ensemble(opt)
     if is_train and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the reference exports CUDA_VISIBLE_DEVICES from gpu_ids (torch on ROCm honours the same variable); under
         # a one-process-per-GPU launcher the launcher owns device visibility, so it is left alone there

@@ -54,6 +54,9 @@ def parse_args(argv=None):
     p.add_argument("--batch", type=int, default=1, help="windows per forward (small frames: 8 fills the chip; no "
                    "cross-window stage-1 reuse when > 1)")
     p.add_argument("--no_reuse", action="store_true", help="recompute the stage-1 calls shared by consecutive windows")
+    p.add_argument("--self_ensemble", type=str, default=None, metavar="G",
+                   help="test-time self-ensemble over a group of the letters h (flip W), v (flip H), t (reverse time), or flipx4 "
+                        "(= hv) / x8 (= hvt): every image is the mean of the 2^k oriented forwards (bin_amd/ensemble.py)")
     p.add_argument("--backend", default=None, help="torch.distributed backend for --launcher pytorch (default: nccl = "
                    "RCCL on a GPU box; gloo lets several ranks share one device)")
     p.add_argument("--manifest", action="store_true", help="each rank also writes written.rank<R>.txt under the result "
@@ -234,6 +237,10 @@ def main(argv=None, stats=None):
     dev = next(netG.parameters()).device
     inner = netG.module if hasattr(netG, "module") else netG
     reuse = (not args.no_reuse) and getattr(inner, "reuse_schedule", False)
+    from .ensemble import SelfEnsemble, parse_group
+    ens = SelfEnsemble(netG, args.self_ensemble) if parse_group(args.self_ensemble) else None
+    if ens is not None:
+        log.info("self-ensemble: group %s, M = %d forwards per window", ens.group, ens.M)
     log.info("In Data: %s | model: %s | parameters: %d | ranks: %d | stage-1 reuse: %s", args.input_path,
              opt["path"]["pretrain_model_G"], sum(p.numel() for p in netG.parameters() if p.requires_grad), world, reuse)
 
@@ -326,10 +333,14 @@ def main(argv=None, stats=None):
         (h, w), (l, r, t, b) = geom[:2], geom[2]
         if len(group) == 1:
             inputs = group[0][3]
-            Ft_p = netG(*inputs, stage1_cache=stage1_cache) if reuse else netG(*inputs)
+            if ens is not None:
+                Ft_p = ens.window(group[0][5], inputs, slots=OUT_KEYS, reuse=reuse)
+            else:
+                Ft_p = netG(*inputs, stage1_cache=stage1_cache) if reuse else netG(*inputs)
         else:
-            Ft_p = netG(*[torch.cat([g[3][k] for g in group], 0) for k in range(6)])
-        for j, (clip, names, owned, _, blurry_path) in enumerate(group):
+            inputs = [torch.cat([g[3][k] for g in group], 0) for k in range(6)]
+            Ft_p = netG(*inputs) if ens is None else ens(inputs, slots=OUT_KEYS)
+        for j, (clip, names, owned, _, blurry_path, _) in enumerate(group):
             outs = torch.stack([ops.frame_to_u8(Ft_p[k][j:j + 1], t, l, h, w) for k in OUT_KEYS])
             ready = torch.cuda.Event()
             ready.record()
@@ -361,6 +372,8 @@ def main(argv=None, stats=None):
                 flush()
                 cur_clip = clip
                 decoded.clear(); frames_dev.clear(); stage1_cache.clear()
+                if ens is not None:
+                    ens.reset()          # the oriented frames and the per-orientation memos belong to the clip
                 os.makedirs(os.path.join(result_root, clip), exist_ok=True)
             if wi == begin + 3:
                 early.clear()            # the early decodes belong to the first three windows; whatever was not taken is dropped
@@ -394,7 +407,7 @@ def main(argv=None, stats=None):
             for fid in [f for f in frames_dev if f < min(ids)]:      # the windows in `group` hold their own references
                 del frames_dev[fid]
                 decoded.pop((clip, fid), None)
-            group.append((clip, names, owned, six, os.path.join(args.input_path, clip, frames[ids[3]])))
+            group.append((clip, names, owned, six, os.path.join(args.input_path, clip, frames[ids[3]]), ids))
             if len(group) >= args.batch:
                 flush()
         flush()

@@ -40,7 +40,9 @@ def validate(model, loader, step, opt, log, max_batches=None):
     metrics = option.val_metrics(opt)
     ema = getattr(model, "weight_ema", None) is not None      # train.ema_decay: the averaged weights are the ones scored
     with (model.ema_scope() if ema else contextlib.nullcontext()):
-        return _validate(model, loader, step, opt, log, max_batches, metrics, " ema" if ema else "")
+        group = option.val_self_ensemble(opt)                 # train.val_self_ensemble: model.test() averages the group's orientations
+        which = (" ema" if ema else "") + (f" ens={group}" if group else "")
+        return _validate(model, loader, step, opt, log, max_batches, metrics, which)
 
 
 def _validate(model, loader, step, opt, log, max_batches, metrics, which):
