@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH
+from .build import EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, YUV_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -109,6 +109,15 @@ class BinEnsOrient(C.Structure):
 
 class BinEnsMerge(C.Structure):
     _fields_ = [("src", C.c_void_p * ENS_MAX_ORIENT), ("dst", C.c_void_p)]
+
+
+YUV_CHROMA_420, YUV_CHROMA_444 = 420, 444                # BINYUV_CHROMA_* (include/binyuv.h, libbinyuv.so)
+YUV_MATRIX_BT601, YUV_MATRIX_BT709 = 0, 1                 # BINYUV_MATRIX_*
+YUV_RANGE_LIMITED, YUV_RANGE_FULL = 0, 1                  # BINYUV_RANGE_*
+
+
+class BinYuvFormat(C.Structure):
+    _fields_ = [("chroma", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32)]
 
 
 _SIGNATURES = {
@@ -230,10 +239,20 @@ _ENS_SIGNATURES = {
     "binens_merge": (C.c_int, [C.POINTER(BinEnsMerge), C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
+# libbinyuv.so (include/binyuv.h): the video library, loaded on first use
+YUV_VERSION = 100                      # BINYUV_VERSION
+_YUV_SIGNATURES = {
+    "binyuv_version": (C.c_int, []),
+    "binyuv_to_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(BinYuvFormat), C.c_int, C.c_int, C.c_int,
+                                  C.c_int, C.c_void_p, C.c_void_p]),
+    "binyuv_from_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BinYuvFormat), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = _optlib = _gradlib = _emalib = _enslib = None
+_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = None
 
 
 def _load(path, built_path, signatures, version=None):
@@ -316,6 +335,19 @@ def enslib():
     if _enslib is None:
         _enslib = _load(ENS_LIB_PATH, ENS_LIB_PATH, _ENS_SIGNATURES, ("binens_version", ENS_VERSION))
     return _enslib
+
+
+def yuv_exported_symbols():
+    """Names every include/binyuv.h entry point must resolve to."""
+    return sorted(_YUV_SIGNATURES)
+
+
+def yuvlib():
+    """Load libbinyuv.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _yuvlib
+    if _yuvlib is None:
+        _yuvlib = _load(YUV_LIB_PATH, YUV_LIB_PATH, _YUV_SIGNATURES, ("binyuv_version", YUV_VERSION))
+    return _yuvlib
 
 
 def check(rc, what):

@@ -33,11 +33,19 @@ ENS_LIB_PATH = os.path.join(CSRC, "libbinens.so")
 ENS_HEADER = os.path.join(os.path.dirname(HERE), "include", "binens.h")
 
 
+# the video library (include/binyuv.h): 8-bit planar YUV <-> padded fp32 frame, the kernels of bin_amd/video.py; a sixth shared object,
+# for the same reason
+YUV_SOURCES = ["binyuv.hip"]
+YUV_LIB_PATH = os.path.join(CSRC, "libbinyuv.so")
+YUV_HEADER = os.path.join(os.path.dirname(HERE), "include", "binyuv.h")
+
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
 # (name, sources, header, path) of every shared object: what drives the compile, the version script and the link
 LIBRARIES = (("binhip", SOURCES, HEADER, LIB_PATH), ("binopt", OPT_SOURCES, OPT_HEADER, OPT_LIB_PATH),
              ("bingrad", GRAD_SOURCES, GRAD_HEADER, GRAD_LIB_PATH), ("binema", EMA_SOURCES, EMA_HEADER, EMA_LIB_PATH),
              ("binens", ENS_SOURCES, ENS_HEADER, ENS_LIB_PATH))
+# the libraries of the input / output side (same tuple layout), built and checked for staleness with the ones above
+IO_LIBRARIES = (("binyuv", YUV_SOURCES, YUV_HEADER, YUV_LIB_PATH),)
 
 
 def _declared(header, macro, prefix):
@@ -72,20 +80,26 @@ def ens_abi_symbols():
     return _declared(ENS_HEADER, "BINENS_API", "binens")
 
 
+def yuv_abi_symbols():
+    """The entry points include/binyuv.h declares (every BINYUV_API declaration), in header order."""
+    return _declared(YUV_HEADER, "BINYUV_API", "binyuv")
+
+
 def _stale():
-    libs = [path for _, _, _, path in LIBRARIES]
+    libs = [path for _, _, _, path in LIBRARIES + IO_LIBRARIES]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    deps += [header for _, _, header, _ in LIBRARIES]
+    deps += [header for _, _, header, _ in LIBRARIES + IO_LIBRARIES]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def build_library(force=False, verbose=True, defines=(), out=None):
     """Compile every HIP source for gfx950 into bin_amd/csrc/libbinhip.so (and, for the product build, the optimizer
     library bin_amd/csrc/libbinopt.so, the gradient-guard library bin_amd/csrc/libbingrad.so, the weight-average library
-    bin_amd/csrc/libbinema.so and the self-ensemble library bin_amd/csrc/libbinens.so beside it).
+    bin_amd/csrc/libbinema.so, the self-ensemble library bin_amd/csrc/libbinens.so and the video library
+    bin_amd/csrc/libbinyuv.so beside it).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain): libbinhip.so alone, under another name.  The
@@ -96,7 +110,7 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     objdir = CSRC if out is None else os.path.dirname(os.path.abspath(out))
     os.makedirs(objdir, exist_ok=True)
     tag = "" if out is None else "." + os.path.splitext(os.path.basename(out))[0]
-    libraries = LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
+    libraries = LIBRARIES + IO_LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
     procs, objs = [], {}
     for name, sources, _, _ in libraries:
         for src in sources:

@@ -38,7 +38,6 @@ def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1, en
     M = 2^k oriented forwards, the flips and the merge being two HIP launches.  With reuse_stage1 every orientation keeps its own
     oriented frames and memo, so the 17 -> 10 RDN calls per window hold in each.  None / "" / "none": off, the path above."""
     from . import ops
-    from .ensemble import SelfEnsemble, parse_group
     dev = next(netG.parameters()).device
     is_u8 = clip.dtype == torch.uint8
     if is_u8:
@@ -59,6 +58,17 @@ def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1, en
         return cache[i]
 
     out = {}
+    for idx, Ft_p in _forward_windows(netG, T, frame, cache, begin, end, reuse_stage1, batch, ensemble):
+        for j, i in enumerate(idx):
+            out[i] = tuple(ops.frame_to_u8(Ft_p[k][j:j + 1], t, l, h, w).cpu().numpy() for k in (13, 8, 12))
+        ops.check_status(dev)             # the .cpu() above synchronised: a saturated fp16 plane is an error, not an image
+    return out
+
+
+def _forward_windows(netG, T, frame, cache, begin, end, reuse_stage1, batch, ensemble):
+    """The window loop interpolate_clip and interpolate_video share: yields (window indices, Ft_p) per forward over the windows
+    [begin, end) of a T-frame clip.  `frame(i)`: the padded frame i, kept in `cache`, which loses the frames no later window names."""
+    from .ensemble import SelfEnsemble, parse_group
     inner = netG.module if hasattr(netG, "module") else netG
     batch = max(1, int(batch))
     stage1_cache = {} if (reuse_stage1 and batch == 1 and getattr(inner, "reuse_schedule", False)) else None
@@ -80,9 +90,52 @@ def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1, en
             Ft_p = netG(*inputs, stage1_cache=stage1_cache)
         else:
             Ft_p = netG(*inputs)
+        yield idx, Ft_p
+
+
+def video_slots(index, n_windows):
+    """The Ft_p slots window `index` of a clip contributes to the output video, in display order: the folder runner's ownership
+    rule (bin_amd/test.py) — the first window opens with its first deblurred frame, the last one has no second."""
+    return ((8,) if index == 0 else ()) + (13,) + ((12,) if index < n_windows - 1 else ())
+
+
+@torch.no_grad()
+def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None):
+    """interpolate_clip's loop over the frames of a Y4M stream.  `payloads`: [T, frame_bytes] uint8 (host or device), the frames of
+    `header` (bin_amd/video.py).  Returns the [2(T-1), frame_bytes] uint8 device tensor of the output payloads in display order,
+    D0, I0, D1, I1, ..., D(T-2), I(T-2): exactly the frames the folder runner writes for a one-clip folder, in name order — window 0
+    yields Ft_p[8], Ft_p[13], Ft_p[12], a middle window Ft_p[13], Ft_p[12], the last one Ft_p[13] (video_slots), so a first-in
+    first-out writer is in order already.  YUV -> padded frame and frame -> YUV are the kernels of libbinyuv.so (ops.yuv_to_frame /
+    ops.frame_to_yuv), the padded frames cached across the 5-of-6 overlap.  matrix / range: video.resolve_format.  reuse_stage1,
+    batch, ensemble: as in interpolate_clip."""
+    from . import ops, video
+    T = payloads.shape[0]
+    if T < 2:
+        raise ValueError(f"interpolate_video needs at least 2 frames (got {T})")
+    fmt = video.resolve_format(header, matrix, range)
+    h, w = header.height, header.width
+    if payloads.dim() != 2 or payloads.dtype != torch.uint8 or payloads.shape[1] != header.frame_bytes:
+        raise ValueError(f"payloads must be uint8 [T, {header.frame_bytes}] for this header (got {payloads.dtype} {tuple(payloads.shape)})")
+    dev = next(netG.parameters()).device
+    pads = util.pad_sizes(h, w)
+    l, r, t, b = pads
+    cache = {}
+
+    def frame(i):
+        if i not in cache:
+            cache[i] = ops.yuv_to_frame(payloads[i].to(dev).contiguous(), h, w, fmt, pads)
+        return cache[i]
+
+    n_win = T - 1
+    out = torch.empty((2 * n_win, header.frame_bytes), dtype=torch.uint8, device=dev)
+    n_out = 0
+    for idx, Ft_p in _forward_windows(netG, T, frame, cache, 0, n_win, reuse_stage1, batch, ensemble):
         for j, i in enumerate(idx):
-            out[i] = tuple(ops.frame_to_u8(Ft_p[k][j:j + 1], t, l, h, w).cpu().numpy() for k in (13, 8, 12))
-        ops.check_status(dev)             # the .cpu() above synchronised: a saturated fp16 plane is an error, not an image
+            for k in video_slots(i, n_win):
+                ops.frame_to_yuv(Ft_p[k][j:j + 1], t, l, h, w, fmt, out=out[n_out])
+                n_out += 1
+        ops.check_status(dev)             # (synchronises, as the image download of interpolate_clip does at this point)
+    assert n_out == 2 * n_win
     return out
 
 

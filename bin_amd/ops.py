@@ -523,6 +523,78 @@ def frame_to_u8(frame, top, left, h, w):
     return out
 
 
+# --------------------------------------------------------------------------------------------- video glue (libbinyuv.so)
+_YUV_MATRIX = {"bt601": L.YUV_MATRIX_BT601, "bt709": L.YUV_MATRIX_BT709}
+_YUV_RANGE = {"limited": L.YUV_RANGE_LIMITED, "full": L.YUV_RANGE_FULL}
+
+
+def yuv_format(fmt):
+    """BinYuvFormat of (chroma, matrix, range) = (420 | 444, "bt601" | "bt709", "limited" | "full")."""
+    chroma, matrix, rng = fmt
+    if chroma not in (420, 444) or matrix not in _YUV_MATRIX or rng not in _YUV_RANGE:
+        raise ValueError(f"bin_amd: unknown YUV format {fmt!r}: (420 | 444, bt601 | bt709, limited | full)")
+    return L.BinYuvFormat(int(chroma), _YUV_MATRIX[matrix], _YUV_RANGE[rng])
+
+
+def yuv_frame_bytes(h, w, chroma):
+    """(bytes of a frame's payload, chroma rows, chroma columns) of an h x w picture."""
+    ch, cw = (h, w) if chroma == 444 else ((h + 1) // 2, (w + 1) // 2)
+    return h * w + 2 * ch * cw, ch, cw
+
+
+def _yuv_planes(payload, h, w, chroma):
+    """Addresses of the Y, U and V planes: of one contiguous uint8 payload, or of a (y, u, v) triple of tensors."""
+    n, ch, cw = yuv_frame_bytes(h, w, chroma)
+    if isinstance(payload, (tuple, list)):
+        if len(payload) != 3:
+            raise ValueError("bin_amd: a YUV payload is one uint8 tensor or a (y, u, v) triple")
+        _need_cuda(*payload)
+        for t, size in zip(payload, (h * w, ch * cw, ch * cw)):
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != size:
+                raise ValueError(f"bin_amd: a plane of a {w}x{h} {chroma} frame is a contiguous uint8 tensor of {size} bytes")
+        return tuple(C.c_void_p(t.data_ptr()) for t in payload)
+    _need_cuda(payload)
+    if payload.dtype != torch.uint8 or payload.dim() != 1 or not payload.is_contiguous() or payload.numel() != n:
+        raise ValueError(f"bin_amd: the payload of a {w}x{h} {chroma} frame is a contiguous uint8 tensor of [{n}] bytes "
+                         f"(got {payload.dtype} {tuple(payload.shape)})")
+    p = payload.data_ptr()
+    return C.c_void_p(p), C.c_void_p(p + h * w), C.c_void_p(p + h * w + ch * cw)
+
+
+def yuv_to_frame(payload_u8, h, w, fmt, pads):
+    """A Y4M frame payload (uint8 [frame_bytes]: the Y, U and V planes; or a (y, u, v) triple of plane tensors) on the device ->
+    padded fp32 [1,3,Hp,Wp] RGB frame, the tensor u8_to_frame gives (include/binyuv.h).  fmt: (chroma, matrix, range)."""
+    f = yuv_format(fmt)
+    if h < 1 or w < 1 or len(pads) != 4 or min(pads) < 0:
+        raise ValueError(f"bin_amd: yuv_to_frame needs a positive size and four non-negative pads (got {h}x{w}, {pads})")
+    y, u, v = _yuv_planes(payload_u8, h, w, fmt[0])
+    l, r, t, b = pads
+    first = payload_u8[0] if isinstance(payload_u8, (tuple, list)) else payload_u8
+    out = torch.empty((1, 3, h + t + b, w + l + r), dtype=torch.float32, device=first.device)
+    with on_device(first):
+        L.check(L.yuvlib().binyuv_to_frame(y, u, v, h, w, C.byref(f), l, r, t, b, _ptr(out), _stream()), "yuv_to_frame")
+    return out
+
+
+def frame_to_yuv(frame, top, left, h, w, fmt, out=None):
+    """fp32 [1,3,Hp,Wp] (or [3,Hp,Wp]) RGB -> the Y4M payload of its crop (uint8 [frame_bytes], into `out` when given; `out` may
+    also be a (y, u, v) triple of plane tensors).  Float all the way: one rounding, so yuv_to_frame -> frame_to_yuv is exact."""
+    f = yuv_format(fmt)
+    _need_cuda(frame)
+    if frame.dim() not in (3, 4) or frame.numel() != 3 * frame.shape[-2] * frame.shape[-1]:
+        raise ValueError(f"bin_amd: frame_to_yuv takes one [1,3,Hp,Wp] frame (got {tuple(frame.shape)})")
+    x = frame.reshape(3, frame.shape[-2], frame.shape[-1]).contiguous().float()
+    hp, wp = x.shape[1], x.shape[2]
+    if h < 1 or w < 1 or top < 0 or left < 0 or top + h > hp or left + w > wp:
+        raise ValueError(f"bin_amd: crop ({top}, {left}, {h}, {w}) leaves the {hp}x{wp} frame")
+    if out is None:
+        out = torch.empty(yuv_frame_bytes(h, w, fmt[0])[0], dtype=torch.uint8, device=x.device)
+    y, u, v = _yuv_planes(out, h, w, fmt[0])
+    with on_device(x):
+        L.check(L.yuvlib().binyuv_from_frame(_ptr(x), hp, wp, top, left, h, w, C.byref(f), y, u, v, _stream()), "frame_to_yuv")
+    return out
+
+
 def pixel_unshuffle(x, r=2):
     """Exact space-to-depth: out[b, c*r*r + i*r + j, y, x] = in[b, c, y*r+i, x*r+j] (reference RDN.py:107-132)."""
     _need_cuda(x)

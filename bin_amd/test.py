@@ -4,6 +4,10 @@ interpolated and deblurred frames against the sharp ground truth) and demo.py (w
     python -m bin_amd.test --netName bin_stage4 --input_path DATA/test_blur --gt_path DATA/test \\
         --output_path OUT --opt bin_amd/options/bin_stage4_adobe240.yml [--time_step 0.5]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m bin_amd.test ... --launcher pytorch
+    DECODER ... -f yuv4mpegpipe - | python -m bin_amd.test --input_video - --output_video - --opt ... | ENCODER ...
+
+With --input_video / --output_video the frames are those of one Y4M stream (bin_amd/video.py) instead of PNG files: same windows,
+same outputs, written in display order at twice the frame rate (run_video below; nothing is scored, one rank).
 
 What the reference does per input frame `index` of a clip (test.py:236-402) and this keeps:
   * the six blurry frames index + [-2..3], clamped to the clip (test.py:257-261, 333);
@@ -20,6 +24,7 @@ combined with one all-reduce at the end."""
 import argparse
 import logging
 import os
+import queue
 import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -42,9 +47,15 @@ METRICS = ("interp_psnr", "interp_ssim", "interp_err", "deblur_psnr", "deblur_ss
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--netName", type=str, default="bin_stage4")
-    p.add_argument("--input_path", type=str, required=True)
+    p.add_argument("--input_path", type=str, default=None, help="folder of clips (folders of PNG frames)")
     p.add_argument("--gt_path", type=str, default=None, help="sharp frames; omit for demo mode (no metrics)")
-    p.add_argument("--output_path", type=str, required=True)
+    p.add_argument("--output_path", type=str, default=None)
+    p.add_argument("--input_video", type=str, default=None, help="a Y4M file, or - for stdin: instead of --input_path / --output_path")
+    p.add_argument("--output_video", type=str, default=None, help="the Y4M file to write at twice the frame rate, or - for stdout")
+    p.add_argument("--yuv_matrix", choices=["auto", "bt601", "bt709"], default="auto",
+                   help="auto: bt709 when W >= 1280 or H > 576, else bt601")
+    p.add_argument("--yuv_range", choices=["auto", "limited", "full"], default="auto",
+                   help="auto: the stream's XCOLORRANGE tag, else limited")
     p.add_argument("--gpu_id", type=str, default=None)
     p.add_argument("--time_step", type=float, default=0.5)
     p.add_argument("--opt", type=str, required=True, help="Path to option YAML file.")
@@ -65,7 +76,27 @@ def parse_args(argv=None):
     p.add_argument("--metrics", choices=["host", "device"], default="host",
                    help="where the scores are computed: host = numpy, as before; device = binhip_image_score on a stream of the "
                    "writer thread, PSNR bit-identical, SSIM always on, plus the *_ssim_sk keys (test.py's skimage SSIM)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.input_video is None and args.output_video is None and (args.input_path is None or args.output_path is None):
+        p.error("the following arguments are required: --input_path, --output_path (or --input_video, --output_video)")
+    check_args(args)
+    return args
+
+
+def check_args(args):
+    """The folder run takes --input_path and --output_path; the video run --input_video and --output_video, and neither a ground
+    truth nor several ranks.  Anything else is refused here: before the options are read or the model is built."""
+    video = args.input_video is not None or args.output_video is not None
+    folder = args.input_path is not None or args.output_path is not None
+    if video and folder:
+        raise ValueError("give either --input_path / --output_path or --input_video / --output_video, not both kinds")
+    if video:
+        if args.input_video is None or args.output_video is None:
+            raise ValueError("--input_video and --output_video go together")
+        if args.gt_path is not None:
+            raise ValueError("--gt_path: scoring a video is not supported (--input_video)")
+        if args.launcher == "pytorch":
+            raise ValueError("--launcher pytorch: a video is not sharded across ranks (--input_video)")
 
 
 def list_windows(input_path):
@@ -155,6 +186,26 @@ class _DeviceScorer:
         sums.add(clip, kind + "_ssim_sk", r["ssim_sk"], tag)
 
 
+class _Uploader:
+    """page-locked uint8 buffer -> device tensor on the upload stream, the compute stream waiting on the event: the launching
+    thread never blocks in a copy.  A buffer goes back through `release` once its upload has finished."""
+
+    def __init__(self, dev, stream, release):
+        self.dev, self.stream, self.release, self.in_flight = dev, stream, release, []
+
+    def __call__(self, buf):
+        with torch.cuda.stream(self.stream):
+            g = buf.to(self.dev, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        torch.cuda.current_stream(self.dev).wait_event(ev)
+        g.record_stream(torch.cuda.current_stream(self.dev))
+        self.in_flight.append((ev, buf))
+        while self.in_flight and self.in_flight[0][0].query():
+            self.release(self.in_flight.pop(0)[1])
+        return g
+
+
 def main(argv=None, stats=None):
     """`stats` (optional dict, filled on rank 0): windows run, wall seconds incl. all IO, net + glue seconds per window —
     what bench.py's `harness` leg reports."""
@@ -180,6 +231,8 @@ def main(argv=None, stats=None):
 
     n_out = round(1 / args.time_step)
     assert n_out == 2, "bin_stage4 interpolates the middle frame (time_step 0.5), as the reference asserts"
+    if args.input_video is not None:
+        return run_video(args, opt, stats)
     result_root = os.path.join(args.output_path, f"{n_out * 30}fps_test_results", opt["name"])
     os.makedirs(result_root, exist_ok=True)
     if rank == 0:
@@ -263,7 +316,6 @@ def main(argv=None, stats=None):
     # then idled for the ~5 ms the host needs to queue the next window (steady state 0.90 of the in-HBM rate).  Now the decoder
     # thread leaves the image in a recycled page-locked buffer and the upload runs on its own stream behind an event.
     upload_stream = torch.cuda.Stream(device=dev)
-    in_flight = []
     if prealloc.ident is not None:                     # (started)
         prealloc.join()
 
@@ -279,19 +331,10 @@ def main(argv=None, stats=None):
         buf.copy_(src)
         return buf
 
-    def upload(buf):
-        """page-locked HWC uint8 image -> device tensor on the upload stream; the compute stream waits on the event."""
-        with torch.cuda.stream(upload_stream):
-            g = buf.to(dev, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        torch.cuda.current_stream(dev).wait_event(ev)
-        g.record_stream(torch.cuda.current_stream(dev))
-        in_flight.append((ev, buf))
-        while in_flight and in_flight[0][0].query():     # finished uploads hand their staging buffer back
-            with stage_lock:
-                stage_pool.append(in_flight.pop(0)[1])
-        return g
+    def release(buf):
+        with stage_lock:
+            stage_pool.append(buf)
+    upload = _Uploader(dev, upload_stream, release)
 
     def want(clip, frames, fid):                       # async decode, at most once per frame
         key = (clip, fid)
@@ -454,6 +497,179 @@ def main(argv=None, stats=None):
         if stats is not None:
             stats.update(windows=n_win, wall=wall, net_s_per_window=timer.avg, stamps=[t - t_all for t in stamps], timeline=timeline,
                          metrics={k: tot[k] for k in METRICS if k in counted})
+    return 0
+
+
+def run_video(args, opt, stats=None):
+    """The folder runner's pipeline over one Y4M stream.  A reader thread fills recycled page-locked payload buffers; each frame is
+    uploaded once on the upload stream behind an event and unpacked by ops.yuv_to_frame on the compute stream, the padded frame
+    cached across the 5-of-6 overlap of consecutive windows; ops.frame_to_yuv packs each output into a device payload, the copy
+    stream moves it to page-locked memory and ONE writer thread writes the frames in the order they were queued, which is display
+    order (harness.video_slots).  The length of a piped stream is not known ahead: window i runs once frame i + 3 or the end of
+    the stream has been read.  Logging goes to stderr and the log file, never to stdout (--output_video -)."""
+    from . import video
+    from .ensemble import SelfEnsemble, parse_group
+    log_root = os.getcwd() if args.output_video == "-" else os.path.dirname(os.path.abspath(args.output_video))
+    os.makedirs(log_root, exist_ok=True)
+    util.setup_logger("base", log_root, "test_video", screen=True, tofile=True)
+    log = logging.getLogger("base")
+    reader = video.Y4MReader(args.input_video)       # (the header is read and checked here: before the model is built)
+    header = reader.header
+    fmt = video.resolve_format(header, args.yuv_matrix, args.yuv_range)
+    h, w, nbytes = header.height, header.width, header.frame_bytes
+    pads = util.pad_sizes(h, w)
+    l, r, t, b = pads
+
+    free_in, filled = queue.Queue(), queue.Queue()
+    for _ in range(12):
+        free_in.put(None)                              # allocated on first use by the reader thread
+
+    def read_frames():                                 # (reader thread) runs ahead of the model's construction, as the decoders do
+        try:
+            while True:
+                buf = free_in.get()
+                if buf is None:
+                    buf = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+                if not reader.readinto(buf.numpy()):
+                    break
+                filled.put(buf)
+            filled.put(None)
+        except BaseException as e:                     # handed to the main thread, which raises it
+            filled.put(e)
+    reader_thread = threading.Thread(target=read_frames, daemon=True)
+    reader_thread.start()
+
+    model = create_model(opt)
+    netG = model.netG
+    netG.eval()
+    dev = next(netG.parameters()).device
+    inner = netG.module if hasattr(netG, "module") else netG
+    reuse = (not args.no_reuse) and getattr(inner, "reuse_schedule", False)
+    ens = SelfEnsemble(netG, args.self_ensemble) if parse_group(args.self_ensemble) else None
+    if ens is not None:
+        log.info("self-ensemble: group %s, M = %d forwards per window", ens.group, ens.M)
+    log.info("In video: %s %dx%d C%s F%d:%d -> %s | YUV: %s %s | model: %s | stage-1 reuse: %s", args.input_video, w, h,
+             header.colorspace or "420", header.rate[0], header.rate[1], args.output_video, fmt[1], fmt[2],
+             opt["path"]["pretrain_model_G"], reuse)
+
+    upload_stream, copy_stream = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    frames_dev, stage1_cache = {}, {}
+    n_read, n_frames = 0, None                         # frames uploaded so far; the stream's length once its end was read
+
+    upload = _Uploader(dev, upload_stream, free_in.put)   # finished uploads hand their buffer back to the reader
+
+    def read_to(i):
+        """Take frames from the reader until frame `i` is on the device or the stream has ended."""
+        nonlocal n_read, n_frames
+        while n_frames is None and n_read <= i:
+            item = filled.get()
+            if item is None:
+                n_frames = n_read
+            elif isinstance(item, BaseException):
+                raise item
+            else:
+                frames_dev[n_read] = ops.yuv_to_frame(upload(item), h, w, fmt, pads)
+                n_read += 1
+
+    out_header = header.doubled()
+    to_write, free_out = queue.Queue(maxsize=10), []
+    write_error = []
+
+    def write_frames():                                # (the ONE writer thread) first in, first out: display order
+        writer = None
+        while True:
+            job = to_write.get()
+            if job is None:
+                break
+            if write_error:
+                continue                               # keep draining, so that the main thread never blocks on a dead writer
+            try:
+                if writer is None:
+                    writer = video.Y4MWriter(args.output_video, out_header)
+                host, n, done = job
+                done.synchronize()
+                for k in range(n):
+                    writer.write(host[k].numpy())
+                free_out.append(host)
+            except BaseException as e:
+                write_error.append(e)
+        if writer is not None and not write_error:
+            writer.close()
+    writer_thread = threading.Thread(target=write_frames, daemon=True)
+    writer_thread.start()
+
+    timer, stamps, group = AverageMeter(), [], []
+    n_written = 0
+
+    def flush():
+        nonlocal n_written
+        if not group:
+            return
+        t0 = time.time()
+        if len(group) == 1:
+            inputs = group[0][1]
+            if ens is not None:
+                Ft_p = ens.window(group[0][2], inputs, slots=OUT_KEYS, reuse=reuse)
+            else:
+                Ft_p = netG(*inputs, stage1_cache=stage1_cache) if reuse else netG(*inputs)
+        else:
+            inputs = [torch.cat([g[1][k] for g in group], 0) for k in range(6)]
+            Ft_p = netG(*inputs) if ens is None else ens(inputs, slots=OUT_KEYS)
+        for j, (slots, _, _) in enumerate(group):
+            outs = torch.empty((3, nbytes), dtype=torch.uint8, device=dev)
+            for k, slot in enumerate(slots):
+                ops.frame_to_yuv(Ft_p[slot][j:j + 1], t, l, h, w, fmt, out=outs[k])
+            ready = torch.cuda.Event()
+            ready.record()
+            host = free_out.pop() if free_out else torch.empty((3, nbytes), dtype=torch.uint8, pin_memory=True)
+            with torch.cuda.stream(copy_stream):
+                copy_stream.wait_event(ready)
+                host[:len(slots)].copy_(outs[:len(slots)], non_blocking=True)
+                outs.record_stream(copy_stream)
+                done = torch.cuda.Event()
+                done.record()
+            to_write.put((host, len(slots), done))
+            n_written += len(slots)
+        if write_error:
+            raise write_error[0]
+        timer.update((time.time() - t0) / len(group), len(group))
+        stamps.extend([time.time()] * len(group))
+        group.clear()
+
+    t_all = time.time()
+    index = 0
+    try:
+        with torch.no_grad():
+            while True:
+                read_to(index + 3)
+                if n_frames is not None and index > n_frames - 2:
+                    break
+                known = n_frames if n_frames is not None else index + 4      # clamping only bites once the end is known
+                ids = harness.window_frame_ids(index, known)
+                slots = harness.video_slots(index, n_frames - 1 if n_frames is not None else index + 2)
+                group.append((slots, [frames_dev[f] for f in ids], ids))
+                for fid in [f for f in frames_dev if f < min(ids)]:
+                    del frames_dev[fid]
+                if len(group) >= args.batch:
+                    flush()
+                index += 1
+            flush()
+            torch.cuda.current_stream(dev).synchronize()
+    finally:
+        to_write.put(None)
+        writer_thread.join()
+        reader.close()
+    if write_error:
+        raise write_error[0]
+    if n_frames < 2:
+        raise ValueError(f"{args.input_video}: a video needs at least 2 frames to interpolate (got {n_frames})")
+    torch.cuda.synchronize()
+    ops.check_status(dev)                 # a frame that left the fp16 storage range is an error, not a result
+    wall = time.time() - t_all
+    log.info("frames in: %d  out: %d  windows: %d  wall: %.2f s  -> %.2f interpolated frames/s (IO included); net+glue per window "
+             "%.4f s", n_frames, n_written, index, wall, index / max(wall, 1e-9), timer.avg)
+    if stats is not None:
+        stats.update(windows=index, wall=wall, net_s_per_window=timer.avg, stamps=[s - t_all for s in stamps], frames_out=n_written)
     return 0
 
 
