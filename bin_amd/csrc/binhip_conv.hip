@@ -12,8 +12,8 @@
 // (buffer_load ... lds, 16 B/lane, zero-fill outside the image = the conv's zero padding) the
 // (TH+k-1) x (32+k-1) x 16-channel input patch and the k*k x COUTB x 16 weight slab into LDS,
 // double-buffered, then every wave runs k*k*MT*R MFMAs straight out of LDS with ds_read_b128: the
-// patch image is [channel half][pixel][16 B] (a 16-lane read group = 256 contiguous bytes, one per-lane
-// base + immediates), the weight slab keeps 16-byte slots XOR-swizzled by (row>>3)&1 from the relayout.
+// patch image and weight-slab swizzle are the ones binhip_conv_common.h defines (patch_offsets, weight_lane_off), shared with
+// the plane-split and fused kernels.
 // Precision: NT=1 -> one fp16 product; NT=3 -> hi/lo split, Ah*Bh + Al*Bh + Ah*Bl (fp32 class).
 #include "binhip_conv_common.h"
 #include <vector>
@@ -44,17 +44,12 @@ struct ConvCfg {
     static_assert(NBUF <= 2 || (NBUF - 2) * PS <= 63, "vmcnt immediate range");
 };
 
-__device__ __forceinline__ half8 lds_ld8(const char* p) { return *reinterpret_cast<const half8*>(p); }
-__device__ __forceinline__ floatx16 mfma16(half8 a, half8 b, floatx16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
 // Issue the LDS-DMA of K-stage `st` (KC chunks x NPL planes: input patch + weight slab) into buffer `buf`.
 // Every wave issues exactly NPJ + NWJ instructions per (plane, chunk) so that s_waitcnt vmcnt(N) can count
 // whole stages; surplus lanes read out of range (zero fill, no memory traffic) into a dummy 1-KiB LDS area.
 template <class C, int KS, int KC>
-__device__ __forceinline__ void issue_stage(const ConvKArgs& a, char* smem, int st, int buf, int wave, int lane, int z,
-                                            const unsigned* voff, long long plane_elems, unsigned plane_bytes) {
+__device__ __forceinline__ void issue_stage(const ConvKArgs& a, char* smem, int st, int buf, int wave, int lane, const ConvTile& t,
+                                            const unsigned* voff) {
     char* bbase = smem + buf * C::BUF_BYTES;
     char* dummy = smem + (C::LDS_BYTES - 1024);
     const int nchunks = a.nchunks;
@@ -64,12 +59,7 @@ __device__ __forceinline__ void issue_stage(const ConvKArgs& a, char* smem, int 
         for (int kc = 0; kc < KC; ++kc) {
             const int c = st * KC + kc;
             if (c < nchunks) {
-                const _Float16* xb = pl ? a.x_lo : a.x_hi;
-                const long long coff = (a.cpg > 0)
-                    ? (long long)(c / a.cpg) * a.group_stride + (long long)(c % a.cpg) * plane_elems
-                    : (long long)c * plane_elems;
-                __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                    (void*)(xb + coff), 0, plane_bytes, 0x00020000);
+                __amdgpu_buffer_rsrc_t rs = patch_plane_grouped(a, c, pl, t);
                 char* lds = bbase + pl * C::PLANE_BYTES + kc * C::CHUNK_BYTES;
 #pragma unroll
                 for (int j = 0; j < C::NPJ; ++j) {
@@ -79,7 +69,7 @@ __device__ __forceinline__ void issue_stage(const ConvKArgs& a, char* smem, int 
                                                              real ? voff[j] : 0x80000000u, 0, 0, 0);
                 }
                 const _Float16* wb = (pl ? a.w_lo : a.w_hi) +
-                                     ((long long)z * nchunks + c) * (KS * KS * C::COUTB * 16);
+                                     ((long long)t.z * nchunks + c) * (KS * KS * C::COUTB * 16);
                 __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(
                     (void*)wb, 0, KS * KS * C::COUTB * 32, 0x00020000);
 #pragma unroll
@@ -97,24 +87,24 @@ __device__ __forceinline__ void issue_stage(const ConvKArgs& a, char* smem, int 
 
 // Operand fragments of one (chunk, dx) step: R+KS-1 patch rows (B) and the KS x MT weight tiles of this tap column (A).
 template <class C, int KS, int MT, int R, int NT>
-__device__ __forceinline__ void load_frags(const char* bbase, int kc, int dx, int wm, int a_lane_off, int b_lane_p, int kg,
+__device__ __forceinline__ void load_frags(const char* bbase, int kc, int dx, int wm, int a_lane_off, int b_lane_off,
                                            half8 (&Bh)[R + KS - 1], half8 (&Bl)[R + KS - 1],
                                            half8 (&Ah)[KS][MT], half8 (&Al)[KS][MT]) {
     const char* pb = bbase + kc * C::CHUNK_BYTES;
     const char* wb = pb + C::PP * 1024 + wm * (MT * 32 * 32);
 #pragma unroll
     for (int rr = 0; rr < R + KS - 1; ++rr) {
-        const int off = (kg * (C::PH * C::PW) + b_lane_p) * 16 + (rr * C::PW + dx) * 16;
-        Bh[rr] = lds_ld8(pb + off);
-        if constexpr (NT == 3) Bl[rr] = lds_ld8(pb + C::PLANE_BYTES + off);
+        const int off = b_lane_off + (rr * C::PW + dx) * 16;
+        Bh[rr] = ld8(pb + off);
+        if constexpr (NT == 3) Bl[rr] = ld8(pb + C::PLANE_BYTES + off);
     }
 #pragma unroll
     for (int dy = 0; dy < KS; ++dy)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int off = ((dy * KS + dx) * C::COUTB + mt * 32) * 32 + a_lane_off;
-            Ah[dy][mt] = lds_ld8(wb + off);
-            if constexpr (NT == 3) Al[dy][mt] = lds_ld8(wb + C::PLANE_BYTES + off);
+            Ah[dy][mt] = ld8(wb + off);
+            if constexpr (NT == 3) Al[dy][mt] = ld8(wb + C::PLANE_BYTES + off);
         }
 }
 
@@ -124,7 +114,7 @@ __device__ __forceinline__ void load_frags(const char* bbase, int kc, int dx, in
 // (it assumes 8 waves/SIMD because the LDS size is dynamic) and the loop degenerates into read -> wait -> MFMA.
 template <class C, int KS, int MT, int R, int KC, int NT>
 __device__ __forceinline__ void compute_stage(const char* smem, int st, int buf, int nchunks, int wm,
-                                              int a_lane_off, int b_lane_p, int kg, floatx16 (&acc)[MT][R]) {
+                                              int a_lane_off, int b_lane_off, floatx16 (&acc)[MT][R]) {
     const char* bbase = smem + buf * C::BUF_BYTES;
     constexpr int NSTEP = KC * KS;
     // register estimate: accumulators + two fragment sets; fall back to one set (no prefetch) when it would spill
@@ -138,16 +128,16 @@ __device__ __forceinline__ void compute_stage(const char* smem, int st, int buf,
         nvalid = (left < KC ? left : KC) * KS;
     }
     if constexpr (PIPE)
-        load_frags<C, KS, MT, R, NT>(bbase, 0, 0, wm, a_lane_off, b_lane_p, kg, Bh[0], Bl[0], Ah[0], Al[0]);
+        load_frags<C, KS, MT, R, NT>(bbase, 0, 0, wm, a_lane_off, b_lane_off, Bh[0], Bl[0], Ah[0], Al[0]);
 #pragma unroll
     for (int s = 0; s < NSTEP; ++s) {
         if (KC == 1 || s < nvalid) {
             if constexpr (PIPE) {
                 if (s + 1 < NSTEP && (KC == 1 || s + 1 < nvalid))
-                    load_frags<C, KS, MT, R, NT>(bbase, (s + 1) / KS, (s + 1) % KS, wm, a_lane_off, b_lane_p, kg,
+                    load_frags<C, KS, MT, R, NT>(bbase, (s + 1) / KS, (s + 1) % KS, wm, a_lane_off, b_lane_off,
                                                  Bh[(s + 1) & 1], Bl[(s + 1) & 1], Ah[(s + 1) & 1], Al[(s + 1) & 1]);
             } else {
-                load_frags<C, KS, MT, R, NT>(bbase, s / KS, s % KS, wm, a_lane_off, b_lane_p, kg, Bh[0], Bl[0], Ah[0], Al[0]);
+                load_frags<C, KS, MT, R, NT>(bbase, s / KS, s % KS, wm, a_lane_off, b_lane_off, Bh[0], Bl[0], Ah[0], Al[0]);
             }
             if constexpr (PIPE) __builtin_amdgcn_sched_barrier(0);   // (single-set kernels: leave the interleaving to hipcc)
 #pragma unroll
@@ -157,10 +147,10 @@ __device__ __forceinline__ void compute_stage(const char* smem, int st, int buf,
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         if constexpr (NT == 3) {
-                            acc[mt][r] = mfma16(Al[s & (NSET - 1)][dy][mt], Bh[s & (NSET - 1)][r + dy], acc[mt][r]);
-                            acc[mt][r] = mfma16(Ah[s & (NSET - 1)][dy][mt], Bl[s & (NSET - 1)][r + dy], acc[mt][r]);
+                            acc[mt][r] = mfma_32x32x16(Al[s & (NSET - 1)][dy][mt], Bh[s & (NSET - 1)][r + dy], acc[mt][r]);
+                            acc[mt][r] = mfma_32x32x16(Ah[s & (NSET - 1)][dy][mt], Bl[s & (NSET - 1)][r + dy], acc[mt][r]);
                         }
-                        acc[mt][r] = mfma16(Ah[s & (NSET - 1)][dy][mt], Bh[s & (NSET - 1)][r + dy], acc[mt][r]);
+                        acc[mt][r] = mfma_32x32x16(Ah[s & (NSET - 1)][dy][mt], Bh[s & (NSET - 1)][r + dy], acc[mt][r]);
                     }
             if constexpr (PIPE) __builtin_amdgcn_sched_barrier(0);
         }
@@ -185,40 +175,9 @@ conv_mfma_kernel(const ConvKArgs a, const float* __restrict__ bias) {
     const int n = lane & 31;     // pixel column (B/N index) and cout row (A/M index) of this lane
     const int kg = lane >> 5;    // which 8-channel half of the 16-channel chunk
 
-    // 1-D grid of tiles x output-channel blocks, block index fastest: the workgroups that share an input patch are
-    // neighbours on ONE XCD after the banding and fetch it into that L2 once (as a (tiles, blocks) grid every block was a
-    // separate sweep: GFF.0's backward-data read its 214 MB gradient six times from HBM, profiles/r02_train_kernel_stats.md)
-    int bid = blockIdx.x;
-    if (a.xcd_remap) bid = xcd_band(bid, gridDim.x);
-    const int z = bid % a.ncol;
-    bid /= a.ncol;
-    const int tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    const int tx0 = tx * 32, ty0 = ty * C::TH;
-    const int H = a.H, W = a.W;
-    const long long plane_elems = (long long)a.N * H * W * 16;
-    const unsigned plane_bytes = (unsigned)(plane_elems * 2);
-
-    // ---- per-lane source offsets of the patch DMA pieces (stage independent) -------------------
+    const ConvTile t = tile_decode<C::TH>(a, a.ncol);
     unsigned voff[C::NPJ];
-#pragma unroll
-    for (int j = 0; j < C::NPJ; ++j) {
-        const int i = wave + C::NW * j;
-        const int q = i * 64 + lane;          // 16-byte slot index in the LDS patch image
-        // image = [channel half cg][patch pixel p][16 B]: a 16-lane ds_read_b128 group reads 16 consecutive pixels of
-        // one half = 256 contiguous bytes (every bank once), and a fragment address is ONE per-lane base + an
-        // immediate (row, dx) offset
-        const int cg = q >= C::PH * C::PW ? 1 : 0;
-        const int p = q - cg * (C::PH * C::PW);
-        const int py = p / C::PW;
-        const int px = p - py * C::PW;
-        const int gy = ty0 + py - C::PAD;
-        const int gx = tx0 + px - C::PAD;
-        const bool ok = (p < C::PH * C::PW) && (gy >= 0) && (gy < H) && (gx >= 0) && (gx < W);
-        voff[j] = ok ? (unsigned)((((long long)img * H + gy) * W + gx) * 32 + cg * 16) : 0x80000000u;
-    }
+    patch_offsets<C, C::PAD>(voff, t, a.H, a.W, wave, lane);
 
     floatx16 acc[MT][R];
 #pragma unroll
@@ -230,14 +189,14 @@ conv_mfma_kernel(const ConvKArgs a, const float* __restrict__ bias) {
 
     const int nchunks = a.nchunks;
     const int nst = (nchunks + KC - 1) / KC;
-    const int a_lane_off = n * 32 + ((kg ^ ((n >> 3) & 1)) << 4);
-    const int b_lane_p = wn * R * C::PW + n;
+    const int a_lane_off = weight_lane_off(n, kg);
+    const int b_lane_off = patch_lane_off<C>(n, kg, wn * R);
 
     // ring of NBUF stage buffers; up to NBUF-1 stages of DMA in flight, counted waits, one barrier per stage
     const int nfull = nchunks / KC;       // stages that issue the full C::PS instructions per wave
 #pragma unroll
     for (int s0 = 0; s0 < NBUF - 1; ++s0)
-        if (s0 < nst) issue_stage<C, KS, KC>(a, smem, s0, s0, wave, lane, z, voff, plane_elems, plane_bytes);
+        if (s0 < nst) issue_stage<C, KS, KC>(a, smem, s0, s0, wave, lane, t, voff);
     int cur = 0, nxt = NBUF - 1;
     for (int st = 0; st < nst; ++st) {
         // younger full-size stages still allowed in flight while stage st must have landed
@@ -249,15 +208,15 @@ conv_mfma_kernel(const ConvKArgs a, const float* __restrict__ bias) {
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         if (st + NBUF - 1 < nst)
-            issue_stage<C, KS, KC>(a, smem, st + NBUF - 1, nxt, wave, lane, z, voff, plane_elems, plane_bytes);
-        compute_stage<C, KS, MT, R, KC, NT>(smem, st, cur, nchunks, wm, a_lane_off, b_lane_p, kg, acc);
+            issue_stage<C, KS, KC>(a, smem, st + NBUF - 1, nxt, wave, lane, t, voff);
+        compute_stage<C, KS, MT, R, KC, NT>(smem, st, cur, nchunks, wm, a_lane_off, b_lane_off, acc);
         cur = (cur + 1 == NBUF) ? 0 : cur + 1;
         nxt = (nxt + 1 == NBUF) ? 0 : nxt + 1;
     }
 
     // ---- epilogue (binhip_conv_common.h) ----------------------------------------------------------
-    conv_epilogue<MT, R, NT, EPI, XTRA>(a, bias, acc, img, ty0 + wn * R, tx0, z * C::COUTB + wm * MT * 32, z == 0 && wm == 0, n, kg,
-                                  plane_elems);
+    conv_epilogue<MT, R, NT, EPI, XTRA>(a, bias, acc, t.img, t.ty0 + wn * R, t.tx0, t.z * C::COUTB + wm * MT * 32, t.z == 0 && wm == 0,
+                                        n, kg, t.plane_elems);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -267,10 +226,7 @@ static int launch_cfg_x(const ConvKArgs& ka, int cout_pad, hipStream_t s) {
     static std::atomic<unsigned long long> lds_set{0};
     if (int rc = bh_set_max_lds(&conv_mfma_kernel<KS, MT, WM, R, WN, KC, NT, NBUF, EPI, XTRA>, C::LDS_BYTES, lds_set)) return rc;
     ConvKArgs a = ka;
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + C::TH - 1) / C::TH;
-    a.ncol = cout_pad / C::COUTB;
-    dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ncol));
+    const dim3 grid(set_tiles<C>(a, cout_pad / C::COUTB));
     conv_mfma_kernel<KS, MT, WM, R, WN, KC, NT, NBUF, EPI, XTRA><<<grid, dim3(64 * C::NW), C::LDS_BYTES, s>>>(a, a.bias);
     BH_CHECK_LAUNCH();
     return 0;
@@ -354,8 +310,6 @@ int bh_prepare_conv(const BhConvCall& c, ConvKArgs* out) {
     a.och_limit = (d.epilogue == BINHIP_EPI_PLANES) ? (d.cout + 15) / 16 : (1 << 30);
     a.tiles_x = a.tiles_y = 0;
     a.ncol = 1;
-    a.xcd_remap = 1;
-    a.dbg = 0;
     a.wt = 0;
     a.prog_prio = 0;
 #if BINHIP_TIMELINE

@@ -1,8 +1,11 @@
-// Shared device-side pieces of the convolution kernels (binhip_conv.hip, binhip_conv_x3.hip): kernel argument block,
-// LDS-DMA / store helpers and the epilogue (bias, residuals, ReLU, ReLU-mask, fp16 hi/lo split, 16-byte plane stores,
-// PixelShuffle scatter, fp32 NCHW final output).  Internal — not part of the C ABI.
+// Shared device-side pieces of the convolution kernels (binhip_conv.hip, binhip_conv_x3.hip, binhip_fused.hip, binhip_fused_x3.hip):
+// kernel argument block, the tile front end (workgroup id -> tile, tile -> LDS-DMA source offsets of the patch image, patch-plane
+// buffer resources, operand lane offsets: the ONE definition of the tile, the patch image and the DMA source), LDS-DMA / store helpers
+// and the epilogue (bias, residuals, ReLU, ReLU-mask, fp16 hi/lo split, 16-byte plane stores, PixelShuffle scatter, fp32 NCHW final
+// output).  Internal — not part of the C ABI.
 #pragma once
 #include "binhip_internal.h"
+#include <type_traits>
 #ifndef BINHIP_TIMELINE
 #define BINHIP_TIMELINE 0     // side builds only: per-workgroup time stamps (BhTl below)
 #endif
@@ -45,10 +48,8 @@ struct ConvKArgs {
     int tiles_x, tiles_y;
     int ncol;                 // plane-split kernel: output columns of 32 rows sharing a tile (1-D grid, column fastest)
     int relu, has_res, nimg, cout;
-    int xcd_remap;            // always 1
     int wt;                   // write-through (sc1) output stores
     int och_limit;            // output chunks that exist at the destination (rows beyond are padding: not stored)
-    int dbg;                  // unread (0); removing it would move every later offset of the block
     int res_chunks;           // residual r applies to output chunks < res_chunks
     int mask_from;            // mask applies to output chunks >= mask_from (when m_hi != null)
     int y_cpg;                // output chunk grouping (<=0: one group)
@@ -154,6 +155,93 @@ __device__ __forceinline__ int xcd_band(int bid, int nwg) {
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
+
+// ---- the tile front end ----------------------------------------------------------------------------
+// Every forward / backward-data kernel owns tiles of TH rows x 32 columns of one image, on a 1-D grid of tiles x output columns,
+// column fastest: after the XCD banding the `ncol` workgroups that share one input patch are neighbours on ONE XCD and fetch it into
+// that L2 once (as a (tiles, columns) grid every column was a separate sweep: UPNet.0's 8 columns fetched 884 MB for 99 MB of input,
+// GFF.0's backward-data read its 214 MB gradient six times from HBM, profiles/r02_train_kernel_stats.md).
+struct ConvTile {
+    int z, tx, ty, img;       // output column, tile coordinates, image
+    int tx0, ty0;             // first pixel column / row of the tile
+    long long plane_elems;    // one 16-channel chunk plane [N][H][W][16], elements
+    unsigned plane_bytes;
+};
+// tile index t (x fastest, then y, then image) of output column z; A = ConvKArgs or TailKArgs
+template <int TH, class A>
+__device__ __forceinline__ ConvTile tile_at(const A& a, int t, int z) {
+    ConvTile o;
+    o.z = z;
+    o.tx = t % a.tiles_x;
+    t /= a.tiles_x;
+    o.ty = t % a.tiles_y;
+    o.img = t / a.tiles_y;
+    o.tx0 = o.tx * 32;
+    o.ty0 = o.ty * TH;
+    o.plane_elems = (long long)a.N * a.H * a.W * 16;
+    o.plane_bytes = (unsigned)(o.plane_elems * 2);
+    return o;
+}
+// blockIdx.x -> XCD band -> (z, tile); ncol = 1: kernels without output columns
+template <int TH, class A>
+__device__ __forceinline__ ConvTile tile_decode(const A& a, int ncol) {
+    const int bid = xcd_band(blockIdx.x, gridDim.x);
+    return tile_at<TH>(a, bid / ncol, bid % ncol);
+}
+// host side: tile counts (and, in ConvKArgs, the column count) of a launch; returns its grid size
+template <class C, class A>
+inline unsigned set_tiles(A& a, int ncol = 1) {
+    a.tiles_x = (a.W + 31) / 32;
+    a.tiles_y = (a.H + C::TH - 1) / C::TH;
+    if constexpr (std::is_same<A, ConvKArgs>::value) a.ncol = ncol;
+    return (unsigned)(a.tiles_x * a.tiles_y * a.N * ncol);
+}
+
+// Per-lane source offsets of the patch DMA pieces (stage independent): wave w issues the 1-KiB pieces w, w + NW, ... and lane l of
+// piece i fills 16-byte slot q = 64 i + l of the LDS patch image = [channel half cg][patch pixel p][16 B], PH x PW pixels around the
+// tile with PAD rows / columns of halo.  A 16-lane ds_read_b128 group then reads 16 consecutive pixels of one half = 256 contiguous
+// bytes (every bank once), and a fragment address is ONE per-lane base + an immediate (row, dx) offset.  Slots outside the image get
+// the out-of-range offset: the DMA zero-fills them (= the convolution's zero padding) without memory traffic.
+// (rdb_tail_kernel in binhip_fused.hip stages a DIFFERENT image — pixel-major, the half swizzled by (p >> 3) & 1 — and keeps its own
+//  offset loop; this helper is not meant to cover both.)
+template <class C, int PAD>
+__device__ __forceinline__ void patch_offsets(unsigned (&voff)[C::NPJ], const ConvTile& t, int H, int W, int wave, int lane) {
+#pragma unroll
+    for (int j = 0; j < C::NPJ; ++j) {
+        const int i = wave + C::NW * j;
+        const int q = i * 64 + lane;
+        const int cg = q >= C::PH * C::PW ? 1 : 0;
+        const int p = q - cg * (C::PH * C::PW);
+        const int py = p / C::PW;
+        const int px = p - py * C::PW;
+        const int gy = t.ty0 + py - PAD;
+        const int gx = t.tx0 + px - PAD;
+        const bool ok = (p < C::PH * C::PW) && (gy >= 0) && (gy < H) && (gx >= 0) && (gx < W);
+        voff[j] = ok ? (unsigned)((((long long)t.img * H + gy) * W + gx) * 32 + cg * 16) : 0x80000000u;
+    }
+}
+
+// buffer resource of precision plane `pl` (0 hi, 1 lo) of input chunk c: the DMA source of one patch plane
+template <class A>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t patch_plane(const A& a, int c, int pl, const ConvTile& t) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)((pl ? a.x_lo : a.x_hi) + (long long)c * t.plane_elems), 0, t.plane_bytes, 0x00020000);
+}
+// the same for an input whose chunks come in groups of a.cpg planes, a.group_stride elements apart (a.cpg <= 0: one group)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t patch_plane_grouped(const ConvKArgs& a, int c, int pl, const ConvTile& t) {
+    const long long coff = (a.cpg > 0) ? (long long)(c / a.cpg) * a.group_stride + (long long)(c % a.cpg) * t.plane_elems
+                                       : (long long)c * t.plane_elems;
+    return __builtin_amdgcn_make_buffer_rsrc((void*)((pl ? a.x_lo : a.x_hi) + coff), 0, t.plane_bytes, 0x00020000);
+}
+
+__device__ __forceinline__ half8 ld8(const char* p) { return *reinterpret_cast<const half8*>(p); }
+__device__ __forceinline__ floatx16 mfma_32x32x16(half8 a, half8 b, floatx16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+// A fragment of lane (n, kg): row n of a 32-row x 32-byte weight tile, its 16-byte slots XOR-swizzled by (row >> 3) & 1 (relayout)
+__device__ __forceinline__ int weight_lane_off(int n, int kg) { return n * 32 + ((kg ^ ((n >> 3) & 1)) << 4); }
+// B fragment of lane (n, kg) in the patch image above: channel half kg, patch row `row`, column n
+template <class C>
+__device__ __forceinline__ int patch_lane_off(int n, int kg, int row) { return (kg * (C::PH * C::PW) + row * C::PW + n) * 16; }
 
 // ---- epilogue ---------------------------------------------------------------------------------------
 // acc[mt][r][4g+j] = D[cout = 8g + 4*kg + j][pixel = n]  (32x32 MFMA C/D layout): a lane holds 4 consecutive

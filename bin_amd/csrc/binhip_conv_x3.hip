@@ -1,8 +1,9 @@
 // binhip_conv_x3.hip — the fp32-class (hi/lo split, three MFMA products) 3x3 / Cout-block-32 convolution with
 // PLANE-SPLIT K-stages, sized so that TWO workgroups share a CU.
 //
-// Same math and data layouts as conv_mfma_kernel<..., NT = 3, ...> (binhip_conv.hip; reference RDN.py:141 RDB_Conv,
-// :207 UPNet.2 and the gather-form dense-block backward-data convs of the same shape), different pipeline.  The
+// Same math as conv_mfma_kernel<..., NT = 3, ...> (binhip_conv.hip; reference RDN.py:141 RDB_Conv, :207 UPNet.2 and the
+// gather-form dense-block backward-data convs of the same shape) on the tile, patch image and weight swizzle that
+// binhip_conv_common.h defines for all of them, different pipeline.  The
 // generic kernel stages BOTH precision planes of a 16-channel chunk per K-stage (patch hi+lo 40 KB, weights hi+lo
 // 18 KB, double-buffered = 117 KB) and holds two full fragment sets (157 VGPRs): one 8-wave workgroup per CU, so a
 // launch of 504 tiles runs as two rounds whose DMA prologues and store epilogues overlap with nothing, and kernels
@@ -45,11 +46,8 @@ struct X3Cfg {
 
 template <class C>
 __device__ __forceinline__ void x3_issue_patch(const ConvKArgs& a, char* smem, int c, int pl, int buf, int wave,
-                                               const unsigned* voff, long long plane_elems, unsigned plane_bytes) {
-    const _Float16* xb = pl ? a.x_lo : a.x_hi;
-    const long long coff = (a.cpg > 0) ? (long long)(c / a.cpg) * a.group_stride + (long long)(c % a.cpg) * plane_elems
-                                       : (long long)c * plane_elems;
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xb + coff), 0, plane_bytes, 0x00020000);
+                                               const unsigned* voff, const ConvTile& t) {
+    __amdgpu_buffer_rsrc_t rs = patch_plane_grouped(a, c, pl, t);
     char* lds = smem + buf * C::PATCH_BYTES;
     // every sub-stage is waited for with vmcnt(0), so waves need not issue equal instruction counts: pieces beyond the
     // image are simply skipped (wave-uniform branch)
@@ -79,11 +77,6 @@ __device__ __forceinline__ void x3_issue_weights(const ConvKArgs& a, char* smem,
     }
 }
 
-__device__ __forceinline__ half8 x3_ld8(const char* p) { return *reinterpret_cast<const half8*>(p); }
-__device__ __forceinline__ floatx16 x3_mfma(half8 a, half8 b, floatx16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
 // One sub-stage out of LDS.  HI: both weight planes against the hi patch (2 products); !HI: hi weights against the lo
 // patch.  Tap order dx-major: the R+KS-1 patch-row fragments of a tap column are fetched once and serve its KS taps;
 // weight fragments are fetched one tap ahead, the next column's patch rows at the column's first tap.
@@ -94,13 +87,13 @@ __device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a
     half8 Ah[2], Al[2];
     auto load_b = [&](int dx, half8 (&dst)[R + KS - 1]) {
 #pragma unroll
-        for (int rr = 0; rr < R + KS - 1; ++rr) dst[rr] = x3_ld8(pb + b_lane_off + (rr * C::PW + dx) * 16);
+        for (int rr = 0; rr < R + KS - 1; ++rr) dst[rr] = ld8(pb + b_lane_off + (rr * C::PW + dx) * 16);
     };
     auto load_a = [&](int s, half8& h, half8& l) {
         const int dx = s / KS, dy = s % KS;
         const int off = ((dy * KS + dx) * 32) * 32 + a_lane_off;
-        h = x3_ld8(wb + off);
-        if constexpr (HI) l = x3_ld8(wb + C::WP * 1024 + off);
+        h = ld8(wb + off);
+        if constexpr (HI) l = ld8(wb + C::WP * 1024 + off);
     };
     load_b(0, B[0]);
     load_a(0, Ah[0], Al[0]);
@@ -113,11 +106,11 @@ __device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a
         if constexpr (HI) {
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                acc[r] = x3_mfma(Al[s & 1], B[dx & 1][r + dy], acc[r]);
+                acc[r] = mfma_32x32x16(Al[s & 1], B[dx & 1][r + dy], acc[r]);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            acc[r] = x3_mfma(Ah[s & 1], B[dx & 1][r + dy], acc[r]);
+            acc[r] = mfma_32x32x16(Ah[s & 1], B[dx & 1][r + dy], acc[r]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -137,20 +130,20 @@ __device__ __forceinline__ void x3_compute_pair(const char* pb, const char* wb, 
     const int a_pair = n * 32 + s16 + kg * (KS * 1024);                // half 0 (slot s) of tap (dy + kg, dx)
     const int a_plain = n * 32 + ((kg << 4) ^ s16);                    // half kg of tap (KS - 1, dx)
     const int b_pair = ((wave * R + kg) * C::PW + n) * 16;             // channel half 0, row + kg
-    const int b_plain = (kg * (C::PH * C::PW) + wave * R * C::PW + n) * 16;
+    const int b_plain = patch_lane_off<C>(n, kg, wave * R);
     half8 Bp[2][R + KS - 3], Bl[2][R];
     half8 Ah[2], Al[2];
     auto load_b = [&](int dx, half8 (&bp)[R + KS - 3], half8 (&bl)[R]) {
 #pragma unroll
-        for (int rr = 0; rr < R + KS - 3; ++rr) bp[rr] = x3_ld8(pb + b_pair + (rr * C::PW + dx) * 16);
+        for (int rr = 0; rr < R + KS - 3; ++rr) bp[rr] = ld8(pb + b_pair + (rr * C::PW + dx) * 16);
 #pragma unroll
-        for (int r = 0; r < R; ++r) bl[r] = x3_ld8(pb + b_plain + ((r + KS - 1) * C::PW + dx) * 16);
+        for (int r = 0; r < R; ++r) bl[r] = ld8(pb + b_plain + ((r + KS - 1) * C::PW + dx) * 16);
     };
     auto load_a = [&](int s, half8& h, half8& l) {                     // step s = dx * (NP + 1) + j ; j < NP: pair (2j, 2j + 1), j == NP: plain
         const int dx = s / (NP + 1), j = s % (NP + 1);
         const int off = (j < NP) ? ((2 * j) * KS + dx) * 1024 + a_pair : ((KS - 1) * KS + dx) * 1024 + a_plain;
-        h = x3_ld8(wb + off);
-        if constexpr (HI) l = x3_ld8(wb + C::WP * 1024 + off);
+        h = ld8(wb + off);
+        if constexpr (HI) l = ld8(wb + C::WP * 1024 + off);
     };
     constexpr int NS = KS * (NP + 1);
     load_b(0, Bp[0], Bl[0]);
@@ -164,8 +157,8 @@ __device__ __forceinline__ void x3_compute_pair(const char* pb, const char* wb, 
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const half8 b = (j < NP) ? Bp[dx & 1][r + 2 * j] : Bl[dx & 1][r];
-            if constexpr (HI) acc[r] = x3_mfma(Al[s & 1], b, acc[r]);
-            acc[r] = x3_mfma(Ah[s & 1], b, acc[r]);
+            if constexpr (HI) acc[r] = mfma_32x32x16(Al[s & 1], b, acc[r]);
+            acc[r] = mfma_32x32x16(Ah[s & 1], b, acc[r]);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -185,8 +178,8 @@ constexpr unsigned RDB3_SPIN_LIMIT = 1u << 22;
 // One output tile (TH x 32 pixels, 32 output channels of column z) from prologue DMA to epilogue stores.  Every wave of
 // the workgroup calls it with the same arguments; LDS must be free of readers on entry.
 template <int KS, int R, int WN, int EPI, bool XTRA, bool GATED = false>
-__device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restrict__ bias, char* smem, int img, int ty, int tx,
-                                        int z, const X3Gate gate = X3Gate{nullptr, 0u, 1 << 30, nullptr}) {
+__device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restrict__ bias, char* smem, const ConvTile& t,
+                                        const X3Gate gate = X3Gate{nullptr, 0u, 1 << 30, nullptr}) {
     using C = X3Cfg<KS, R, WN>;
     BH_TL_DECL;
     BH_TL_BEGIN();
@@ -195,26 +188,9 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 31;     // pixel column (B/N index) and cout row (A/M index) of this lane
     const int kg = lane >> 5;    // which 8-channel half of the 16-channel chunk
-    const int tx0 = tx * 32, ty0 = ty * C::TH;
-    const int H = a.H, W = a.W;
-    const long long plane_elems = (long long)a.N * H * W * 16;
-    const unsigned plane_bytes = (unsigned)(plane_elems * 2);
-
-    // per-lane source offsets of the patch DMA pieces (stage independent); LDS image = [channel half][patch pixel][16 B]
+    const int img = t.img, ty = t.ty, tx = t.tx, z = t.z;
     unsigned voff[C::NPJ];
-#pragma unroll
-    for (int j = 0; j < C::NPJ; ++j) {
-        const int i = wave + C::NW * j;
-        const int q = i * 64 + lane;
-        const int cg = q >= C::PH * C::PW ? 1 : 0;
-        const int p = q - cg * (C::PH * C::PW);
-        const int py = p / C::PW;
-        const int px = p - py * C::PW;
-        const int gy = ty0 + py - C::PAD;
-        const int gx = tx0 + px - C::PAD;
-        const bool ok = (p < C::PH * C::PW) && (gy >= 0) && (gy < H) && (gx >= 0) && (gx < W);
-        voff[j] = ok ? (unsigned)((((long long)img * H + gy) * W + gx) * 32 + cg * 16) : 0x80000000u;
-    }
+    patch_offsets<C, C::PAD>(voff, t, a.H, a.W, wave, lane);
 
     floatx16 acc[1][R];
 #pragma unroll
@@ -223,8 +199,8 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
         for (int e = 0; e < 16; ++e) acc[0][r][e] = 0.f;
 
     const int nchunks = a.nchunks;
-    const int a_lane_off = n * 32 + ((kg ^ ((n >> 3) & 1)) << 4);
-    const int b_lane_off = (kg * (C::PH * C::PW) + wave * R * C::PW + n) * 16;
+    const int a_lane_off = weight_lane_off(n, kg);
+    const int b_lane_off = patch_lane_off<C>(n, kg, wave * R);
 
     // K loop at priority 2, epilogue at 0: the epilogue's VALU work does not take issue slots from the CU partner's MFMAs
     // (window -0.46 %, training step -0.15 %, profiles/r06_experiments.md)
@@ -250,7 +226,7 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    x3_issue_patch<C>(a, smem, 0, 0, 0, wave, voff, plane_elems, plane_bytes);
+    x3_issue_patch<C>(a, smem, 0, 0, 0, wave, voff, t);
     for (int c = 0; c < nchunks; ++c) {
         const char* wb = smem + 2 * C::PATCH_BYTES + (c & 1) * C::WBUF_BYTES;
         // Progress-ordered priority (ONE-ROUND grids): of the two workgroups sharing a CU the
@@ -272,7 +248,7 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
 #if BINHIP_TIMELINE
         if (c == 0) BH_TL_STAMP(1);
 #endif
-        x3_issue_patch<C>(a, smem, c, 1, 1, wave, voff, plane_elems, plane_bytes);
+        x3_issue_patch<C>(a, smem, c, 1, 1, wave, voff, t);
         if (c + 1 < nchunks) x3_issue_weights<C, KS>(a, smem, c + 1, (c + 1) & 1, wave, lane, z);
         // GATED: one sub-stage before the first DMA of a gated chunk (the hi plane of chunk c + 1, issued in the lo sub-stage
         // below), lanes 0-8 of wave 0 fetch the flags of the 3 x 3 tile neighbourhood; the loads ride under this sub-stage's MFMAs
@@ -316,7 +292,7 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (c + 1 < nchunks) x3_issue_patch<C>(a, smem, c + 1, 0, 0, wave, voff, plane_elems, plane_bytes);
+        if (c + 1 < nchunks) x3_issue_patch<C>(a, smem, c + 1, 0, 0, wave, voff, t);
         if constexpr (KS == 5 && !XTRA) {
             if (pair) x3_compute_pair<C, KS, R, false>(smem + C::PATCH_BYTES, wb, n, kg, wave, acc[0]);
             else x3_compute<C, KS, R, false>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0]);
@@ -326,7 +302,7 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
     }
     BH_TL_STAMP(2);
     __builtin_amdgcn_s_setprio(0);
-    conv_epilogue<1, R, 3, EPI, XTRA>(a, bias, acc, img, ty0 + wave * R, tx0, z * 32, z == 0, n, kg, plane_elems);
+    conv_epilogue<1, R, 3, EPI, XTRA>(a, bias, acc, img, t.ty0 + wave * R, t.tx0, z * 32, z == 0, n, kg, t.plane_elems);
     BH_TL_FINISH(a, (((img * a.tiles_y + ty) * a.tiles_x + tx) * a.ncol + z));
 }
 
@@ -341,19 +317,7 @@ __global__ void __launch_bounds__(64 * WN)
     __attribute__((amdgpu_waves_per_eu((KS == 5 && !XTRA) ? WN / 4 : WN / 2, (KS == 5 && !XTRA) ? WN / 4 : WN / 2)))
 conv_x3_kernel(const ConvKArgs a, const float* __restrict__ bias) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // 1-D grid of tiles x output columns, column fastest: after the XCD banding the `ncol` workgroups that share one input
-    // patch are neighbours on ONE XCD, so the patch is fetched into that L2 once (a (tiles, ncol) grid ran each column as a
-    // separate sweep: UPNet.0's 8 columns fetched 884 MB for 99 MB of input)
-    int bid = blockIdx.x;
-    if (a.xcd_remap) bid = xcd_band(bid, gridDim.x);
-    const int ncol = a.ncol;
-    const int z = bid % ncol;
-    bid /= ncol;
-    const int tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    x3_tile<KS, R, WN, EPI, XTRA>(a, bias, smem, img, ty, tx, z);
+    x3_tile<KS, R, WN, EPI, XTRA>(a, bias, smem, tile_decode<X3Cfg<KS, R, WN>::TH>(a, a.ncol));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -393,7 +357,6 @@ __global__ void __launch_bounds__(64 * WN) __attribute__((amdgpu_waves_per_eu(WN
 conv_x3_rdbs_kernel(const Rdb3Args a, const float* __restrict__ bias0, const float* __restrict__ bias1,
                     const float* __restrict__ bias2) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tiles_x = a.conv[0].tiles_x, tiles_y = a.conv[0].tiles_y;
     const int G = (int)gridDim.x;
     const int b = xcd_band((int)blockIdx.x, G);           // consecutive owners = neighbouring tiles on one XCD
 #pragma unroll 1
@@ -407,12 +370,7 @@ conv_x3_rdbs_kernel(const Rdb3Args a, const float* __restrict__ bias0, const flo
         gate.status = ka.flags;
 #pragma unroll 1
         for (int t0 = b; t0 < a.T; t0 += G) {
-            int t = t0;
-            const int tx = t % tiles_x;
-            t /= tiles_x;
-            const int ty = t % tiles_y;
-            const int img = t / tiles_y;
-            x3_tile<3, R, WN, BINHIP_EPI_PLANES, false, true>(ka, bias, smem, img, ty, tx, 0, gate);
+            x3_tile<3, R, WN, BINHIP_EPI_PLANES, false, true>(ka, bias, smem, tile_at<R * WN>(ka, t0, 0), gate);
             // publish: this wave's write-through stores have left (vmcnt(0)), then all waves', then the flag; the barrier
             // also frees LDS for the next tile's prologue
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -429,10 +387,7 @@ static int launch_x3_x(const ConvKArgs& ka, int cout_pad, hipStream_t s) {
     static std::atomic<unsigned long long> lds_set{0};
     if (int rc = bh_set_max_lds(&conv_x3_kernel<KS, R, WN, EPI, WIDE, XTRA>, C::LDS_BYTES, lds_set)) return rc;
     ConvKArgs a = ka;
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + C::TH - 1) / C::TH;
-    a.ncol = cout_pad / 32;
-    dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ncol));
+    const dim3 grid(set_tiles<C>(a, cout_pad / 32));
     // progress-ordered wave priority: only for launches whose workgroups are all resident at once (two per CU), forward layers only
     a.prog_prio = (KS == 3 && !XTRA && (long long)grid.x <= 2ll * binhip_device_cus()) ? 1 : 0;
 #if BINHIP_TIMELINE
@@ -473,8 +428,7 @@ int bh_launch_rdb3_x3(const ConvKArgs* convs, unsigned* flags, unsigned epoch, i
     Rdb3Args a;
     for (int p = 0; p < 3; ++p) {
         a.conv[p] = convs[p];
-        a.conv[p].tiles_x = (convs[p].W + 31) / 32;
-        a.conv[p].tiles_y = (convs[p].H + C::TH - 1) / C::TH;
+        set_tiles<C>(a.conv[p]);
         if (!a.conv[p].wt || a.conv[p].nchunks < 3) return BINHIP_E_SHAPE;
 #if BINHIP_TIMELINE
         // kinds 4, 5, 6 = phases 0, 1, 2 of the one-launch dense block
@@ -501,46 +455,26 @@ int bh_launch_rdb3_x3(const ConvKArgs* convs, unsigned* flags, unsigned epoch, i
 // matrix cores.  With three output channels a 32-row MFMA tile is 91 % padding (round 2: 110 us per launch at 720p, 2.6 % of
 // the window, 0.04 of the MFMA peak); here every lane owns ONE output pixel and accumulates its three channels with
 // v_dot2_f32_f16 (two fp16 products + fp32 add per lane and instruction): operands stay fp16 — the patch planes as they sit in
-// LDS, the weights as wave-uniform scalar loads straight from the relayouted rows 0..2 (no swizzle below row 8) — and the
-// hi / lo split keeps its three products (x_hi w_hi + x_hi w_lo + x_lo w_hi), each exact in fp32.
-//   * tile 8 x 32 pixels, 4 waves (lane = pixel column, wave / lane half = row), patch planes DMA'd per 16-channel chunk and
-//     per precision plane into a two-slot ring exactly like x3_tile (20 KB of LDS: many workgroups per CU);
-//   * per chunk and lane: 72 ds_read_b128 (9 taps x 2 channel halves x 2 planes x ... ) and 648 dot2 (f16x3) / 216 (f16).
-template <int NT>
+// LDS, the weights as wave-uniform scalar loads straight from the relayouted rows 0..2 (no swizzle below row 8).  The
+// single-product mode only: the f16x3 form (three products per operand pair) measured 224 us against the matrix tile's 110 and was
+// dropped (profiles/r03_experiments.md); nterms = 3 runs final_m16_kernel below.
+//   * tile 8 x 32 pixels, 4 waves (lane = pixel column, wave / lane half = row), the hi patch plane DMA'd per 16-channel chunk
+//     into a two-slot ring (the patch image of binhip_conv_common.h; 22 KB of LDS: many workgroups per CU);
+//   * per chunk and lane: 18 ds_read_b128 (9 taps x 2 channel halves) and 216 dot2.
 __global__ void __launch_bounds__(256)
-final_dot2_kernel(const ConvKArgs a, const unsigned* __restrict__ w_hi32, const unsigned* __restrict__ w_lo32) {
-    // (the weight planes come as separate `const __restrict__` kernel parameters: only then does the compiler know that the
-    //  kernel's own stores cannot clobber them and turns the wave-uniform loads into s_load_dwordx8)
+final_dot2_kernel(const ConvKArgs a, const unsigned* __restrict__ w_hi32) {
+    // (the weight plane comes as a separate `const __restrict__` kernel parameter: only then does the compiler know that the
+    //  kernel's own stores cannot clobber it and turns the wave-uniform loads into s_load_dwordx8)
     using C = X3Cfg<3, 2, 4>;                     // TH = 8, patch 10 x 34, 11 DMA pieces per plane, 4 waves
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid = blockIdx.x;
-    if (a.xcd_remap) bid = xcd_band(bid, gridDim.x);
-    const int tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    const int tx0 = tx * 32, ty0 = ty * C::TH;
+    const ConvTile t = tile_decode<C::TH>(a, 1);
+    const int img = t.img, tx0 = t.tx0, ty0 = t.ty0;
     const int H = a.H, W = a.W;
-    const long long plane_elems = (long long)a.N * H * W * 16;
-    const unsigned plane_bytes = (unsigned)(plane_elems * 2);
-
     unsigned voff[C::NPJ];
-#pragma unroll
-    for (int j = 0; j < C::NPJ; ++j) {
-        const int i = wave + C::NW * j;
-        const int q = i * 64 + lane;
-        const int cg = q >= C::PH * C::PW ? 1 : 0;
-        const int p = q - cg * (C::PH * C::PW);
-        const int py = p / C::PW;
-        const int px = p - py * C::PW;
-        const int gy = ty0 + py - 1;
-        const int gx = tx0 + px - 1;
-        const bool ok = (p < C::PH * C::PW) && (gy >= 0) && (gy < H) && (gx >= 0) && (gx < W);
-        voff[j] = ok ? (unsigned)((((long long)img * H + gy) * W + gx) * 32 + cg * 16) : 0x80000000u;
-    }
+    patch_offsets<C, C::PAD>(voff, t, H, W, wave, lane);
     const int px = lane & 31, py = 2 * wave + (lane >> 5);          // this lane's pixel inside the tile
     const int base_off = (py * C::PW + px) * 16;                      // patch pixel (py, px) = tap (0, 0) of the output pixel
     float acc[3] = {0.f, 0.f, 0.f};
@@ -549,10 +483,9 @@ final_dot2_kernel(const ConvKArgs a, const unsigned* __restrict__ w_hi32, const 
     union W2 { unsigned u; half2v p; };
 
     const int nchunks = a.nchunks;
-    auto compute = [&](const char* pb, int c, bool hi_plane) {
+    auto compute = [&](const char* pb, int c) {
         // weights of chunk c: rows 0..2 of every tap are 3 x 32 B contiguous (row stride 32 B, no slot swizzle below row 8)
         const unsigned* wh = w_hi32 + (long long)c * (9 * 32 * 8);
-        const unsigned* wl = w_lo32 + (long long)c * (9 * 32 * 8);
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int dy = t / 3, dx = t % 3;
@@ -567,34 +500,19 @@ final_dot2_kernel(const ConvKArgs a, const unsigned* __restrict__ w_hi32, const 
                         W2 w;
                         w.u = wh[(t * 32 + r) * 8 + cg * 4 + k];
                         acc[r] = __builtin_amdgcn_fdot2(x.p[k], w.p, acc[r], false);
-                        if (NT == 3 && hi_plane) {
-                            W2 v;
-                            v.u = wl[(t * 32 + r) * 8 + cg * 4 + k];
-                            acc[r] = __builtin_amdgcn_fdot2(x.p[k], v.p, acc[r], false);
-                        }
                     }
                 }
             }
         }
     };
 
-    x3_issue_patch<C>(a, smem, 0, 0, 0, wave, voff, plane_elems, plane_bytes);
+    x3_issue_patch<C>(a, smem, 0, 0, 0, wave, voff, t);
     for (int c = 0; c < nchunks; ++c) {
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (NT == 3) {
-            x3_issue_patch<C>(a, smem, c, 1, 1, wave, voff, plane_elems, plane_bytes);
-            compute(smem, c, true);
-            wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            if (c + 1 < nchunks) x3_issue_patch<C>(a, smem, c + 1, 0, 0, wave, voff, plane_elems, plane_bytes);
-            compute(smem + C::PATCH_BYTES, c, false);
-        } else {
-            if (c + 1 < nchunks) x3_issue_patch<C>(a, smem, c + 1, 0, (c + 1) & 1, wave, voff, plane_elems, plane_bytes);
-            compute(smem + (c & 1) * C::PATCH_BYTES, c, true);
-        }
+        if (c + 1 < nchunks) x3_issue_patch<C>(a, smem, c + 1, 0, (c + 1) & 1, wave, voff, t);
+        compute(smem + (c & 1) * C::PATCH_BYTES, c);
     }
     const int gy = ty0 + py, gx = tx0 + px;
     if (gy < H && gx < W) {
@@ -663,13 +581,13 @@ __device__ __forceinline__ void m16_compute(const char* pb, const char* wb, int 
     auto load = [&](int p, half8& ah, half8& al, half8 (&b)[2][2]) {
         // tap slab = 128 B (rows 0-3 x 32 B); pair 4's second tap: row 3 of tap 8 (zeros) for every lane
         const int aoff = (p < 4) ? (2 * p + slot) * 128 + a_lane_off : (slot ? 8 * 128 + a_zero : 8 * 128 + a_lane_off);
-        ah = x3_ld8(wb + aoff);
-        if constexpr (HI) al = x3_ld8(wb + M16::WPIECES * 1024 + aoff);
+        ah = ld8(wb + aoff);
+        if constexpr (HI) al = ld8(wb + M16::WPIECES * 1024 + aoff);
         const int boff = b_lane_off + tap_off(2 * p) + slot * (p < 4 ? tap_off(2 * p + 1) - tap_off(2 * p) : 0);
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
-            for (int g = 0; g < 2; ++g) b[r][g] = x3_ld8(pb + boff + (r * C::PW + g * 16) * 16);
+            for (int g = 0; g < 2; ++g) b[r][g] = ld8(pb + boff + (r * C::PW + g * 16) * 16);
     };
     load(0, Ah[0], Al[0], B[0]);
 #pragma unroll
@@ -694,31 +612,11 @@ final_m16_kernel(const ConvKArgs a, const float* __restrict__ bias) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid = blockIdx.x;
-    if (a.xcd_remap) bid = xcd_band(bid, gridDim.x);
-    const int tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    const int tx0 = tx * 32, ty0 = ty * C::TH;
+    const ConvTile t = tile_decode<C::TH>(a, 1);
+    const int img = t.img, tx0 = t.tx0, ty0 = t.ty0;
     const int H = a.H, W = a.W;
-    const long long plane_elems = (long long)a.N * H * W * 16;
-    const unsigned plane_bytes = (unsigned)(plane_elems * 2);
-
     unsigned voff[C::NPJ];
-#pragma unroll
-    for (int j = 0; j < C::NPJ; ++j) {
-        const int i = wave + C::NW * j;
-        const int q = i * 64 + lane;
-        const int cg = q >= C::PH * C::PW ? 1 : 0;
-        const int p = q - cg * (C::PH * C::PW);
-        const int py = p / C::PW;
-        const int px = p - py * C::PW;
-        const int gy = ty0 + py - 1;
-        const int gx = tx0 + px - 1;
-        const bool ok = (p < C::PH * C::PW) && (gy >= 0) && (gy < H) && (gx >= 0) && (gx < W);
-        voff[j] = ok ? (unsigned)((((long long)img * H + gy) * W + gx) * 32 + cg * 16) : 0x80000000u;
-    }
+    patch_offsets<C, C::PAD>(voff, t, H, W, wave, lane);
     const int n16 = lane & 15, kb = lane >> 4;
     const int slot = kb >> 1;
     const int a_lane_off = ((n16 < 3 ? n16 : 3) * 2 + (kb & 1)) * 16;  // row min(n16, 3) of a tap's 4-row slab, channel half kb & 1
@@ -743,8 +641,8 @@ final_m16_kernel(const ConvKArgs a, const float* __restrict__ bias) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(smem + M16::W_OFF + i * 1024), 16, off, 0, 0, 0);
         }
     }
-    x3_issue_patch<C>(a, smem, 0, 0, 0, wave, voff, plane_elems, plane_bytes);
-    if (nstage > 1) x3_issue_patch<C>(a, smem, 0, 1, 1, wave, voff, plane_elems, plane_bytes);
+    x3_issue_patch<C>(a, smem, 0, 0, 0, wave, voff, t);
+    if (nstage > 1) x3_issue_patch<C>(a, smem, 0, 1, 1, wave, voff, t);
     const bool three = wave < (C::PP - 2 * C::NW);        // this wave issues 3 patch pieces per stage (else 2)
     for (int s = 0; s < nstage; ++s) {
         // stage s landed: at most the pieces of stage s + 1 (issued one sub-stage ago) may still be in flight
@@ -755,7 +653,7 @@ final_m16_kernel(const ConvKArgs a, const float* __restrict__ bias) {
         }
         __builtin_amdgcn_s_barrier();                      // every wave's pieces of stage s landed; stage s - 1's slot is free
         __builtin_amdgcn_sched_barrier(0);
-        if (s + 2 < nstage) x3_issue_patch<C>(a, smem, (s + 2) >> 1, (s + 2) & 1, (s + 2) % 3, wave, voff, plane_elems, plane_bytes);
+        if (s + 2 < nstage) x3_issue_patch<C>(a, smem, (s + 2) >> 1, (s + 2) & 1, (s + 2) % 3, wave, voff, t);
         const char* pb = smem + (s % 3) * C::PATCH_BYTES;
         const char* wb = smem + M16::W_OFF + (s >> 1) * (9 * 128);
         if (s & 1) m16_compute<false>(pb, wb, a_lane_off, b_lane_off, slot, a_zero, acc);
@@ -827,24 +725,17 @@ int bh_launch_final_m16(const ConvKArgs& ka, hipStream_t s) {
     if (ka.nchunks * 9 > M16::WPIECES * 8) return BINHIP_E_SHAPE;   // 5 weight pieces per plane = 40 taps = 4 chunks (UPNet.2: 64 inputs)
     if (int rc = bh_set_max_lds(&final_m16_kernel, M16::LDS_BYTES, lds_set)) return rc;
     ConvKArgs a = ka;
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + C::TH - 1) / C::TH;
-    a.ncol = 1;
-    final_m16_kernel<<<dim3((unsigned)(a.tiles_x * a.tiles_y * a.N)), dim3(512), M16::LDS_BYTES, s>>>(a, a.bias);
+    final_m16_kernel<<<dim3(set_tiles<C>(a)), dim3(512), M16::LDS_BYTES, s>>>(a, a.bias);
     BH_CHECK_LAUNCH();
     return 0;
 }
 
-// FINAL epilogue with <= 3 output channels (UPNet.2), both precisions
+// FINAL epilogue with <= 3 output channels (UPNet.2) in the single-product mode
 int bh_launch_final_dot2(const ConvKArgs& ka, hipStream_t s) {
     using C = X3Cfg<3, 2, 4>;
     ConvKArgs a = ka;
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + C::TH - 1) / C::TH;
-    a.ncol = 1;
-    dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N));
-    const unsigned* wh = reinterpret_cast<const unsigned*>(a.w_hi);
-    final_dot2_kernel<1><<<grid, dim3(256), 2 * C::PATCH_BYTES, s>>>(a, wh, wh);
+    const dim3 grid(set_tiles<C>(a));
+    final_dot2_kernel<<<grid, dim3(256), 2 * C::PATCH_BYTES, s>>>(a, reinterpret_cast<const unsigned*>(a.w_hi));
     BH_CHECK_LAUNCH();
     return 0;
 }

@@ -8,7 +8,8 @@
 //
 // 512 threads (8 wave64), tile 16 rows x 32 cols, wave w owns rows 2w, 2w+1: 2 conv accumulators + 6 LFF accumulators
 // (128 regs).  K-stage = patch 18x34x16ch (20 KiB) + conv weights (9 KiB) + LFF weights (3 KiB) per precision plane,
-// LDS-DMA ring with counted vmcnt (see binhip_conv.hip for the layout / swizzle conventions, which are shared).
+// LDS-DMA ring with counted vmcnt.  Tile decode, plane resources and the weight swizzle are those of binhip_conv_common.h; the patch
+// image is this kernel's own (pixel-major, see the offset loop below).
 #include "binhip_conv_common.h"
 
 #include "binhip_fused.h"
@@ -30,17 +31,14 @@ struct TailCfg {
     static_assert(NW * R * 32 * 2 * 32 * NPL <= BUF_BYTES, "o3 staging tile must fit one stage buffer");
 };
 
-__device__ __forceinline__ half8 ld8(const char* p) { return *reinterpret_cast<const half8*>(p); }
-
 template <class C>
 __device__ __forceinline__ void tail_issue(const TailKArgs& a, char* smem, int c, int buf, int wave, int lane,
-                                           const unsigned (&voff)[C::NPJ], long long plane_elems, unsigned plane_bytes) {
+                                           const unsigned (&voff)[C::NPJ], const ConvTile& t) {
     char* dummy = smem + (C::LDS_BYTES - 1024);
 #pragma unroll
     for (int pl = 0; pl < C::NPL; ++pl) {
         char* lds = smem + buf * C::BUF_BYTES + pl * C::PLANE_BYTES;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((pl ? a.x_lo : a.x_hi) + (long long)c * plane_elems), 0, plane_bytes, 0x00020000);
+        __amdgpu_buffer_rsrc_t rs = patch_plane(a, c, pl, t);
 #pragma unroll
         for (int j = 0; j < C::NPJ; ++j) {
             const int i = wave + C::NW * j;
@@ -79,17 +77,12 @@ rdb_tail_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 31, kg = lane >> 5;
 
-    int bid = blockIdx.x;
-    if (a.xcd_remap) bid = xcd_band(bid, gridDim.x);
-    const int tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    const int tx0 = tx * 32, ty0 = ty * C::TH;
+    const ConvTile t = tile_decode<C::TH>(a, 1);
+    const int img = t.img, tx0 = t.tx0, ty0 = t.ty0;
     const int H = a.H, W = a.W;
-    const long long plane_elems = (long long)a.N * H * W * 16;
-    const unsigned plane_bytes = (unsigned)(plane_elems * 2);
+    const long long plane_elems = t.plane_elems;
 
+    // patch image of THIS kernel: [patch pixel p][channel half, swizzled by (p >> 3) & 1][16 B] — not patch_offsets' image
     unsigned voff[C::NPJ];
 #pragma unroll
     for (int j = 0; j < C::NPJ; ++j) {
@@ -125,9 +118,9 @@ rdb_tail_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float
     }
 #pragma unroll
     for (int s0 = 0; s0 < NBUF - 1; ++s0)
-        tail_issue<C>(a, smem, s0, s0, wave, lane, voff, plane_elems, plane_bytes);
+        tail_issue<C>(a, smem, s0, s0, wave, lane, voff, t);
 
-    const int a_lane_off = n * 32 + ((kg ^ ((n >> 3) & 1)) << 4);
+    const int a_lane_off = weight_lane_off(n, kg);
     const int b_lane_p = wave * C::R * C::PW + n;
     // identity A fragments: row m selects input channel k of the chunk when m == 16*half + k.  The RDB residual
     // (`+ x`, RDN.py:165) is then one extra MFMA per row in the K-steps of chunks 0..5 — x is already in registers as
@@ -147,7 +140,7 @@ rdb_tail_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         if (st + NBUF - 1 < C::NCHUNK)
-            tail_issue<C>(a, smem, st + NBUF - 1, nxt, wave, lane, voff, plane_elems, plane_bytes);
+            tail_issue<C>(a, smem, st + NBUF - 1, nxt, wave, lane, voff, t);
         const char* pb = smem + cur * C::BUF_BYTES;
         const char* wb = pb + C::PP * 1024;
         const char* lb = wb + C::CWP * 1024;
@@ -170,10 +163,10 @@ rdb_tail_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float
 #pragma unroll
                 for (int r = 0; r < C::R; ++r) {
                     if constexpr (NT == 3) {
-                        accc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[r + dy], accc[r], 0, 0, 0);
-                        accc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[r + dy], accc[r], 0, 0, 0);
+                        accc[r] = mfma_32x32x16(Al, Bh[r + dy], accc[r]);
+                        accc[r] = mfma_32x32x16(Ah, Bl[r + dy], accc[r]);
                     }
-                    accc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[r + dy], accc[r], 0, 0, 0);
+                    accc[r] = mfma_32x32x16(Ah, Bh[r + dy], accc[r]);
                 }
             }
             if (dx == 1) {   // the 1x1 LFF sees the centre tap's fragment
@@ -183,9 +176,9 @@ rdb_tail_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float
 #pragma unroll
                         for (int mt = 0; mt < 3; ++mt) {
                             if (mt == (st >> 1)) {
-                                accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ident[st & 1], Bh[r + 1], accl[mt][r], 0, 0, 0);
+                                accl[mt][r] = mfma_32x32x16(ident[st & 1], Bh[r + 1], accl[mt][r]);
                                 if constexpr (NT == 3)
-                                    accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ident[st & 1], Bl[r + 1], accl[mt][r], 0, 0, 0);
+                                    accl[mt][r] = mfma_32x32x16(ident[st & 1], Bl[r + 1], accl[mt][r]);
                             }
                         }
                     }
@@ -199,10 +192,10 @@ rdb_tail_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float
 #pragma unroll
                     for (int r = 0; r < C::R; ++r) {
                         if constexpr (NT == 3) {
-                            accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[r + 1], accl[mt][r], 0, 0, 0);
-                            accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[r + 1], accl[mt][r], 0, 0, 0);
+                            accl[mt][r] = mfma_32x32x16(Al, Bh[r + 1], accl[mt][r]);
+                            accl[mt][r] = mfma_32x32x16(Ah, Bl[r + 1], accl[mt][r]);
                         }
-                        accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[r + 1], accl[mt][r], 0, 0, 0);
+                        accl[mt][r] = mfma_32x32x16(Ah, Bh[r + 1], accl[mt][r]);
                     }
                 }
             }
@@ -241,7 +234,7 @@ rdb_tail_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float
                 *reinterpret_cast<half4*>(o3 + off) = hv[ge].h;
                 if constexpr (NT == 3) *reinterpret_cast<half4*>(o3 + O3_PLANE + off) = lv[ge].h;
             }
-            if (a.o3_hi) {      // training only: keep o3 for the backward pass (16-byte coalesced stores, see binhip_conv.hip)
+            if (a.o3_hi) {      // training only: keep o3 for the backward pass (16-byte coalesced stores, see conv_epilogue in binhip_conv_common.h)
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     auto sw = __builtin_amdgcn_permlane32_swap(hv[0].u[k], hv[1].u[k], false, false);
@@ -282,10 +275,10 @@ rdb_tail_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float
 #pragma unroll
             for (int r = 0; r < C::R; ++r) {
                 if constexpr (NT == 3) {
-                    accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[r], accl[mt][r], 0, 0, 0);
-                    accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[r], accl[mt][r], 0, 0, 0);
+                    accl[mt][r] = mfma_32x32x16(Al, Bh[r], accl[mt][r]);
+                    accl[mt][r] = mfma_32x32x16(Ah, Bl[r], accl[mt][r]);
                 }
-                accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[r], accl[mt][r], 0, 0, 0);
+                accl[mt][r] = mfma_32x32x16(Ah, Bh[r], accl[mt][r]);
             }
         }
     }
@@ -343,9 +336,7 @@ static int launch_tail(const TailKArgs& a0, hipStream_t s) {
     static std::atomic<unsigned long long> lds_set{0};
     if (int rc = bh_set_max_lds(&rdb_tail_kernel<NT, NBUF>, C::LDS_BYTES, lds_set)) return rc;
     TailKArgs a = a0;
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + C::TH - 1) / C::TH;
-    rdb_tail_kernel<NT, NBUF><<<dim3((unsigned)(a.tiles_x * a.tiles_y * a.N)), dim3(512), C::LDS_BYTES, s>>>(a, a.bc, a.bl);
+    rdb_tail_kernel<NT, NBUF><<<dim3(set_tiles<C>(a)), dim3(512), C::LDS_BYTES, s>>>(a, a.bc, a.bl);
     BH_CHECK_LAUNCH();
     return 0;
 }
@@ -370,7 +361,7 @@ int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* blk_hi, con
     a.o3_hi = store_o3 ? (_Float16*)blk_hi + 12 * plane : nullptr;
     a.o3_lo = (store_o3 && nterms == 3) ? (_Float16*)blk_lo + 12 * plane : nullptr;
     a.flags = (unsigned*)status;
-    a.N = N; a.H = H; a.W = W; a.tiles_x = a.tiles_y = 0; a.xcd_remap = 1;
+    a.N = N; a.H = H; a.W = W; a.tiles_x = a.tiles_y = 0;
     a.wt = (6 * plane * 2 < (1ll << 32) - 64) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     if (nterms == 1) return launch_tail<1, 2>(a, s);             // ring depth 2: measured best on MI355X (56.7 vs 63 us at 384x672)

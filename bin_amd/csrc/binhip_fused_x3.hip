@@ -10,7 +10,8 @@
 // planes of fragments (~200 VGPRs): ONE workgroup owns a whole CU, so its DMA prologue, its o3 / output epilogues and
 // every barrier wait run with the matrix pipe idle, and no kernel of another stream can share the CU.
 // Here: 4 waves (256 threads), tile 8 rows x 32 cols (wave w owns rows 2w, 2w+1: still R = 2, so every weight fragment
-// feeds two MFMAs), K-stages split by precision plane as in binhip_conv_x3.hip:
+// feeds two MFMAs), K-stages split by precision plane as in binhip_conv_x3.hip, tile / patch image / weight swizzle from
+// binhip_conv_common.h:
 //     hi:  conv  += Wlo*Xhi, Whi*Xhi      LFF += Llo*Xhi(centre), Lhi*Xhi(centre)   [acc += Xhi(centre), chunks 0-5]
 //     lo:  conv  += Whi*Xlo               LFF += Lhi*Xlo(centre)                    [acc += Xlo(centre)]
 // LDS: patch plane 11 KB double-buffered per sub-stage + (conv 9 + LFF 3 KB) x 2 planes double-buffered per chunk
@@ -38,12 +39,9 @@ struct TX {
     static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 };
 
-__device__ __forceinline__ half8 ld8(const char* p) { return *reinterpret_cast<const half8*>(p); }
-
 __device__ __forceinline__ void tx_issue_patch(const TailKArgs& a, char* smem, int c, int pl, int wave, const unsigned* voff,
-                                               long long plane_elems, unsigned plane_bytes) {
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((pl ? a.x_lo : a.x_hi) + (long long)c * plane_elems), 0, plane_bytes, 0x00020000);
+                                               const ConvTile& t) {
+    __amdgpu_buffer_rsrc_t rs = patch_plane(a, c, pl, t);
     char* lds = smem + pl * TX::PATCH_BYTES;                   // hi planes live in ring slot 0, lo planes in slot 1
 #pragma unroll
     for (int j = 0; j < TX::NPJ; ++j) {
@@ -163,20 +161,20 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
             if constexpr (HI) {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
-                    accc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[s & 1], B[set][r + k], accc[r], 0, 0, 0);
+                    accc[r] = mfma_32x32x16(Al[s & 1], B[set][r + k], accc[r]);
             }
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                accc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[s & 1], B[set][r + k], accc[r], 0, 0, 0);
+                accc[r] = mfma_32x32x16(Ah[s & 1], B[set][r + k], accc[r]);
         } else {
             if constexpr (HI) {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
-                    accl[k][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[s & 1], B[1][r + 1], accl[k][r], 0, 0, 0);
+                    accl[k][r] = mfma_32x32x16(Al[s & 1], B[1][r + 1], accl[k][r]);
             }
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                accl[k][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[s & 1], B[1][r + 1], accl[k][r], 0, 0, 0);
+                accl[k][r] = mfma_32x32x16(Ah[s & 1], B[1][r + 1], accl[k][r]);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -195,29 +193,12 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 31, kg = lane >> 5;
 
-    int bid = blockIdx.x;
-    if (a.xcd_remap) bid = xcd_band(bid, gridDim.x);
-    const int tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    const int tx0 = tx * 32, ty0 = ty * TX::TH;
+    const ConvTile t = tile_decode<TX::TH>(a, 1);
+    const int img = t.img, tx0 = t.tx0, ty0 = t.ty0;
     const int H = a.H, W = a.W;
-    const long long plane_elems = (long long)a.N * H * W * 16;
-    const unsigned plane_bytes = (unsigned)(plane_elems * 2);
-
+    const long long plane_elems = t.plane_elems;
     unsigned voff[TX::NPJ];
-#pragma unroll
-    for (int j = 0; j < TX::NPJ; ++j) {
-        const int i = wave + TX::NW * j;
-        const int q = i * 64 + lane;                            // LDS image = [channel half][patch pixel][16 B]
-        const int cg = q >= TX::PH * TX::PW ? 1 : 0;
-        const int p = q - cg * (TX::PH * TX::PW);
-        const int py = p / TX::PW, px = p - py * TX::PW;
-        const int gy = ty0 + py - 1, gx = tx0 + px - 1;
-        const bool ok = (p < TX::PH * TX::PW) && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        voff[j] = ok ? (unsigned)((((long long)img * H + gy) * W + gx) * 32 + cg * 16) : 0x80000000u;
-    }
+    patch_offsets<TX, 1>(voff, t, H, W, wave, lane);
 
     floatx16 accc[TX::R];
     floatx16 accl[3][TX::R];
@@ -228,12 +209,12 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
             accc[r][e] = 0.f;
             accl[0][r][e] = 0.f; accl[1][r][e] = 0.f; accl[2][r][e] = 0.f;
         }
-    const int a_lane_off = n * 32 + ((kg ^ ((n >> 3) & 1)) << 4);
-    const int b_lane_off = (kg * (TX::PH * TX::PW) + wave * TX::R * TX::PW + n) * 16;
+    const int a_lane_off = weight_lane_off(n, kg);
+    const int b_lane_off = patch_lane_off<TX>(n, kg, wave * TX::R);
 
     __builtin_amdgcn_s_setprio(2);       // K loop above the CU partner's epilogue (binhip_conv_x3.hip)
     tx_issue_weights(a, smem, 0, 0, wave, lane);
-    tx_issue_patch(a, smem, 0, 0, wave, voff, plane_elems, plane_bytes);
+    tx_issue_patch(a, smem, 0, 0, wave, voff, t);
     // one 16-channel chunk = a hi and a lo sub-stage.  Chunks 0-5 (the block input) also carry the residual, with their index
     // as a compile-time constant (which accumulator registers it lands in): those six are peeled, 6-11 stay a loop.
     half8 carry[TX::R];
@@ -247,7 +228,7 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
 #if BINHIP_TIMELINE
         if (c == 0) BH_TL_STAMP(1);
 #endif
-        tx_issue_patch(a, smem, c, 1, wave, voff, plane_elems, plane_bytes);
+        tx_issue_patch(a, smem, c, 1, wave, voff, t);
         if (c + 1 < TX::NCHUNK) tx_issue_weights(a, smem, c + 1, (c + 1) & 1, wave, lane);
         else tx_issue_tailw(a, smem, wave, lane);                // weight buffer 0: chunk 10's, read for the last time in lo(10)
         tx_compute<true, RH>(smem, wb, a_lane_off, b_lane_off, accc, accl, carry);
@@ -255,7 +236,7 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (c + 1 < TX::NCHUNK) tx_issue_patch(a, smem, c + 1, 0, wave, voff, plane_elems, plane_bytes);
+        if (c + 1 < TX::NCHUNK) tx_issue_patch(a, smem, c + 1, 0, wave, voff, t);
         tx_compute<false, RL>(smem + TX::PATCH_BYTES, wb, a_lane_off, b_lane_off, accc, accl, carry);
     };
     using std::integral_constant;
@@ -334,9 +315,9 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
             const half8 Al = ld8(tailw + 6 * 1024 + off);
 #pragma unroll
             for (int r = 0; r < TX::R; ++r) {
-                accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[t][r], accl[mt][r], 0, 0, 0);
-                accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[t][r], accl[mt][r], 0, 0, 0);
-                accl[mt][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[t][r], accl[mt][r], 0, 0, 0);
+                accl[mt][r] = mfma_32x32x16(Al, Bh[t][r], accl[mt][r]);
+                accl[mt][r] = mfma_32x32x16(Ah, Bh[t][r], accl[mt][r]);
+                accl[mt][r] = mfma_32x32x16(Ah, Bl[t][r], accl[mt][r]);
             }
         }
     }
@@ -361,13 +342,12 @@ int bh_launch_tail_x3(const TailKArgs& a0, hipStream_t s) {
     static std::atomic<unsigned long long> lds_set{0};
     if (int rc = bh_set_max_lds(&rdb_tail_x3_kernel, TX::LDS_BYTES, lds_set)) return rc;
     TailKArgs a = a0;
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + TX::TH - 1) / TX::TH;
+    const unsigned grid = set_tiles<TX>(a);
 #if BINHIP_TIMELINE
-    a.tl = bh_tl_reserve((unsigned)(a.tiles_x * a.tiles_y * a.N), &a.tl_base);
+    a.tl = bh_tl_reserve(grid, &a.tl_base);
     a.tl_launch = (2u << 24) | (g_bh_tl_serial.fetch_add(1) & 0xFFFFFFu);      // kind 2 = the fused tail
 #endif
-    rdb_tail_x3_kernel<<<dim3((unsigned)(a.tiles_x * a.tiles_y * a.N)), dim3(256), TX::LDS_BYTES, s>>>(a, a.bc, a.bl);
+    rdb_tail_x3_kernel<<<dim3(grid), dim3(256), TX::LDS_BYTES, s>>>(a, a.bc, a.bl);
     BH_CHECK_LAUNCH();
     return 0;
 }

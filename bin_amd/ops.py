@@ -234,7 +234,7 @@ def conv2d(x, cw, relu=False, residual=None, out=None, epilogue=L.EPI_PLANES, im
         _ptr(out.lo) if out is not None else C.c_void_p(0),
         _ptr(y_f32), arr, _stream())
     L.check(rc, "conv2d_fwd")
-    return y_f32 if epilogue == L.EPI_FINAL else out
+    return out if epilogue in (L.EPI_PLANES, L.EPI_SHUFFLE) else y_f32
 
 
 def convlstm_cell(x, state, weight, bias, forget_bias=1.0):

@@ -511,3 +511,23 @@ def test_packed_split_equals_the_scalar_split(ks, relu):
     same_hi = (y.hi.view(torch.int16) == hi.view(torch.int16)) | ((y.hi == 0) & (hi == 0))      # (+0 / -0 are the same stored value)
     same_lo = (y.lo.view(torch.int16) == lo.view(torch.int16)) | ((y.lo == 0) & (lo == 0))
     assert bool(same_hi.all()) and bool(same_lo.all()), (int((~same_hi).sum()), int((~same_lo).sum()))
+
+
+# ------------------------------------------------------------------------------------------------ the forward kernels' own bits
+def _recorded_conv_bits():
+    with open(os.path.join(REPO, "tests", "golden", "conv_bits.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("key", sorted(_recorded_conv_bits()["bits"]))
+def test_conv_bits_are_the_recorded_ones(key):
+    """Every reachable row of bh_dispatch_conv and the fused dense-block tail, at both precisions and three front-end shapes
+    (tests/conv_cases.py), return bit for bit what tests/golden/make_conv_bits.py recorded from the commit named in
+    tests/golden/conv_bits.json: the tile decode, the patch image and the DMA sources may move between files, the sums may not.
+    No atomics and no device-dependent summation order in these kernels, so nothing may be left out of the fixture."""
+    import conv_cases as cc
+    rec = _recorded_conv_bits()
+    assert not rec["left_out"], f"cases that did not reproduce when the fixture was recorded: {rec['left_out']}"
+    assert sorted(rec["bits"]) == sorted(cc.KEYS), "tests/golden/conv_bits.json and tests/conv_cases.py name different cases"
+    got = cc.white_noise_bits(*cc.parse_key(key))
+    assert got == rec["bits"][key], f"{key}: the bits differ from those recorded from {rec['recorded_from']}"
