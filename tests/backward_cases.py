@@ -3,7 +3,7 @@ op-by-op dense-block forward / gather-form backward shared with tests/test_gpu_c
 with its tie rule are shared with tests/test_gpu_rdn_configs.py (any (G0, D, C, G)).
 
 Frames are (N, H, W) at full resolution; the network runs at half resolution h = H / 2, w = W / 2.  The fused UPNet's ring kernels
-(binhip_misc.hip: upnet_ring_dgrad_kernel's band of rows {0, 1, 2, h-3, h-2, h-1} with its h <= 6 / w <= 6 branches,
+(binhip_upnet_bwd.hip: upnet_ring_dgrad_kernel's band of rows {0, 1, 2, h-3, h-2, h-1} with its h <= 6 / w <= 6 branches,
 upnet_ring_wgrad_kernel's twelve (variant, sub-pixel) pairs and per-image partials) are only reached in full at half-resolution sizes
 below 7, odd, and with N > 1 — what the aligned shapes of the older tests never are."""
 import torch

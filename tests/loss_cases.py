@@ -12,7 +12,7 @@ import torch
 
 KINDS = ("cb", "l1", "l2")                                  # bin_amd._lib.LOSS_CHARBONNIER, LOSS_L1_SUM, LOSS_L2_SUM = 0, 1, 2
 KIND_ID = {"cb": 0, "l1": 1, "l2": 2}
-FWD_CAP, BWD_CAP = 1024 * 256, 4096 * 256                   # threads of the capped forward / backward grids (binhip_misc.hip)
+FWD_CAP, BWD_CAP = 1024 * 256, 4096 * 256                   # threads of the capped forward / backward grids (binhip_loss.hip)
 NUMELS = [1, 2, 255, 256, 257, 65535, FWD_CAP - 1, FWD_CAP, FWD_CAP + 1, BWD_CAP - 1, BWD_CAP, BWD_CAP + 1, 2 ** 24 + 3]
 CAP_NUMELS = [FWD_CAP - 1, FWD_CAP, FWD_CAP + 1, BWD_CAP - 1, BWD_CAP, BWD_CAP + 1]
 EPS_VALUES = (1e-6, 1e-3, 1e-12)

@@ -15,7 +15,7 @@ import torch
 
 from oracle import rdn_oracle as O
 
-TILE_W, TILE_H = 64, 8                 # convlstm_bwd_weight_kernel's tile (binhip_misc.hip CL_TW x CL_TH)
+TILE_W, TILE_H = 64, 8                 # convlstm_bwd_weight_kernel's tile (binhip_convlstm.hip CL_TW x CL_TH)
 FINAL_STRIDE = 256                     # convlstm_bwd_weight_final_kernel's strided loop: tiles i, i + 256, ...
 
 # B: forward c', h' max-abs; gradients max-abs over max-abs of the reference tensor (`rel`)
@@ -218,7 +218,7 @@ def compare(tag, names, got, ref64, ref32, bars=BARS, label="kernel"):
 
 
 def off1(t):
-    """A copy of `t` whose data pointer is 4 bytes past a 16-byte boundary (forces the one-pixel ConvLSTM kernels)."""
+    """A copy of `t` whose data pointer is 4 bytes past a 16-byte boundary (forces the one-pixel-per-thread ConvLSTM kernels)."""
     buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
     assert buf.data_ptr() % 16 == 0
     v = buf[1:1 + t.numel()].view(t.shape)

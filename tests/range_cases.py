@@ -129,13 +129,13 @@ _CONV_FWD = ["conv_planes_k1_c32_relu0", "conv_planes_k1_c32_relu1", "conv_plane
 _BWD_IDS = ["bwd_plain", "bwd_res", "bwd_acc", "bwd_mask", "bwd_unshuf", "bwd_lffd", "bwd_lff_generic"]
 _TAIL = ["rdb_tail_store0_o3", "rdb_tail_store0_y", "rdb_tail_store1_o3", "rdb_tail_store1_y"]
 SITES = {
-    ("binhip_misc.hip", "nchw_to_planes_kernel"): dict(split_hi=1, atomicOr=1,
+    ("binhip_layout.hip", "nchw_to_planes_kernel"): dict(split_hi=1, atomicOr=1,
                                                        cases=["nchw_to_planes", "nchw_to_planes_scaled", "rdn_backward",
                                                              "rdn_backward_glue"]),
-    ("binhip_misc.hip", "pack_inputs_kernel"): dict(split_hi=1, atomicOr=1,
+    ("binhip_layout.hip", "pack_inputs_kernel"): dict(split_hi=1, atomicOr=1,
                                                     cases=["pack_inputs_2", "pack_inputs_3", "pack_inputs_5", "status_null"]),
-    ("binhip_misc.hip", "upnet_gsub_kernel"): dict(split_hi=1, atomicOr=1, cases=["rdn_backward", "rdn_backward_glue"]),
-    ("binhip_misc.hip", "upnet_ring_dgrad_kernel"): dict(split_hi=1, atomicOr=1,
+    ("binhip_upnet_bwd.hip", "upnet_gsub_kernel"): dict(split_hi=1, atomicOr=1, cases=["rdn_backward", "rdn_backward_glue"]),
+    ("binhip_upnet_bwd.hip", "upnet_ring_dgrad_kernel"): dict(split_hi=1, atomicOr=1,
                                                          cases=["rdn_backward", "rdn_backward_glue"]),
     # the LFF backward-data instantiation's two split_pair calls and the generic epilogue's two, one status store
     ("binhip_conv_common.h", "conv_epilogue"): dict(split_pair=4, atomicOr=1,

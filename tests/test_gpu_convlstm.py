@@ -1,4 +1,4 @@
-"""-m gpu: ConvLSTMCell (reference RDN.py:9-95) — fused forward/backward kernels, the four-pixel variants, cells of other sizes on the general path."""
+"""-m gpu: ConvLSTMCell (reference RDN.py:9-95) — fused forward/backward kernels, both widths of the gate path, cells of other sizes on the general path."""
 import hashlib
 import json
 import os
@@ -117,10 +117,11 @@ def test_general_convlstm_conv_refuses_a_weight_changed_before_backward():
 @pytest.mark.parametrize("with_state", [False, True])
 @pytest.mark.parametrize("shape", [(1, 16, 24), (2, 9, 20), (1, 33, 4), (1, 5, 64)])
 def test_convlstm_four_pixel_kernels_equal_the_one_pixel_kernels(shape, with_state):
-    """Round 5: `binhip_convlstm_fwd` / `_bwd` run four pixels per thread (float4 rows, weights as ds_read_b128, every epilogue
-    load before the first store) when W % 4 == 0 and the planes are 16-byte aligned, and the round-1 one-pixel kernels otherwise.
-    Same fmaf chains per pixel -> the two must agree BIT FOR BIT: the same data is run through both by mis-aligning the planes
-    by one float.  (Both are pinned to the reference by test_convlstm_golden above.)"""
+    """`binhip_convlstm_fwd` / `_bwd` run the gate path (binhip_convlstm.hip: one template over the pixels a thread owns) with four
+    pixels per thread (float4 rows) when W % 4 == 0 and the planes are 16-byte aligned, and with one pixel per thread otherwise.  The
+    two instantiations differ in the row load and the vector width of the epilogue alone; each pixel's fmaf chain is the same -> they
+    must agree BIT FOR BIT: the same data is run through both by mis-aligning the planes by one float.  (Both are pinned to the
+    reference by test_convlstm_golden above.)"""
     import ctypes as C
     from bin_amd import _lib as L
     lib = L.lib()

@@ -1,12 +1,14 @@
-"""-m gpu: every kernel of binhip_misc.hip that is not a convolution on chunk planes — the fused ConvLSTM cell and its three-pass
-backward, the elementwise gate kernels of the general cell, the pixel-loss reductions (single and multi-term), the gradient-scale
-reduction and the layout / frame glue — against float64 (or, where the contract is bit-exactness, numpy) at the shapes, sizes and
+"""-m gpu: every kernel of binhip_convlstm.hip, binhip_loss.hip and binhip_layout.hip — the fused ConvLSTM cell and its three-pass
+backward, the elementwise gate kernels of the general cell, the pixel-loss reductions (one path for one and for many terms), the
+gradient-scale reduction and the layout / frame glue — against float64 (or, where the contract is bit-exactness, numpy) at the shapes, sizes and
 magnitudes where such kernels go wrong.  Case tables, references and bars: lstm_cases.py, loss_cases.py, glue_cases.py; their CPU
 pins: test_cpu_small_kernels.py.  Each comparison prints e32 (float32 torch against float64), the bar max(B, 4 * e32) and the kernel's
 error on a line that starts with `[small-kernels]`.
 
 Measured on an MI355X when this module was written, largest error / bar over all cases: see DESIGN.md ("Small kernels")."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
@@ -15,6 +17,8 @@ import torch
 import glue_cases as GC
 import loss_cases as LS
 import lstm_cases as LC
+import small_kernel_bit_cases as BC
+from conftest import REPO
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +45,7 @@ def _nan_like(t):
 # ------------------------------------------------------------------------------------------------------- A. fused ConvLSTM cell
 def _run_fused(case, inp, conv):
     """binhip_convlstm_fwd + _bwd through the C ABI with the variant's NULL pointers; `conv` places every plane (identity copy =
-    16-byte aligned = four-pixel kernels when W % 4 == 0; lstm_cases.off1 = one-pixel kernels).  Outputs start as NaN, so an element
+    16-byte aligned = four pixels per thread when W % 4 == 0; lstm_cases.off1 = one pixel per thread).  Outputs start as NaN, so an element
     the kernels do not write fails the comparison."""
     L, lib = _lib()
     names = LC.wanted(case)
@@ -70,8 +74,8 @@ def _run_fused(case, inp, conv):
 
 @pytest.mark.parametrize("tag", [c.tag for c in LC.CASES])
 def test_fused_convlstm_vs_float64(tag):
-    """Both kernel families against float64: aligned planes (the four-pixel kernels when W % 4 == 0) and every plane offset by one
-    float (the one-pixel kernels); where both exist they must also agree bit for bit."""
+    """Both widths of the gate path against float64: aligned planes (four pixels per thread when W % 4 == 0) and every plane offset by
+    one float (one pixel per thread); where both run they must also agree bit for bit."""
     case = LC.CASE_BY_TAG[tag]
     inp = LC.make_inputs(case)
     r64, r32 = LC.reference(case, inp, torch.float64), LC.reference(case, inp, torch.float32)
@@ -261,6 +265,25 @@ def test_grad_scale_vs_exact_exponent_arithmetic(numel):
     sc = torch.full((2,), float("nan"), device="cuda")
     L.check(lib.binhip_grad_scale(_p(torch.zeros_like(base)), numel, 16.0, _p(part), _p(sc), _stream()), "grad_scale")
     assert sc.tolist() == [1.0, 1.0]
+
+
+# ------------------------------------------------------------------------------------------------------- B'. the bit pin
+def _recorded_small_kernel_bits():
+    with open(os.path.join(REPO, "tests", "golden", "small_kernel_bits.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("key", BC.KEYS)
+def test_small_kernel_bits_are_the_recorded_ones(key):
+    """The ConvLSTM, gate, pixel-criterion and gradient-scale entry points at the shapes of tests/small_kernel_bit_cases.py return bit
+    for bit what tests/golden/make_small_kernel_bits.py recorded from the commit named in tests/golden/small_kernel_bits.json: these
+    kernels may move between files and share their gate accumulation, their criterion and their block reductions; the roundings and
+    the pairing of every sum may not change.  No atomics and no device-dependent summation order, so nothing may be left out."""
+    rec = _recorded_small_kernel_bits()
+    assert not rec["left_out"], f"cases that did not reproduce when the fixture was recorded: {rec['left_out']}"
+    assert sorted(rec["bits"]) == sorted(BC.KEYS), "tests/golden/small_kernel_bits.json and tests/small_kernel_bit_cases.py name different cases"
+    got = BC.bits(key)
+    assert got == rec["bits"][key], f"{key}: the bits differ from those recorded from {rec['recorded_from']}"
 
 
 # ------------------------------------------------------------------------------------------------------- C. layout glue
