@@ -296,6 +296,8 @@ int bh_prepare_conv(const BhConvCall& c, ConvKArgs* out) {
     a.y_cpg_inv = c.y_cpg > 0 ? (unsigned)(((1u << 20) + c.y_cpg - 1) / c.y_cpg) : 0u;
     if (c.y_cpg > 128 || (c.y_cpg > 0 && d.cout_pad / 16 >= 4096)) return BINHIP_E_SHAPE;
     a.half_last = (d.reserved & BINHIP_CONV_HALF_LAST_CHUNK) ? 1 : 0;
+    a.upnet_fold = (d.reserved & BINHIP_CONV_UPNET_FOLD) ? 1 : 0;
+    if (a.upnet_fold && (d.epilogue != BINHIP_EPI_FINAL_SUBPIX || d.nterms != 3)) return BINHIP_E_ARG;
     a.y_unshuf = c.y_unshuf;
     if (c.y_unshuf && (d.epilogue != BINHIP_EPI_PLANES || c.y_cpg > 0 || (d.H & 1) || (d.W & 1) || c.y_unshuf * 16 < d.cout))
         return BINHIP_E_SHAPE;
@@ -778,9 +780,10 @@ int binhip_conv2d_fwd(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
                       const void* w_lo, const float* bias, const void* res_hi, const void* res_lo,
                       void* y_hi, void* y_lo, float* y_f32, const float* const* images, void* stream) {
     if (!d) return BINHIP_E_ARG;
-    // `reserved`: the one defined bit, and only where it is legal (the promise concerns the 5x5 layer's last chunk; a wrong promise
-    // would give wrong sums silently because the real cin is not in the descriptor) — advisor r05
-    if (d->reserved & ~BINHIP_CONV_HALF_LAST_CHUNK) return BINHIP_E_ARG;
+    // `reserved`: the defined bits, each only where it is legal (the 5x5 bit's promise concerns that layer's last chunk; a wrong promise
+    // would give wrong sums silently because the real cin is not in the descriptor — advisor r05; BINHIP_CONV_UPNET_FOLD is checked in
+    // bh_prepare_conv)
+    if (d->reserved & ~(BINHIP_CONV_HALF_LAST_CHUNK | BINHIP_CONV_UPNET_FOLD)) return BINHIP_E_ARG;
     if ((d->reserved & BINHIP_CONV_HALF_LAST_CHUNK) && d->ksize != 5) return BINHIP_E_ARG;
     BhConvCall c;
     c.d = *d;

@@ -62,6 +62,7 @@ struct ConvKArgs {
     unsigned tl_launch;       // (kernel kind << 24) | launch serial
     unsigned tl_base;         // first record of this launch (records are pre-assigned: base + tile index, no atomics)
 #endif
+    int upnet_fold;           // FINAL_SUBPIX in the fp32-class mode: w_hi / w_lo are the folded slab (BINHIP_CONV_UPNET_FOLD)
     int y_unshuf;             // XTRA kernels only: > 0 = the output goes out through an inverse PixelShuffle(2) — full-resolution
                               // pixel (Y, X), chunk c -> plane (2 (Y & 1) + (X & 1)) * y_unshuf + c at (Y / 2, X / 2) of the half-
                               // resolution tensor (the channel order UPNet.0's permuted rows use); y_unshuf = chunks per sub-position
@@ -130,6 +131,8 @@ struct BhTl {
 
 // internal epilogue code (never crosses the ABI): chunk planes with the extras pattern of the LFF backward-data tile
 #define BINHIP_EPI_PLANES_LFFD 3
+// internal: BINHIP_EPI_FINAL_SUBPIX on the folded walk of the fused UPNet (x3_compute_fold / upnet_fold_epilogue)
+#define BINHIP_EPI_SUBPIX_FOLD 5
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -242,6 +245,73 @@ __device__ __forceinline__ int weight_lane_off(int n, int kg) { return n * 32 + 
 // B fragment of lane (n, kg) in the patch image above: channel half kg, patch row `row`, column n
 template <class C>
 __device__ __forceinline__ int patch_lane_off(int n, int kg, int row) { return (kg * (C::PH * C::PW) + row * C::PW + n) * 16; }
+
+// ---- epilogue of the folded fused UPNet (BINHIP_PLAN_UPNET_FOLD, x3_compute_fold in binhip_conv_x3.hip) --------------------------
+// acc = ONE 32x32 tile for the wave's two matrix rows: M rows 0-11 = the 12 sub-pixel channels c * 4 + i * 2 + j at position
+// (Y = row0, X = tx0 + n), rows 16-27 the same channels at (row0 + 1, X).  Channel (c, i, j) at (Y, X) is colour c of full-resolution
+// pixel (2 Y - i, 2 X - j): a lane's four consecutive channels are still one colour's 2 x 2 block, at rows 2 Y - 1, 2 Y and columns
+// 2 X - 1, 2 X — 4-byte aligned, so everything here is a dword access (32 lanes of a row = 256 contiguous bytes).  In the C layout
+// lane (n, kg) holds rows 8 g + 4 kg + q in acc[4 g + q]: g = 2 r + g', colour 2 g' + kg of position row0 + r.  + bias + mean of the
+// input frames, as BINHIP_EPI_FINAL_SUBPIX.  Stored: full-resolution rows 1 .. 2 H - 2 and columns 1 .. 2 W - 2 only — the border ring is
+// upnet_ring_kernel's (it runs after this launch), row / column -1 and everything past the image do not exist.  Every load before the
+// first store, pinned (loads and stores share vmcnt).
+__device__ __forceinline__ void upnet_fold_epilogue(const ConvKArgs& a, const float* __restrict__ bias, const floatx16& acc, int img,
+                                                    int row0, int tx0, int n, int kg) {
+    const int H2 = 2 * a.H, W2 = 2 * a.W, ncolour = a.cout >> 2, nimg = a.nimg;
+    const int X = tx0 + n;
+    float bv[2][4];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        float b8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b8[j] = bias[8 * g + j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bv[g][q] = kg ? b8[4 + q] : b8[q];
+    }
+    auto pixel = [&](int r, int g, int q, bool& ok) -> long long {      // output index of acc[4 (2 r + g) + q], clamped into the image
+        const int c = 2 * g + kg;
+        const int Y2 = 2 * (row0 + r) - (q >> 1), X2 = 2 * X - (q & 1);
+        ok = c < ncolour && Y2 >= 1 && Y2 <= H2 - 2 && X2 >= 1 && X2 <= W2 - 2;
+        const int cc = c < ncolour ? c : 0;
+        const int yc = Y2 < 0 ? 0 : (Y2 > H2 - 1 ? H2 - 1 : Y2), xc = X2 < 0 ? 0 : (X2 > W2 - 1 ? W2 - 1 : X2);
+        return (((long long)img * ncolour + cc) * H2 + yc) * W2 + xc;
+    };
+    float sum[2][2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                bool ok;
+                const long long idx = pixel(r, g, q, ok);
+                float v[5];
+#pragma unroll
+                for (int t = 0; t < 5; ++t) v[t] = (ok && t < nimg) ? a.img[t][idx] : 0.f;
+                float sj = v[0];
+#pragma unroll
+                for (int t = 1; t < 5; ++t)
+                    if (t < nimg) sj += v[t];
+                sum[r][g][q] = (ok && nimg > 0) ? sj / (float)nimg : 0.f;
+            }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(sum[r][g][q]));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                bool ok;
+                const long long idx = pixel(r, g, q, ok);
+                if (ok) a.out_f32[idx] = (acc[4 * (2 * r + g) + q] + bv[g][q]) + sum[r][g][q];
+            }
+}
 
 // ---- epilogue ---------------------------------------------------------------------------------------
 // acc[mt][r][4g+j] = D[cout = 8g + 4*kg + j][pixel = n]  (32x32 MFMA C/D layout): a lane holds 4 consecutive

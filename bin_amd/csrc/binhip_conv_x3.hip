@@ -25,14 +25,15 @@
 // wave tile of every instantiation: X3_R output rows per wave, X3_WN waves per workgroup (tile = 16 x 32 pixels)
 constexpr int X3_R = 2, X3_WN = 8;
 
-template <int KS, int R, int WN>
+// NTAP: tap positions of the weight slab — KS * KS, or the folded fused UPNet's 5 rows x 4 columns (x3_compute_fold)
+template <int KS, int R, int WN, int NTAP = KS * KS>
 struct X3Cfg {
     static constexpr int PAD = KS / 2;
     static constexpr int TH = R * WN;
     static constexpr int PH = TH + KS - 1;
     static constexpr int PW = 32 + KS - 1;
     static constexpr int PP = (PH * PW * 2 + 63) / 64;     // 1-KiB DMA pieces of one patch plane
-    static constexpr int WP = KS * KS;                     // 1-KiB pieces of one weight plane (32 rows x 32 B per tap)
+    static constexpr int WP = NTAP;                        // 1-KiB pieces of one weight plane (32 rows x 32 B per tap)
     static constexpr int NW = WN;
     static constexpr int PATCH_BYTES = PP * 1024;
     static constexpr int WBUF_BYTES = 2 * WP * 1024;       // hi taps, then lo taps
@@ -43,6 +44,9 @@ struct X3Cfg {
     // — still with both rings double-buffered (the generic kernel had to single-buffer its 96 KB stage: NBUF = 1, nothing overlapped)
     static_assert((KS == 3 ? 2 : 1) * LDS_BYTES <= 160 * 1024, "LDS budget");
 };
+constexpr int X3_FOLD_TAPS = 20;
+template <int KS, int R, int WN, int EPI>
+using X3CfgOf = X3Cfg<KS, R, WN, EPI == BINHIP_EPI_SUBPIX_FOLD ? X3_FOLD_TAPS : KS * KS>;
 
 template <class C>
 __device__ __forceinline__ void x3_issue_patch(const ConvKArgs& a, char* smem, int c, int pl, int buf, int wave,
@@ -59,11 +63,11 @@ __device__ __forceinline__ void x3_issue_patch(const ConvKArgs& a, char* smem, i
     }
 }
 
-template <class C, int KS>
+template <class C>
 __device__ __forceinline__ void x3_issue_weights(const ConvKArgs& a, char* smem, int c, int buf, int wave, int lane, int z) {
-    const long long woff = ((long long)z * a.nchunks + c) * (KS * KS * 32 * 16);
-    __amdgpu_buffer_rsrc_t wh = __builtin_amdgcn_make_buffer_rsrc((void*)(a.w_hi + woff), 0, KS * KS * 1024, 0x00020000);
-    __amdgpu_buffer_rsrc_t wl = __builtin_amdgcn_make_buffer_rsrc((void*)(a.w_lo + woff), 0, KS * KS * 1024, 0x00020000);
+    const long long woff = ((long long)z * a.nchunks + c) * (C::WP * 32 * 16);
+    __amdgpu_buffer_rsrc_t wh = __builtin_amdgcn_make_buffer_rsrc((void*)(a.w_hi + woff), 0, C::WP * 1024, 0x00020000);
+    __amdgpu_buffer_rsrc_t wl = __builtin_amdgcn_make_buffer_rsrc((void*)(a.w_lo + woff), 0, C::WP * 1024, 0x00020000);
     char* lds = smem + 2 * C::PATCH_BYTES + buf * C::WBUF_BYTES;
 #pragma unroll
     for (int j = 0; j < C::NWJ; ++j) {
@@ -111,6 +115,45 @@ __device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a
 #pragma unroll
         for (int r = 0; r < R; ++r)
             acc[r] = mfma_32x32x16(Ah[s & 1], B[dx & 1][r + dy], acc[r]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// The folded main launch of the fused UPNet (BINHIP_PLAN_UPNET_FOLD; slab: bin_amd/rdn_plan.py folded_upnet_weights).  Of the 5x5
+// operator's 25 taps a sub-pixel channel has 4 x 4, and which 16 depends on its sub-pixel (i, j) alone: with channel (c, i, j) at matrix
+// position (Y, X) computing half-resolution pixel (Y - i, X - j), EVERY channel reads input rows Y - 2 .. Y + 1 and columns X - 2 .. X + 1.
+// Only 12 of the 32 M rows carry a channel, so rows 16-27 take position (Y + 1, X): the wave's two output rows share ONE accumulator
+// tile and the B fragments of the five patch rows Y - 2 + t; weight row t is zero for the first position at t = 4 and for the second at
+// t = 0.  5 x 4 tap positions = 20 MFMAs per product for the row pair (the 5x5 walk: 2 x 25), b-major like x3_compute: the five
+// patch-row fragments of a tap column are fetched once, weight fragments one tap ahead.  That order meets a channel's non-zero taps in
+// the order the 5x5 walk does, and what it skips added exact zeros: the outputs are the 5x5 launch's bit for bit
+// (tests/test_gpu_upnet_fold.py).
+template <class C, bool HI>
+__device__ __forceinline__ void x3_compute_fold(const char* pb, const char* wb, int a_lane_off, int b_lane_off, floatx16& acc) {
+    constexpr int NT = 5, NB = 4;
+    static_assert(C::WP == NT * NB && C::PH >= 2 * (C::NW - 1) + NT && C::PW >= 32 + NB - 1, "slab and patch of the folded walk");
+    half8 B[2][NT];
+    half8 Ah[2], Al[2];
+    auto load_b = [&](int b, half8 (&dst)[NT]) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) dst[t] = ld8(pb + b_lane_off + (t * C::PW + b) * 16);
+    };
+    auto load_a = [&](int s, half8& h, half8& l) {
+        const int b = s / NT, t = s % NT;
+        const int off = (t * NB + b) * 1024 + a_lane_off;
+        h = ld8(wb + off);
+        if constexpr (HI) l = ld8(wb + C::WP * 1024 + off);
+    };
+    load_b(0, B[0]);
+    load_a(0, Ah[0], Al[0]);
+#pragma unroll
+    for (int s = 0; s < NT * NB; ++s) {
+        const int b = s / NT, t = s % NT;
+        if (s + 1 < NT * NB) load_a(s + 1, Ah[(s + 1) & 1], Al[(s + 1) & 1]);
+        if (t == 0 && b + 1 < NB) load_b(b + 1, B[(b + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (HI) acc = mfma_32x32x16(Al[s & 1], B[b & 1][t], acc);
+        acc = mfma_32x32x16(Ah[s & 1], B[b & 1][t], acc);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -180,7 +223,10 @@ constexpr unsigned RDB3_SPIN_LIMIT = 1u << 22;
 template <int KS, int R, int WN, int EPI, bool XTRA, bool GATED = false>
 __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restrict__ bias, char* smem, const ConvTile& t,
                                         const X3Gate gate = X3Gate{nullptr, 0u, 1 << 30, nullptr}) {
-    using C = X3Cfg<KS, R, WN>;
+    constexpr bool FOLD = EPI == BINHIP_EPI_SUBPIX_FOLD;       // the folded fused UPNet: one accumulator tile for the wave's row pair
+    static_assert(!FOLD || (KS == 5 && R == 2 && !XTRA && !GATED), "the folded walk is the 5x5 FINAL_SUBPIX layer's");
+    constexpr int RA = FOLD ? 1 : R;
+    using C = X3CfgOf<KS, R, WN, EPI>;
     BH_TL_DECL;
     BH_TL_BEGIN();
     const int tid = threadIdx.x;
@@ -192,9 +238,9 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
     unsigned voff[C::NPJ];
     patch_offsets<C, C::PAD>(voff, t, a.H, a.W, wave, lane);
 
-    floatx16 acc[1][R];
+    floatx16 acc[1][RA];
 #pragma unroll
-    for (int r = 0; r < R; ++r)
+    for (int r = 0; r < RA; ++r)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[0][r][e] = 0.f;
 
@@ -205,7 +251,7 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
     // K loop at priority 2, epilogue at 0: the epilogue's VALU work does not take issue slots from the CU partner's MFMAs
     // (window -0.46 %, training step -0.15 %, profiles/r06_experiments.md)
     __builtin_amdgcn_s_setprio(2);
-    x3_issue_weights<C, KS>(a, smem, 0, 0, wave, lane, z);
+    x3_issue_weights<C>(a, smem, 0, 0, wave, lane, z);
     if constexpr (GATED) {
         if (gate.chunk <= 0 && gate.flags) {              // every input chunk is gated: wait before the first patch DMA
             if (tid < 9) {
@@ -249,7 +295,7 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
         if (c == 0) BH_TL_STAMP(1);
 #endif
         x3_issue_patch<C>(a, smem, c, 1, 1, wave, voff, t);
-        if (c + 1 < nchunks) x3_issue_weights<C, KS>(a, smem, c + 1, (c + 1) & 1, wave, lane, z);
+        if (c + 1 < nchunks) x3_issue_weights<C>(a, smem, c + 1, (c + 1) & 1, wave, lane, z);
         // GATED: one sub-stage before the first DMA of a gated chunk (the hi plane of chunk c + 1, issued in the lo sub-stage
         // below), lanes 0-8 of wave 0 fetch the flags of the 3 x 3 tile neighbourhood; the loads ride under this sub-stage's MFMAs
         unsigned gate_seen = gate.epoch;
@@ -264,8 +310,10 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
             }
         }
         // (5x5 only: the last chunk of a 24- / 36-channel layer on tap pairs, see x3_compute_pair)
-        const bool pair = (KS == 5) && !XTRA && a.half_last && (c + 1 == nchunks);
-        if constexpr (KS == 5 && !XTRA) {
+        const bool pair = (KS == 5) && !XTRA && !FOLD && a.half_last && (c + 1 == nchunks);
+        if constexpr (FOLD) {
+            x3_compute_fold<C, true>(smem, wb, a_lane_off, b_lane_off, acc[0][0]);
+        } else if constexpr (KS == 5 && !XTRA) {
             if (pair) x3_compute_pair<C, KS, R, true>(smem, wb, n, kg, wave, acc[0]);
             else x3_compute<C, KS, R, true>(smem, wb, a_lane_off, b_lane_off, acc[0]);
         } else {
@@ -293,7 +341,9 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
             }
         }
         if (c + 1 < nchunks) x3_issue_patch<C>(a, smem, c + 1, 0, 0, wave, voff, t);
-        if constexpr (KS == 5 && !XTRA) {
+        if constexpr (FOLD) {
+            x3_compute_fold<C, false>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0][0]);
+        } else if constexpr (KS == 5 && !XTRA) {
             if (pair) x3_compute_pair<C, KS, R, false>(smem + C::PATCH_BYTES, wb, n, kg, wave, acc[0]);
             else x3_compute<C, KS, R, false>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0]);
         } else {
@@ -302,7 +352,8 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
     }
     BH_TL_STAMP(2);
     __builtin_amdgcn_s_setprio(0);
-    conv_epilogue<1, R, 3, EPI, XTRA>(a, bias, acc, img, t.ty0 + wave * R, t.tx0, z * 32, z == 0, n, kg, t.plane_elems);
+    if constexpr (FOLD) upnet_fold_epilogue(a, bias, acc[0][0], img, t.ty0 + wave * R, t.tx0, n, kg);
+    else conv_epilogue<1, R, 3, EPI, XTRA>(a, bias, acc, img, t.ty0 + wave * R, t.tx0, z * 32, z == 0, n, kg, t.plane_elems);
     BH_TL_FINISH(a, (((img * a.tiles_y + ty) * a.tiles_x + tx) * a.ncol + z));
 }
 
@@ -317,7 +368,7 @@ __global__ void __launch_bounds__(64 * WN)
     __attribute__((amdgpu_waves_per_eu((KS == 5 && !XTRA) ? WN / 4 : WN / 2, (KS == 5 && !XTRA) ? WN / 4 : WN / 2)))
 conv_x3_kernel(const ConvKArgs a, const float* __restrict__ bias) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    x3_tile<KS, R, WN, EPI, XTRA>(a, bias, smem, tile_decode<X3Cfg<KS, R, WN>::TH>(a, a.ncol));
+    x3_tile<KS, R, WN, EPI, XTRA>(a, bias, smem, tile_decode<X3CfgOf<KS, R, WN, EPI>::TH>(a, a.ncol));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -383,7 +434,7 @@ conv_x3_rdbs_kernel(const Rdb3Args a, const float* __restrict__ bias0, const flo
 
 template <int KS, int R, int WN, int EPI, int WIDE, bool XTRA>
 static int launch_x3_x(const ConvKArgs& ka, int cout_pad, hipStream_t s) {
-    using C = X3Cfg<KS, R, WN>;
+    using C = X3CfgOf<KS, R, WN, EPI>;
     static std::atomic<unsigned long long> lds_set{0};
     if (int rc = bh_set_max_lds(&conv_x3_kernel<KS, R, WN, EPI, WIDE, XTRA>, C::LDS_BYTES, lds_set)) return rc;
     ConvKArgs a = ka;
@@ -748,8 +799,10 @@ int bh_launch_conv_x3_k5(const ConvKArgs& a, int cout_pad, hipStream_t s) {
     return launch_x3<5, X3_R, X3_WN, BINHIP_EPI_PLANES, 1>(a, cout_pad, s);
 }
 
-// the fused UPNet (BINHIP_PLAN_FUSED_UPNET): 5x5, G0 -> 12 sub-pixel channels at half resolution, fp32 NCHW full-resolution output
+// the fused UPNet (BINHIP_PLAN_FUSED_UPNET): 5x5, G0 -> 12 sub-pixel channels at half resolution, fp32 NCHW full-resolution output;
+// a.upnet_fold (BINHIP_PLAN_UPNET_FOLD): the folded 5 x 4 walk on the folded slab
 int bh_launch_conv_x3_k5_subpix(const ConvKArgs& a, hipStream_t s) {
+    if (a.upnet_fold) return launch_x3<5, X3_R, X3_WN, BINHIP_EPI_SUBPIX_FOLD, 0>(a, 32, s);
     return launch_x3<5, X3_R, X3_WN, BINHIP_EPI_FINAL_SUBPIX, 0>(a, 32, s);
 }
 

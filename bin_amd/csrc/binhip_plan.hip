@@ -104,6 +104,7 @@ struct Conv {
     int x_cpg = 0;                                          // input chunk grouping (BinConvDesc)
     int64_t x_group_stride = 0;
     Planes y, res;                                          // (the FINAL epilogues write `out` instead)
+    int reserved = 0;                                       // BINHIP_CONV_* bits of the call (BinConvDesc.reserved)
 };
 
 }  // namespace
@@ -132,6 +133,8 @@ int binhip_rdn_forward(const BinRdnPlan* p, const float* const* inputs, float* o
     const int N = p->N, H = p->H, W = p->W, nin = p->n_inputs, nt = p->nterms;
     if (!frames_ok(N, H, W, nin)) return BINHIP_E_SHAPE;
     if (nt != 1 && nt != 3) return BINHIP_E_ARG;
+    if ((p->reserved & BINHIP_PLAN_UPNET_FOLD) && (nt != 3 || (p->reserved & BINHIP_PLAN_KEEP_ACTS) || !(p->reserved & BINHIP_PLAN_FUSED_UPNET)))
+        return BINHIP_E_ARG;              // the folded slab exists for the fused UPNet of fp32-class inference only
     Shp sh;
     if (!resolve_shape(&p->shape, &sh)) return BINHIP_E_SHAPE;
     const size_t need = binhip_rdn_workspace_bytes(N, H, W, nin, nt, &p->shape);
@@ -151,7 +154,7 @@ int binhip_rdn_forward(const BinRdnPlan* p, const float* const* inputs, float* o
         BhConvCall c;
         c.d.N = N; c.d.H = l.H ? l.H : h; c.d.W = l.W ? l.W : ww; c.d.ksize = l.ks; c.d.cin_chunks = l.cin_chunks; c.d.cout = l.cout;
         c.d.cout_pad = l.cout_pad ? l.cout_pad : l.cout; c.d.nterms = nt; c.d.epilogue = l.epi; c.d.relu = l.relu;
-        c.d.x_cpg = l.x_cpg; c.d.x_group_stride = l.x_group_stride; c.d.status = p->status;
+        c.d.x_cpg = l.x_cpg; c.d.x_group_stride = l.x_group_stride; c.d.status = p->status; c.d.reserved = l.reserved;
         // a 1x1 convolution is pointwise: any reshape of the pixel grid computes the same values.  [H][W] -> [H * W / 32][32] makes a
         // workgroup's TH x 32 tile TH KiB of CONTIGUOUS bytes per plane instead of TH runs of 1 KiB at a row pitch of W * 32 B:
         // 720p window -0.3 %; the same reshape in the backward plan did not pay (profiles/r06_experiments.md)
@@ -228,8 +231,11 @@ int binhip_rdn_forward(const BinRdnPlan* p, const float* const* inputs, float* o
                           (!(p->reserved & BINHIP_PLAN_KEEP_ACTS) || (p->reserved & BINHIP_PLAN_FUSED_UPNET_TRAIN)) &&
                           sh.L + 1 < BINHIP_RDN_MAX_LAYERS && p->w_hi[sh.L] && (nt == 1 || p->w_lo[sh.L]) && p->bias[sh.L] &&
                           p->w_hi[sh.L + 1] && p->bias[sh.L + 1];
+    // BINHIP_PLAN_UPNET_FOLD: slot L holds the folded slab, the main launch walks it (fp32-class inference only)
+    const bool fold = (p->reserved & BINHIP_PLAN_UPNET_FOLD) != 0;
     if (fused_up) {
-        if ((rc = conv({.layer = sh.L, .ks = 5, .cin_chunks = c0, .cout = 12, .cout_pad = 32, .epi = BINHIP_EPI_FINAL_SUBPIX, .x = w.g1})))
+        if ((rc = conv({.layer = sh.L, .ks = 5, .cin_chunks = c0, .cout = 12, .cout_pad = 32, .epi = BINHIP_EPI_FINAL_SUBPIX, .x = w.g1,
+                        .reserved = fold ? BINHIP_CONV_UPNET_FOLD : 0})))
             return rc;
         // ... and the one-pixel full-resolution border ring from its own operators (UPNet.2 pads the intermediate, not the input)
         return bh_launch_upnet_ring(A.hi(w.g1), A.lo(w.g1), (const float*)p->w_hi[sh.L + 1], p->bias[sh.L + 1], out, inputs, nin, N, h, ww,

@@ -74,6 +74,43 @@ def fused_upnet_weights(w0, b0, w2, b2):
     return W, B
 
 
+def folded_upnet_weights(w4):
+    """The interior operator of `fused_upnet_weights` (W[4]: [12, G0, 5, 5]) re-indexed for the folded main launch
+    (BINHIP_PLAN_UPNET_FOLD).  Sub-pixel row i = 0 of a channel only has the operator rows a = 0..3 and i = 1 only a = 1..4 (columns
+    alike with j), so when channel c * 4 + i * 2 + j at matrix position (Y, X) computes its sub-pixel of half-resolution pixel
+    (Y - i, X - j), every channel reads input rows Y - 2 .. Y + 1 and columns X - 2 .. X + 1: 4 x 4 tap positions with the weight
+    W[a = t' + i][b + j], and a lane's four channels are the full-resolution block rows 2Y - 1, 2Y x columns 2X - 1, 2X.  Two matrix
+    positions (Y, X) and (Y + 1, X) then share their input rows Y - 2 + t, t = 0..4: rows 0-11 of a 32-row tile hold position Y
+    (W[a = t + i], nothing at t = 4), rows 16-27 position Y + 1 (W[a = t - 1 + i], nothing at t = 0), rows 12-15 and 28-31 are zero.
+    Returns the float64 slab [G0 / 16][t = 0..4][b = 0..3][32 rows][16 channels]; no arithmetic, every non-zero entry is one of w4's."""
+    w4 = w4.double()
+    g0 = w4.shape[1]
+    assert tuple(w4.shape) == (12, g0, 5, 5) and g0 % 16 == 0
+    wc = w4.view(12, g0 // 16, 16, 5, 5)                                # [row, chunk, channel, a, b]
+    slab = w4.new_zeros(g0 // 16, 5, 4, 32, 16)
+    for i in range(2):
+        for j in range(2):
+            rows = slice(2 * i + j, 12, 4)                              # the three colours of sub-pixel (i, j)
+            taps = wc[rows, :, :, i:i + 4, j:j + 4].permute(1, 3, 4, 0, 2)   # [chunk, t', b, colour, channel]
+            slab[:, 0:4, :, rows] = taps
+            slab[:, 1:5, :, slice(16 + 2 * i + j, 28, 4)] = taps
+    return slab
+
+
+def folded_upnet_planes(slab):
+    """The folded slab in the kernels' weight layout: rounded once to fp32, split hi = fp16(w), lo = fp16(w - hi) as
+    binhip_weights_relayout does, the two 16-byte slots of rows 8-15 and 24-31 swapped (the fragment reads' XOR swizzle)."""
+    w = slab.float()
+    hi = w.half()
+    lo = (w - hi.float()).half()
+    odd = ((torch.arange(32, device=w.device) >> 3) & 1).bool().view(32, 1, 1)
+
+    def swizzle(p):
+        p = p.view(*p.shape[:-1], 2, 8)
+        return torch.where(odd, p.flip(-2), p).reshape(-1).contiguous()
+    return swizzle(hi), swizzle(lo)
+
+
 _FUSED_MAPS = {}
 
 
@@ -217,6 +254,7 @@ class RdnWeights:
         fusable = tuple(w0.shape[2:]) == (3, 3) and w0.shape[0] == 256 and tuple(w2.shape) == (3, 64, 3, 3)
         self._up_src = src if fusable else None          # None: this weight set's UPNet is not the 256 -> shuffle -> 3 one
         self.fused_up = None
+        self.fused_fold = None             # (hi, lo) planes of the folded interior operator: inference in the fp32-class mode only
         self.fused_w4 = None
         self.fused_train = None
         self.fused_train_w4 = None
@@ -247,11 +285,14 @@ class RdnWeights:
                 self.fused_w4 = W[4].float().contiguous()
                 main = ConvWeights(self.fused_w4, B[4].float().contiguous(), nterms=self.nterms)
                 ring_w = W.permute(0, 1, 3, 4, 2).reshape(9, 12, 25, W.shape[2]).float().contiguous()
+                if self.nterms == 3:
+                    self.fused_fold = folded_upnet_planes(folded_upnet_weights(W[4]))
                 self.fused_up = (main, ring_w, B.float().contiguous())
         return self.fused_up
 
-    def fill_plan(self, plan, fused=None):
-        """`fused`: the fused UPNet's operands of THIS call (one of ensure_fused_upnet's two sets) for slots L, L + 1, or None."""
+    def fill_plan(self, plan, fused=None, fold=False):
+        """`fused`: the fused UPNet's operands of THIS call (one of ensure_fused_upnet's two sets) for slots L, L + 1, or None;
+        `fold`: slot L's weights are the folded slab of the inference set (BINHIP_PLAN_UPNET_FOLD) instead of the 5x5 form."""
         plan.shape = c_shape(self.shape)
         for i, cw in enumerate(self.layers):
             plan.w_hi[i] = cw.w_hi.data_ptr()
@@ -262,6 +303,8 @@ class RdnWeights:
             main, ring_w, ring_b = fused
             plan.w_hi[n], plan.bias[n] = main.w_hi.data_ptr(), main.bias.data_ptr()
             plan.w_lo[n] = main.w_lo.data_ptr() if main.w_lo is not None else None
+            if fold:
+                plan.w_hi[n], plan.w_lo[n] = (t.data_ptr() for t in self.fused_fold)
             plan.w_hi[n + 1], plan.w_lo[n + 1], plan.bias[n + 1] = ring_w.data_ptr(), None, ring_b.data_ptr()
 
     def dgrad(self, module, nterms=None, fused=False):
@@ -403,6 +446,10 @@ def default_plan_flags():
     # multiply-adds.  BIN_AMD_FUSED_UPNET=0: the two layers everywhere
     if _os.environ.get("BIN_AMD_FUSED_UPNET", "1") != "0":
         flags |= L.PLAN_FUSED_UPNET
+        # ... and its main launch on the folded 5 x 4 tap walk (fp32-class inference only: `_rdn_forward` clears the bit for every
+        # other call).  BIN_AMD_UPNET_FOLD=0: the 5x5 kernel and layout
+        if _os.environ.get("BIN_AMD_UPNET_FOLD", "1") != "0":
+            flags |= L.PLAN_UPNET_FOLD
     return flags
 
 
@@ -425,13 +472,17 @@ def _rdn_forward(weights, inputs, out, ws, flags, profiler):
     plan.reserved = int(flags or 0)
     plan.status = status_word(inputs[0].device).data_ptr()
     plan.profiler = profiler if profiler else None
-    fused = None
+    fused, fold = None, False
     if plan.reserved & L.PLAN_FUSED_UPNET:
         if plan.reserved & L.PLAN_FUSED_UPNET_TRAIN:
             fused = weights.ensure_fused_upnet(train=True)
         elif not (plan.reserved & L.PLAN_KEEP_ACTS):
             fused = weights.ensure_fused_upnet()
-    weights.fill_plan(plan, fused)
+            # the folded main launch exists for fp32-class inference: the bit reaches the library only with the folded slab in slot L
+            fold = bool(plan.reserved & L.PLAN_UPNET_FOLD) and fused is not None and weights.fused_fold is not None
+    if not fold:
+        plan.reserved &= ~L.PLAN_UPNET_FOLD
+    weights.fill_plan(plan, fused, fold)
     nbytes = lib.binhip_rdn_workspace_bytes(n, h, w, weights.n_inputs, weights.nterms, C.byref(plan.shape))
     if nbytes == 0:
         raise RuntimeError(f"bin_amd: unsupported RDN shape N={n} H={h} W={w} (H, W must be even)")

@@ -119,10 +119,15 @@ typedef struct BinConvDesc {
                               /*   — the 5x5 fp32-class kernel then spends that chunk's K on tap pairs and never   */
                               /*   reads x's channels 8-15 of it; other kernels ignore the bit.  Any other bit, or */
                               /*   the bit with ksize != 5, is BINHIP_E_ARG.  0 everywhere else.                   */
+                              /*   BINHIP_CONV_UPNET_FOLD (BINHIP_EPI_FINAL_SUBPIX with nterms 3 only, else        */
+                              /*   BINHIP_E_ARG): w_hi / w_lo are the FOLDED slab of the fused UPNet's operator    */
+                              /*   (BINHIP_PLAN_UPNET_FOLD below) and the launch leaves the full-resolution border */
+                              /*   ring unwritten.                                                                 */
     void*   status;           /* device uint32 status word (BINHIP_STATUS_*), OR-ed into; or NULL */
 } BinConvDesc;
 
 #define BINHIP_CONV_HALF_LAST_CHUNK 1
+#define BINHIP_CONV_UPNET_FOLD 2
 
 /* Rows per weight block for a (ksize, cout_pad, nterms) configuration (relayout needs it). */
 BINHIP_API int binhip_conv_cout_block(int ksize, int cout_pad, int nterms);
@@ -307,6 +312,18 @@ BINHIP_API int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* 
                                   /* summation order; bin_amd/rdn_plan.py builds the operands (RdnWeights.ensure_fused_upnet).     */
 #define BINHIP_PLAN_FUSED_UPNET_TRAIN 16 /* with KEEP_ACTS: the fused UPNet in the TRAINING forward too (needs the slots of          */
                                         /* BINHIP_PLAN_FUSED_UPNET); its backward is BINHIP_BWD_FUSED_UPNET                          */
+#define BINHIP_PLAN_UPNET_FOLD 32 /* with _FUSED_UPNET, nterms 3, without KEEP_ACTS (any other combination: BINHIP_E_ARG): the main  */
+                                  /* launch walks 5 input rows x 4 columns of tap positions with TWO output rows per 32-row matrix  */
+                                  /* tile.  A sub-pixel channel (c, i, j) has 4 x 4 non-zero taps of the 25; computed at matrix      */
+                                  /* position (y + i, x + j) they are the same 16 positions for every channel, and the 12 channels  */
+                                  /* of the next row fill M rows 16-27: 20 instead of 2 x 25 matrix instructions per row pair, chunk */
+                                  /* and product; the non-zero products in the same order: the same bits.  Slot L's w_hi / w_lo are */
+                                  /* then the folded                                                                                */
+                                  /* slab fp16 [G0/16][t = 0..4][b = 0..3][32 rows][16] (rows 0-11: W_eff[c,i,j][a = t + i][b + j], */
+                                  /* rows 16-27: W_eff[c,i,j][a = t - 1 + i][b + j], out-of-range a and the other rows zero; slots  */
+                                  /* swizzled as binhip_weights_relayout does), bias as before; bin_amd/rdn_plan.py                 */
+                                  /* folded_upnet_weights builds it.  The main launch then writes full-resolution rows 1 .. H - 2   */
+                                  /* and columns 1 .. W - 2; the ring launch (unchanged) writes the rest.                           */
 typedef struct BinRdnPlan {
     int32_t N, H, W;          /* full-resolution frame size (H, W even)                          */
     int32_t n_inputs;         /* 2, 3 or 5 input frames                                          */
