@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, YUV_LIB_PATH
+from .build import EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, SCENE_LIB_PATH, YUV_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -120,6 +120,13 @@ YUV_RANGE_LIMITED, YUV_RANGE_FULL = 0, 1                  # BINYUV_RANGE_*
 
 class BinYuvFormat(C.Structure):
     _fields_ = [("chroma", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32)]
+
+
+SCENE_BINS = 64                        # BINSCENE_BINS (include/binscene.h, libbinscene.so)
+
+
+class BinSceneRecord(C.Structure):
+    _fields_ = [("sad", C.c_uint64), ("hist", C.c_uint32 * SCENE_BINS)]
 
 
 _SIGNATURES = {
@@ -251,10 +258,17 @@ _YUV_SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# libbinscene.so (include/binscene.h): the scene library, loaded on first use
+SCENE_VERSION = 100                    # BINSCENE_VERSION
+_SCENE_SIGNATURES = {
+    "binscene_version": (C.c_int, []),
+    "binscene_luma_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = None
+_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = None
 
 
 def _load(path, built_path, signatures, version=None):
@@ -350,6 +364,19 @@ def yuvlib():
     if _yuvlib is None:
         _yuvlib = _load(YUV_LIB_PATH, YUV_LIB_PATH, _YUV_SIGNATURES, ("binyuv_version", YUV_VERSION))
     return _yuvlib
+
+
+def scene_exported_symbols():
+    """Names every include/binscene.h entry point must resolve to."""
+    return sorted(_SCENE_SIGNATURES)
+
+
+def scenelib():
+    """Load libbinscene.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _scenelib
+    if _scenelib is None:
+        _scenelib = _load(SCENE_LIB_PATH, SCENE_LIB_PATH, _SCENE_SIGNATURES, ("binscene_version", SCENE_VERSION))
+    return _scenelib
 
 
 def check(rc, what):

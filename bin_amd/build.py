@@ -39,6 +39,12 @@ YUV_SOURCES = ["binyuv.hip"]
 YUV_LIB_PATH = os.path.join(CSRC, "libbinyuv.so")
 YUV_HEADER = os.path.join(os.path.dirname(HERE), "include", "binyuv.h")
 
+# the scene library (include/binscene.h): luma histogram and SAD of a frame pair, the kernel of bin_amd/scene.py; a seventh shared
+# object, for the same reason
+SCENE_SOURCES = ["binscene.hip"]
+SCENE_LIB_PATH = os.path.join(CSRC, "libbinscene.so")
+SCENE_HEADER = os.path.join(os.path.dirname(HERE), "include", "binscene.h")
+
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
 # (name, sources, header, path) of every shared object: what drives the compile, the version script and the link
 LIBRARIES = (("binhip", SOURCES, HEADER, LIB_PATH), ("binopt", OPT_SOURCES, OPT_HEADER, OPT_LIB_PATH),
@@ -46,6 +52,9 @@ LIBRARIES = (("binhip", SOURCES, HEADER, LIB_PATH), ("binopt", OPT_SOURCES, OPT_
              ("binens", ENS_SOURCES, ENS_HEADER, ENS_LIB_PATH))
 # the libraries of the input / output side (same tuple layout), built and checked for staleness with the ones above
 IO_LIBRARIES = (("binyuv", YUV_SOURCES, YUV_HEADER, YUV_LIB_PATH),)
+# the libraries that measure frames without changing them (same tuple layout), built and checked likewise
+ANALYSIS_LIBRARIES = (("binscene", SCENE_SOURCES, SCENE_HEADER, SCENE_LIB_PATH),)
+PRODUCT_LIBRARIES = LIBRARIES + IO_LIBRARIES + ANALYSIS_LIBRARIES
 
 
 def _declared(header, macro, prefix):
@@ -85,21 +94,26 @@ def yuv_abi_symbols():
     return _declared(YUV_HEADER, "BINYUV_API", "binyuv")
 
 
+def scene_abi_symbols():
+    """The entry points include/binscene.h declares (every BINSCENE_API declaration), in header order."""
+    return _declared(SCENE_HEADER, "BINSCENE_API", "binscene")
+
+
 def _stale():
-    libs = [path for _, _, _, path in LIBRARIES + IO_LIBRARIES]
+    libs = [path for _, _, _, path in PRODUCT_LIBRARIES]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    deps += [header for _, _, header, _ in LIBRARIES + IO_LIBRARIES]
+    deps += [header for _, _, header, _ in PRODUCT_LIBRARIES]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def build_library(force=False, verbose=True, defines=(), out=None):
     """Compile every HIP source for gfx950 into bin_amd/csrc/libbinhip.so (and, for the product build, the optimizer
     library bin_amd/csrc/libbinopt.so, the gradient-guard library bin_amd/csrc/libbingrad.so, the weight-average library
-    bin_amd/csrc/libbinema.so, the self-ensemble library bin_amd/csrc/libbinens.so and the video library
-    bin_amd/csrc/libbinyuv.so beside it).
+    bin_amd/csrc/libbinema.so, the self-ensemble library bin_amd/csrc/libbinens.so, the video library
+    bin_amd/csrc/libbinyuv.so and the scene library bin_amd/csrc/libbinscene.so beside it).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain): libbinhip.so alone, under another name.  The
@@ -110,7 +124,7 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     objdir = CSRC if out is None else os.path.dirname(os.path.abspath(out))
     os.makedirs(objdir, exist_ok=True)
     tag = "" if out is None else "." + os.path.splitext(os.path.basename(out))[0]
-    libraries = LIBRARIES + IO_LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
+    libraries = PRODUCT_LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
     procs, objs = [], {}
     for name, sources, _, _ in libraries:
         for src in sources:

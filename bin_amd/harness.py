@@ -6,6 +6,8 @@ import torch
 
 from .utils import util
 
+builtins_range = range                     # (interpolate_video has a parameter called `range`)
+
 
 def shard_windows(n_windows, rank, world):
     """Contiguous, balanced [begin, end) range of the flattened (clip, frame) window list for `rank`."""
@@ -100,18 +102,24 @@ def video_slots(index, n_windows):
 
 
 @torch.no_grad()
-def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None):
+def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None, scene_cut=None):
     """interpolate_clip's loop over the frames of a Y4M stream.  `payloads`: [T, frame_bytes] uint8 (host or device), the frames of
     `header` (bin_amd/video.py).  Returns the [2(T-1), frame_bytes] uint8 device tensor of the output payloads in display order,
     D0, I0, D1, I1, ..., D(T-2), I(T-2): exactly the frames the folder runner writes for a one-clip folder, in name order — window 0
     yields Ft_p[8], Ft_p[13], Ft_p[12], a middle window Ft_p[13], Ft_p[12], the last one Ft_p[13] (video_slots), so a first-in
     first-out writer is in order already.  YUV -> padded frame and frame -> YUV are the kernels of libbinyuv.so (ops.yuv_to_frame /
     ops.frame_to_yuv), the padded frames cached across the 5-of-6 overlap.  matrix / range: video.resolve_format.  reuse_stage1,
-    batch, ensemble: as in interpolate_clip."""
+    batch, ensemble: as in interpolate_clip.
+    scene_cut: None = the stream is one clip (the path above).  A number is the threshold of `detect_cuts`, an iterable of ints the
+    cut positions themselves (c: frames c-1 and c are of different scenes).  The windows then stay inside their scene
+    (bin_amd/scene.py::plan): every scene comes out as if it ran alone, plus its last deblurred frame, and the frame between two
+    scenes is the deblurred frame before the cut, held.  Same length, same layout."""
     from . import ops, video
     T = payloads.shape[0]
     if T < 2:
         raise ValueError(f"interpolate_video needs at least 2 frames (got {T})")
+    if scene_cut is not None:
+        return _interpolate_video_scenes(netG, payloads, header, matrix, range, reuse_stage1, batch, ensemble, scene_cut)
     fmt = video.resolve_format(header, matrix, range)
     h, w = header.height, header.width
     if payloads.dim() != 2 or payloads.dtype != torch.uint8 or payloads.shape[1] != header.frame_bytes:
@@ -136,6 +144,108 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
                 n_out += 1
         ops.check_status(dev)             # (synchronises, as the image download of interpolate_clip does at this point)
     assert n_out == 2 * n_win
+    return out
+
+
+def luma_records(payloads, header, device=None):
+    """[(sad, hist)] of the T frames of a stream (ops.luma_stats over the Y planes, frame 0 against nothing): one launch per frame
+    into one [T, 264] device buffer, one download."""
+    from . import ops
+    h, w = header.height, header.width
+    if payloads.dim() != 2 or payloads.dtype != torch.uint8 or payloads.shape[1] != header.frame_bytes:
+        raise ValueError(f"payloads must be uint8 [T, {header.frame_bytes}] for this header (got {payloads.dtype} {tuple(payloads.shape)})")
+    if not payloads.is_cuda:
+        payloads = payloads.to(device if device is not None else "cuda")
+    payloads = payloads.contiguous()
+    T = payloads.shape[0]
+    recs = torch.empty((T, ops.LUMA_RECORD_BYTES), dtype=torch.uint8, device=payloads.device)
+    for i in builtins_range(T):
+        ops.luma_stats(payloads[i, :h * w], payloads[i - 1, :h * w] if i else None, h, w, out=recs[i])
+    host = recs.cpu()
+    return [ops.read_luma_record(host[i]) for i in builtins_range(T)]
+
+
+def detect_cuts(payloads, header, threshold, min_mad=0.0, device=None):
+    """The cut positions of a stream: every i in 1 .. T-1 whose frame opens a scene by scene.is_cut on the luma statistics the
+    kernel of libbinscene.so measures.  `payloads`: [T, frame_bytes] uint8, host or device (a host stream goes to `device`, default the current one)."""
+    from . import scene
+    recs = luma_records(payloads, header, device)
+    h, w = header.height, header.width
+    return [i for i in builtins_range(1, len(recs)) if scene.is_cut(recs[i - 1], recs[i], h, w, threshold, min_mad)]
+
+
+def _interpolate_video_scenes(netG, payloads, header, matrix, range, reuse_stage1, batch, ensemble, scene_cut):
+    """interpolate_video with scene cuts: the windows of scene.plan.  Windows of different scenes may share a batched forward (they
+    are independent); the memos that assume consecutive windows (the stage-1 memo, the ensemble's per-orientation ones) are dropped
+    whenever a window's scene is not the one of the forward before."""
+    from . import ops, scene, video
+    from .ensemble import SelfEnsemble, parse_group
+    T = payloads.shape[0]
+    fmt = video.resolve_format(header, matrix, range)
+    h, w = header.height, header.width
+    dev = next(netG.parameters()).device
+    if isinstance(scene_cut, (int, float)):
+        cuts = detect_cuts(payloads, header, float(scene_cut), device=dev)
+    else:
+        cuts = scene.check_cuts(scene_cut, T)
+    if payloads.dim() != 2 or payloads.dtype != torch.uint8 or payloads.shape[1] != header.frame_bytes:
+        raise ValueError(f"payloads must be uint8 [T, {header.frame_bytes}] for this header (got {payloads.dtype} {tuple(payloads.shape)})")
+    pads = util.pad_sizes(h, w)
+    l, r, t, b = pads
+    cache = {}
+
+    def frame(i):
+        if i not in cache:
+            cache[i] = ops.yuv_to_frame(payloads[i].to(dev).contiguous(), h, w, fmt, pads)
+        return cache[i]
+
+    work, holds = [], []                                  # (scene start, ids, outputs) per forward; the held positions
+    for s, e in scene.segments(T, cuts):
+        for i in builtins_range(s, min(e, T - 1)):
+            ids, outputs = scene.plan(i, s, e, T)
+            holds += [pos for pos, slot in outputs if slot is scene.HOLD]
+            if ids is not None:
+                work.append((s, ids, [(pos, slot) for pos, slot in outputs if slot is not scene.HOLD]))
+
+    inner = netG.module if hasattr(netG, "module") else netG
+    batch = max(1, int(batch))
+    stage1_cache = {} if (reuse_stage1 and batch == 1 and getattr(inner, "reuse_schedule", False)) else None
+    ens = SelfEnsemble(netG, ensemble) if parse_group(ensemble) else None
+    n_win = T - 1
+    out = torch.empty((2 * n_win, header.frame_bytes), dtype=torch.uint8, device=dev)
+    written, current = set(), None
+    for first in builtins_range(0, len(work), batch):
+        group = work[first:first + batch]
+        for k in [k for k in cache if k < min(group[0][1])]:
+            del cache[k]
+        if group[0][0] != current:                        # a scene change: nothing memoised belongs to this scene
+            current = group[0][0]
+            if stage1_cache is not None:
+                stage1_cache.clear()
+            if ens is not None:
+                ens.reset()
+        if len(group) == 1:
+            ids = group[0][1]
+            inputs = [frame(i) for i in ids]
+            if ens is not None:
+                Ft_p = ens.window(ids, inputs, slots=(13, 8, 12), reuse=stage1_cache is not None)
+            elif stage1_cache is not None:
+                Ft_p = netG(*inputs, stage1_cache=stage1_cache)
+            else:
+                Ft_p = netG(*inputs)
+        else:
+            inputs = [torch.cat([frame(ids[k]) for _, ids, _ in group], 0) for k in builtins_range(6)]
+            Ft_p = ens(inputs, slots=(13, 8, 12)) if ens is not None else netG(*inputs)
+        for j, (_, _, outputs) in enumerate(group):
+            for pos, slot in outputs:
+                ops.frame_to_yuv(Ft_p[slot][j:j + 1], t, l, h, w, fmt, out=out[pos])
+                written.add(pos)
+        ops.check_status(dev)
+    for pos in holds:                                     # I_i across a cut: D_i again, the same payload bytes
+        assert pos - 1 in written
+        out[pos].copy_(out[pos - 1])
+        written.add(pos)
+    assert written == set(builtins_range(2 * n_win))
     return out
 
 

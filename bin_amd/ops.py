@@ -595,6 +595,48 @@ def frame_to_yuv(frame, top, left, h, w, fmt, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------------- scene glue (libbinscene.so)
+LUMA_RECORD_BYTES = C.sizeof(L.BinSceneRecord)          # 264: a uint64 SAD, then 64 uint32 bins
+
+
+def luma_stats(cur_y, prev_y, h, w, out=None):
+    """The scene-cut statistics of a luma plane (include/binscene.h): `cur_y`, `prev_y` (or None) are contiguous uint8 device tensors
+    of h*w bytes, views into a payload at any byte offset included.  Returns the device uint8 [264] record (`out` when given; it must
+    be 8-byte aligned): the sum of |cur - prev| and the 64-bin histogram of cur >> 2.  `read_luma_record` reads a downloaded one."""
+    _need_cuda(cur_y, prev_y, out)
+    if h < 1 or w < 1:
+        raise ValueError(f"bin_amd: luma_stats needs a positive size (got {h}x{w})")
+    for name, t in (("cur_y", cur_y), ("prev_y", prev_y)):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != h * w):
+            raise ValueError(f"bin_amd: {name} of a {w}x{h} frame is a contiguous uint8 tensor of {h * w} bytes "
+                             f"(got {t.dtype} {tuple(t.shape)})")
+    if prev_y is not None and prev_y.device != cur_y.device:
+        raise ValueError("bin_amd: luma_stats takes two planes of one device")
+    if out is None:
+        out = torch.empty(LUMA_RECORD_BYTES, dtype=torch.uint8, device=cur_y.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() != LUMA_RECORD_BYTES or \
+            out.device != cur_y.device:
+        raise ValueError(f"bin_amd: a luma record is a contiguous uint8 tensor of [{LUMA_RECORD_BYTES}] bytes on the planes' device "
+                         f"(got {out.dtype} {tuple(out.shape)})")
+    with on_device(cur_y):
+        L.check(L.scenelib().binscene_luma_stats(_ptr(cur_y), _ptr(prev_y), h, w, _ptr(out), _stream()), "luma_stats")
+    return out
+
+
+def read_luma_record(record):
+    """(sad: int, hist: np.ndarray[64] of int64) of a luma record on the host: a uint8 [264] tensor or array, or its bytes."""
+    import numpy as np
+    if isinstance(record, torch.Tensor):
+        if record.is_cuda:
+            raise ValueError("bin_amd: read_luma_record reads a downloaded record (record.cpu())")
+        record = record.numpy()
+    raw = bytes(memoryview(np.ascontiguousarray(record)).cast("B"))
+    if len(raw) != LUMA_RECORD_BYTES:
+        raise ValueError(f"bin_amd: a luma record has {LUMA_RECORD_BYTES} bytes (got {len(raw)})")
+    rec = L.BinSceneRecord.from_buffer_copy(raw)
+    return int(rec.sad), np.array(rec.hist, dtype=np.int64)
+
+
 def pixel_unshuffle(x, r=2):
     """Exact space-to-depth: out[b, c*r*r + i*r + j, y, x] = in[b, c, y*r+i, x*r+j] (reference RDN.py:107-132)."""
     _need_cuda(x)

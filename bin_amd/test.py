@@ -56,6 +56,11 @@ def parse_args(argv=None):
                    help="auto: bt709 when W >= 1280 or H > 576, else bt601")
     p.add_argument("--yuv_range", choices=["auto", "limited", "full"], default="auto",
                    help="auto: the stream's XCOLORRANGE tag, else limited")
+    p.add_argument("--scene_cut", type=float, default=None, metavar="T",
+                   help="--input_video: detect scene cuts (luma histogram distance >= T, bin_amd/scene.py) and interpolate within "
+                        "scenes only; off by default")
+    p.add_argument("--scene_cut_min_mad", type=float, default=0.0, metavar="M",
+                   help="--scene_cut: a cut also needs a mean absolute luma difference >= M")
     p.add_argument("--gpu_id", type=str, default=None)
     p.add_argument("--time_step", type=float, default=0.5)
     p.add_argument("--opt", type=str, required=True, help="Path to option YAML file.")
@@ -88,6 +93,10 @@ def check_args(args):
     truth nor several ranks.  Anything else is refused here: before the options are read or the model is built."""
     video = args.input_video is not None or args.output_video is not None
     folder = args.input_path is not None or args.output_path is not None
+    if not video and (getattr(args, "scene_cut", None) is not None or getattr(args, "scene_cut_min_mad", 0.0)):
+        raise ValueError("--scene_cut / --scene_cut_min_mad: scene cuts are looked for in a video only (--input_video)")
+    if getattr(args, "scene_cut", None) is None and getattr(args, "scene_cut_min_mad", 0.0):
+        raise ValueError("--scene_cut_min_mad goes with --scene_cut")
     if video and folder:
         raise ValueError("give either --input_path / --output_path or --input_video / --output_video, not both kinds")
     if video:
@@ -506,8 +515,12 @@ def run_video(args, opt, stats=None):
     cached across the 5-of-6 overlap of consecutive windows; ops.frame_to_yuv packs each output into a device payload, the copy
     stream moves it to page-locked memory and ONE writer thread writes the frames in the order they were queued, which is display
     order (harness.video_slots).  The length of a piped stream is not known ahead: window i runs once frame i + 3 or the end of
-    the stream has been read.  Logging goes to stderr and the log file, never to stdout (--output_video -)."""
-    from . import video
+    the stream has been read.  Logging goes to stderr and the log file, never to stdout (--output_video -).
+    --scene_cut: ops.luma_stats runs on the upload stream right behind each frame's upload (its inputs are the payloads alone), its
+    264-byte record comes back through a page-locked buffer and an event of that stream; the compute stream is never waited on for
+    it.  Window i needs the cut flags up to the pair (i + 2, i + 3), frames read_to(i + 3) has taken already; the windows are those
+    of scene.plan, the memos are dropped at a scene change."""
+    from . import scene, video
     from .ensemble import SelfEnsemble, parse_group
     log_root = os.getcwd() if args.output_video == "-" else os.path.dirname(os.path.abspath(args.output_video))
     os.makedirs(log_root, exist_ok=True)
@@ -558,6 +571,40 @@ def run_video(args, opt, stats=None):
 
     upload = _Uploader(dev, upload_stream, free_in.put)   # finished uploads hand their buffer back to the reader
 
+    scene_on = args.scene_cut is not None
+    cuts, n_dup = [], 0                                # cut positions found so far; frames equal to the one before
+    rec_pending, rec_free, rec_prev = {}, [], None     # frame -> (page-locked record, event); spare buffers; (sad, hist) of the frame before
+    prev_payload, n_resolved = None, 0                 # kept alive until the next frame's statistics are queued; frames decided so far
+
+    def queue_stats(i, g):
+        """Frame i's statistics on the upload stream, behind its upload; the record goes to page-locked memory behind an event."""
+        nonlocal prev_payload
+        with torch.cuda.stream(upload_stream):
+            rec = ops.luma_stats(g[:h * w], None if prev_payload is None else prev_payload[:h * w], h, w)
+            host = rec_free.pop() if rec_free else torch.empty(ops.LUMA_RECORD_BYTES, dtype=torch.uint8, pin_memory=True)
+            host.copy_(rec, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        rec_pending[i] = (host, ev)
+        prev_payload = g
+
+    def resolve_cuts():
+        """Decide every frame whose statistics were queued (waits on the upload stream's events only)."""
+        nonlocal n_resolved, n_dup, rec_prev
+        while n_resolved < n_read:
+            host, ev = rec_pending.pop(n_resolved)
+            ev.synchronize()
+            rec = ops.read_luma_record(host)
+            rec_free.append(host)
+            if n_resolved > 0:
+                n_dup += scene.is_duplicate(rec)
+                if scene.is_cut(rec_prev, rec, h, w, args.scene_cut, args.scene_cut_min_mad):
+                    cuts.append(n_resolved)
+                    log.info("scene cut at input frame %d (output frame %d): distance %.4f, mean |dY| %.3f", n_resolved, 2 * n_resolved,
+                             scene.distance(rec_prev[1], rec[1], h, w), rec[0] / float(h * w))
+            rec_prev = rec
+            n_resolved += 1
+
     def read_to(i):
         """Take frames from the reader until frame `i` is on the device or the stream has ended."""
         nonlocal n_read, n_frames
@@ -568,7 +615,10 @@ def run_video(args, opt, stats=None):
             elif isinstance(item, BaseException):
                 raise item
             else:
-                frames_dev[n_read] = ops.yuv_to_frame(upload(item), h, w, fmt, pads)
+                g = upload(item)
+                if scene_on:
+                    queue_stats(n_read, g)
+                frames_dev[n_read] = ops.yuv_to_frame(g, h, w, fmt, pads)
                 n_read += 1
 
     out_header = header.doubled()
@@ -600,25 +650,39 @@ def run_video(args, opt, stats=None):
 
     timer, stamps, group = AverageMeter(), [], []
     n_written = 0
+    memo_scene, last_payload = 0, None                 # the scene the memos belong to; the device payload queued last (a hold repeats it)
 
     def flush():
-        nonlocal n_written
+        nonlocal n_written, memo_scene, last_payload
         if not group:
             return
         t0 = time.time()
-        if len(group) == 1:
-            inputs = group[0][1]
+        runs = [g for g in group if g[1] is not None]  # (with --scene_cut a window may only hold a frame: no forward)
+        if len(runs) == 1:
+            if scene_on and runs[0][3] != memo_scene:  # a scene change: nothing memoised belongs to this scene
+                memo_scene = runs[0][3]
+                stage1_cache.clear()
+                if ens is not None:
+                    ens.reset()
+            inputs = runs[0][1]
             if ens is not None:
-                Ft_p = ens.window(group[0][2], inputs, slots=OUT_KEYS, reuse=reuse)
+                Ft_p = ens.window(runs[0][2], inputs, slots=OUT_KEYS, reuse=reuse)
             else:
                 Ft_p = netG(*inputs, stage1_cache=stage1_cache) if reuse else netG(*inputs)
-        else:
-            inputs = [torch.cat([g[1][k] for g in group], 0) for k in range(6)]
+        elif runs:
+            memo_scene = None                          # (a batched forward uses no memo; a single one after it starts afresh)
+            inputs = [torch.cat([g[1][k] for g in runs], 0) for k in range(6)]
             Ft_p = netG(*inputs) if ens is None else ens(inputs, slots=OUT_KEYS)
-        for j, (slots, _, _) in enumerate(group):
+        j = -1
+        for slots, frames, _, _ in group:
+            j += frames is not None
             outs = torch.empty((3, nbytes), dtype=torch.uint8, device=dev)
             for k, slot in enumerate(slots):
-                ops.frame_to_yuv(Ft_p[slot][j:j + 1], t, l, h, w, fmt, out=outs[k])
+                if slot is scene.HOLD:
+                    outs[k].copy_(last_payload)
+                else:
+                    ops.frame_to_yuv(Ft_p[slot][j:j + 1], t, l, h, w, fmt, out=outs[k])
+                last_payload = outs[k]
             ready = torch.cuda.Event()
             ready.record()
             host = free_out.pop() if free_out else torch.empty((3, nbytes), dtype=torch.uint8, pin_memory=True)
@@ -638,6 +702,7 @@ def run_video(args, opt, stats=None):
 
     t_all = time.time()
     index = 0
+    scene_start = 0
     try:
         with torch.no_grad():
             while True:
@@ -645,12 +710,21 @@ def run_video(args, opt, stats=None):
                 if n_frames is not None and index > n_frames - 2:
                     break
                 known = n_frames if n_frames is not None else index + 4      # clamping only bites once the end is known
-                ids = harness.window_frame_ids(index, known)
-                slots = harness.video_slots(index, n_frames - 1 if n_frames is not None else index + 2)
-                group.append((slots, [frames_dev[f] for f in ids], ids))
-                for fid in [f for f in frames_dev if f < min(ids)]:
+                if scene_on:
+                    resolve_cuts()                      # every pair up to (index + 2, index + 3), or up to the stream's end
+                    if index in cuts:
+                        scene_start = index
+                    # the scene's end: the next cut when it is in sight; beyond index + 3 any end gives the same window
+                    scene_end = next((c for c in cuts if c > index), known)
+                    ids, outputs = scene.plan(index, scene_start, scene_end, n_frames)
+                    slots = tuple(slot for _, slot in outputs)
+                else:
+                    ids = harness.window_frame_ids(index, known)
+                    slots = harness.video_slots(index, n_frames - 1 if n_frames is not None else index + 2)
+                group.append((slots, None if ids is None else [frames_dev[f] for f in ids], ids, scene_start))
+                for fid in [f for f in frames_dev if ids is not None and f < min(ids)]:
                     del frames_dev[fid]
-                if len(group) >= args.batch:
+                if sum(g[1] is not None for g in group) >= args.batch:
                     flush()
                 index += 1
             flush()
@@ -668,8 +742,12 @@ def run_video(args, opt, stats=None):
     wall = time.time() - t_all
     log.info("frames in: %d  out: %d  windows: %d  wall: %.2f s  -> %.2f interpolated frames/s (IO included); net+glue per window "
              "%.4f s", n_frames, n_written, index, wall, index / max(wall, 1e-9), timer.avg)
+    if scene_on:
+        log.info("scene cuts: %d at input frames %s; duplicates: %d", len(cuts), ", ".join(str(c) for c in cuts) or "-", n_dup)
     if stats is not None:
         stats.update(windows=index, wall=wall, net_s_per_window=timer.avg, stamps=[s - t_all for s in stamps], frames_out=n_written)
+        if scene_on:
+            stats.update(cuts=list(cuts))
     return 0
 
 
