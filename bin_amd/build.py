@@ -9,7 +9,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["binhip_conv.hip", "binhip_conv_x3.hip", "binhip_fused.hip", "binhip_fused_x3.hip", "binhip_wgrad.hip", "binhip_layout.hip",
+SOURCES = ["binhip_conv.hip", "binhip_relayout.hip", "binhip_conv_x3.hip", "binhip_fused.hip", "binhip_fused_x3.hip", "binhip_wgrad.hip", "binhip_layout.hip",
            "binhip_convlstm.hip", "binhip_loss.hip", "binhip_upnet_bwd.hip", "binhip_plan.hip", "binhip_metrics.hip", "binhip_data.hip"]
 LIB_PATH = os.path.join(CSRC, "libbinhip.so")
 # the optimizer library (include/binopt.h): a shared object of its own, so that libbinhip.so's interface does not change with it

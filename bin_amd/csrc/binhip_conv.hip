@@ -428,258 +428,8 @@ static int bh_dispatch_conv(const ConvKArgs& a, int k, int cp, int nt, int e, hi
     return BINHIP_E_SHAPE;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Weight relayout: OIHW fp32 -> [cout_pad/cb][cin_chunks][k*k][cb][16] fp16 hi/lo, slot-swizzled.
-__device__ __forceinline__ void relayout_body(long long t, const float* __restrict__ w, const float* __restrict__ bias,
-                                              int cout, int cin, int ks, int cout_pad, int nchunks, int cb, int shuffle,
-                                              _Float16* __restrict__ w_hi, _Float16* __restrict__ w_lo,
-                                              float* __restrict__ bias_out) {
-    const long long total = (long long)cout_pad * nchunks * ks * ks * 2;   // 16-byte slots
-    if (t < cout_pad) {
-        int src = (int)t;
-        if (shuffle) { const int cq = cout / 4; const int sub = (int)t / cq, cc = (int)t % cq; src = cc * 4 + sub; }
-        bias_out[t] = (src < cout && bias) ? bias[src] : 0.f;
-    }
-    if (t >= total) return;
-    const int s = (int)(t & 1);
-    long long u = t >> 1;
-    const int row = (int)(u % cb); u /= cb;
-    const int tap = (int)(u % (ks * ks)); u /= (ks * ks);
-    const int c = (int)(u % nchunks); u /= nchunks;
-    const int zb = (int)u;
-    const int rg = zb * cb + row;
-    int src = rg;
-    if (shuffle) { const int cq = cout / 4; const int sub = rg / cq, cc = rg % cq; src = cc * 4 + sub; }
-    const int cg = s ^ ((row >> 3) & 1);
-    const int dy = tap / ks, dx = tap % ks;
-    half8 hv, lv;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int ci = c * 16 + cg * 8 + e;
-        float v = 0.f;
-        if (src < cout && ci < cin) v = w[(((long long)src * cin + ci) * ks + dy) * ks + dx];
-        hv[e] = (_Float16)v;
-        lv[e] = (_Float16)(v - (float)hv[e]);
-    }
-    *reinterpret_cast<half8*>(w_hi + t * 8) = hv;
-    if (w_lo) *reinterpret_cast<half8*>(w_lo + t * 8) = lv;
-}
-__global__ void relayout_kernel(const float* __restrict__ w, const float* __restrict__ bias, int cout, int cin,
-                                int ks, int cout_pad, int nchunks, int cb, int shuffle,
-                                _Float16* __restrict__ w_hi, _Float16* __restrict__ w_lo,
-                                float* __restrict__ bias_out) {
-    relayout_body((long long)blockIdx.x * blockDim.x + threadIdx.x, w, bias, cout, cin, ks, cout_pad, nchunks, cb, shuffle,
-                  w_hi, w_lo, bias_out);
-}
-
-// Backward-data weights: the dgrad of a stride-1 "same" conv is the same conv with in/out channels swapped and the
-// taps flipped: W'[r = ci][j = co][dy][dx] = W[co][ci][k-1-dy][k-1-dx].  shuffle != 0: the dgrad input channels j
-// are in the PixelShuffle-permuted order of UPNet.0's rows (j = sub*(cout/4) + c  <->  co = c*4 + sub).
-__device__ __forceinline__ void relayout_dgrad_body(long long t, const float* __restrict__ w, int cout, int cin, int ks,
-                                                    int rows_pad, int nchunks, int cb, int shuffle,
-                                                    _Float16* __restrict__ w_hi, _Float16* __restrict__ w_lo,
-                                                    float* __restrict__ bias_out) {
-    const long long total = (long long)rows_pad * nchunks * ks * ks * 2;
-    if (t < rows_pad) bias_out[t] = 0.f;
-    if (t >= total) return;
-    const int s = (int)(t & 1);
-    long long u = t >> 1;
-    const int row = (int)(u % cb); u /= cb;
-    const int tap = (int)(u % (ks * ks)); u /= (ks * ks);
-    const int c = (int)(u % nchunks); u /= nchunks;
-    const int zb = (int)u;
-    const int r = zb * cb + row;                      // = original input channel
-    const int cg = s ^ ((row >> 3) & 1);
-    const int dy = ks - 1 - tap / ks, dx = ks - 1 - tap % ks;
-    half8 hv, lv;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int j = c * 16 + cg * 8 + e;            // dgrad input channel = original output channel (maybe permuted)
-        int co = j;
-        if (shuffle) { const int cq = cout / 4; const int sub = j / cq, cc = j % cq; co = cc * 4 + sub; }
-        float v = 0.f;
-        if (r < cin && j < cout) v = w[(((long long)co * cin + r) * ks + dy) * ks + dx];
-        hv[e] = (_Float16)v;
-        lv[e] = (_Float16)(v - (float)hv[e]);
-    }
-    *reinterpret_cast<half8*>(w_hi + t * 8) = hv;
-    if (w_lo) *reinterpret_cast<half8*>(w_lo + t * 8) = lv;
-}
-__global__ void relayout_dgrad_kernel(const float* __restrict__ w, int cout, int cin, int ks, int rows_pad,
-                                      int nchunks, int cb, int shuffle, _Float16* __restrict__ w_hi,
-                                      _Float16* __restrict__ w_lo, float* __restrict__ bias_out) {
-    relayout_dgrad_body((long long)blockIdx.x * blockDim.x + threadIdx.x, w, cout, cin, ks, rows_pad, nchunks, cb, shuffle,
-                        w_hi, w_lo, bias_out);
-}
-
-// Backward-data of a residual dense block in GATHER form.  Group g of the block's concat buffer (g = 0: the 96 input
-// channels, g = 1..3: the 32 outputs of conv g-1) receives dgrad contributions from every later conv c >= cmin
-// (cmin = g for g >= 1, 0 for g = 0).  Stacking those convs' masked output gradients G_c (32 channels each, contiguous
-// in the gradient buffer) along K turns the sum into ONE forward-shaped conv per group:
-//   Wg[r][32 (c - cmin) + co][dy][dx] = W_c[co][base_g + r][2-dy][2-dx],   base_0 = 0, base_g = 96 + 32 (g - 1).
-//   General block (G0, C, G): rows = G0 (group 0) or G, K = (C - group) G stacked output gradients, base_g = G0 + G (g - 1).
-struct GatherSrc { const float* w[BINHIP_RDN_MAX_CONVS + 1]; int G0, G; };
-__device__ __forceinline__ void relayout_rdb_gather_body(long long t, const GatherSrc& src, int group, int rows, int nchunks,
-                                                         int cb, _Float16* __restrict__ w_hi, _Float16* __restrict__ w_lo,
-                                                         float* __restrict__ bias_out) {
-    const long long total = (long long)rows * nchunks * 9 * 2;
-    if (t < rows) bias_out[t] = 0.f;
-    if (t >= total) return;
-    const int s = (int)(t & 1);
-    long long u = t >> 1;
-    const int row = (int)(u % cb); u /= cb;
-    const int tap = (int)(u % 9); u /= 9;
-    const int c = (int)(u % nchunks); u /= nchunks;
-    const int r = (int)u * cb + row;
-    const int cg = s ^ ((row >> 3) & 1);
-    const int dy = 2 - tap / 3, dx = 2 - tap % 3;
-    const int G0 = src.G0, G = src.G;
-    const int cmin = group;                            // group 0 and group 1.. both start at conv index == group
-    const int ci = (group == 0) ? r : G0 + G * (group - 1) + r;
-    const int j0 = c * 16 + cg * 8;                    // 8 consecutive K entries never straddle a conv (G is a multiple of 32)
-    const int conv = cmin + j0 / G;
-    const int cin_c = G0 + G * conv;
-    const float* w = src.w[conv];
-    half8 hv, lv;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int co = (j0 % G) + e;
-        const float v = w[(((long long)co * cin_c + ci) * 3 + dy) * 3 + dx];
-        hv[e] = (_Float16)v;
-        lv[e] = (_Float16)(v - (float)hv[e]);
-    }
-    *reinterpret_cast<half8*>(w_hi + t * 8) = hv;
-    if (w_lo) *reinterpret_cast<half8*>(w_lo + t * 8) = lv;
-}
-__global__ void relayout_rdb_gather_kernel(GatherSrc src, int group, int rows, int nchunks, int cb,
-                                           _Float16* __restrict__ w_hi, _Float16* __restrict__ w_lo,
-                                           float* __restrict__ bias_out) {
-    relayout_rdb_gather_body((long long)blockIdx.x * blockDim.x + threadIdx.x, src, group, rows, nchunks, cb, w_hi, w_lo, bias_out);
-}
-
-// ---- batched relayout: a training step re-lays-out every weight of a set after each optimizer update (66 forward + 66
-// backward layouts per set); one launch per <= RELAYOUT_BATCH layers instead of one per layer (round 3: 528 -> 24 launches
-// per step of ~4.5 us each).  Block b of the grid belongs to the item whose block range contains it.
-#define RELAYOUT_BATCH 22
-struct RelayoutBatch {
-    BinRelayoutItem it[RELAYOUT_BATCH];
-    unsigned start[RELAYOUT_BATCH + 1];
-    int n;
-};
-__global__ void __launch_bounds__(256)
-relayout_batch_kernel(const RelayoutBatch rb) {
-    const unsigned b = blockIdx.x;
-    int li = 0;
-#pragma unroll
-    for (int i = 1; i < RELAYOUT_BATCH; ++i)
-        if (i < rb.n && b >= rb.start[i]) li = i;
-    const BinRelayoutItem& L = rb.it[li];
-    const long long t = (long long)(b - rb.start[li]) * 256 + threadIdx.x;
-    if (L.kind == BINHIP_RELAYOUT_FWD) {
-        relayout_body(t, L.w[0], L.bias, L.cout, L.cin, L.ksize, L.rows_pad, L.cin_chunks, L.cout_block, L.shuffle_or_group,
-                      (_Float16*)L.w_hi, (_Float16*)L.w_lo, L.bias_out);
-    } else if (L.kind == BINHIP_RELAYOUT_DGRAD) {
-        relayout_dgrad_body(t, L.w[0], L.cout, L.cin, L.ksize, L.rows_pad, L.cin_chunks, L.cout_block, L.shuffle_or_group,
-                            (_Float16*)L.w_hi, (_Float16*)L.w_lo, L.bias_out);
-    } else {
-        GatherSrc src;
-#pragma unroll
-        for (int i = 0; i <= BINHIP_RDN_MAX_CONVS; ++i) src.w[i] = L.w[i];
-        src.G0 = L.shape.G0 > 0 ? L.shape.G0 : 96;
-        src.G = L.shape.G > 0 ? L.shape.G : 32;
-        relayout_rdb_gather_body(t, src, L.shuffle_or_group, L.rows_pad, L.cin_chunks, L.cout_block, (_Float16*)L.w_hi,
-                                 (_Float16*)L.w_lo, L.bias_out);
-    }
-}
-
+// (the weight relayout that feeds these kernels: binhip_relayout.hip)
 extern "C" {
-
-int binhip_weights_relayout_batch(const BinRelayoutItem* items, int n, void* stream) {
-    if (!items || n <= 0) return BINHIP_E_ARG;
-    for (int i = 0; i < n; ++i) {                      // validate everything before the first launch
-        const BinRelayoutItem& L = items[i];
-        if (!L.w[0] || !L.w_hi || !L.bias_out) return BINHIP_E_ARG;
-        if (L.kind == BINHIP_RELAYOUT_FWD) {
-            if (L.rows_pad % 32 || L.cout_block <= 0 || L.rows_pad % L.cout_block || L.cout_block % 32) return BINHIP_E_SHAPE;
-            if (L.cin > L.cin_chunks * 16 || L.cout > L.rows_pad) return BINHIP_E_SHAPE;
-            if (L.shuffle_or_group && (L.cout % 4 || L.cout != L.rows_pad)) return BINHIP_E_SHAPE;
-        } else if (L.kind == BINHIP_RELAYOUT_DGRAD) {
-            if (L.rows_pad % 32 || L.cout_block <= 0 || L.rows_pad % L.cout_block || L.cout_block % 32) return BINHIP_E_SHAPE;
-            if (L.cin > L.rows_pad || L.cout > L.cin_chunks * 16) return BINHIP_E_SHAPE;
-            if (L.shuffle_or_group && L.cout % 4) return BINHIP_E_SHAPE;
-        } else if (L.kind == BINHIP_RELAYOUT_RDB_GATHER) {
-            const int g = L.shuffle_or_group;
-            const int G0 = L.shape.G0 > 0 ? L.shape.G0 : 96, G = L.shape.G > 0 ? L.shape.G : 32, C = L.shape.C > 0 ? L.shape.C : 4;
-            if (C > BINHIP_RDN_MAX_CONVS || G0 % 32 || G % 32) return BINHIP_E_SHAPE;
-            if (g < 0 || g >= C) return BINHIP_E_ARG;
-            if (L.rows_pad != (g == 0 ? G0 : G) || L.cin_chunks != (C - g) * G / 16 || L.ksize != 3) return BINHIP_E_SHAPE;
-            if (L.cout_block <= 0 || L.rows_pad % L.cout_block || L.cout_block % 32) return BINHIP_E_SHAPE;
-            for (int k = g; k < C; ++k) if (!L.w[k]) return BINHIP_E_ARG;
-        } else {
-            return BINHIP_E_ARG;
-        }
-    }
-    for (int i0 = 0; i0 < n; i0 += RELAYOUT_BATCH) {
-        RelayoutBatch rb;
-        const int m = (n - i0 < RELAYOUT_BATCH) ? n - i0 : RELAYOUT_BATCH;
-        unsigned blocks = 0;
-        for (int i = 0; i < m; ++i) {
-            rb.it[i] = items[i0 + i];
-            rb.start[i] = blocks;
-            const BinRelayoutItem& L = rb.it[i];
-            const long long total = (long long)L.rows_pad * L.cin_chunks * L.ksize * L.ksize * 2;
-            blocks += (unsigned)((total + 255) / 256);
-        }
-        for (int i = m; i < RELAYOUT_BATCH; ++i) rb.it[i] = rb.it[0];
-        for (int i = m; i <= RELAYOUT_BATCH; ++i) rb.start[i] = blocks;
-        rb.n = m;
-        hipLaunchKernelGGL(relayout_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rb);
-        BH_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-int binhip_dgrad_rows_pad(int ksize, int cin) {
-    // rows of the backward-data conv = original input channels, padded to the kernel's cout granularity (the LFF
-    // dgrad's 224 rows form ONE 224-row workgroup column, so its input — the 96-channel output gradient — is read once)
-    return ((cin + 31) / 32) * 32;
-}
-
-int binhip_weights_relayout_dgrad(const float* w_oihw, int cout, int cin, int ksize, int rows_pad, int cin_chunks,
-                                  int cout_block, int shuffle_perm, void* w_hi, void* w_lo, float* bias_out,
-                                  void* stream) {
-    if (!w_oihw || !w_hi || !bias_out) return BINHIP_E_ARG;
-    if (rows_pad % 32 || cout_block <= 0 || rows_pad % cout_block || cout_block % 32) return BINHIP_E_SHAPE;
-    if (cin > rows_pad || cout > cin_chunks * 16) return BINHIP_E_SHAPE;
-    if (shuffle_perm && cout % 4) return BINHIP_E_SHAPE;
-    const long long total = (long long)rows_pad * cin_chunks * ksize * ksize * 2;
-    const long long nb = (total + 255) / 256;
-    hipLaunchKernelGGL(relayout_dgrad_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w_oihw, cout, cin,
-                       ksize, rows_pad, cin_chunks, cout_block, shuffle_perm, (_Float16*)w_hi, (_Float16*)w_lo, bias_out);
-    BH_CHECK_LAUNCH();
-    return 0;
-}
-
-int binhip_weights_relayout_rdb_gather(const float* const* w_oihw4, int group, int cout_block, void* w_hi, void* w_lo,
-                                       float* bias_out, void* stream) {
-    if (!w_oihw4 || !w_hi || !bias_out || group < 0 || group > 3) return BINHIP_E_ARG;
-    const int rows = group == 0 ? 96 : 32;
-    const int nchunks = 2 * (4 - group);
-    if (cout_block <= 0 || rows % cout_block || cout_block % 32) return BINHIP_E_SHAPE;
-    GatherSrc src;
-    for (int i = 0; i <= BINHIP_RDN_MAX_CONVS; ++i) src.w[i] = nullptr;
-    src.G0 = 96; src.G = 32;
-    for (int i = 0; i < 4; ++i) {
-        src.w[i] = w_oihw4[i];
-        if (i >= group && !src.w[i]) return BINHIP_E_ARG;
-    }
-    const long long total = (long long)rows * nchunks * 9 * 2;
-    hipLaunchKernelGGL(relayout_rdb_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, src, group, rows, nchunks, cout_block, (_Float16*)w_hi, (_Float16*)w_lo,
-                       bias_out);
-    BH_CHECK_LAUNCH();
-    return 0;
-}
 
 int binhip_conv2d_bwd_data(const BinConvDesc* d, const void* gy_hi, const void* gy_lo, const void* wt_hi,
                            const void* wt_lo, const float* zero_bias, const void* res_hi, const void* res_lo,
@@ -754,27 +504,6 @@ void binhip_profiler_destroy(BinhipProfiler* p) {
 }
 
 int binhip_conv_cout_block(int ksize, int cout_pad, int nterms) { return bh_conv_cout_block(ksize, cout_pad, nterms); }
-
-size_t binhip_weights_bytes(int cout_pad, int cin_chunks, int ksize) {
-    return (size_t)cout_pad * cin_chunks * ksize * ksize * 32;
-}
-
-int binhip_weights_relayout(const float* w_oihw, const float* bias, int cout, int cin, int ksize,
-                            int cout_pad, int cin_chunks, int cout_block, int shuffle_perm,
-                            void* w_hi, void* w_lo, float* bias_out, void* stream) {
-    if (!w_oihw || !w_hi || !bias_out) return BINHIP_E_ARG;
-    if (cout_pad % 32 || cout_block <= 0 || cout_pad % cout_block || cout_block % 32) return BINHIP_E_SHAPE;
-    if (cin > cin_chunks * 16 || cout > cout_pad) return BINHIP_E_SHAPE;
-    if (shuffle_perm && (cout % 4 || cout != cout_pad)) return BINHIP_E_SHAPE;
-    const long long total = (long long)cout_pad * cin_chunks * ksize * ksize * 2;
-    const int th = 256;
-    const long long nb = (total + th - 1) / th;
-    hipLaunchKernelGGL(relayout_kernel, dim3((unsigned)nb), dim3(th), 0, (hipStream_t)stream, w_oihw, bias, cout, cin,
-                       ksize, cout_pad, cin_chunks, cout_block, shuffle_perm, (_Float16*)w_hi, (_Float16*)w_lo,
-                       bias_out);
-    BH_CHECK_LAUNCH();
-    return 0;
-}
 
 int binhip_conv2d_fwd(const BinConvDesc* d, const void* x_hi, const void* x_lo, const void* w_hi,
                       const void* w_lo, const float* bias, const void* res_hi, const void* res_lo,

@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, streams); every computation is a hand-w
 Activations between layers are "chunk planes" (CP): fp16 [C/16][N][H][W][16], optionally hi+lo.
 """
 import ctypes as C
+import functools
 import os
 
 import torch
@@ -142,15 +143,17 @@ def relayout_item(kind, srcs, bias, w_hi, w_lo, bias_out, cout, cin, ks, rows_pa
     """One BinRelayoutItem (include/binhip.h).  `srcs`: the fp32 OIHW source tensor(s); the caller keeps them alive until
     relayout_batch() has enqueued the launch."""
     it = L.BinRelayoutItem()
+    w = it.w
     for i, t in enumerate(srcs):
-        it.w[i] = t.data_ptr() if t is not None else None
+        w[i] = t.data_ptr() if t is not None else None
     it.bias = bias.data_ptr() if bias is not None else None
     it.w_hi, it.w_lo = w_hi.data_ptr(), (w_lo.data_ptr() if w_lo is not None else None)
     it.bias_out = bias_out.data_ptr()
     it.kind, it.cout, it.cin, it.ksize, it.rows_pad = kind, cout, cin, ks, rows_pad
     it.cin_chunks, it.cout_block, it.shuffle_or_group = cin_chunks, cout_block, shuffle_or_group
     if shape is not None:                  # RDB_GATHER of a block other than bin_stage4's
-        it.shape.G0, it.shape.D, it.shape.C, it.shape.G = shape
+        sh = it.shape
+        sh.G0, sh.D, sh.C, sh.G = shape
     return it
 
 
@@ -168,33 +171,63 @@ def relayout_batch(items):
     L.check(lib.binhip_weights_relayout_batch(arr, len(items), _stream()), "weights_relayout_batch")
 
 
-class ConvWeights:
-    """Kernel-layout weights of one convolution (see binhip_weights_relayout).  `defer`: a list that receives this
-    layer's relayout item instead of launching it (RdnWeights batches the 66 layers of a weight set)."""
+def _source(t):
+    """A relayout source: on the device, as a contiguous fp32 tensor outside autograd — `t` itself when it already is one (a weight
+    set hands each source to several relayouts: this is on its construction's critical path, which is host time)."""
+    if t.is_cuda and t.dtype is torch.float32 and t.is_contiguous() and not t.requires_grad:
+        return t
+    _need_cuda(t)
+    return t.detach().contiguous().float()
+
+
+# The library's answers about a layout are pure functions of a few small integers; a weight set asks them for each of its 66 + 66
+# layers after every optimizer step, where a ctypes call costs as much as an allocation
+@functools.lru_cache(maxsize=None)
+def _plane_elems(rows_pad, cin_chunks, ks):
+    return L.lib().binhip_weights_bytes(rows_pad, cin_chunks, ks) // 2
+
+
+@functools.lru_cache(maxsize=None)
+def _cout_block(ks, cout_pad, nterms):
+    return L.lib().binhip_conv_cout_block(ks, cout_pad, nterms)
+
+
+def alloc_weights(rows_pad, cin_chunks, ks, nterms, device):
+    """(w_hi, w_lo or None, bias): the uninitialised kernel-layout buffers of one relayout (include/binhip.h)."""
+    n = _plane_elems(rows_pad, cin_chunks, ks)
+    return (torch.empty(n, dtype=torch.float16, device=device),
+            torch.empty(n, dtype=torch.float16, device=device) if nterms == 3 else None,
+            torch.empty(rows_pad, dtype=torch.float32, device=device))
+
+
+class _KernelWeights:
+    """What the three kinds of kernel-layout weights share: the geometry the convolution launch reads (ks, nterms, cout, cout_pad,
+    cin_chunks, cout_block), the buffers, and one launch route.  `defer`: a list that receives the relayout item instead of
+    launching it (RdnWeights / RdnDgradWeights batch the layers of a weight set); `_src` then keeps the sources alive."""
+
+    def _relayout(self, kind, srcs, bias, cout, cin, shuffle_or_group, defer, shape=None):
+        srcs = [_source(w) for w in srcs]
+        bias = _source(bias) if bias is not None else None
+        self.cout_block = _cout_block(self.ks, self.cout_pad, self.nterms)
+        self.w_hi, self.w_lo, self.bias = alloc_weights(self.cout_pad, self.cin_chunks, self.ks, self.nterms, srcs[0].device)
+        item = relayout_item(kind, srcs, bias, self.w_hi, self.w_lo, self.bias, cout, cin, self.ks, self.cout_pad, self.cin_chunks,
+                             self.cout_block, shuffle_or_group, shape)
+        if defer is None:
+            relayout_batch([item])
+        else:
+            self._src = (srcs, bias)
+            defer.append(item)
+
+
+class ConvWeights(_KernelWeights):
+    """Kernel-layout weights of one convolution (see binhip_weights_relayout)."""
 
     def __init__(self, weight, bias, nterms=1, shuffle=False, cout_pad=None, cin_chunks=None, defer=None):
-        _need_cuda(weight)
         cout, cin, ks, _ = weight.shape
         self.cout, self.cin, self.ks, self.nterms, self.shuffle = cout, cin, ks, nterms, shuffle
         self.cout_pad = cout_pad if cout_pad is not None else ((cout + 31) // 32) * 32
         self.cin_chunks = cin_chunks if cin_chunks is not None else chunks(cin)
-        lib = L.lib()
-        self.cout_block = lib.binhip_conv_cout_block(ks, self.cout_pad, nterms)
-        nbytes = lib.binhip_weights_bytes(self.cout_pad, self.cin_chunks, ks)
-        dev = weight.device
-        self.w_hi = torch.empty(nbytes // 2, dtype=torch.float16, device=dev)
-        self.w_lo = torch.empty(nbytes // 2, dtype=torch.float16, device=dev) if nterms == 3 else None
-        self.bias = torch.empty(self.cout_pad, dtype=torch.float32, device=dev)
-        w = weight.detach().contiguous().float()
-        b = bias.detach().contiguous().float() if bias is not None else None
-        if defer is not None:
-            self._src = (w, b)
-            defer.append(relayout_item(L.RELAYOUT_FWD, [w], b, self.w_hi, self.w_lo, self.bias, cout, cin, ks, self.cout_pad,
-                                       self.cin_chunks, self.cout_block, 1 if shuffle else 0))
-            return
-        L.check(lib.binhip_weights_relayout(_ptr(w), _ptr(b), cout, cin, ks, self.cout_pad, self.cin_chunks,
-                                            self.cout_block, 1 if shuffle else 0, _ptr(self.w_hi), _ptr(self.w_lo),
-                                            _ptr(self.bias), _stream()), "weights_relayout")
+        self._relayout(L.RELAYOUT_FWD, [weight], bias, cout, cin, 1 if shuffle else 0, defer)
 
 
 def conv2d(x, cw, relu=False, residual=None, out=None, epilogue=L.EPI_PLANES, images=None, x_cpg=0,
@@ -337,52 +370,30 @@ def charbonnier_grad(x, y, gloss, eps=1e-6):
 
 
 # --------------------------------------------------------------------------------------------- backward ops
-class DgradWeights:
+class DgradWeights(_KernelWeights):
     """Backward-data weights of one convolution (binhip_weights_relayout_dgrad)."""
 
-    def __init__(self, weight, nterms=1, shuffle=False):
-        _need_cuda(weight)
+    def __init__(self, weight, nterms=1, shuffle=False, defer=None):
         cout, cin, ks, _ = weight.shape
-        lib = L.lib()
         self.ks, self.nterms = ks, nterms
         self.cout = cin                                   # the dgrad conv's outputs = original inputs
-        self.cout_pad = lib.binhip_dgrad_rows_pad(ks, cin)
+        self.cout_pad = L.lib().binhip_dgrad_rows_pad(ks, cin)
         self.cin_chunks = chunks(cout)
-        cb = lib.binhip_conv_cout_block(ks, self.cout_pad, nterms)
-        nbytes = lib.binhip_weights_bytes(self.cout_pad, self.cin_chunks, ks)
-        dev = weight.device
-        self.w_hi = torch.empty(nbytes // 2, dtype=torch.float16, device=dev)
-        self.w_lo = torch.empty(nbytes // 2, dtype=torch.float16, device=dev) if nterms == 3 else None
-        self.bias = torch.empty(self.cout_pad, dtype=torch.float32, device=dev)
-        w = weight.detach().contiguous().float()
-        L.check(lib.binhip_weights_relayout_dgrad(_ptr(w), cout, cin, ks, self.cout_pad, self.cin_chunks, cb,
-                                                  1 if shuffle else 0, _ptr(self.w_hi), _ptr(self.w_lo),
-                                                  _ptr(self.bias), _stream()), "weights_relayout_dgrad")
+        self._relayout(L.RELAYOUT_DGRAD, [weight], None, cout, cin, 1 if shuffle else 0, defer)
 
 
-class RdbGatherWeights:
-    """Backward-data weights of ONE concat group of a residual dense block in gather form
-    (binhip_weights_relayout_rdb_gather, include/binhip.h): group g = 0 produces the gradient of the block's 96 input
-    channels, g = 1..3 that of conv g-1's 32 outputs, each as one forward-shaped 3x3 conv over the stacked output
-    gradients of convs g..3.  `weights4`: the block's four OIHW fp32 conv weights."""
+class RdbGatherWeights(_KernelWeights):
+    """Backward-data weights of ONE concat group of a residual dense block (G0, C, G) in gather form
+    (binhip_weights_relayout_rdb_gather, include/binhip.h): group g = 0 produces the gradient of the block's G0 input
+    channels, g >= 1 that of conv g-1's G outputs, each as one forward-shaped 3x3 conv over the stacked output
+    gradients of convs g..C-1.  `weights`: the block's C OIHW fp32 conv weights (bin_stage4: four, (96, 4, 32))."""
 
-    def __init__(self, weights4, group, nterms=1):
-        _need_cuda(*weights4)
-        lib = L.lib()
+    def __init__(self, weights, group, nterms=1, defer=None):
+        (G, G0, _, _), C_ = weights[0].shape, len(weights)
         self.ks, self.nterms = 3, nterms
-        self.cout = 96 if group == 0 else 32
-        self.cout_pad = self.cout
-        self.cin_chunks = 2 * (4 - group)
-        cb = lib.binhip_conv_cout_block(3, self.cout_pad, nterms)
-        nbytes = lib.binhip_weights_bytes(self.cout_pad, self.cin_chunks, 3)
-        dev = weights4[0].device
-        self.w_hi = torch.empty(nbytes // 2, dtype=torch.float16, device=dev)
-        self.w_lo = torch.empty(nbytes // 2, dtype=torch.float16, device=dev) if nterms == 3 else None
-        self.bias = torch.empty(self.cout_pad, dtype=torch.float32, device=dev)
-        self._src = [w.detach().contiguous().float() for w in weights4]
-        arr = (C.c_void_p * 4)(*[w.data_ptr() for w in self._src])
-        L.check(lib.binhip_weights_relayout_rdb_gather(arr, group, cb, _ptr(self.w_hi), _ptr(self.w_lo), _ptr(self.bias),
-                                                       _stream()), "weights_relayout_rdb_gather")
+        self.cout = self.cout_pad = G0 if group == 0 else G
+        self.cin_chunks = (C_ - group) * G // 16
+        self._relayout(L.RELAYOUT_RDB_GATHER, weights, None, G, G0 + G * group, group, defer, shape=(G0, 0, C_, G))
 
 
 def rdb_tail(blk, cw3, cwl, out=None, store_o3=False):

@@ -5,7 +5,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .ops import ConvWeights, _ptr, _stream, _need_cuda, on_device, relayout_batch, relayout_item, status_word
+from .ops import ConvWeights, DgradWeights, RdbGatherWeights, _ptr, _stream, _need_cuda, on_device, relayout_batch, status_word
 
 STAGE4_SHAPE = (96, 12, 4, 32)          # (G0, D, C, G) of bin_stage4's sub-networks (reference RDN.py:418, :171-172)
 
@@ -333,58 +333,26 @@ class RdnDgradWeights:
     gradients of convs g..3 - what binhip_rdn_backward expects (include/binhip.h, BinRdnBwdPlan)."""
 
     def __init__(self, params, n_inputs, nterms, prefix="", shape=STAGE4_SHAPE, fused=None):
-        lib = L.lib()
         self.shape = G0, D, C, G = check_shape(shape)
-        self.w_hi, self.w_lo = [], []
         self.fused_ring_w = None
-        dev = None
         names = layer_names(self.shape)
-        fp32 = {nm: params[f"{prefix}{nm}.weight"].detach().contiguous().float() for nm in names}
-
-        def alloc(rows, chunks, ks):
-            nbytes = lib.binhip_weights_bytes(rows, chunks, ks)
-            hi = torch.empty(nbytes // 2, dtype=torch.float16, device=dev)
-            lo = torch.empty(nbytes // 2, dtype=torch.float16, device=dev) if nterms == 3 else None
-            return hi, lo, torch.empty(rows, dtype=torch.float32, device=dev)
-
-        items, scratch = [], []              # scratch: per-layer zero-bias outputs, only needed until the launch is queued
-        self._src = fp32
+        self._src = fp32 = {nm: params[f"{prefix}{nm}.weight"].detach().contiguous().float() for nm in names}
+        blocks = [[fp32[f"RDBs.{d}.convs.{c}.conv.0"] for c in range(C)] for d in range(D)]
+        items, slots = [], []      # slots: one weights object per slot; only their planes are kept (the bias outputs are zeros)
         for nm in names:
-            w = fp32[nm]
-            dev = w.device
-            cout, cin, ks, _ = w.shape
             if ".convs." in nm:
-                d, g = int(nm.split(".")[1]), int(nm.split(".")[3])
-                rows, chunks = (G0 if g == 0 else G), (C - g) * G // 16
-                hi, lo, zb = alloc(rows, chunks, 3)
-                srcs = [fp32[f"RDBs.{d}.convs.{c}.conv.0"] for c in range(C)]
-                cb = lib.binhip_conv_cout_block(3, rows, nterms)
-                items.append(relayout_item(L.RELAYOUT_RDB_GATHER, srcs, None, hi, lo, zb, G, G0 + G * g, 3, rows, chunks, cb, g,
-                                           shape=self.shape))
+                _, d, _, g = nm.split(".")[:4]
+                slots.append(RdbGatherWeights(blocks[int(d)], int(g), nterms, defer=items))
             else:
-                rows_pad = lib.binhip_dgrad_rows_pad(ks, cin)
-                cin_chunks = (cout + 15) // 16
-                cb = lib.binhip_conv_cout_block(ks, rows_pad, nterms)
-                hi, lo, zb = alloc(rows_pad, cin_chunks, ks)
-                items.append(relayout_item(L.RELAYOUT_DGRAD, [w], None, hi, lo, zb, cout, cin, ks, rows_pad, cin_chunks, cb,
-                                           1 if nm == "UPNet.0" else 0))
-            self.w_hi.append(hi)
-            self.w_lo.append(lo)
-            scratch.append(zb)
+                slots.append(DgradWeights(fp32[nm], nterms, shuffle=nm == "UPNet.0", defer=items))
         if fused is not None:
             # BINHIP_BWD_FUSED_UPNET: slot L = the transposed interior operator of the fused UPNet ([12][G0][5][5] -> 5x5, 12 -> G0),
             # slot L + 1 = its fp32 ring operators as the forward uses them
             w4, self.fused_ring_w = fused
-            rows_pad = lib.binhip_dgrad_rows_pad(5, G0)
-            cb = lib.binhip_conv_cout_block(5, rows_pad, nterms)
-            hi, lo, zb = alloc(rows_pad, 1, 5)
-            items.append(relayout_item(L.RELAYOUT_DGRAD, [w4], None, hi, lo, zb, 12, G0, 5, rows_pad, 1, cb, 0))
-            self.w_hi.append(hi)
-            self.w_lo.append(lo)
-            scratch.append(zb)
+            slots.append(DgradWeights(w4, nterms, defer=items))
         relayout_batch(items)
-        del scratch
-        self.zero_bias = torch.zeros(max(D * G0, G0 + C * G, 256, 1152), dtype=torch.float32, device=dev)
+        self.w_hi, self.w_lo = [s.w_hi for s in slots], [s.w_lo for s in slots]
+        self.zero_bias = torch.zeros(max(D * G0, G0 + C * G, 256, 1152), dtype=torch.float32, device=self.w_hi[0].device)
 
     def fill_plan(self, plan):
         plan.shape = c_shape(self.shape)
