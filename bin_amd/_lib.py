@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, SCENE_LIB_PATH, YUV_LIB_PATH
+from .build import CHAIN_LIB_PATH, EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, SCENE_LIB_PATH, YUV_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -127,6 +127,13 @@ SCENE_BINS = 64                        # BINSCENE_BINS (include/binscene.h, libb
 
 class BinSceneRecord(C.Structure):
     _fields_ = [("sad", C.c_uint64), ("hist", C.c_uint32 * SCENE_BINS)]
+
+
+CHAIN_MAX_ITEMS = 24                   # BINCHAIN_MAX_ITEMS (include/binchain.h, libbinchain.so)
+
+
+class BinChainItem(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)]
 
 
 _SIGNATURES = {
@@ -265,10 +272,17 @@ _SCENE_SIGNATURES = {
     "binscene_luma_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
+# libbinchain.so (include/binchain.h): the chain library, loaded on first use
+CHAIN_VERSION = 100                    # BINCHAIN_VERSION
+_CHAIN_SIGNATURES = {
+    "binchain_version": (C.c_int, []),
+    "binchain_reframe": (C.c_int, [C.POINTER(BinChainItem), C.c_int] + [C.c_int] * 11 + [C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = None
+_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = _chainlib = None
 
 
 def _load(path, built_path, signatures, version=None):
@@ -377,6 +391,19 @@ def scenelib():
     if _scenelib is None:
         _scenelib = _load(SCENE_LIB_PATH, SCENE_LIB_PATH, _SCENE_SIGNATURES, ("binscene_version", SCENE_VERSION))
     return _scenelib
+
+
+def chain_exported_symbols():
+    """Names every include/binchain.h entry point must resolve to."""
+    return sorted(_CHAIN_SIGNATURES)
+
+
+def chainlib():
+    """Load libbinchain.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _chainlib
+    if _chainlib is None:
+        _chainlib = _load(CHAIN_LIB_PATH, CHAIN_LIB_PATH, _CHAIN_SIGNATURES, ("binchain_version", CHAIN_VERSION))
+    return _chainlib
 
 
 def check(rc, what):

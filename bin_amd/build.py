@@ -45,6 +45,12 @@ SCENE_SOURCES = ["binscene.hip"]
 SCENE_LIB_PATH = os.path.join(CSRC, "libbinscene.so")
 SCENE_HEADER = os.path.join(os.path.dirname(HERE), "include", "binscene.h")
 
+# the chain library (include/binchain.h): the fp32 hand-off between chained interpolation passes, the kernel of bin_amd/chain.py
+# (--factor 4 | 8); an eighth shared object, for the same reason
+CHAIN_SOURCES = ["binchain.hip"]
+CHAIN_LIB_PATH = os.path.join(CSRC, "libbinchain.so")
+CHAIN_HEADER = os.path.join(os.path.dirname(HERE), "include", "binchain.h")
+
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
 # (name, sources, header, path) of every shared object: what drives the compile, the version script and the link
 LIBRARIES = (("binhip", SOURCES, HEADER, LIB_PATH), ("binopt", OPT_SOURCES, OPT_HEADER, OPT_LIB_PATH),
@@ -55,6 +61,9 @@ IO_LIBRARIES = (("binyuv", YUV_SOURCES, YUV_HEADER, YUV_LIB_PATH),)
 # the libraries that measure frames without changing them (same tuple layout), built and checked likewise
 ANALYSIS_LIBRARIES = (("binscene", SCENE_SOURCES, SCENE_HEADER, SCENE_LIB_PATH),)
 PRODUCT_LIBRARIES = LIBRARIES + IO_LIBRARIES + ANALYSIS_LIBRARIES
+# the libraries of the chained passes (same tuple layout); ALL_LIBRARIES is what the product build makes and checks for staleness
+CHAIN_LIBRARIES = (("binchain", CHAIN_SOURCES, CHAIN_HEADER, CHAIN_LIB_PATH),)
+ALL_LIBRARIES = PRODUCT_LIBRARIES + CHAIN_LIBRARIES
 
 
 def _declared(header, macro, prefix):
@@ -99,13 +108,18 @@ def scene_abi_symbols():
     return _declared(SCENE_HEADER, "BINSCENE_API", "binscene")
 
 
+def chain_abi_symbols():
+    """The entry points include/binchain.h declares (every BINCHAIN_API declaration), in header order."""
+    return _declared(CHAIN_HEADER, "BINCHAIN_API", "binchain")
+
+
 def _stale():
-    libs = [path for _, _, _, path in PRODUCT_LIBRARIES]
+    libs = [path for _, _, _, path in ALL_LIBRARIES]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    deps += [header for _, _, header, _ in PRODUCT_LIBRARIES]
+    deps += [header for _, _, header, _ in ALL_LIBRARIES]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -113,7 +127,8 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     """Compile every HIP source for gfx950 into bin_amd/csrc/libbinhip.so (and, for the product build, the optimizer
     library bin_amd/csrc/libbinopt.so, the gradient-guard library bin_amd/csrc/libbingrad.so, the weight-average library
     bin_amd/csrc/libbinema.so, the self-ensemble library bin_amd/csrc/libbinens.so, the video library
-    bin_amd/csrc/libbinyuv.so and the scene library bin_amd/csrc/libbinscene.so beside it).
+    bin_amd/csrc/libbinyuv.so, the scene library bin_amd/csrc/libbinscene.so and the chain library bin_amd/csrc/libbinchain.so
+    beside it).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain): libbinhip.so alone, under another name.  The
@@ -124,7 +139,7 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     objdir = CSRC if out is None else os.path.dirname(os.path.abspath(out))
     os.makedirs(objdir, exist_ok=True)
     tag = "" if out is None else "." + os.path.splitext(os.path.basename(out))[0]
-    libraries = PRODUCT_LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
+    libraries = ALL_LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
     procs, objs = [], {}
     for name, sources, _, _ in libraries:
         for src in sources:

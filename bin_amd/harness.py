@@ -102,7 +102,8 @@ def video_slots(index, n_windows):
 
 
 @torch.no_grad()
-def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None, scene_cut=None):
+def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None, factor=2,
+                      scene_cut=None):
     """interpolate_clip's loop over the frames of a Y4M stream.  `payloads`: [T, frame_bytes] uint8 (host or device), the frames of
     `header` (bin_amd/video.py).  Returns the [2(T-1), frame_bytes] uint8 device tensor of the output payloads in display order,
     D0, I0, D1, I1, ..., D(T-2), I(T-2): exactly the frames the folder runner writes for a one-clip folder, in name order — window 0
@@ -113,8 +114,12 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
     scene_cut: None = the stream is one clip (the path above).  A number is the threshold of `detect_cuts`, an iterable of ints the
     cut positions themselves (c: frames c-1 and c are of different scenes).  The windows then stay inside their scene
     (bin_amd/scene.py::plan): every scene comes out as if it ran alone, plus its last deblurred frame, and the frame between two
-    scenes is the deblurred frame before the cut, held.  Same length, same layout."""
+    scenes is the deblurred frame before the cut, held.  Same length, same layout.
+    factor: 2 (the path above), 4 or 8: the passes of bin_amd/chain.py on the fp32 outputs, which never leave the device.  Returns
+    [factor (T-1), frame_bytes]; every second payload is the output at factor / 2."""
     from . import ops, video
+    if factor != 2 or type(factor) is not int:
+        return _interpolate_video_chain(netG, payloads, header, matrix, range, reuse_stage1, batch, ensemble, scene_cut, factor)
     T = payloads.shape[0]
     if T < 2:
         raise ValueError(f"interpolate_video needs at least 2 frames (got {T})")
@@ -246,6 +251,111 @@ def _interpolate_video_scenes(netG, payloads, header, matrix, range, reuse_stage
         out[pos].copy_(out[pos - 1])
         written.add(pos)
     assert written == set(builtins_range(2 * n_win))
+    return out
+
+
+class ChainNet:
+    """The device side of chain.Chain's callables for one stream: the generator on the windows of a pass, and the hand-off.  Every
+    pass (level 1, the pass on the input frames, included) owns its memo dict and, with `ensemble`, its SelfEnsemble: both key on
+    the identity of long-lived input tensors, and the passes interleave.  batch > 1: no memo, as in interpolate_clip."""
+
+    def __init__(self, netG, k, h, w, reuse_stage1=True, batch=1, ensemble=None):
+        from .ensemble import SelfEnsemble, parse_group
+        inner = netG.module if hasattr(netG, "module") else netG
+        self.netG, self.h, self.w, self.pads = netG, h, w, util.pad_sizes(h, w)
+        self.batch = max(1, int(batch))
+        memo = reuse_stage1 and self.batch == 1 and getattr(inner, "reuse_schedule", False)
+        self.caches = [{} if memo else None for _ in builtins_range(k)]
+        self.ens = [SelfEnsemble(netG, ensemble) if parse_group(ensemble) else None for _ in builtins_range(k)]
+
+    def new_scene(self):
+        for cache, ens in zip(self.caches, self.ens):
+            if cache is not None:
+                cache.clear()
+            if ens is not None:
+                ens.reset()
+
+    def run(self, level, jobs, slots):
+        """Ft_p of the generator on `jobs` = [(ids, six frames)], windows of pass `level`, batched along N when there are several."""
+        cache, ens = self.caches[level - 1], self.ens[level - 1]
+        if len(jobs) == 1:
+            ids, inputs = jobs[0]
+            if ens is not None:
+                return ens.window(ids, inputs, slots=slots, reuse=cache is not None)
+            return self.netG(*inputs, stage1_cache=cache) if cache is not None else self.netG(*inputs)
+        inputs = [torch.cat([frames[k] for _, frames in jobs], 0) for k in builtins_range(6)]
+        return ens(inputs, slots=slots) if ens is not None else self.netG(*inputs)
+
+    def forward(self, level, jobs):
+        out = self.run(level, jobs, (13,))[13]
+        return [out] if len(jobs) == 1 else [out[j:j + 1] for j in builtins_range(len(jobs))]
+
+    def reframe(self, frames):
+        from . import _lib, ops
+        l, r, t, b = self.pads
+        out = []
+        for first in builtins_range(0, len(frames), _lib.CHAIN_MAX_ITEMS):
+            out += ops.reframe(frames[first:first + _lib.CHAIN_MAX_ITEMS], t, l, self.h, self.w, self.pads)
+        return out
+
+
+def _interpolate_video_chain(netG, payloads, header, matrix, range, reuse_stage1, batch, ensemble, scene_cut, factor):
+    """interpolate_video at factor 4 or 8: level 1 is the generator on the input frames scene by scene (chain.level1_plan: the
+    windows of scene.plan, with the last window's slot 12 kept), the passes above are chain.Chain's."""
+    from . import chain, ops, scene, video
+    k = chain.levels(factor)
+    T = payloads.shape[0]
+    if T < 2:
+        raise ValueError(f"interpolate_video needs at least 2 frames (got {T})")
+    fmt = video.resolve_format(header, matrix, range)
+    h, w = header.height, header.width
+    dev = next(netG.parameters()).device
+    if scene_cut is None:
+        cuts = []
+    elif isinstance(scene_cut, (int, float)):
+        cuts = detect_cuts(payloads, header, float(scene_cut), device=dev)
+    else:
+        cuts = scene.check_cuts(scene_cut, T)
+    if payloads.dim() != 2 or payloads.dtype != torch.uint8 or payloads.shape[1] != header.frame_bytes:
+        raise ValueError(f"payloads must be uint8 [T, {header.frame_bytes}] for this header (got {payloads.dtype} {tuple(payloads.shape)})")
+    net = ChainNet(netG, k, h, w, reuse_stage1, batch, ensemble)
+    l, r, t, b = net.pads
+    cache = {}
+
+    def frame(i):
+        if i not in cache:
+            cache[i] = ops.yuv_to_frame(payloads[i].to(dev).contiguous(), h, w, fmt, net.pads)
+        return cache[i]
+
+    out = torch.empty((factor * (T - 1), header.frame_bytes), dtype=torch.uint8, device=dev)
+    written = []
+
+    def emit(pos, f):
+        assert pos == len(written)                        # display order
+        if f is chain.HOLD:
+            out[pos].copy_(out[pos - 1])
+        else:
+            ops.frame_to_yuv(f, t, l, h, w, fmt, out=out[pos])
+        written.append(pos)
+
+    passes = chain.Chain(factor, net.forward, net.reframe, emit, batch=net.batch, new_scene=net.new_scene)
+    for s, e in scene.segments(T, cuts):
+        work = [chain.level1_plan(i, s, e) for i in builtins_range(s, min(e, T - 1))]
+        work = [(ids, slots) for ids, slots, _ in work if ids is not None]
+        if not work:
+            continue                                      # the stream's last frame alone: nothing comes after it
+        passes.begin(s)
+        for first in builtins_range(0, len(work), net.batch):
+            group = work[first:first + net.batch]
+            for i in [i for i in cache if i < min(group[0][0])]:
+                del cache[i]
+            Ft_p = net.run(1, [(ids, [frame(i) for i in ids]) for ids, _ in group], (13, 8, 12))
+            for j, (_, slots) in enumerate(group):
+                passes.push([Ft_p[slot] if len(group) == 1 else Ft_p[slot][j:j + 1] for slot in slots])
+            ops.check_status(dev)                         # (synchronises, as interpolate_video does per forward)
+        passes.end(final=e == T)
+    ops.check_status(dev)
+    assert len(written) == factor * (T - 1)
     return out
 
 

@@ -1087,3 +1087,43 @@ def ens_merge(srcs_per_slot, flip_of, out=None):
     with on_device(outs[0]):
         L.check(L.enslib().binens_merge(table, len(srcs), m, (C.c_uint8 * max(m, 1))(*flip_of), planes, h, w, _stream()), "ens_merge")
     return outs
+
+
+# --------------------------------------------------------------------------------------------- chained passes (libbinchain.so)
+def reframe(frames, top, left, h, w, pads, out=None):
+    """binchain_reframe, one launch, current stream, no host sync: the hand-off between two interpolation passes (include/binchain.h).
+    `frames`: a float32 device tensor [N,3,Hs,Ws] (or [3,Hs,Ws]), or a list of at most BINCHAIN_MAX_ITEMS of them, of one shape on one
+    device (batch slices and views at any 4-byte offset are fine).  Of each, the crop [top:top+h, left:left+w] goes through
+    frame_to_u8's clamp to [0, 1] and is replicate-padded by pads = (left, right, top, bottom).  Returns FRESH tensors
+    [..., h+t+b, w+l+r] (one for a tensor, a list for a list), or fills `out` (the same form): the frames are often outputs the
+    network's memo shares with later forwards, and are only read."""
+    single = isinstance(frames, torch.Tensor)
+    srcs = [frames] if single else list(frames)
+    if len(pads) != 4 or min(pads) < 0 or h < 1 or w < 1 or top < 0 or left < 0:
+        raise ValueError(f"bin_amd: reframe needs a positive crop at a non-negative offset and four non-negative pads "
+                         f"(got ({top}, {left}, {h}, {w}), {tuple(pads)})")
+    if not srcs:
+        return []
+    if len(srcs) > L.CHAIN_MAX_ITEMS:
+        raise ValueError(f"reframe: at most {L.CHAIN_MAX_ITEMS} frames per call, got {len(srcs)}")
+    planes, hs, ws = _ens_geometry("reframe", srcs)
+    if top + h > hs or left + w > ws:
+        raise ValueError(f"bin_amd: crop ({top}, {left}, {h}, {w}) leaves the {hs}x{ws} frame")
+    l, r, t, b = (int(p) for p in pads)
+    shape = tuple(srcs[0].shape[:-2]) + (h + t + b, w + l + r)
+    if out is None:
+        dsts = [torch.empty(shape, dtype=torch.float32, device=srcs[0].device) for _ in srcs]
+    else:
+        dsts = [out] if isinstance(out, torch.Tensor) else list(out)
+        if len(dsts) != len(srcs):
+            raise ValueError("reframe: one output per frame")
+        _ens_geometry("reframe", dsts)
+        if any(tuple(d.shape) != shape or d.device != srcs[0].device for d in dsts):
+            raise ValueError(f"reframe: outputs of shape {shape} on the frames' device")
+    table = (L.BinChainItem * len(srcs))()
+    for it, x, d in zip(table, srcs, dsts):
+        it.src, it.dst = x.data_ptr(), d.data_ptr()
+    with on_device(srcs[0]):
+        L.check(L.chainlib().binchain_reframe(table, len(srcs), planes, hs, ws, int(top), int(left), int(h), int(w), l, r, t, b,
+                                              _stream()), "reframe")
+    return dsts[0] if single else dsts

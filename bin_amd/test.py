@@ -7,7 +7,8 @@ interpolated and deblurred frames against the sharp ground truth) and demo.py (w
     DECODER ... -f yuv4mpegpipe - | python -m bin_amd.test --input_video - --output_video - --opt ... | ENCODER ...
 
 With --input_video / --output_video the frames are those of one Y4M stream (bin_amd/video.py) instead of PNG files: same windows,
-same outputs, written in display order at twice the frame rate (run_video below; nothing is scored, one rank).
+same outputs, written in display order at twice the frame rate (run_video below; nothing is scored, one rank).  --factor 4 | 8
+chains passes on the fp32 outputs for four or eight times the frame rate (run_video_chain, bin_amd/chain.py).
 
 What the reference does per input frame `index` of a clip (test.py:236-402) and this keeps:
   * the six blurry frames index + [-2..3], clamped to the clip (test.py:257-261, 333);
@@ -61,6 +62,9 @@ def parse_args(argv=None):
                         "scenes only; off by default")
     p.add_argument("--scene_cut_min_mad", type=float, default=0.0, metavar="M",
                    help="--scene_cut: a cut also needs a mean absolute luma difference >= M")
+    p.add_argument("--factor", type=int, choices=[2, 4, 8], default=2,
+                   help="--input_video: the output's frame rate over the input's; 4 and 8 chain passes on the fp32 outputs "
+                        "(bin_amd/chain.py), every second frame of a factor's stream being the stream of half the factor")
     p.add_argument("--gpu_id", type=str, default=None)
     p.add_argument("--time_step", type=float, default=0.5)
     p.add_argument("--opt", type=str, required=True, help="Path to option YAML file.")
@@ -95,6 +99,8 @@ def check_args(args):
     folder = args.input_path is not None or args.output_path is not None
     if not video and (getattr(args, "scene_cut", None) is not None or getattr(args, "scene_cut_min_mad", 0.0)):
         raise ValueError("--scene_cut / --scene_cut_min_mad: scene cuts are looked for in a video only (--input_video)")
+    if not video and getattr(args, "factor", 2) != 2:
+        raise ValueError("--factor: passes are chained on a video only (--input_video)")
     if getattr(args, "scene_cut", None) is None and getattr(args, "scene_cut_min_mad", 0.0):
         raise ValueError("--scene_cut_min_mad goes with --scene_cut")
     if video and folder:
@@ -241,7 +247,7 @@ def main(argv=None, stats=None):
     n_out = round(1 / args.time_step)
     assert n_out == 2, "bin_stage4 interpolates the middle frame (time_step 0.5), as the reference asserts"
     if args.input_video is not None:
-        return run_video(args, opt, stats)
+        return run_video(args, opt, stats) if getattr(args, "factor", 2) == 2 else run_video_chain(args, opt, stats)
     result_root = os.path.join(args.output_path, f"{n_out * 30}fps_test_results", opt["name"])
     os.makedirs(result_root, exist_ok=True)
     if rank == 0:
@@ -509,6 +515,128 @@ def main(argv=None, stats=None):
     return 0
 
 
+class _VideoFeed:
+    """The input side of the video runners.  A reader thread fills recycled page-locked payload buffers (it starts with the
+    object: ahead of the model's construction, as the folder runner's decoders do); `attach(dev)` creates the upload stream once the
+    device is known; `read_to(i)` uploads frames behind an event and unpacks them with ops.yuv_to_frame into `frames_dev` until
+    frame i is on the device or the stream has ended (`n_frames`).  With --scene_cut, ops.luma_stats runs on the upload stream
+    right behind each upload, its 264-byte record comes back through a page-locked buffer and an event of that stream, and
+    `resolve_cuts()` decides every frame read so far into `cuts` (log lines name output frame `factor` x the input frame)."""
+
+    def __init__(self, args, reader, fmt, pads, factor, log):
+        self.args, self.reader, self.fmt, self.pads, self.factor, self.log = args, reader, fmt, pads, factor, log
+        self.h, self.w, self.nbytes = reader.header.height, reader.header.width, reader.header.frame_bytes
+        self.free_in, self.filled = queue.Queue(), queue.Queue()
+        for _ in range(12):
+            self.free_in.put(None)                     # allocated on first use by the reader thread
+        self.frames_dev = {}
+        self.n_read, self.n_frames = 0, None           # frames uploaded so far; the stream's length once its end was read
+        self.scene_on = args.scene_cut is not None
+        self.cuts, self.n_dup = [], 0                  # cut positions found so far; frames equal to the one before
+        self.rec_pending, self.rec_free, self.rec_prev = {}, [], None   # frame -> (page-locked record, event); spare buffers; (sad, hist) of the frame before
+        self.prev_payload, self.n_resolved = None, 0   # kept alive until the next frame's statistics are queued; frames decided so far
+        threading.Thread(target=self._read_frames, daemon=True).start()
+
+    def _read_frames(self):                            # (reader thread)
+        try:
+            while True:
+                buf = self.free_in.get()
+                if buf is None:
+                    buf = torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=True)
+                if not self.reader.readinto(buf.numpy()):
+                    break
+                self.filled.put(buf)
+            self.filled.put(None)
+        except BaseException as e:                     # handed to the main thread, which raises it
+            self.filled.put(e)
+
+    def attach(self, dev):
+        self.upload_stream = torch.cuda.Stream(device=dev)
+        self.upload = _Uploader(dev, self.upload_stream, self.free_in.put)   # finished uploads hand their buffer back to the reader
+
+    def _queue_stats(self, i, g):
+        """Frame i's statistics on the upload stream, behind its upload; the record goes to page-locked memory behind an event."""
+        h, w = self.h, self.w
+        with torch.cuda.stream(self.upload_stream):
+            rec = ops.luma_stats(g[:h * w], None if self.prev_payload is None else self.prev_payload[:h * w], h, w)
+            host = self.rec_free.pop() if self.rec_free else torch.empty(ops.LUMA_RECORD_BYTES, dtype=torch.uint8, pin_memory=True)
+            host.copy_(rec, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self.rec_pending[i] = (host, ev)
+        self.prev_payload = g
+
+    def resolve_cuts(self):
+        """Decide every frame whose statistics were queued (waits on the upload stream's events only)."""
+        from . import scene
+        h, w, args = self.h, self.w, self.args
+        while self.n_resolved < self.n_read:
+            host, ev = self.rec_pending.pop(self.n_resolved)
+            ev.synchronize()
+            rec = ops.read_luma_record(host)
+            self.rec_free.append(host)
+            if self.n_resolved > 0:
+                self.n_dup += scene.is_duplicate(rec)
+                if scene.is_cut(self.rec_prev, rec, h, w, args.scene_cut, args.scene_cut_min_mad):
+                    self.cuts.append(self.n_resolved)
+                    self.log.info("scene cut at input frame %d (output frame %d): distance %.4f, mean |dY| %.3f", self.n_resolved,
+                                  self.factor * self.n_resolved, scene.distance(self.rec_prev[1], rec[1], h, w), rec[0] / float(h * w))
+            self.rec_prev = rec
+            self.n_resolved += 1
+
+    def read_to(self, i):
+        """Take frames from the reader until frame `i` is on the device or the stream has ended."""
+        while self.n_frames is None and self.n_read <= i:
+            item = self.filled.get()
+            if item is None:
+                self.n_frames = self.n_read
+            elif isinstance(item, BaseException):
+                raise item
+            else:
+                g = self.upload(item)
+                if self.scene_on:
+                    self._queue_stats(self.n_read, g)
+                self.frames_dev[self.n_read] = ops.yuv_to_frame(g, self.h, self.w, self.fmt, self.pads)
+                self.n_read += 1
+
+
+class _VideoWriter:
+    """The ONE writer thread of the video runners: jobs (page-locked [3, frame_bytes] buffer, rows to write, event after which they
+    are complete) are written first in, first out, which is display order; buffers come back through `free_out`.  An error is kept
+    in `error` (the thread keeps draining, so that the main thread never blocks on a dead writer) and raised by the main thread."""
+
+    def __init__(self, target, out_header):
+        from . import video
+        self.to_write, self.free_out, self.error = queue.Queue(maxsize=10), [], []
+
+        def write_frames():
+            writer = None
+            while True:
+                job = self.to_write.get()
+                if job is None:
+                    break
+                if self.error:
+                    continue
+                try:
+                    if writer is None:
+                        writer = video.Y4MWriter(target, out_header)
+                    host, n, done = job
+                    done.synchronize()
+                    for k in range(n):
+                        writer.write(host[k].numpy())
+                    self.free_out.append(host)
+                except BaseException as e:
+                    self.error.append(e)
+            if writer is not None and not self.error:
+                writer.close()
+        self.thread = threading.Thread(target=write_frames, daemon=True)
+        self.thread.start()
+
+    def finish(self):
+        self.to_write.put(None)
+        self.thread.join()
+
+
 def run_video(args, opt, stats=None):
     """The folder runner's pipeline over one Y4M stream.  A reader thread fills recycled page-locked payload buffers; each frame is
     uploaded once on the upload stream behind an event and unpacked by ops.yuv_to_frame on the compute stream, the padded frame
@@ -533,24 +661,7 @@ def run_video(args, opt, stats=None):
     pads = util.pad_sizes(h, w)
     l, r, t, b = pads
 
-    free_in, filled = queue.Queue(), queue.Queue()
-    for _ in range(12):
-        free_in.put(None)                              # allocated on first use by the reader thread
-
-    def read_frames():                                 # (reader thread) runs ahead of the model's construction, as the decoders do
-        try:
-            while True:
-                buf = free_in.get()
-                if buf is None:
-                    buf = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-                if not reader.readinto(buf.numpy()):
-                    break
-                filled.put(buf)
-            filled.put(None)
-        except BaseException as e:                     # handed to the main thread, which raises it
-            filled.put(e)
-    reader_thread = threading.Thread(target=read_frames, daemon=True)
-    reader_thread.start()
+    feed = _VideoFeed(args, reader, fmt, pads, 2, log)
 
     model = create_model(opt)
     netG = model.netG
@@ -565,88 +676,11 @@ def run_video(args, opt, stats=None):
              header.colorspace or "420", header.rate[0], header.rate[1], args.output_video, fmt[1], fmt[2],
              opt["path"]["pretrain_model_G"], reuse)
 
-    upload_stream, copy_stream = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-    frames_dev, stage1_cache = {}, {}
-    n_read, n_frames = 0, None                         # frames uploaded so far; the stream's length once its end was read
-
-    upload = _Uploader(dev, upload_stream, free_in.put)   # finished uploads hand their buffer back to the reader
-
-    scene_on = args.scene_cut is not None
-    cuts, n_dup = [], 0                                # cut positions found so far; frames equal to the one before
-    rec_pending, rec_free, rec_prev = {}, [], None     # frame -> (page-locked record, event); spare buffers; (sad, hist) of the frame before
-    prev_payload, n_resolved = None, 0                 # kept alive until the next frame's statistics are queued; frames decided so far
-
-    def queue_stats(i, g):
-        """Frame i's statistics on the upload stream, behind its upload; the record goes to page-locked memory behind an event."""
-        nonlocal prev_payload
-        with torch.cuda.stream(upload_stream):
-            rec = ops.luma_stats(g[:h * w], None if prev_payload is None else prev_payload[:h * w], h, w)
-            host = rec_free.pop() if rec_free else torch.empty(ops.LUMA_RECORD_BYTES, dtype=torch.uint8, pin_memory=True)
-            host.copy_(rec, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        rec_pending[i] = (host, ev)
-        prev_payload = g
-
-    def resolve_cuts():
-        """Decide every frame whose statistics were queued (waits on the upload stream's events only)."""
-        nonlocal n_resolved, n_dup, rec_prev
-        while n_resolved < n_read:
-            host, ev = rec_pending.pop(n_resolved)
-            ev.synchronize()
-            rec = ops.read_luma_record(host)
-            rec_free.append(host)
-            if n_resolved > 0:
-                n_dup += scene.is_duplicate(rec)
-                if scene.is_cut(rec_prev, rec, h, w, args.scene_cut, args.scene_cut_min_mad):
-                    cuts.append(n_resolved)
-                    log.info("scene cut at input frame %d (output frame %d): distance %.4f, mean |dY| %.3f", n_resolved, 2 * n_resolved,
-                             scene.distance(rec_prev[1], rec[1], h, w), rec[0] / float(h * w))
-            rec_prev = rec
-            n_resolved += 1
-
-    def read_to(i):
-        """Take frames from the reader until frame `i` is on the device or the stream has ended."""
-        nonlocal n_read, n_frames
-        while n_frames is None and n_read <= i:
-            item = filled.get()
-            if item is None:
-                n_frames = n_read
-            elif isinstance(item, BaseException):
-                raise item
-            else:
-                g = upload(item)
-                if scene_on:
-                    queue_stats(n_read, g)
-                frames_dev[n_read] = ops.yuv_to_frame(g, h, w, fmt, pads)
-                n_read += 1
-
-    out_header = header.doubled()
-    to_write, free_out = queue.Queue(maxsize=10), []
-    write_error = []
-
-    def write_frames():                                # (the ONE writer thread) first in, first out: display order
-        writer = None
-        while True:
-            job = to_write.get()
-            if job is None:
-                break
-            if write_error:
-                continue                               # keep draining, so that the main thread never blocks on a dead writer
-            try:
-                if writer is None:
-                    writer = video.Y4MWriter(args.output_video, out_header)
-                host, n, done = job
-                done.synchronize()
-                for k in range(n):
-                    writer.write(host[k].numpy())
-                free_out.append(host)
-            except BaseException as e:
-                write_error.append(e)
-        if writer is not None and not write_error:
-            writer.close()
-    writer_thread = threading.Thread(target=write_frames, daemon=True)
-    writer_thread.start()
+    feed.attach(dev)
+    copy_stream = torch.cuda.Stream(device=dev)
+    frames_dev, stage1_cache = feed.frames_dev, {}
+    scene_on = feed.scene_on
+    out = _VideoWriter(args.output_video, header.doubled())
 
     timer, stamps, group = AverageMeter(), [], []
     n_written = 0
@@ -685,17 +719,17 @@ def run_video(args, opt, stats=None):
                 last_payload = outs[k]
             ready = torch.cuda.Event()
             ready.record()
-            host = free_out.pop() if free_out else torch.empty((3, nbytes), dtype=torch.uint8, pin_memory=True)
+            host = out.free_out.pop() if out.free_out else torch.empty((3, nbytes), dtype=torch.uint8, pin_memory=True)
             with torch.cuda.stream(copy_stream):
                 copy_stream.wait_event(ready)
                 host[:len(slots)].copy_(outs[:len(slots)], non_blocking=True)
                 outs.record_stream(copy_stream)
                 done = torch.cuda.Event()
                 done.record()
-            to_write.put((host, len(slots), done))
+            out.to_write.put((host, len(slots), done))
             n_written += len(slots)
-        if write_error:
-            raise write_error[0]
+        if out.error:
+            raise out.error[0]
         timer.update((time.time() - t0) / len(group), len(group))
         stamps.extend([time.time()] * len(group))
         group.clear()
@@ -706,12 +740,13 @@ def run_video(args, opt, stats=None):
     try:
         with torch.no_grad():
             while True:
-                read_to(index + 3)
+                feed.read_to(index + 3)
+                n_frames, cuts = feed.n_frames, feed.cuts
                 if n_frames is not None and index > n_frames - 2:
                     break
                 known = n_frames if n_frames is not None else index + 4      # clamping only bites once the end is known
                 if scene_on:
-                    resolve_cuts()                      # every pair up to (index + 2, index + 3), or up to the stream's end
+                    feed.resolve_cuts()                 # every pair up to (index + 2, index + 3), or up to the stream's end
                     if index in cuts:
                         scene_start = index
                     # the scene's end: the next cut when it is in sight; beyond index + 3 any end gives the same window
@@ -730,11 +765,11 @@ def run_video(args, opt, stats=None):
             flush()
             torch.cuda.current_stream(dev).synchronize()
     finally:
-        to_write.put(None)
-        writer_thread.join()
+        out.finish()
         reader.close()
-    if write_error:
-        raise write_error[0]
+    if out.error:
+        raise out.error[0]
+    n_frames, cuts, n_dup = feed.n_frames, feed.cuts, feed.n_dup
     if n_frames < 2:
         raise ValueError(f"{args.input_video}: a video needs at least 2 frames to interpolate (got {n_frames})")
     torch.cuda.synchronize()
@@ -747,6 +782,150 @@ def run_video(args, opt, stats=None):
     if stats is not None:
         stats.update(windows=index, wall=wall, net_s_per_window=timer.avg, stamps=[s - t_all for s in stamps], frames_out=n_written)
         if scene_on:
+            stats.update(cuts=list(cuts))
+    return 0
+
+def run_video_chain(args, opt, stats=None):
+    """run_video at --factor 4 | 8: the same feed and the same single writer thread, with the passes of bin_amd/chain.py between the
+    generator and the writer.  Level 1 is run_video's window loop (chain.level1_plan: window i runs once frame i + 3 or the end of
+    the stream has been read, inside its scene with --scene_cut); its fp32 outputs go to chain.Chain, which runs the higher passes as
+    their frames appear and emits in display order, so the stream's length need not be known and the frames resident on the device
+    do not grow with it.  The bytes are harness.interpolate_video's at the same factor."""
+    from . import chain, video
+    factor = args.factor
+    k = chain.levels(factor)
+    log_root = os.getcwd() if args.output_video == "-" else os.path.dirname(os.path.abspath(args.output_video))
+    os.makedirs(log_root, exist_ok=True)
+    util.setup_logger("base", log_root, "test_video", screen=True, tofile=True)
+    log = logging.getLogger("base")
+    reader = video.Y4MReader(args.input_video)       # (the header is read and checked here: before the model is built)
+    header = reader.header
+    fmt = video.resolve_format(header, args.yuv_matrix, args.yuv_range)
+    h, w, nbytes = header.height, header.width, header.frame_bytes
+    pads = util.pad_sizes(h, w)
+    l, r, t, b = pads
+    feed = _VideoFeed(args, reader, fmt, pads, factor, log)
+
+    model = create_model(opt)
+    netG = model.netG
+    netG.eval()
+    dev = next(netG.parameters()).device
+    net = harness.ChainNet(netG, k, h, w, reuse_stage1=not args.no_reuse, batch=args.batch, ensemble=args.self_ensemble)
+    log.info("In video: %s %dx%d C%s F%d:%d -> %s at factor %d | YUV: %s %s | model: %s | stage-1 reuse: %s", args.input_video, w, h,
+             header.colorspace or "420", header.rate[0], header.rate[1], args.output_video, factor, fmt[1], fmt[2],
+             opt["path"]["pretrain_model_G"], net.caches[0] is not None)
+    feed.attach(dev)
+    copy_stream = torch.cuda.Stream(device=dev)
+    frames_dev = feed.frames_dev
+    out = _VideoWriter(args.output_video, header.multiplied(factor))
+
+    emitted = []                                       # device payloads the passes emitted since the last hand-over to the writer
+    n_written, last_payload = 0, None
+
+    def emit(pos, frame):
+        nonlocal last_payload
+        assert pos == n_written + len(emitted)         # display order
+        if frame is not chain.HOLD:
+            last_payload = ops.frame_to_yuv(frame, t, l, h, w, fmt)
+        emitted.append(last_payload)
+
+    def hand_over():
+        """What was emitted goes to page-locked memory on the copy stream and to the writer, three payloads per job, in order."""
+        nonlocal n_written
+        for first in range(0, len(emitted), 3):
+            rows = emitted[first:first + 3]
+            outs = torch.stack(rows)
+            ready = torch.cuda.Event()
+            ready.record()
+            host = out.free_out.pop() if out.free_out else torch.empty((3, nbytes), dtype=torch.uint8, pin_memory=True)
+            with torch.cuda.stream(copy_stream):
+                copy_stream.wait_event(ready)
+                host[:len(rows)].copy_(outs, non_blocking=True)
+                outs.record_stream(copy_stream)
+                done = torch.cuda.Event()
+                done.record()
+            out.to_write.put((host, len(rows), done))
+            n_written += len(rows)
+        emitted.clear()
+        if out.error:
+            raise out.error[0]
+
+    passes = chain.Chain(factor, net.forward, net.reframe, emit, batch=net.batch, new_scene=net.new_scene)
+    timer, stamps, group = AverageMeter(), [], []      # group: (ids, six frames, slots) of level-1 windows waiting for one forward
+    n_level1 = 0
+
+    def flush():
+        nonlocal n_level1
+        if not group:
+            return
+        t0 = time.time()
+        Ft_p = net.run(1, [(ids, frames) for ids, frames, _ in group], OUT_KEYS)
+        for j, (_, _, slots) in enumerate(group):
+            passes.push([Ft_p[slot] if len(group) == 1 else Ft_p[slot][j:j + 1] for slot in slots])
+        hand_over()
+        n_level1 += len(group)
+        timer.update((time.time() - t0) / len(group), len(group))
+        stamps.extend([time.time()] * len(group))
+        group.clear()
+
+    t_all = time.time()
+    index, scene_start, scene_open = 0, 0, False
+    try:
+        with torch.no_grad():
+            while True:
+                feed.read_to(index + 3)
+                n_frames, cuts = feed.n_frames, feed.cuts
+                if n_frames is not None and index > n_frames - 2:
+                    break
+                known = n_frames if n_frames is not None else index + 4      # clamping only bites once the end is known
+                scene_end = known
+                if feed.scene_on:
+                    feed.resolve_cuts()                 # every pair up to (index + 2, index + 3), or up to the stream's end
+                    if index in cuts:
+                        scene_start = index
+                    # the scene's end: the next cut when it is in sight; beyond index + 3 any end gives the same window
+                    scene_end = next((c for c in cuts if c > index), known)
+                if not scene_open:
+                    passes.begin(scene_start)
+                    scene_open = True
+                ids, slots, last = chain.level1_plan(index, scene_start, scene_end)
+                if ids is not None:
+                    group.append((ids, [frames_dev[f] for f in ids], slots))
+                    for fid in [f for f in frames_dev if f < min(ids)]:
+                        del frames_dev[fid]
+                if last or len(group) >= net.batch:
+                    flush()
+                if last:                                # a cut follows this frame: the scene's last frame, then the holds
+                    passes.end(final=False)
+                    scene_open = False
+                    hand_over()
+                index += 1
+            flush()
+            if scene_open:
+                passes.end(final=True)
+                hand_over()
+            torch.cuda.current_stream(dev).synchronize()
+    finally:
+        out.finish()
+        reader.close()
+    if out.error:
+        raise out.error[0]
+    n_frames, cuts = feed.n_frames, feed.cuts
+    if n_frames < 2:
+        raise ValueError(f"{args.input_video}: a video needs at least 2 frames to interpolate (got {n_frames})")
+    torch.cuda.synchronize()
+    ops.check_status(dev)                 # a frame that left the fp16 storage range is an error, not a result
+    wall = time.time() - t_all
+    windows_per_pass = [n_level1] + list(passes.windows)
+    log.info("frames in: %d  out: %d  factor: %d  windows per pass: %s  wall: %.2f s  -> %.2f output frames/s (IO included); frames "
+             "resident in the passes at most %d", n_frames, n_written, factor, windows_per_pass, wall, n_written / max(wall, 1e-9),
+             passes.frames_resident_peak)
+    if feed.scene_on:
+        log.info("scene cuts: %d at input frames %s; duplicates: %d", len(cuts), ", ".join(str(c) for c in cuts) or "-", feed.n_dup)
+    if stats is not None:
+        stats.update(windows=index, wall=wall, net_s_per_window=timer.avg, stamps=[s - t_all for s in stamps], frames_out=n_written,
+                     factor=factor, windows_per_pass=windows_per_pass, frames_resident_peak=passes.frames_resident_peak)
+        if feed.scene_on:
             stats.update(cuts=list(cuts))
     return 0
 

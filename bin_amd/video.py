@@ -54,6 +54,12 @@ class Y4MHeader:
         """The header of the interpolated stream: F = 2n:d, everything else unchanged."""
         return replace(self, rate=(2 * self.rate[0], self.rate[1]))
 
+    def multiplied(self, f):
+        """The header of a stream interpolated to f times the frame rate (--factor): F = f n:d, everything else unchanged."""
+        if type(f) is not int or f < 1:
+            raise ValueError(f"a frame rate is multiplied by a positive integer (got {f!r})")
+        return replace(self, rate=(f * self.rate[0], self.rate[1]))
+
     def line(self):
         tags = [f"W{self.width}", f"H{self.height}", f"F{self.rate[0]}:{self.rate[1]}"]
         if self.interlace is not None:

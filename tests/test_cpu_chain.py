@@ -1,0 +1,336 @@
+"""CPU: the chained interpolation passes (--factor 4 | 8) without a device — libbinchain.so's ABI bookkeeping and its refusals before
+any launch, chain.Chain on stub frames against the definition restated by brute force (chain_cases.py), the scene composition for
+every cut set of every short stream, the entry point's argument checks and the Y4M header.  GPU side: test_gpu_chain.py."""
+import ctypes as C
+import inspect
+import os
+import re
+import subprocess
+from fractions import Fraction
+
+import pytest
+import torch
+
+import chain_cases as CC
+from conftest import REPO
+
+
+def _defined(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()}
+
+
+# ------------------------------------------------------------------------------------------------ ABI bookkeeping
+def test_chain_library_header_and_binding_agree():
+    """libbinchain.so is a library of its own beside the other seven, whose tuples do not change with it: its dynamic symbols are
+    exactly include/binchain.h's declarations, the binding's and nothing else."""
+    from bin_amd import _lib, build
+    hdr = open(os.path.join(REPO, "include", "binchain.h")).read()
+    want = ["binchain_version", "binchain_reframe"]
+    assert build.chain_abi_symbols() == want and build.CHAIN_SOURCES == ["binchain.hip"]
+    assert set(_lib.chain_exported_symbols()) == set(want)
+    assert set(re.findall(r"\b(binchain_[a-z0-9_]+)\s*\(", hdr)) == set(want)
+    assert os.path.basename(build.CHAIN_LIB_PATH) == "libbinchain.so" and os.path.basename(build.CHAIN_HEADER) == "binchain.h"
+    assert build.CHAIN_LIBRARIES == (("binchain", build.CHAIN_SOURCES, build.CHAIN_HEADER, build.CHAIN_LIB_PATH),)
+    assert _defined(build.CHAIN_LIB_PATH) == set(want)
+    # the tuples existing tests pin are what they were; ALL_LIBRARIES is what the product build makes
+    assert build.ALL_LIBRARIES == build.PRODUCT_LIBRARIES + build.CHAIN_LIBRARIES
+    assert build.PRODUCT_LIBRARIES == build.LIBRARIES + build.IO_LIBRARIES + build.ANALYSIS_LIBRARIES
+    assert [name for name, _, _, _ in build.LIBRARIES] == ["binhip", "binopt", "bingrad", "binema", "binens"]
+    assert [name for name, _, _, _ in build.IO_LIBRARIES] == ["binyuv"] and [name for name, _, _, _ in build.ANALYSIS_LIBRARIES] == ["binscene"]
+    assert [name for name, _, _, _ in build.ALL_LIBRARIES][-1] == "binchain" and len(build.ALL_LIBRARIES) == 8
+    for name, _, header, _ in build.PRODUCT_LIBRARIES:
+        assert "binchain" not in open(header).read().lower(), name
+    assert "ALL_LIBRARIES" in inspect.getsource(build._stale) and "ALL_LIBRARIES" in inspect.getsource(build.build_library)
+    assert '(("binhip", SOURCES, HEADER, out),)' in inspect.getsource(build.build_library), "the side build makes libbinhip alone"
+    # macros, version, codes
+    assert all(m.startswith("BINCHAIN_") for m in re.findall(r"#\s*define\s+(\w+)", hdr))
+    switches = re.findall(r"(?m)^\s*#\s*(?:if|ifdef|ifndef|elif)\b\s*(.*)$", hdr)
+    assert switches == ["__cplusplus", "__cplusplus"], "#pragma once: no include-guard macro, no switches"
+    lib = _lib.chainlib()
+    ver = int(re.search(r"#define\s+BINCHAIN_VERSION\s+(\d+)", hdr).group(1))
+    assert lib.binchain_version() == ver == _lib.CHAIN_VERSION == 100
+    for name, value in (("BINCHAIN_E_ARG", -1), ("BINCHAIN_E_SHAPE", -2)):
+        assert int(re.search(rf"#define\s+{name}\s+\((-?\d+)\)", hdr).group(1)) == value
+    assert int(re.search(r"#define\s+BINCHAIN_MAX_ITEMS\s+(\d+)", hdr).group(1)) == _lib.CHAIN_MAX_ITEMS >= 8
+    # the struct: as the C compiler lays it out (the source asserts the size)
+    assert re.search(r"typedef struct BinChainItem \{\s*const float\* src;\s*float\* dst;\s*\} BinChainItem;", hdr)
+    item = _lib.BinChainItem
+    assert C.sizeof(item) == 16 and (item.src.offset, item.dst.offset) == (0, 8)
+    src = open(os.path.join(REPO, "bin_amd", "csrc", "binchain.hip")).read()
+    assert "static_assert(sizeof(BinChainItem) == 16" in src
+    assert not re.search(r"(?m)^\s*#\s*(if|ifdef|ifndef|elif|define)\b", src), "no preprocessor switches in the source"
+    assert "asm" not in re.sub(r"//.*", "", src) and "__shared__" not in src, "plain HIP C++, no LDS"
+    assert "_lib.chainlib()" in open(os.path.join(REPO, "__graft_entry__.py")).read()
+    ignored = subprocess.run(["git", "check-ignore", "bin_amd/csrc/libbinchain.so", "bin_amd/csrc/binchain.o",
+                              "bin_amd/csrc/binhip_exports.binchain.map"], cwd=REPO, capture_output=True, text=True)
+    if ignored.returncode != 128:                                 # (128: not a git checkout)
+        assert len(ignored.stdout.split()) == 3, "the built files stay out of git"
+
+
+def test_chain_module_is_host_only():
+    src = open(os.path.join(REPO, "bin_amd", "chain.py")).read()
+    assert not re.search(r"(?m)^\s*(import|from)\s", src), "no imports at all: neither torch nor the device code"
+
+
+# ------------------------------------------------------------------------------------------------ refusals before any launch
+def test_reframe_refuses_bad_arguments_before_any_hip_call():
+    """Every refusal comes before the first HIP call, so it runs without a device (the pointers below are never dereferenced)."""
+    from bin_amd import _lib
+    lib = _lib.chainlib()
+    SRC, DST = 0x1000000, 0x4000000
+    src_bytes, dst_bytes = 3 * 12 * 16 * 4, 3 * 9 * 13 * 4
+
+    def call(items=((SRC, DST),), n=None, planes=3, hs=12, ws=16, top=3, left=1, h=6, w=10, pads=(1, 2, 3, 0)):
+        table = (_lib.BinChainItem * max(len(items), 1))()
+        for it, (s, d) in zip(table, items):
+            it.src, it.dst = s, d
+        return lib.binchain_reframe(table, len(items) if n is None else n, planes, hs, ws, top, left, h, w, *pads, None)
+    assert call(items=(), n=0) == 0 and lib.binchain_reframe(None, 0, 3, 12, 16, 3, 1, 6, 10, 1, 2, 3, 0, None) == 0, "n == 0: no launch"
+    assert call(n=-1) == -1 and call(n=_lib.CHAIN_MAX_ITEMS + 1) == -1
+    assert lib.binchain_reframe(None, 1, 3, 12, 16, 3, 1, 6, 10, 1, 2, 3, 0, None) == -1, "a null table"
+    for s, d in ((None, DST), (SRC, None), (SRC + 2, DST), (SRC, DST + 1), (SRC + 3, DST + 3)):
+        assert call(items=((s, d),)) == -1, (s, d)
+    for kw in (dict(planes=0), dict(planes=-3), dict(hs=0), dict(ws=0), dict(h=0), dict(w=0), dict(h=-6), dict(w=-1), dict(hs=-12)):
+        assert call(**kw) == -1, kw
+        assert call(items=(), n=0, **kw) == -1, "a bad shape is refused whatever n"
+    for pads in ((-1, 0, 0, 0), (0, -1, 0, 0), (0, 0, -1, 0), (0, 0, 0, -1)):
+        assert call(pads=pads) == -1
+    for kw in (dict(top=-1), dict(left=-1), dict(top=7), dict(left=7), dict(h=10), dict(w=16), dict(top=2 ** 31 - 1), dict(left=2 ** 31 - 1),
+               dict(h=2 ** 31 - 1), dict(w=2 ** 31 - 1)):
+        assert call(**kw) == -1, kw
+    # element counts beyond 2^40, padded sides beyond 2^31 - 1
+    big = 2 ** 31 - 1
+    assert call(hs=2 ** 20, ws=2 ** 20, planes=3) == -2, "the source beyond 2^40"
+    assert call(pads=(0, 0, big, 0)) == -2 and call(pads=(0, big, 0, 0)) == -2 and call(pads=(big, big, 0, 0)) == -2, "a side beyond 2^31 - 1"
+    assert call(pads=(2 ** 20, 0, 2 ** 20, 0)) == -2, "the destination beyond 2^40"
+    # overlaps: a destination on its source, on another item's source or destination; shared sources are fine (but not called: they
+    # would launch)
+    assert call(items=((SRC, SRC),)) == -1 and call(items=((SRC, SRC + src_bytes - 4),)) == -1 and call(items=((SRC, SRC - dst_bytes + 4),)) == -1
+    far = DST + 0x1000000
+    assert call(items=((SRC, DST), (far, SRC + 64))) == -1, "item 1's destination on item 0's source"
+    assert call(items=((SRC, DST), (far, DST + dst_bytes - 4))) == -1, "two destinations overlap"
+    assert call(items=((SRC, DST), (SRC, DST))) == -1
+
+
+def test_ops_reframe_refuses_cpu_tensors_and_wrong_layouts():
+    from bin_amd import _lib, ops
+    x = torch.zeros(1, 3, 12, 16)
+    with pytest.raises(RuntimeError, match="HIP device"):
+        ops.reframe(x, 3, 1, 6, 10, (1, 2, 3, 0))
+    with pytest.raises(RuntimeError, match="HIP device"):
+        ops.reframe([x, x], 3, 1, 6, 10, (1, 2, 3, 0))
+    for kw in (dict(pads=(0, -1, 0, 0)), dict(pads=(0, 0, 0)), dict(h=0), dict(w=0), dict(top=-1), dict(left=-2)):
+        args = dict(top=3, left=1, h=6, w=10, pads=(1, 2, 3, 0))
+        args.update(kw)
+        with pytest.raises(ValueError):
+            ops.reframe(x, **args)
+    with pytest.raises(ValueError, match="at most"):
+        ops.reframe([x] * (_lib.CHAIN_MAX_ITEMS + 1), 3, 1, 6, 10, (1, 2, 3, 0))
+    assert ops.reframe([], 3, 1, 6, 10, (1, 2, 3, 0)) == []
+    assert list(inspect.signature(ops.reframe).parameters) == ["frames", "top", "left", "h", "w", "pads", "out"]
+
+
+# ------------------------------------------------------------------------------------------------ level arithmetic
+def test_level_arithmetic():
+    from bin_amd import chain, harness, scene
+    assert [chain.levels(f) for f in (2, 4, 8)] == [1, 2, 3] and chain.FACTORS == CC.FACTORS and chain.HOLD is scene.HOLD
+    for bad in (0, 1, 3, 6, 16, -2, 2.0, 4.0, True, "4", None):
+        with pytest.raises(ValueError, match="factor"):
+            chain.levels(bad)
+    for n in range(1, 12):
+        assert chain.sequence_length(n, 1) == 2 * (n - 1) + 1
+        for p in (2, 3):
+            assert chain.sequence_length(n, p) == 2 * chain.sequence_length(n, p - 1) - 1
+        for j in range(n):
+            assert chain.window_ids(j, n) == harness.window_frame_ids(j, n) == CC.window_ids(j, n)
+    for T in range(2, 9):
+        for F, k in ((2, 1), (4, 2), (8, 3)):
+            levels, _ = CC.scene_levels(T, k)
+            assert len(levels[-1]) == chain.sequence_length(T, k) == F * (T - 1) + 1
+            assert levels[-1] == [Fraction(j, F) for j in range(F * (T - 1) + 1)], "the restatement itself: every 1/F"
+
+
+def test_level1_plan_is_scene_plans_windows_with_the_last_deblurred_frame_kept():
+    from bin_amd import chain, scene
+    for T in range(2, 8):
+        for cuts in CC.all_cut_sets(T):
+            for s, e in scene.segments(T, cuts):
+                for i in range(s, min(e, T - 1)):
+                    ids, slots, last = chain.level1_plan(i, s, e)
+                    ref_ids, ref_out = scene.plan(i, s, e, T)
+                    assert ids == ref_ids and last == (i + 1 == e)
+                    ref_slots = tuple(slot for _, slot in ref_out if slot is not scene.HOLD)
+                    if i + 1 < e:                       # scene.plan drops slot 12 of the stream's last window; the chain keeps it
+                        assert slots == (((8,) if i == s else ()) + (13, 12)) and slots[:len(ref_slots)] == ref_slots
+                    else:
+                        assert slots == ref_slots == ((8,) if i == s else ())
+    with pytest.raises(ValueError):
+        chain.level1_plan(3, 0, 3)
+
+
+# ------------------------------------------------------------------------------------------------ the scheduler on stub frames
+def _forwards(run, level, scene_index=None):
+    """[window ids] of the forwards of pass `level`, in order (of one scene of the run when given)."""
+    out, scene_no = [], 0
+    for entry in run.log:
+        if entry == ("scene",):
+            scene_no += 1
+        elif entry[0] == "forward" and entry[1] == level and scene_index in (None, scene_no - 1):
+            out.append(entry[2])
+    return out
+
+
+@pytest.mark.parametrize("F", CC.FACTORS)
+@pytest.mark.parametrize("T", CC.LENGTHS)
+def test_scheduler_equals_the_definition(T, F):
+    from bin_amd import chain
+    k = chain.levels(F)
+    run = CC.StubRun(T, F)
+    assert run.emitted == [Fraction(j, F) for j in range(F * (T - 1))], "every 1/F in display order, all but the last"
+    levels, ids = CC.scene_levels(T, k)
+    for p in range(2, k + 1):
+        L = chain.sequence_length(T, p - 1)
+        assert _forwards(run, p) == ids[p] == [chain.window_ids(j, L) for j in range(L - 1)]
+    assert run.chain.windows == [chain.sequence_length(T, p - 1) - 1 for p in range(2, k + 1)]
+    assert run.level1_ids == CC.expected_level1_ids(T, ()) == [chain.window_ids(i, T) for i in range(T - 1)]
+    # every frame a pass consumes is reframed exactly once over the whole run: the level-1 frames and every pass's outputs but the last's
+    n_consumed = chain.sequence_length(T, k - 1) if k > 1 else 0
+    assert len(run.reframed) == len(set(run.reframed)) == n_consumed
+    # the same object is handed over for the same frame in every window of a pass that names it
+    assert run.seen or k == 1
+    assert all(len(objs) == 1 for objs in run.seen.values())
+    # ... and the passes share it: pass p + 1's sequence id 2j is pass p's j
+    for (scene_no, level, i), objs in run.seen.items():
+        if level < k and (scene_no, level + 1, 2 * i) in run.seen:
+            assert run.seen[(scene_no, level + 1, 2 * i)] == objs
+    assert sum(1 for entry in run.log if entry == ("scene",)) == 1
+
+
+@pytest.mark.parametrize("F", CC.FACTORS)
+@pytest.mark.parametrize("T", CC.LENGTHS)
+def test_incremental_driver_equals_the_all_at_once_driver_and_runs_windows_as_early_as_it_may(T, F):
+    from bin_amd import chain
+    k = chain.levels(F)
+    whole, single = CC.StubRun(T, F), CC.StubRun(T, F, step=1)
+    strip = lambda log: [entry for entry in log if entry[0] != "push"]
+    assert single.emitted == whole.emitted and strip(single.log) == strip(whole.log)
+    # pass p runs window j in the push that makes frame j + 3 of its input exist, or when the end is known.  Its input's frames
+    # exist in order: the level-1 frames as pushed, S(p)[0 .. 2c-1] after c windows of pass p (and the last one at the end).
+    exist, ended = {1: 0}, False
+    done = {p: 0 for p in range(2, k + 1)}
+    for entry in single.log:
+        if entry[0] == "push":
+            exist[1] = entry[1]
+        elif entry == ("end",):
+            ended = True
+        elif entry[0] == "forward":
+            _, p, ids = entry
+            j = done[p]
+            have = exist[1] if p == 2 else 2 * done[p - 1]
+            if not ended:
+                assert j + 3 < have, "its frame j + 3 exists"
+                assert j + 3 >= have - (1 if p == 2 else 2), "... and came with this very push"
+            done[p] += 1
+    assert ended and all(done[p] == chain.sequence_length(T, p - 1) - 1 for p in done)
+
+
+def test_live_frames_do_not_grow_with_the_stream():
+    for F in (4, 8):
+        peaks = {T: CC.StubRun(T, F, step=1).chain.frames_resident_peak for T in (10, 40, 41)}
+        assert peaks[10] == peaks[40] == peaks[41] > 0, peaks
+        # per pass at most seven sequence ids (a window's six and the next one) with two objects each and the two frames being
+        # handed on; the emitter holds one
+        assert peaks[10] <= 16 * (F.bit_length() - 2) + 1
+    assert CC.StubRun(10, 2).chain.frames_resident_peak == CC.StubRun(40, 2).chain.frames_resident_peak == 1
+
+
+@pytest.mark.parametrize("batch", [2, 3, 8])
+def test_batched_passes_emit_the_same_stream(batch):
+    for F in (4, 8):
+        for T in (2, 3, 6, 9):
+            a, b = CC.StubRun(T, F), CC.StubRun(T, F, batch=batch)
+            assert a.emitted == b.emitted
+            for level in range(2, F.bit_length()):
+                assert _forwards(a, level) == _forwards(b, level)
+
+
+# ------------------------------------------------------------------------------------------------ scene cuts
+@pytest.mark.parametrize("F", CC.FACTORS)
+def test_every_cut_set_of_every_short_stream_equals_its_scenes_run_alone(F):
+    from bin_amd import chain
+    k = chain.levels(F)
+    n_cases = 0
+    for T in range(2, 7):
+        for cuts in CC.all_cut_sets(T):
+            run = CC.StubRun(T, F, cuts=cuts)
+            want = CC.expected_stream(T, cuts, F)
+            assert run.emitted == want and len(run.emitted) == F * (T - 1), (T, cuts)
+            assert run.level1_ids == CC.expected_level1_ids(T, cuts), (T, cuts)
+            begun = [(s, e) for s, e in CC.segments(T, cuts) if s < T - 1]        # (the stream's last frame alone is no scene of the run)
+            assert sum(1 for entry in run.log if entry == ("scene",)) == len(begun)
+            for index, (s, e) in enumerate(begun):
+                _, ids = CC.scene_levels(e - s, k)
+                for p in range(2, k + 1):
+                    assert _forwards(run, p, index) == ids[p], (T, cuts, s, e, p)
+                # positions: the scene's own stream from F s on, then the holds up to F e
+                if e < T:
+                    alone = CC.StubRun(e - s + 1, F, cuts=[e - s]).emitted       # the scene and one more frame behind a cut
+                    assert [t if t == CC.HOLD else t + s for t in alone[:F * (e - s)]] == run.emitted[F * s:F * e]
+                    assert run.emitted[F * (e - 1) + 1:F * e] == [CC.HOLD] * (F - 1) and run.emitted[F * (e - 1)] == e - 1
+                else:
+                    alone = CC.StubRun(e - s, F).emitted
+                    assert [t + s for t in alone] == run.emitted[F * s:]
+            n_cases += 1
+    assert n_cases == sum(2 ** (T - 1) for T in range(2, 7))
+
+
+def test_a_chain_refuses_a_scene_inside_a_scene():
+    from bin_amd import chain
+    c = chain.Chain(4, lambda level, jobs: [], lambda frames: [], lambda pos, f: None)
+    c.begin(0)
+    with pytest.raises(RuntimeError):
+        c.begin(3)
+
+
+# ------------------------------------------------------------------------------------------------ the entry point and the header
+def test_cli_factor_argument_and_its_refusals_come_before_the_model_is_built(monkeypatch):
+    from bin_amd import harness, test as T, video as V
+    monkeypatch.setattr(T, "create_model", lambda *a, **k: pytest.fail("the model must not be built"))
+    monkeypatch.setattr(T.option, "parse", lambda *a, **k: pytest.fail("the options must not be read"))
+    base = ["--opt", "c", "--input_video", "in.y4m", "--output_video", "-"]
+    assert T.parse_args(base).factor == 2
+    assert [T.parse_args(base + ["--factor", str(f)]).factor for f in (2, 4, 8)] == [2, 4, 8]
+    for bad in ("3", "16", "0", "4.0"):
+        with pytest.raises(SystemExit):
+            T.parse_args(base + ["--factor", bad])
+    folder = ["--opt", "c", "--input_path", "a", "--output_path", "b"]
+    assert T.parse_args(folder).factor == 2 and T.parse_args(folder + ["--factor", "2"]).factor == 2
+    for f in ("4", "8"):
+        with pytest.raises(ValueError, match="--factor"):
+            T.main(folder + ["--factor", f])
+    import argparse
+    T.check_args(argparse.Namespace(input_video=None, output_video=None, input_path="a", output_path="b", gt_path=None, launcher="none"))
+    with pytest.raises(ValueError, match="--factor"):
+        T.check_args(argparse.Namespace(input_video=None, output_video=None, input_path="a", output_path="b", gt_path=None,
+                                        launcher="none", factor=4))
+    sig = inspect.signature(harness.interpolate_video).parameters
+    assert sig["factor"].default == 2 and list(sig)[-2:] == ["factor", "scene_cut"], "scene_cut stays the last parameter"
+    header = V.Y4MHeader(40, 24)
+    for bad in (3, 1, 0, 16, 4.0, "4"):
+        with pytest.raises(ValueError, match="factor"):
+            harness.interpolate_video(None, torch.zeros(3, header.frame_bytes, dtype=torch.uint8), header, factor=bad)
+    with pytest.raises(ValueError, match="at least 2 frames"):
+        harness.interpolate_video(None, torch.zeros(1, header.frame_bytes, dtype=torch.uint8), header, factor=4)
+
+
+def test_header_multiplied():
+    from bin_amd import video as V
+    h = V.parse_header(b"YUV4MPEG2 W40 H24 F30000:1001 Ip A1:1 C444 XCOLORRANGE=FULL")
+    assert h.multiplied(2) == h.doubled() and h.doubled().rate == (60000, 1001)
+    assert h.multiplied(4).rate == (120000, 1001) and h.multiplied(8).rate == (240000, 1001)
+    assert h.multiplied(4).line() == b"YUV4MPEG2 W40 H24 F120000:1001 Ip A1:1 C444 XCOLORRANGE=FULL\n"
+    assert h.multiplied(1) == h and h.multiplied(8) == h.multiplied(2).multiplied(4)
+    for bad in (0, -2, 1.5):
+        with pytest.raises(ValueError):
+            h.multiplied(bad)
