@@ -19,10 +19,14 @@ end of that sequence is known, hands S[j] and the new frame on to pass p+1 in or
 the number of live frames per pass does not depend on the length of the stream.  The last level is emitted in display order at
 positions F*start + index; the scene's last frame D_(n-1) is followed by F-1 holds when a cut follows it (the positions up to the
 next scene's F*e) and is not emitted at all when the stream ends there: a stream of T frames gives F(T-1) outputs, and every second
-one of them is the output at F/2."""
+one of them is the output at F/2.
 
-HOLD = None                                # emit()'s frame of a held position: the payload emitted just before, once more (= scene.HOLD)
+`run_stream` is the window loop of every video run (bin_amd.test's on a pipe, harness.interpolate_video's in memory): level 1 over a
+feed of frames into a Chain.  Factor 2 is the same loop: levels(2) == 1, the Chain is its emitter alone."""
+
+HOLD = None                                # emit()'s frame of a held position: the payload emitted just before, once more
 FACTORS = (2, 4, 8)
+SLOTS = (13, 8, 12)                        # what a level-1 forward is asked for: interpolated, first deblurred, second deblurred
 
 
 def levels(factor):
@@ -38,13 +42,13 @@ def sequence_length(n_frames, level):
 
 
 def window_ids(index, length):
-    """The six sequence ids of the window centred on `index` (harness.window_frame_ids): index + [-2 .. 3], clamped."""
+    """The six sequence ids of the window centred on `index` (the reference's test.py:257-261): index + [-2 .. 3], clamped."""
     return [min(max(index + d, 0), length - 1) for d in (-2, -1, 0, 1, 2, 3)]
 
 
 def level1_plan(i, s, e):
     """Window i of the scene [s, e) of input frames, s <= i < e: (ids, slots, last).  ids: the six input frame ids of the forward
-    (scene.plan's: clamped to the scene), or None when none is run; slots: the Ft_p slots that are the next level-1 frames, in
+    (clamped to the scene: the reference's end-of-clip rule, applied at scene ends), or None when none is run; slots: the Ft_p slots that are the next level-1 frames, in
     order; last: whether the scene ends with this window (a cut follows frame i).  The window of a scene's last frame exists only
     when a cut follows; at the end of the stream the scene ends with window e-2."""
     if not s <= i < e:
@@ -193,3 +197,70 @@ class Chain:
     def _note(self):
         live = len({id(t) for stage in self.stages for t in stage.held()})
         self.frames_resident_peak = max(self.frames_resident_peak, live)
+
+
+def run_stream(feed, net, emit, factor, batch=1, around=lambda flush: flush()):
+    """The window loop of every video run, factor 2 included: level 1 over the frames of `feed`, scene by scene, into a Chain.
+
+        feed    read_to(i) makes the frames up to i exist in `frames_dev` (id -> frame) or learns the stream's length `n_frames`
+                (None until then); with `scene_on`, resolve_cuts() decides every frame read so far into the sorted list `cuts`;
+        net     run(level, [(ids, six frames)], slots) -> one {slot: frame} per window, forward, reframe, new_scene (Chain's);
+        emit    Chain's;
+        around  around(flush) is called where a level-1 forward is due; flush() runs it with everything that follows from
+                it (the passes above, the emits) and returns how many windows it took care of.  For timing and for handing over.
+
+    The length of a piped stream is not known ahead: window i runs once frame i + 3 or the end of the stream has been read, and
+    needs the cuts up to the pair (i + 2, i + 3) only.  Consecutive forward-running windows share a forward in groups of `batch`,
+    whether or not a scene ends inside the group (windows are independent; a window that only holds a frame runs no forward and does
+    not count); what a group's windows mean to the Chain (a scene begins, frames to push, a scene ends) is replayed in order around
+    the forward, which is queued when the replay reaches the group's first window: with batch 1 the end of the scene before and the
+    `begin` come ahead of it, so new_scene() follows the last forward of every pass of that scene and precedes the scene's first.  Frames no later window names are dropped from
+    `frames_dev`.  Returns {windows, windows_per_pass, frames_resident_peak}: the windows considered (T - 1), the forwards per pass."""
+    passes = Chain(factor, net.forward, net.reframe, emit, batch=batch, new_scene=net.new_scene)
+    group, jobs, level1 = [], [], [0]              # (scene start to begin or None, slots, ends its scene) per window; [(ids, frames)]
+    index, start, is_open = 0, 0, False
+
+    def flush(final=False):
+        outs = None
+        for begin, slots, last in group:
+            if begin is not None:
+                passes.begin(begin)
+            if slots:
+                if outs is None:
+                    outs = iter(net.run(1, jobs, SLOTS))
+                out = next(outs)
+                passes.push([out[slot] for slot in slots])
+            if last:
+                passes.end(final=False)
+        if final and is_open:
+            passes.end(final=True)
+        n = len(group)
+        level1[0] += len(jobs)
+        group.clear()
+        jobs.clear()
+        return n
+
+    while True:
+        feed.read_to(index + 3)
+        n_frames = feed.n_frames
+        if n_frames is not None and index > n_frames - 2:
+            break
+        end = n_frames if n_frames is not None else index + 4      # clamping only bites once the end is known
+        if feed.scene_on:
+            feed.resolve_cuts()                     # every pair up to (index + 2, index + 3), or up to the stream's end
+            if index in feed.cuts:
+                start = index
+            # the scene's end: the next cut when it is in sight; beyond index + 3 any end gives the same window
+            end = next((c for c in feed.cuts if c > index), end)
+        ids, slots, last = level1_plan(index, start, end)
+        group.append((None if is_open else start, slots, last))
+        is_open = not last
+        if ids is not None:
+            jobs.append((ids, [feed.frames_dev[f] for f in ids]))   # (the windows in `jobs` hold their own references)
+            for f in [f for f in feed.frames_dev if f < min(ids)]:
+                del feed.frames_dev[f]
+        if len(jobs) >= passes.batch:
+            around(flush)
+        index += 1
+    around(lambda: flush(final=True))
+    return {"windows": index, "windows_per_pass": level1 + passes.windows, "frames_resident_peak": passes.frames_resident_peak}

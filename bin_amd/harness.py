@@ -4,6 +4,7 @@ window rule (test.py:257-261), the padding rule (test.py:348-366), which outputs
 clip — the 8 Adobe240 clips have 63-418 frames, so per-clip sharding caps the 8-GPU speed-up at 3.1x)."""
 import torch
 
+from . import chain
 from .utils import util
 
 builtins_range = range                     # (interpolate_video has a parameter called `range`)
@@ -16,10 +17,60 @@ def shard_windows(n_windows, rank, world):
     return begin, begin + base + (1 if rank < rem else 0)
 
 
-def window_frame_ids(index, n_frames):
-    """Indices of the 6 blurry frames of the window centred on frame `index` (test.py:257-261):
-    index + [-2, -1, 0, 1, 2, 3], clamped to the clip."""
-    return [min(max(index + d, 0), n_frames - 1) for d in (-2, -1, 0, 1, 2, 3)]
+window_frame_ids = chain.window_ids        # (index, n_frames) -> the 6 blurry frames of the window centred on frame `index` (test.py:257-261)
+
+
+class WindowRunner:
+    """The one place that turns "these windows" into generator calls, for the folder runner, interpolate_clip and the video loop
+    (chain.run_stream, whose `net` this is).  Every pass (level 1, the pass on the input frames, included) owns its memo dict and,
+    with `ensemble`, its SelfEnsemble: both key on the identity of long-lived input tensors, and the passes interleave.
+    reuse_stage1 (N3): consecutive windows share 4 of their 5 stage-1 frame pairs, 2 stage-2 calls and 1 stage-3 call; their RDN
+    results are reused (exact: same inputs, same kernels), 17 -> 10 RDN calls per window.  batch > 1: the windows of a call go through
+    the net as ONE forward along N (per-image arithmetic is unchanged, so the images are bit-identical), and there is no memo.
+    `geometry` = (h, w) of the unpadded frame: what `reframe` needs, so only a run with passes above level 1."""
+
+    def __init__(self, netG, levels=1, reuse_stage1=True, batch=1, ensemble=None, geometry=None):
+        from .ensemble import SelfEnsemble, parse_group
+        inner = netG.module if hasattr(netG, "module") else netG
+        self.netG, self.geometry, self.batch = netG, geometry, max(1, int(batch))
+        self.reuse = bool(reuse_stage1 and self.batch == 1 and getattr(inner, "reuse_schedule", False))
+        self.caches = [{} if self.reuse else None for _ in builtins_range(levels)]
+        self.ens = [SelfEnsemble(netG, ensemble) if parse_group(ensemble) else None for _ in builtins_range(levels)]
+
+    def new_scene(self):
+        """A scene or a clip begins: nothing memoised belongs to it."""
+        for cache, ens in zip(self.caches, self.ens):
+            if cache is not None:
+                cache.clear()
+            if ens is not None:
+                ens.reset()
+
+    def run(self, level, jobs, slots):
+        """The generator on `jobs` = [(ids, six frames)], windows of pass `level`, batched along N when there are several: one
+        {slot: [1,3,H,W] estimate} per window."""
+        cache, ens = self.caches[level - 1], self.ens[level - 1]
+        if len(jobs) == 1:
+            ids, inputs = jobs[0]
+            if ens is not None:
+                Ft_p = ens.window(ids, inputs, slots=slots, reuse=cache is not None)
+            else:
+                Ft_p = self.netG(*inputs, stage1_cache=cache) if cache is not None else self.netG(*inputs)
+            return [{k: Ft_p[k] for k in slots}]
+        inputs = [torch.cat([frames[k] for _, frames in jobs], 0) for k in builtins_range(6)]
+        Ft_p = ens(inputs, slots=slots) if ens is not None else self.netG(*inputs)
+        return [{k: Ft_p[k][j:j + 1] for k in slots} for j in builtins_range(len(jobs))]
+
+    def forward(self, level, jobs):
+        return [out[13] for out in self.run(level, jobs, (13,))]
+
+    def reframe(self, frames):
+        from . import _lib, ops
+        h, w = self.geometry
+        pads = util.pad_sizes(h, w)
+        out = []
+        for first in builtins_range(0, len(frames), _lib.CHAIN_MAX_ITEMS):
+            out += ops.reframe(frames[first:first + _lib.CHAIN_MAX_ITEMS], pads[2], pads[0], h, w, pads)
+        return out
 
 
 @torch.no_grad()
@@ -29,16 +80,12 @@ def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1, en
     u8_to_frame / frame_to_u8 kernels, each padded frame cached because 5 of a window's 6 frames recur in the
     next window) or [T,3,H,W] fp32 RGB in [0,1].  Returns {window index: (interp, deblur_first, deblur_second)}
     as cropped HWC BGR uint8 images — what test.py writes with cv2.imwrite (test.py:380-402).
-    reuse_stage1 (N3): consecutive windows share 4 of their 5 stage-1 frame pairs, 2 stage-2 calls and 1 stage-3 call
-    (every call of the first sub-window that the next forward repeats; none sees ConvLSTM state); their RDN results are
-    reused (exact: same inputs, same kernels), 17 -> 10 RDN calls per window (rounds 1-3 reused stage 1 only: 13).
-    batch > 1: that many consecutive windows go through the net as ONE forward along N.  A small frame does not fill
-    the chip (a 320x320 window is 50 tiles per launch on 256 CUs): 8 windows per forward give 2.5x the windows/s at
-    256x256 and 1.75x at 448x256 (tools/bench_small.py); per-image arithmetic is unchanged, so the images are
-    bit-identical to batch = 1.  Windows are independent (the net re-zeros its LSTM state per call).
+    reuse_stage1, batch: WindowRunner's.  A small frame does not fill the chip (a 320x320 window is 50 tiles per launch on 256
+    CUs): 8 windows per forward give 2.5x the windows/s at 256x256 and 1.75x at 448x256 (tools/bench_small.py).  Windows are
+    independent (the net re-zeros its LSTM state per call).
     ensemble: a self-ensemble group (bin_amd/ensemble.py: letters of `hvt`, `flipx4`, `x8`); every image is then the mean of the
     M = 2^k oriented forwards, the flips and the merge being two HIP launches.  With reuse_stage1 every orientation keeps its own
-    oriented frames and memo, so the 17 -> 10 RDN calls per window hold in each.  None / "" / "none": off, the path above."""
+    oriented frames and memo, so the 17 -> 10 RDN calls per window hold in each.  None / "" / "none": off."""
     from . import ops
     dev = next(netG.parameters()).device
     is_u8 = clip.dtype == torch.uint8
@@ -59,96 +106,90 @@ def interpolate_clip(netG, clip, rank=0, world=1, reuse_stage1=True, batch=1, en
                 cache[i] = util.replicate_pad(clip[i:i + 1].to(dev), pads)
         return cache[i]
 
+    net = WindowRunner(netG, 1, reuse_stage1, batch, ensemble)
     out = {}
-    for idx, Ft_p in _forward_windows(netG, T, frame, cache, begin, end, reuse_stage1, batch, ensemble):
-        for j, i in enumerate(idx):
-            out[i] = tuple(ops.frame_to_u8(Ft_p[k][j:j + 1], t, l, h, w).cpu().numpy() for k in (13, 8, 12))
+    for first in range(begin, end, net.batch):
+        idx = list(range(first, min(first + net.batch, end)))
+        ids = [window_frame_ids(i, T) for i in idx]
+        for k in [k for k in cache if k < min(ids[0])]:  # the frames no later window names
+            del cache[k]
+        outs = net.run(1, [(six, [frame(i) for i in six]) for six in ids], (13, 8, 12))
+        for i, Ft_p in zip(idx, outs):
+            out[i] = tuple(ops.frame_to_u8(Ft_p[k], t, l, h, w).cpu().numpy() for k in (13, 8, 12))
         ops.check_status(dev)             # the .cpu() above synchronised: a saturated fp16 plane is an error, not an image
     return out
 
 
-def _forward_windows(netG, T, frame, cache, begin, end, reuse_stage1, batch, ensemble):
-    """The window loop interpolate_clip and interpolate_video share: yields (window indices, Ft_p) per forward over the windows
-    [begin, end) of a T-frame clip.  `frame(i)`: the padded frame i, kept in `cache`, which loses the frames no later window names."""
-    from .ensemble import SelfEnsemble, parse_group
-    inner = netG.module if hasattr(netG, "module") else netG
-    batch = max(1, int(batch))
-    stage1_cache = {} if (reuse_stage1 and batch == 1 and getattr(inner, "reuse_schedule", False)) else None
-    ens = SelfEnsemble(netG, ensemble) if parse_group(ensemble) else None
-    for first in range(begin, end, batch):
-        idx = list(range(first, min(first + batch, end)))
-        ids = [window_frame_ids(i, T) for i in idx]
-        for k in [k for k in cache if k < min(ids[0])]:
-            del cache[k]
-        if len(idx) == 1:
-            inputs = [frame(i) for i in ids[0]]
-        else:
-            inputs = [torch.cat([frame(w_ids[k]) for w_ids in ids], 0) for k in range(6)]
-        if ens is not None and len(idx) == 1:
-            Ft_p = ens.window(ids[0], inputs, slots=(13, 8, 12), reuse=stage1_cache is not None)
-        elif ens is not None:
-            Ft_p = ens(inputs, slots=(13, 8, 12))
-        elif stage1_cache is not None:
-            Ft_p = netG(*inputs, stage1_cache=stage1_cache)
-        else:
-            Ft_p = netG(*inputs)
-        yield idx, Ft_p
+class _MemoryFeed:
+    """chain.run_stream's feed over a stream that is all there: the length and the cuts are known from the start, `frames_dev` is
+    filled frame by frame as the loop asks (ops.yuv_to_frame) and emptied by the loop."""
 
+    def __init__(self, payloads, header, fmt, pads, dev, cuts):
+        self.payloads, self.geometry, self.dev = payloads, (header.height, header.width, fmt, pads), dev
+        self.n_frames, self.cuts, self.scene_on = payloads.shape[0], cuts, bool(cuts)
+        self.frames_dev, self.n_read = {}, 0
 
-def video_slots(index, n_windows):
-    """The Ft_p slots window `index` of a clip contributes to the output video, in display order: the folder runner's ownership
-    rule (bin_amd/test.py) — the first window opens with its first deblurred frame, the last one has no second."""
-    return ((8,) if index == 0 else ()) + (13,) + ((12,) if index < n_windows - 1 else ())
+    def read_to(self, i):
+        from . import ops
+        while self.n_read <= min(i, self.n_frames - 1):
+            self.frames_dev[self.n_read] = ops.yuv_to_frame(self.payloads[self.n_read].to(self.dev).contiguous(), *self.geometry)
+            self.n_read += 1
+
+    def resolve_cuts(self):
+        pass
 
 
 @torch.no_grad()
 def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None, factor=2,
                       scene_cut=None):
-    """interpolate_clip's loop over the frames of a Y4M stream.  `payloads`: [T, frame_bytes] uint8 (host or device), the frames of
-    `header` (bin_amd/video.py).  Returns the [2(T-1), frame_bytes] uint8 device tensor of the output payloads in display order,
-    D0, I0, D1, I1, ..., D(T-2), I(T-2): exactly the frames the folder runner writes for a one-clip folder, in name order — window 0
-    yields Ft_p[8], Ft_p[13], Ft_p[12], a middle window Ft_p[13], Ft_p[12], the last one Ft_p[13] (video_slots), so a first-in
-    first-out writer is in order already.  YUV -> padded frame and frame -> YUV are the kernels of libbinyuv.so (ops.yuv_to_frame /
+    """The window loop of the video runner (chain.run_stream) over the frames of a Y4M stream held in memory.  `payloads`:
+    [T, frame_bytes] uint8 (host or device), the frames of `header` (bin_amd/video.py).  Returns the [factor (T-1), frame_bytes] uint8
+    device tensor of the output payloads in display order; at factor 2 D0, I0, D1, I1, ..., D(T-2), I(T-2): exactly the frames the
+    folder runner writes for a one-clip folder, in name order — window 0 yields Ft_p[8], Ft_p[13], Ft_p[12], a middle window Ft_p[13],
+    Ft_p[12], the last one Ft_p[13].  YUV -> padded frame and frame -> YUV are the kernels of libbinyuv.so (ops.yuv_to_frame /
     ops.frame_to_yuv), the padded frames cached across the 5-of-6 overlap.  matrix / range: video.resolve_format.  reuse_stage1,
     batch, ensemble: as in interpolate_clip.
-    scene_cut: None = the stream is one clip (the path above).  A number is the threshold of `detect_cuts`, an iterable of ints the
-    cut positions themselves (c: frames c-1 and c are of different scenes).  The windows then stay inside their scene
-    (bin_amd/scene.py::plan): every scene comes out as if it ran alone, plus its last deblurred frame, and the frame between two
-    scenes is the deblurred frame before the cut, held.  Same length, same layout.
-    factor: 2 (the path above), 4 or 8: the passes of bin_amd/chain.py on the fp32 outputs, which never leave the device.  Returns
-    [factor (T-1), frame_bytes]; every second payload is the output at factor / 2."""
-    from . import ops, video
-    if factor != 2 or type(factor) is not int:
-        return _interpolate_video_chain(netG, payloads, header, matrix, range, reuse_stage1, batch, ensemble, scene_cut, factor)
+    scene_cut: None = the stream is one clip.  A number is the threshold of `detect_cuts`, an iterable of ints the cut positions
+    themselves (c: frames c-1 and c are of different scenes).  The windows then stay inside their scene (chain.level1_plan): every
+    scene comes out as if it ran alone, plus its last deblurred frame, and the frames up to the next scene are that frame, held.
+    Same length, same layout.
+    factor: 2, 4 or 8: above 2 the passes of bin_amd/chain.py on the fp32 outputs, which never leave the device; every second
+    payload is the output at factor / 2."""
+    from . import ops, scene, video
+    k = chain.levels(factor)
     T = payloads.shape[0]
     if T < 2:
         raise ValueError(f"interpolate_video needs at least 2 frames (got {T})")
-    if scene_cut is not None:
-        return _interpolate_video_scenes(netG, payloads, header, matrix, range, reuse_stage1, batch, ensemble, scene_cut)
     fmt = video.resolve_format(header, matrix, range)
     h, w = header.height, header.width
     if payloads.dim() != 2 or payloads.dtype != torch.uint8 or payloads.shape[1] != header.frame_bytes:
         raise ValueError(f"payloads must be uint8 [T, {header.frame_bytes}] for this header (got {payloads.dtype} {tuple(payloads.shape)})")
     dev = next(netG.parameters()).device
+    if scene_cut is None:
+        cuts = []
+    elif isinstance(scene_cut, (int, float)):
+        cuts = detect_cuts(payloads, header, float(scene_cut), device=dev)
+    else:
+        cuts = scene.check_cuts(scene_cut, T)
     pads = util.pad_sizes(h, w)
     l, r, t, b = pads
-    cache = {}
+    out = torch.empty((factor * (T - 1), header.frame_bytes), dtype=torch.uint8, device=dev)
+    written = []
 
-    def frame(i):
-        if i not in cache:
-            cache[i] = ops.yuv_to_frame(payloads[i].to(dev).contiguous(), h, w, fmt, pads)
-        return cache[i]
+    def emit(pos, f):
+        if f is chain.HOLD:
+            out[pos].copy_(out[pos - 1])
+        else:
+            ops.frame_to_yuv(f, t, l, h, w, fmt, out=out[pos])
+        written.append(pos)
 
-    n_win = T - 1
-    out = torch.empty((2 * n_win, header.frame_bytes), dtype=torch.uint8, device=dev)
-    n_out = 0
-    for idx, Ft_p in _forward_windows(netG, T, frame, cache, 0, n_win, reuse_stage1, batch, ensemble):
-        for j, i in enumerate(idx):
-            for k in video_slots(i, n_win):
-                ops.frame_to_yuv(Ft_p[k][j:j + 1], t, l, h, w, fmt, out=out[n_out])
-                n_out += 1
+    def checked(flush):
+        flush()
         ops.check_status(dev)             # (synchronises, as the image download of interpolate_clip does at this point)
-    assert n_out == 2 * n_win
+
+    net = WindowRunner(netG, k, reuse_stage1, batch, ensemble, (h, w))
+    chain.run_stream(_MemoryFeed(payloads, header, fmt, pads, dev, cuts), net, emit, factor, net.batch, checked)
+    assert written == list(builtins_range(factor * (T - 1)))    # display order
     return out
 
 
@@ -177,186 +218,6 @@ def detect_cuts(payloads, header, threshold, min_mad=0.0, device=None):
     recs = luma_records(payloads, header, device)
     h, w = header.height, header.width
     return [i for i in builtins_range(1, len(recs)) if scene.is_cut(recs[i - 1], recs[i], h, w, threshold, min_mad)]
-
-
-def _interpolate_video_scenes(netG, payloads, header, matrix, range, reuse_stage1, batch, ensemble, scene_cut):
-    """interpolate_video with scene cuts: the windows of scene.plan.  Windows of different scenes may share a batched forward (they
-    are independent); the memos that assume consecutive windows (the stage-1 memo, the ensemble's per-orientation ones) are dropped
-    whenever a window's scene is not the one of the forward before."""
-    from . import ops, scene, video
-    from .ensemble import SelfEnsemble, parse_group
-    T = payloads.shape[0]
-    fmt = video.resolve_format(header, matrix, range)
-    h, w = header.height, header.width
-    dev = next(netG.parameters()).device
-    if isinstance(scene_cut, (int, float)):
-        cuts = detect_cuts(payloads, header, float(scene_cut), device=dev)
-    else:
-        cuts = scene.check_cuts(scene_cut, T)
-    if payloads.dim() != 2 or payloads.dtype != torch.uint8 or payloads.shape[1] != header.frame_bytes:
-        raise ValueError(f"payloads must be uint8 [T, {header.frame_bytes}] for this header (got {payloads.dtype} {tuple(payloads.shape)})")
-    pads = util.pad_sizes(h, w)
-    l, r, t, b = pads
-    cache = {}
-
-    def frame(i):
-        if i not in cache:
-            cache[i] = ops.yuv_to_frame(payloads[i].to(dev).contiguous(), h, w, fmt, pads)
-        return cache[i]
-
-    work, holds = [], []                                  # (scene start, ids, outputs) per forward; the held positions
-    for s, e in scene.segments(T, cuts):
-        for i in builtins_range(s, min(e, T - 1)):
-            ids, outputs = scene.plan(i, s, e, T)
-            holds += [pos for pos, slot in outputs if slot is scene.HOLD]
-            if ids is not None:
-                work.append((s, ids, [(pos, slot) for pos, slot in outputs if slot is not scene.HOLD]))
-
-    inner = netG.module if hasattr(netG, "module") else netG
-    batch = max(1, int(batch))
-    stage1_cache = {} if (reuse_stage1 and batch == 1 and getattr(inner, "reuse_schedule", False)) else None
-    ens = SelfEnsemble(netG, ensemble) if parse_group(ensemble) else None
-    n_win = T - 1
-    out = torch.empty((2 * n_win, header.frame_bytes), dtype=torch.uint8, device=dev)
-    written, current = set(), None
-    for first in builtins_range(0, len(work), batch):
-        group = work[first:first + batch]
-        for k in [k for k in cache if k < min(group[0][1])]:
-            del cache[k]
-        if group[0][0] != current:                        # a scene change: nothing memoised belongs to this scene
-            current = group[0][0]
-            if stage1_cache is not None:
-                stage1_cache.clear()
-            if ens is not None:
-                ens.reset()
-        if len(group) == 1:
-            ids = group[0][1]
-            inputs = [frame(i) for i in ids]
-            if ens is not None:
-                Ft_p = ens.window(ids, inputs, slots=(13, 8, 12), reuse=stage1_cache is not None)
-            elif stage1_cache is not None:
-                Ft_p = netG(*inputs, stage1_cache=stage1_cache)
-            else:
-                Ft_p = netG(*inputs)
-        else:
-            inputs = [torch.cat([frame(ids[k]) for _, ids, _ in group], 0) for k in builtins_range(6)]
-            Ft_p = ens(inputs, slots=(13, 8, 12)) if ens is not None else netG(*inputs)
-        for j, (_, _, outputs) in enumerate(group):
-            for pos, slot in outputs:
-                ops.frame_to_yuv(Ft_p[slot][j:j + 1], t, l, h, w, fmt, out=out[pos])
-                written.add(pos)
-        ops.check_status(dev)
-    for pos in holds:                                     # I_i across a cut: D_i again, the same payload bytes
-        assert pos - 1 in written
-        out[pos].copy_(out[pos - 1])
-        written.add(pos)
-    assert written == set(builtins_range(2 * n_win))
-    return out
-
-
-class ChainNet:
-    """The device side of chain.Chain's callables for one stream: the generator on the windows of a pass, and the hand-off.  Every
-    pass (level 1, the pass on the input frames, included) owns its memo dict and, with `ensemble`, its SelfEnsemble: both key on
-    the identity of long-lived input tensors, and the passes interleave.  batch > 1: no memo, as in interpolate_clip."""
-
-    def __init__(self, netG, k, h, w, reuse_stage1=True, batch=1, ensemble=None):
-        from .ensemble import SelfEnsemble, parse_group
-        inner = netG.module if hasattr(netG, "module") else netG
-        self.netG, self.h, self.w, self.pads = netG, h, w, util.pad_sizes(h, w)
-        self.batch = max(1, int(batch))
-        memo = reuse_stage1 and self.batch == 1 and getattr(inner, "reuse_schedule", False)
-        self.caches = [{} if memo else None for _ in builtins_range(k)]
-        self.ens = [SelfEnsemble(netG, ensemble) if parse_group(ensemble) else None for _ in builtins_range(k)]
-
-    def new_scene(self):
-        for cache, ens in zip(self.caches, self.ens):
-            if cache is not None:
-                cache.clear()
-            if ens is not None:
-                ens.reset()
-
-    def run(self, level, jobs, slots):
-        """Ft_p of the generator on `jobs` = [(ids, six frames)], windows of pass `level`, batched along N when there are several."""
-        cache, ens = self.caches[level - 1], self.ens[level - 1]
-        if len(jobs) == 1:
-            ids, inputs = jobs[0]
-            if ens is not None:
-                return ens.window(ids, inputs, slots=slots, reuse=cache is not None)
-            return self.netG(*inputs, stage1_cache=cache) if cache is not None else self.netG(*inputs)
-        inputs = [torch.cat([frames[k] for _, frames in jobs], 0) for k in builtins_range(6)]
-        return ens(inputs, slots=slots) if ens is not None else self.netG(*inputs)
-
-    def forward(self, level, jobs):
-        out = self.run(level, jobs, (13,))[13]
-        return [out] if len(jobs) == 1 else [out[j:j + 1] for j in builtins_range(len(jobs))]
-
-    def reframe(self, frames):
-        from . import _lib, ops
-        l, r, t, b = self.pads
-        out = []
-        for first in builtins_range(0, len(frames), _lib.CHAIN_MAX_ITEMS):
-            out += ops.reframe(frames[first:first + _lib.CHAIN_MAX_ITEMS], t, l, self.h, self.w, self.pads)
-        return out
-
-
-def _interpolate_video_chain(netG, payloads, header, matrix, range, reuse_stage1, batch, ensemble, scene_cut, factor):
-    """interpolate_video at factor 4 or 8: level 1 is the generator on the input frames scene by scene (chain.level1_plan: the
-    windows of scene.plan, with the last window's slot 12 kept), the passes above are chain.Chain's."""
-    from . import chain, ops, scene, video
-    k = chain.levels(factor)
-    T = payloads.shape[0]
-    if T < 2:
-        raise ValueError(f"interpolate_video needs at least 2 frames (got {T})")
-    fmt = video.resolve_format(header, matrix, range)
-    h, w = header.height, header.width
-    dev = next(netG.parameters()).device
-    if scene_cut is None:
-        cuts = []
-    elif isinstance(scene_cut, (int, float)):
-        cuts = detect_cuts(payloads, header, float(scene_cut), device=dev)
-    else:
-        cuts = scene.check_cuts(scene_cut, T)
-    if payloads.dim() != 2 or payloads.dtype != torch.uint8 or payloads.shape[1] != header.frame_bytes:
-        raise ValueError(f"payloads must be uint8 [T, {header.frame_bytes}] for this header (got {payloads.dtype} {tuple(payloads.shape)})")
-    net = ChainNet(netG, k, h, w, reuse_stage1, batch, ensemble)
-    l, r, t, b = net.pads
-    cache = {}
-
-    def frame(i):
-        if i not in cache:
-            cache[i] = ops.yuv_to_frame(payloads[i].to(dev).contiguous(), h, w, fmt, net.pads)
-        return cache[i]
-
-    out = torch.empty((factor * (T - 1), header.frame_bytes), dtype=torch.uint8, device=dev)
-    written = []
-
-    def emit(pos, f):
-        assert pos == len(written)                        # display order
-        if f is chain.HOLD:
-            out[pos].copy_(out[pos - 1])
-        else:
-            ops.frame_to_yuv(f, t, l, h, w, fmt, out=out[pos])
-        written.append(pos)
-
-    passes = chain.Chain(factor, net.forward, net.reframe, emit, batch=net.batch, new_scene=net.new_scene)
-    for s, e in scene.segments(T, cuts):
-        work = [chain.level1_plan(i, s, e) for i in builtins_range(s, min(e, T - 1))]
-        work = [(ids, slots) for ids, slots, _ in work if ids is not None]
-        if not work:
-            continue                                      # the stream's last frame alone: nothing comes after it
-        passes.begin(s)
-        for first in builtins_range(0, len(work), net.batch):
-            group = work[first:first + net.batch]
-            for i in [i for i in cache if i < min(group[0][0])]:
-                del cache[i]
-            Ft_p = net.run(1, [(ids, [frame(i) for i in ids]) for ids, _ in group], (13, 8, 12))
-            for j, (_, slots) in enumerate(group):
-                passes.push([Ft_p[slot] if len(group) == 1 else Ft_p[slot][j:j + 1] for slot in slots])
-            ops.check_status(dev)                         # (synchronises, as interpolate_video does per forward)
-        passes.end(final=e == T)
-    ops.check_status(dev)
-    assert len(written) == factor * (T - 1)
-    return out
 
 
 class GraphedNet:

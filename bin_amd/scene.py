@@ -1,5 +1,5 @@
 """Scene cuts in a video stream: the decision on the luma statistics of libbinscene.so (ops.luma_stats, include/binscene.h) and the
-plan that keeps the sliding 6-frame window inside one scene.  Host side only, pure Python / numpy: nothing here touches a device.
+scenes a set of cuts divides a stream into.  Host side only, pure Python / numpy: nothing here touches a device.
 
 A record is (sad, hist): the sum of |Y - Y of the frame before| over the luma plane and the 64-bin histogram of Y >> 2
 (ops.read_luma_record).  Frames i-1 and i are in different scenes (a cut at position i) when the histograms lie far apart and the
@@ -9,12 +9,10 @@ planes differ enough:
     cut      = distance >= threshold  and  sad / (h w) >= min_mad  and  sad != 0
 
 The output keeps the length and layout of a run without cuts: 2 (T - 1) payloads, position 2i = D_i (frame i deblurred), position
-2i + 1 = I_i (the frame between i and i + 1), so frame timing does not depend on the option.  `plan` gives, per window, the six
-frame ids (clamped to the window's scene: the reference's end-of-clip rule, applied at scene ends) and what it contributes; across
-a cut there is no midpoint, I_i is D_i held."""
+2i + 1 = I_i (the frame between i and i + 1), so frame timing does not depend on the option.  The sliding 6-frame window stays
+inside one scene (chain.level1_plan: the six frame ids clamped to the window's scene, the reference's end-of-clip rule applied at
+scene ends); across a cut there is no midpoint, I_i is D_i held."""
 import numpy as np
-
-HOLD = None                                # plan()'s slot of a held frame: the payload emitted just before, once more
 
 
 def distance(hist_a, hist_b, h, w):
@@ -49,31 +47,3 @@ def segments(T, cuts):
     and c belong to different scenes."""
     edges = [0] + check_cuts(cuts, T) + [T]
     return [(s, e) for s, e in zip(edges[:-1], edges[1:])]
-
-
-def plan(i, s, e, T):
-    """Window i (0 <= i <= T-2) of a T-frame stream, frame i lying in the scene [s, e): (ids, outputs).  ids: the six frame ids of
-    the forward, or None when none is run.  outputs: ((position, slot), ...) in display order, slot being the Ft_p slot of that
-    forward or HOLD (the payload emitted just before this one, again).  T may be None while the stream's end is unknown; it then
-    must lie beyond i + 2."""
-    if not (0 <= s <= i < e) or (T is not None and (e > T or i > T - 2)):
-        raise ValueError(f"plan: window {i} of scene [{s}, {e}) in {T} frames")
-    if i + 1 < e:
-        ids = [min(max(i + d, s), e - 1) for d in (-2, -1, 0, 1, 2, 3)]
-        out = ((2 * i, 8),) if i == s else ()
-        out += ((2 * i + 1, 13),)
-        if T is None or i + 1 <= T - 2:
-            out += ((2 * i + 2, 12),)
-        return ids, out
-    # a cut follows frame i: no midpoint across it
-    if i > s:
-        return None, ((2 * i + 1, HOLD),)              # D_i came from window i-1's slot 12
-    return [s] * 6, ((2 * i, 8), (2 * i + 1, HOLD))     # a one-frame scene
-
-
-def scene_of(i, cuts, T):
-    """The scene [s, e) of frame i."""
-    for s, e in segments(T, cuts):
-        if s <= i < e:
-            return s, e
-    raise ValueError(f"frame {i} of {T}")

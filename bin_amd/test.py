@@ -8,7 +8,8 @@ interpolated and deblurred frames against the sharp ground truth) and demo.py (w
 
 With --input_video / --output_video the frames are those of one Y4M stream (bin_amd/video.py) instead of PNG files: same windows,
 same outputs, written in display order at twice the frame rate (run_video below; nothing is scored, one rank).  --factor 4 | 8
-chains passes on the fp32 outputs for four or eight times the frame rate (run_video_chain, bin_amd/chain.py).
+chains passes on the fp32 outputs for four or eight times the frame rate (the same run_video: bin_amd/chain.py has the window loop
+of every factor).
 
 What the reference does per input frame `index` of a clip (test.py:236-402) and this keeps:
   * the six blurry frames index + [-2..3], clamped to the clip (test.py:257-261, 333);
@@ -247,7 +248,7 @@ def main(argv=None, stats=None):
     n_out = round(1 / args.time_step)
     assert n_out == 2, "bin_stage4 interpolates the middle frame (time_step 0.5), as the reference asserts"
     if args.input_video is not None:
-        return run_video(args, opt, stats) if getattr(args, "factor", 2) == 2 else run_video_chain(args, opt, stats)
+        return run_video(args, opt, stats)
     result_root = os.path.join(args.output_path, f"{n_out * 30}fps_test_results", opt["name"])
     os.makedirs(result_root, exist_ok=True)
     if rank == 0:
@@ -303,14 +304,11 @@ def main(argv=None, stats=None):
     netG = model.netG
     netG.eval()
     dev = next(netG.parameters()).device
-    inner = netG.module if hasattr(netG, "module") else netG
-    reuse = (not args.no_reuse) and getattr(inner, "reuse_schedule", False)
-    from .ensemble import SelfEnsemble, parse_group
-    ens = SelfEnsemble(netG, args.self_ensemble) if parse_group(args.self_ensemble) else None
-    if ens is not None:
-        log.info("self-ensemble: group %s, M = %d forwards per window", ens.group, ens.M)
+    net = harness.WindowRunner(netG, 1, not args.no_reuse, args.batch, args.self_ensemble)
+    if net.ens[0] is not None:
+        log.info("self-ensemble: group %s, M = %d forwards per window", net.ens[0].group, net.ens[0].M)
     log.info("In Data: %s | model: %s | parameters: %d | ranks: %d | stage-1 reuse: %s", args.input_path,
-             opt["path"]["pretrain_model_G"], sum(p.numel() for p in netG.parameters() if p.requires_grad), world, reuse)
+             opt["path"]["pretrain_model_G"], sum(p.numel() for p in netG.parameters() if p.requires_grad), world, net.reuse)
 
     sums = _Sums()
     device_score = _DeviceScorer(dev) if args.metrics == "device" else None
@@ -321,7 +319,7 @@ def main(argv=None, stats=None):
         else:
             _score(sums, clip, kind, img_bgr, gt_path, args.ssim, tag)
     copy_stream = torch.cuda.Stream(device=dev)
-    decoded, frames_dev, stage1_cache, pending = {}, {}, {}, []
+    decoded, frames_dev, pending = {}, {}, []
     geom = None                                        # (h, w, pads) of the current clip
     claimed = set()                                    # (`pinned`: recycled page-locked output buffers, pre-allocated above)
     cur_clip, timer = None, AverageMeter()
@@ -389,17 +387,9 @@ def main(argv=None, stats=None):
             return
         t0 = time.time()
         (h, w), (l, r, t, b) = geom[:2], geom[2]
-        if len(group) == 1:
-            inputs = group[0][3]
-            if ens is not None:
-                Ft_p = ens.window(group[0][5], inputs, slots=OUT_KEYS, reuse=reuse)
-            else:
-                Ft_p = netG(*inputs, stage1_cache=stage1_cache) if reuse else netG(*inputs)
-        else:
-            inputs = [torch.cat([g[3][k] for g in group], 0) for k in range(6)]
-            Ft_p = netG(*inputs) if ens is None else ens(inputs, slots=OUT_KEYS)
-        for j, (clip, names, owned, _, blurry_path, _) in enumerate(group):
-            outs = torch.stack([ops.frame_to_u8(Ft_p[k][j:j + 1], t, l, h, w) for k in OUT_KEYS])
+        results = net.run(1, [(ids, six) for _, _, _, six, _, ids in group], OUT_KEYS)
+        for (clip, names, owned, _, blurry_path, _), Ft_p in zip(group, results):
+            outs = torch.stack([ops.frame_to_u8(Ft_p[k], t, l, h, w) for k in OUT_KEYS])
             ready = torch.cuda.Event()
             ready.record()
             host = pinned.pop() if pinned and pinned[-1].shape == outs.shape else torch.empty(
@@ -429,9 +419,8 @@ def main(argv=None, stats=None):
             if clip != cur_clip:
                 flush()
                 cur_clip = clip
-                decoded.clear(); frames_dev.clear(); stage1_cache.clear()
-                if ens is not None:
-                    ens.reset()          # the oriented frames and the per-orientation memos belong to the clip
+                decoded.clear(); frames_dev.clear()
+                net.new_scene()          # the memos, the oriented frames and the per-orientation memos belong to the clip
                 os.makedirs(os.path.join(result_root, clip), exist_ok=True)
             if wi == begin + 3:
                 early.clear()            # the early decodes belong to the first three windows; whatever was not taken is dropped
@@ -516,7 +505,7 @@ def main(argv=None, stats=None):
 
 
 class _VideoFeed:
-    """The input side of the video runners.  A reader thread fills recycled page-locked payload buffers (it starts with the
+    """The input side of the video runner, chain.run_stream's feed.  A reader thread fills recycled page-locked payload buffers (it starts with the
     object: ahead of the model's construction, as the folder runner's decoders do); `attach(dev)` creates the upload stream once the
     device is known; `read_to(i)` uploads frames behind an event and unpacks them with ops.yuv_to_frame into `frames_dev` until
     frame i is on the device or the stream has ended (`n_frames`).  With --scene_cut, ops.luma_stats runs on the upload stream
@@ -601,12 +590,17 @@ class _VideoFeed:
 
 
 class _VideoWriter:
-    """The ONE writer thread of the video runners: jobs (page-locked [3, frame_bytes] buffer, rows to write, event after which they
-    are complete) are written first in, first out, which is display order; buffers come back through `free_out`.  An error is kept
-    in `error` (the thread keeps draining, so that the main thread never blocks on a dead writer) and raised by the main thread."""
+    """The output side of the video runner.  `emit` (chain.Chain's) packs each frame with ops.frame_to_yuv straight into a row of a
+    [3, frame_bytes] device staging tensor (a hold copies the row before it); `hand_over` sends what was staged to page-locked memory
+    on the copy stream and to the ONE writer thread: jobs (page-locked [3, frame_bytes] buffer, rows to write, event after which they
+    are complete) are written first in, first out, which is display order; buffers come back through `free_out`.  An error of the
+    thread is kept in `error` (it keeps draining, so that the main thread never blocks on a dead writer) and raised by hand_over."""
 
-    def __init__(self, target, out_header):
+    def __init__(self, target, out_header, fmt, pads, dev):
         from . import video
+        self.header, self.fmt, self.pads, self.dev = out_header, fmt, pads, dev
+        self.copy_stream = torch.cuda.Stream(device=dev)
+        self.staged, self.last_row, self.n_written = [], None, 0      # [device staging tensor, rows filled]; the row packed last
         self.to_write, self.free_out, self.error = queue.Queue(maxsize=10), [], []
 
         def write_frames():
@@ -632,168 +626,55 @@ class _VideoWriter:
         self.thread = threading.Thread(target=write_frames, daemon=True)
         self.thread.start()
 
+    def emit(self, pos, frame):
+        from . import chain
+        assert pos == self.n_written + sum(n for _, n in self.staged)          # display order
+        if not self.staged or self.staged[-1][1] == 3:
+            self.staged.append([torch.empty((3, self.header.frame_bytes), dtype=torch.uint8, device=self.dev), 0])
+        outs, n = self.staged[-1]
+        if frame is chain.HOLD:
+            outs[n].copy_(self.last_row)
+        else:
+            l, r, t, b = self.pads
+            ops.frame_to_yuv(frame, t, l, self.header.height, self.header.width, self.fmt, out=outs[n])
+        self.last_row = outs[n]
+        self.staged[-1][1] = n + 1
+
+    def hand_over(self):
+        for outs, n in self.staged:
+            ready = torch.cuda.Event()
+            ready.record()
+            host = self.free_out.pop() if self.free_out else torch.empty(outs.shape, dtype=torch.uint8, pin_memory=True)
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(ready)
+                host[:n].copy_(outs[:n], non_blocking=True)
+                outs.record_stream(self.copy_stream)
+                done = torch.cuda.Event()
+                done.record()
+            self.to_write.put((host, n, done))
+            self.n_written += n
+        self.staged.clear()
+        if self.error:
+            raise self.error[0]
+
     def finish(self):
         self.to_write.put(None)
         self.thread.join()
 
 
 def run_video(args, opt, stats=None):
-    """The folder runner's pipeline over one Y4M stream.  A reader thread fills recycled page-locked payload buffers; each frame is
-    uploaded once on the upload stream behind an event and unpacked by ops.yuv_to_frame on the compute stream, the padded frame
-    cached across the 5-of-6 overlap of consecutive windows; ops.frame_to_yuv packs each output into a device payload, the copy
-    stream moves it to page-locked memory and ONE writer thread writes the frames in the order they were queued, which is display
-    order (harness.video_slots).  The length of a piped stream is not known ahead: window i runs once frame i + 3 or the end of
-    the stream has been read.  Logging goes to stderr and the log file, never to stdout (--output_video -).
+    """The folder runner's pipeline over one Y4M stream, at every --factor.  A reader thread fills recycled page-locked payload
+    buffers; each frame is uploaded once on the upload stream behind an event and unpacked by ops.yuv_to_frame on the compute stream
+    (_VideoFeed); chain.run_stream is the window loop: window i runs once frame i + 3 or the end of the stream has been read (the
+    length of a piped stream is not known ahead), inside its scene with --scene_cut, through harness.WindowRunner; its fp32 outputs go
+    to chain.Chain, which at --factor 4 | 8 runs the higher passes as their frames appear and emits in display order, so the frames
+    resident on the device do not grow with the stream; _VideoWriter packs, copies and writes.  The bytes are
+    harness.interpolate_video's at the same factor.  Logging goes to stderr and the log file, never to stdout (--output_video -).
     --scene_cut: ops.luma_stats runs on the upload stream right behind each frame's upload (its inputs are the payloads alone), its
     264-byte record comes back through a page-locked buffer and an event of that stream; the compute stream is never waited on for
-    it.  Window i needs the cut flags up to the pair (i + 2, i + 3), frames read_to(i + 3) has taken already; the windows are those
-    of scene.plan, the memos are dropped at a scene change."""
-    from . import scene, video
-    from .ensemble import SelfEnsemble, parse_group
-    log_root = os.getcwd() if args.output_video == "-" else os.path.dirname(os.path.abspath(args.output_video))
-    os.makedirs(log_root, exist_ok=True)
-    util.setup_logger("base", log_root, "test_video", screen=True, tofile=True)
-    log = logging.getLogger("base")
-    reader = video.Y4MReader(args.input_video)       # (the header is read and checked here: before the model is built)
-    header = reader.header
-    fmt = video.resolve_format(header, args.yuv_matrix, args.yuv_range)
-    h, w, nbytes = header.height, header.width, header.frame_bytes
-    pads = util.pad_sizes(h, w)
-    l, r, t, b = pads
-
-    feed = _VideoFeed(args, reader, fmt, pads, 2, log)
-
-    model = create_model(opt)
-    netG = model.netG
-    netG.eval()
-    dev = next(netG.parameters()).device
-    inner = netG.module if hasattr(netG, "module") else netG
-    reuse = (not args.no_reuse) and getattr(inner, "reuse_schedule", False)
-    ens = SelfEnsemble(netG, args.self_ensemble) if parse_group(args.self_ensemble) else None
-    if ens is not None:
-        log.info("self-ensemble: group %s, M = %d forwards per window", ens.group, ens.M)
-    log.info("In video: %s %dx%d C%s F%d:%d -> %s | YUV: %s %s | model: %s | stage-1 reuse: %s", args.input_video, w, h,
-             header.colorspace or "420", header.rate[0], header.rate[1], args.output_video, fmt[1], fmt[2],
-             opt["path"]["pretrain_model_G"], reuse)
-
-    feed.attach(dev)
-    copy_stream = torch.cuda.Stream(device=dev)
-    frames_dev, stage1_cache = feed.frames_dev, {}
-    scene_on = feed.scene_on
-    out = _VideoWriter(args.output_video, header.doubled())
-
-    timer, stamps, group = AverageMeter(), [], []
-    n_written = 0
-    memo_scene, last_payload = 0, None                 # the scene the memos belong to; the device payload queued last (a hold repeats it)
-
-    def flush():
-        nonlocal n_written, memo_scene, last_payload
-        if not group:
-            return
-        t0 = time.time()
-        runs = [g for g in group if g[1] is not None]  # (with --scene_cut a window may only hold a frame: no forward)
-        if len(runs) == 1:
-            if scene_on and runs[0][3] != memo_scene:  # a scene change: nothing memoised belongs to this scene
-                memo_scene = runs[0][3]
-                stage1_cache.clear()
-                if ens is not None:
-                    ens.reset()
-            inputs = runs[0][1]
-            if ens is not None:
-                Ft_p = ens.window(runs[0][2], inputs, slots=OUT_KEYS, reuse=reuse)
-            else:
-                Ft_p = netG(*inputs, stage1_cache=stage1_cache) if reuse else netG(*inputs)
-        elif runs:
-            memo_scene = None                          # (a batched forward uses no memo; a single one after it starts afresh)
-            inputs = [torch.cat([g[1][k] for g in runs], 0) for k in range(6)]
-            Ft_p = netG(*inputs) if ens is None else ens(inputs, slots=OUT_KEYS)
-        j = -1
-        for slots, frames, _, _ in group:
-            j += frames is not None
-            outs = torch.empty((3, nbytes), dtype=torch.uint8, device=dev)
-            for k, slot in enumerate(slots):
-                if slot is scene.HOLD:
-                    outs[k].copy_(last_payload)
-                else:
-                    ops.frame_to_yuv(Ft_p[slot][j:j + 1], t, l, h, w, fmt, out=outs[k])
-                last_payload = outs[k]
-            ready = torch.cuda.Event()
-            ready.record()
-            host = out.free_out.pop() if out.free_out else torch.empty((3, nbytes), dtype=torch.uint8, pin_memory=True)
-            with torch.cuda.stream(copy_stream):
-                copy_stream.wait_event(ready)
-                host[:len(slots)].copy_(outs[:len(slots)], non_blocking=True)
-                outs.record_stream(copy_stream)
-                done = torch.cuda.Event()
-                done.record()
-            out.to_write.put((host, len(slots), done))
-            n_written += len(slots)
-        if out.error:
-            raise out.error[0]
-        timer.update((time.time() - t0) / len(group), len(group))
-        stamps.extend([time.time()] * len(group))
-        group.clear()
-
-    t_all = time.time()
-    index = 0
-    scene_start = 0
-    try:
-        with torch.no_grad():
-            while True:
-                feed.read_to(index + 3)
-                n_frames, cuts = feed.n_frames, feed.cuts
-                if n_frames is not None and index > n_frames - 2:
-                    break
-                known = n_frames if n_frames is not None else index + 4      # clamping only bites once the end is known
-                if scene_on:
-                    feed.resolve_cuts()                 # every pair up to (index + 2, index + 3), or up to the stream's end
-                    if index in cuts:
-                        scene_start = index
-                    # the scene's end: the next cut when it is in sight; beyond index + 3 any end gives the same window
-                    scene_end = next((c for c in cuts if c > index), known)
-                    ids, outputs = scene.plan(index, scene_start, scene_end, n_frames)
-                    slots = tuple(slot for _, slot in outputs)
-                else:
-                    ids = harness.window_frame_ids(index, known)
-                    slots = harness.video_slots(index, n_frames - 1 if n_frames is not None else index + 2)
-                group.append((slots, None if ids is None else [frames_dev[f] for f in ids], ids, scene_start))
-                for fid in [f for f in frames_dev if ids is not None and f < min(ids)]:
-                    del frames_dev[fid]
-                if sum(g[1] is not None for g in group) >= args.batch:
-                    flush()
-                index += 1
-            flush()
-            torch.cuda.current_stream(dev).synchronize()
-    finally:
-        out.finish()
-        reader.close()
-    if out.error:
-        raise out.error[0]
-    n_frames, cuts, n_dup = feed.n_frames, feed.cuts, feed.n_dup
-    if n_frames < 2:
-        raise ValueError(f"{args.input_video}: a video needs at least 2 frames to interpolate (got {n_frames})")
-    torch.cuda.synchronize()
-    ops.check_status(dev)                 # a frame that left the fp16 storage range is an error, not a result
-    wall = time.time() - t_all
-    log.info("frames in: %d  out: %d  windows: %d  wall: %.2f s  -> %.2f interpolated frames/s (IO included); net+glue per window "
-             "%.4f s", n_frames, n_written, index, wall, index / max(wall, 1e-9), timer.avg)
-    if scene_on:
-        log.info("scene cuts: %d at input frames %s; duplicates: %d", len(cuts), ", ".join(str(c) for c in cuts) or "-", n_dup)
-    if stats is not None:
-        stats.update(windows=index, wall=wall, net_s_per_window=timer.avg, stamps=[s - t_all for s in stamps], frames_out=n_written)
-        if scene_on:
-            stats.update(cuts=list(cuts))
-    return 0
-
-def run_video_chain(args, opt, stats=None):
-    """run_video at --factor 4 | 8: the same feed and the same single writer thread, with the passes of bin_amd/chain.py between the
-    generator and the writer.  Level 1 is run_video's window loop (chain.level1_plan: window i runs once frame i + 3 or the end of
-    the stream has been read, inside its scene with --scene_cut); its fp32 outputs go to chain.Chain, which runs the higher passes as
-    their frames appear and emits in display order, so the stream's length need not be known and the frames resident on the device
-    do not grow with it.  The bytes are harness.interpolate_video's at the same factor."""
+    it.  Window i needs the cut flags up to the pair (i + 2, i + 3), frames read_to(i + 3) has taken already."""
     from . import chain, video
-    factor = args.factor
-    k = chain.levels(factor)
+    factor = getattr(args, "factor", 2)
     log_root = os.getcwd() if args.output_video == "-" else os.path.dirname(os.path.abspath(args.output_video))
     os.makedirs(log_root, exist_ok=True)
     util.setup_logger("base", log_root, "test_video", screen=True, tofile=True)
@@ -801,109 +682,36 @@ def run_video_chain(args, opt, stats=None):
     reader = video.Y4MReader(args.input_video)       # (the header is read and checked here: before the model is built)
     header = reader.header
     fmt = video.resolve_format(header, args.yuv_matrix, args.yuv_range)
-    h, w, nbytes = header.height, header.width, header.frame_bytes
+    h, w = header.height, header.width
     pads = util.pad_sizes(h, w)
-    l, r, t, b = pads
     feed = _VideoFeed(args, reader, fmt, pads, factor, log)
 
     model = create_model(opt)
     netG = model.netG
     netG.eval()
     dev = next(netG.parameters()).device
-    net = harness.ChainNet(netG, k, h, w, reuse_stage1=not args.no_reuse, batch=args.batch, ensemble=args.self_ensemble)
+    net = harness.WindowRunner(netG, chain.levels(factor), not args.no_reuse, args.batch, args.self_ensemble, (h, w))
+    if net.ens[0] is not None:
+        log.info("self-ensemble: group %s, M = %d forwards per window", net.ens[0].group, net.ens[0].M)
     log.info("In video: %s %dx%d C%s F%d:%d -> %s at factor %d | YUV: %s %s | model: %s | stage-1 reuse: %s", args.input_video, w, h,
              header.colorspace or "420", header.rate[0], header.rate[1], args.output_video, factor, fmt[1], fmt[2],
-             opt["path"]["pretrain_model_G"], net.caches[0] is not None)
+             opt["path"]["pretrain_model_G"], net.reuse)
     feed.attach(dev)
-    copy_stream = torch.cuda.Stream(device=dev)
-    frames_dev = feed.frames_dev
-    out = _VideoWriter(args.output_video, header.multiplied(factor))
+    out = _VideoWriter(args.output_video, header.multiplied(factor), fmt, pads, dev)
+    timer, stamps = AverageMeter(), []
 
-    emitted = []                                       # device payloads the passes emitted since the last hand-over to the writer
-    n_written, last_payload = 0, None
-
-    def emit(pos, frame):
-        nonlocal last_payload
-        assert pos == n_written + len(emitted)         # display order
-        if frame is not chain.HOLD:
-            last_payload = ops.frame_to_yuv(frame, t, l, h, w, fmt)
-        emitted.append(last_payload)
-
-    def hand_over():
-        """What was emitted goes to page-locked memory on the copy stream and to the writer, three payloads per job, in order."""
-        nonlocal n_written
-        for first in range(0, len(emitted), 3):
-            rows = emitted[first:first + 3]
-            outs = torch.stack(rows)
-            ready = torch.cuda.Event()
-            ready.record()
-            host = out.free_out.pop() if out.free_out else torch.empty((3, nbytes), dtype=torch.uint8, pin_memory=True)
-            with torch.cuda.stream(copy_stream):
-                copy_stream.wait_event(ready)
-                host[:len(rows)].copy_(outs, non_blocking=True)
-                outs.record_stream(copy_stream)
-                done = torch.cuda.Event()
-                done.record()
-            out.to_write.put((host, len(rows), done))
-            n_written += len(rows)
-        emitted.clear()
-        if out.error:
-            raise out.error[0]
-
-    passes = chain.Chain(factor, net.forward, net.reframe, emit, batch=net.batch, new_scene=net.new_scene)
-    timer, stamps, group = AverageMeter(), [], []      # group: (ids, six frames, slots) of level-1 windows waiting for one forward
-    n_level1 = 0
-
-    def flush():
-        nonlocal n_level1
-        if not group:
-            return
+    def timed(flush):
         t0 = time.time()
-        Ft_p = net.run(1, [(ids, frames) for ids, frames, _ in group], OUT_KEYS)
-        for j, (_, _, slots) in enumerate(group):
-            passes.push([Ft_p[slot] if len(group) == 1 else Ft_p[slot][j:j + 1] for slot in slots])
-        hand_over()
-        n_level1 += len(group)
-        timer.update((time.time() - t0) / len(group), len(group))
-        stamps.extend([time.time()] * len(group))
-        group.clear()
+        n = flush()
+        out.hand_over()
+        if n:
+            timer.update((time.time() - t0) / n, n)
+            stamps.extend([time.time()] * n)
 
     t_all = time.time()
-    index, scene_start, scene_open = 0, 0, False
     try:
         with torch.no_grad():
-            while True:
-                feed.read_to(index + 3)
-                n_frames, cuts = feed.n_frames, feed.cuts
-                if n_frames is not None and index > n_frames - 2:
-                    break
-                known = n_frames if n_frames is not None else index + 4      # clamping only bites once the end is known
-                scene_end = known
-                if feed.scene_on:
-                    feed.resolve_cuts()                 # every pair up to (index + 2, index + 3), or up to the stream's end
-                    if index in cuts:
-                        scene_start = index
-                    # the scene's end: the next cut when it is in sight; beyond index + 3 any end gives the same window
-                    scene_end = next((c for c in cuts if c > index), known)
-                if not scene_open:
-                    passes.begin(scene_start)
-                    scene_open = True
-                ids, slots, last = chain.level1_plan(index, scene_start, scene_end)
-                if ids is not None:
-                    group.append((ids, [frames_dev[f] for f in ids], slots))
-                    for fid in [f for f in frames_dev if f < min(ids)]:
-                        del frames_dev[fid]
-                if last or len(group) >= net.batch:
-                    flush()
-                if last:                                # a cut follows this frame: the scene's last frame, then the holds
-                    passes.end(final=False)
-                    scene_open = False
-                    hand_over()
-                index += 1
-            flush()
-            if scene_open:
-                passes.end(final=True)
-                hand_over()
+            run = chain.run_stream(feed, net, out.emit, factor, net.batch, timed)
             torch.cuda.current_stream(dev).synchronize()
     finally:
         out.finish()
@@ -916,15 +724,14 @@ def run_video_chain(args, opt, stats=None):
     torch.cuda.synchronize()
     ops.check_status(dev)                 # a frame that left the fp16 storage range is an error, not a result
     wall = time.time() - t_all
-    windows_per_pass = [n_level1] + list(passes.windows)
-    log.info("frames in: %d  out: %d  factor: %d  windows per pass: %s  wall: %.2f s  -> %.2f output frames/s (IO included); frames "
-             "resident in the passes at most %d", n_frames, n_written, factor, windows_per_pass, wall, n_written / max(wall, 1e-9),
-             passes.frames_resident_peak)
+    log.info("frames in: %d  out: %d  factor: %d  windows per pass: %s  wall: %.2f s  -> %.2f output frames/s (IO included); net+glue "
+             "per window %.4f s; frames resident in the passes at most %d", n_frames, out.n_written, factor, run["windows_per_pass"], wall,
+             out.n_written / max(wall, 1e-9), timer.avg, run["frames_resident_peak"])
     if feed.scene_on:
         log.info("scene cuts: %d at input frames %s; duplicates: %d", len(cuts), ", ".join(str(c) for c in cuts) or "-", feed.n_dup)
     if stats is not None:
-        stats.update(windows=index, wall=wall, net_s_per_window=timer.avg, stamps=[s - t_all for s in stamps], frames_out=n_written,
-                     factor=factor, windows_per_pass=windows_per_pass, frames_resident_peak=passes.frames_resident_peak)
+        stats.update(run, wall=wall, net_s_per_window=timer.avg, stamps=[s - t_all for s in stamps], frames_out=out.n_written,
+                     factor=factor)
         if feed.scene_on:
             stats.update(cuts=list(cuts))
     return 0

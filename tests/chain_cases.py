@@ -1,5 +1,5 @@
 """Case table of the chained interpolation passes (bin_amd/chain.py, include/binchain.h): the definition restated by brute force on
-stub frames that carry a rational timestamp, the stub driver of chain.Chain the CPU tests run, and the shapes of the reframe kernel
+stub frames that carry a rational timestamp, the stub feed and runner the CPU tests hand to chain.run_stream, and the shapes of the reframe kernel
 the GPU tests run.  Host side only."""
 import itertools
 from fractions import Fraction
@@ -65,46 +65,100 @@ def all_cut_sets(T):
 
 # ------------------------------------------------------------------------------------------------ the stub driver
 class Stub:
-    """A frame: a timestamp, whether it is a reframed copy, and of what."""
+    """A frame: a timestamp, whether it is a reframed copy, and of what; a level-1 frame's `src` is (window, Ft_p slot)."""
 
-    def __init__(self, t, of=None):
-        self.t, self.of = Fraction(t), of
+    def __init__(self, t, of=None, src=None):
+        self.t, self.of, self.src = Fraction(t), of, src
+
+
+class StubFeed:
+    """The feed of chain.run_stream over T stub frames.  `live`: nothing is known ahead, as on a pipe: read_to reads no further than
+    asked, the length is learnt by reading past the last frame, and `cuts` knows a cut once both frames of its pair were read and
+    raises when asked about a frame that was not.  Otherwise everything is known from the start, as in harness.interpolate_video."""
+
+    def __init__(self, T, cuts=(), live=False, log=None):
+        self.T, self.all_cuts, self.live, self.log = T, sorted(cuts), live, [] if log is None else log
+        self.frames_dev, self.n_read, self.n_frames = {}, 0, None if live else T
+        self.scene_on, self.n_resolved, self.cuts = bool(cuts) or live, 0 if live else T, self
+        self.asked = []                                 # the argument of every read_to
+
+    def read_to(self, i):
+        self.asked.append(i)
+        self.log.append(("read", i))
+        while self.n_read <= i and self.n_read < self.T:
+            self.frames_dev[self.n_read] = Stub(self.n_read)
+            self.n_read += 1
+        if self.n_read <= i:
+            self.n_frames = self.T                      # read past the last frame
+
+    def resolve_cuts(self):
+        self.n_resolved = self.n_read if self.live else self.T
+
+    def __contains__(self, i):                          # `cuts`
+        if i >= self.n_resolved:
+            raise AssertionError(f"asked whether frame {i} opens a scene with {self.n_resolved} frames decided")
+        return i in self.all_cuts
+
+    def __iter__(self):
+        return iter([c for c in self.all_cuts if c < self.n_resolved])
 
 
 class StubRun:
-    """chain.Chain over stub frames, level 1 driven by chain.level1_plan as the runners drive it.  `step`: level-1 frames per push
-    (None: all of a window's at once).  Records everything the tests look at."""
+    """chain.run_stream, the loop that ships, over a StubFeed and this stub runner.  `step`: level-1 frames per Chain.push (None: all
+    of a window's at once, as the loop pushes them).  Records everything the tests look at; in `log`: ("read", i) per read_to(i), ("scene",) per new_scene,
+    ("run", [ids, ...]) per level-1 forward, ("push", level-1 frames so far), ("forward", level, ids) per window of a pass above,
+    ("end",) per scene."""
 
-    def __init__(self, T, F, cuts=(), batch=1, step=None):
+    def __init__(self, T, F, cuts=(), batch=1, step=None, live=False):
         from bin_amd import chain
         self.T, self.F, self.emitted, self.reframed, self.log, self.level1_ids = T, F, [], [], [], []
+        self.sources = []                               # per output position: the `src` of the frame emitted there (None: a hold, a pass's frame)
         self.seen = {}                                  # (level, sequence id) -> the objects handed over for it
         self.pushed, self.keep = 0, []                  # (every stub stays alive: ids are unique for the whole run)
-        self.chain = chain.Chain(F, self.forward, self.reframe, self.emit, batch=batch, new_scene=lambda: self.log.append(("scene",)))
-        for s, e in segments(T, cuts):
-            begun = False
-            for i in range(s, min(e, T - 1)):
-                ids, slots, last = chain.level1_plan(i, s, e)
-                if not begun:
-                    self.chain.begin(s)
-                    begun = True
-                if ids is None:
-                    continue
-                self.level1_ids.append(ids)
-                t = {8: ids[2], 13: Fraction(ids[2] + ids[3], 2), 12: ids[3]}
-                frames = [Stub(t[slot]) for slot in slots]
-                self.keep += frames
+        self.batch, self.feed, self.flushes = batch, StubFeed(T, cuts, live, self.log), []
+        run = self
+
+        class Recording(chain.Chain):                   # the loop's own Chain, with its pushes split into `step`s and logged
+            def __init__(self, *args, **kwargs):
+                super().__init__(*args, **kwargs)
+                run.chain = self
+
+            def push(self, frames):
                 for first in range(0, len(frames), step or len(frames)):
                     part = frames[first:first + (step or len(frames))]
-                    self.pushed += len(part)
-                    self.log.append(("push", self.pushed))
-                    self.chain.push(part)
-            if begun:
-                self.log.append(("end",))
-                self.chain.end(final=e == T)
+                    run.pushed += len(part)
+                    run.log.append(("push", run.pushed))
+                    super().push(part)
+
+            def end(self, final):
+                run.log.append(("end",))
+                super().end(final)
+
+        def around(flush):
+            self.flushes.append(flush())
+
+        shipped, chain.Chain = chain.Chain, Recording
+        try:
+            self.stats = chain.run_stream(self.feed, self, self.emit, F, batch, around)
+        finally:
+            chain.Chain = shipped
+
+    def new_scene(self):
+        self.log.append(("scene",))
+
+    def run(self, level, jobs, slots):
+        assert level == 1 and 1 <= len(jobs) <= self.batch and tuple(slots) == (13, 8, 12)
+        for ids, frames in jobs:
+            assert [f.t for f in frames] == ids, "the six frames are the feed's frames of the six ids"
+        self.log.append(("run", [ids for ids, _ in jobs]))
+        self.level1_ids += [ids for ids, _ in jobs]
+        out = [{8: Stub(ids[2], src=(ids[2], 8)), 13: Stub(Fraction(ids[2] + ids[3], 2), src=(ids[2], 13)), 12: Stub(ids[3], src=(ids[2], 12))}
+               for ids, _ in jobs]
+        self.keep += [f for o in out for f in o.values()]
+        return out
 
     def forward(self, level, jobs):
-        assert 1 <= len(jobs) <= self.chain.batch
+        assert level >= 2 and 1 <= len(jobs) <= self.chain.batch
         out = []
         for ids, frames in jobs:
             assert all(f.of is not None for f in frames), "the inputs of a pass are reframed frames"
@@ -125,6 +179,7 @@ class StubRun:
     def emit(self, pos, frame):
         assert pos == len(self.emitted), "display order"
         self.emitted.append(HOLD if frame is None else frame.t)
+        self.sources.append(None if frame is None else frame.src)
 
 
 # ------------------------------------------------------------------------------------------------ the reframe kernel's shapes (GPU)

@@ -134,7 +134,8 @@ def test_ops_reframe_refuses_cpu_tensors_and_wrong_layouts():
 # ------------------------------------------------------------------------------------------------ level arithmetic
 def test_level_arithmetic():
     from bin_amd import chain, harness, scene
-    assert [chain.levels(f) for f in (2, 4, 8)] == [1, 2, 3] and chain.FACTORS == CC.FACTORS and chain.HOLD is scene.HOLD
+    assert [chain.levels(f) for f in (2, 4, 8)] == [1, 2, 3] and chain.FACTORS == CC.FACTORS
+    assert chain.HOLD is None and not hasattr(scene, "HOLD") and harness.window_frame_ids is chain.window_ids, "one of each"
     for bad in (0, 1, 3, 6, 16, -2, 2.0, 4.0, True, "4", None):
         with pytest.raises(ValueError, match="factor"):
             chain.levels(bad)
@@ -151,22 +152,12 @@ def test_level_arithmetic():
             assert levels[-1] == [Fraction(j, F) for j in range(F * (T - 1) + 1)], "the restatement itself: every 1/F"
 
 
-def test_level1_plan_is_scene_plans_windows_with_the_last_deblurred_frame_kept():
-    from bin_amd import chain, scene
-    for T in range(2, 8):
-        for cuts in CC.all_cut_sets(T):
-            for s, e in scene.segments(T, cuts):
-                for i in range(s, min(e, T - 1)):
-                    ids, slots, last = chain.level1_plan(i, s, e)
-                    ref_ids, ref_out = scene.plan(i, s, e, T)
-                    assert ids == ref_ids and last == (i + 1 == e)
-                    ref_slots = tuple(slot for _, slot in ref_out if slot is not scene.HOLD)
-                    if i + 1 < e:                       # scene.plan drops slot 12 of the stream's last window; the chain keeps it
-                        assert slots == (((8,) if i == s else ()) + (13, 12)) and slots[:len(ref_slots)] == ref_slots
-                    else:
-                        assert slots == ref_slots == ((8,) if i == s else ())
-    with pytest.raises(ValueError):
-        chain.level1_plan(3, 0, 3)
+def test_level1_plan_refuses_what_is_not_a_window_of_the_scene():
+    """(What the plan gives for every window of every cut set: test_cpu_scene.py::test_plan_and_segments_over_every_cut_set.)"""
+    from bin_amd import chain
+    for i, s, e in ((3, 0, 3), (2, 3, 5), (-1, 0, 2), (5, 0, 5)):
+        with pytest.raises(ValueError):
+            chain.level1_plan(i, s, e)
 
 
 # ------------------------------------------------------------------------------------------------ the scheduler on stub frames
@@ -291,6 +282,101 @@ def test_a_chain_refuses_a_scene_inside_a_scene():
     c.begin(0)
     with pytest.raises(RuntimeError):
         c.begin(3)
+
+
+# ------------------------------------------------------------------------------------------------ the loop's stream handling
+def _level1_runs(run):
+    return [entry[1] for entry in run.log if entry[0] == "run"]
+
+
+def _short_streams():
+    """(T, cuts): every cut set of T = 2 .. 6, and T = 7 .. 9 without cuts and with a few."""
+    for T in range(2, 7):
+        for cuts in CC.all_cut_sets(T):
+            yield T, cuts
+    for T in range(7, 10):
+        for cuts in ((), (T - 1,), (1, 4), (3, 4, T - 2)):
+            yield T, cuts
+
+
+@pytest.mark.parametrize("F", CC.FACTORS)
+def test_a_feed_that_learns_everything_late_gives_the_run_of_a_feed_that_knows_everything(F):
+    for T, cuts in _short_streams():
+        known, live = CC.StubRun(T, F, cuts=cuts), CC.StubRun(T, F, cuts=cuts, live=True)
+        assert live.log == known.log and live.emitted == known.emitted == CC.expected_stream(T, cuts, F), (T, cuts)
+        assert live.stats == known.stats and live.stats["windows"] == T - 1 == sum(live.flushes)
+        assert live.stats["windows_per_pass"][0] == len(live.level1_ids) and live.stats["windows_per_pass"][1:] == live.chain.windows
+        # window i asked for frame i + 3 and nothing beyond; the last question found the end
+        assert live.feed.asked == [i + 3 for i in range(len(live.feed.asked))] and live.feed.asked[-1] >= T
+        assert live.feed.n_frames == T and not live.feed.frames_dev.keys() - set(range(T - 6, T)), "frames are dropped as the windows pass"
+
+
+def test_a_cut_is_honoured_as_soon_as_its_pair_is_in_sight_and_nothing_beyond_is_asked():
+    """The cut at i + 3 comes into sight with frame i + 3, the last one window i waits for: window i must not name that frame.  The
+    live feed raises when the loop asks about a frame that was not read (StubFeed.__contains__), and window i's forward is logged
+    before the feed is asked for frame i + 4: no later frame and no later cut can have shaped it."""
+    for F in CC.FACTORS:
+        for T in range(5, 10):
+            for i in range(T - 3):
+                run = CC.StubRun(T, F, cuts=(i + 3,), live=True)
+                mine = [ids for ids in run.level1_ids if ids[2] == i]
+                assert mine == [[max(i - 2, 0), max(i - 1, 0), i, i + 1, i + 2, i + 2]], (T, i, mine)
+                assert run.emitted == CC.expected_stream(T, (i + 3,), F)
+                order = [entry for entry in run.log if entry[0] in ("read", "run")]
+                for at, entry in enumerate(order):
+                    if entry[0] == "run":
+                        (ids,) = entry[1]
+                        assert ("read", ids[2] + 3) in order[:at] and ("read", ids[2] + 4) not in order[:at], (T, i, ids)
+    feed = CC.StubFeed(6, cuts=(2,), live=True)
+    feed.read_to(3)
+    feed.resolve_cuts()
+    assert 2 in feed.cuts and 3 not in feed.cuts and list(feed.cuts) == [2]
+    with pytest.raises(AssertionError, match="asked whether frame 4"):
+        4 in feed.cuts
+
+
+@pytest.mark.parametrize("batch", [1, 2, 3, 8])
+def test_level1_forwards_are_the_forward_running_windows_in_groups_of_batch(batch):
+    for F in CC.FACTORS:
+        for T in range(2, 7):
+            for cuts in CC.all_cut_sets(T):
+                for live in (False, True):
+                    run, one = CC.StubRun(T, F, cuts=cuts, batch=batch, live=live), CC.StubRun(T, F, cuts=cuts)
+                    want = CC.expected_level1_ids(T, cuts)              # the forward-running windows in order, scene ends or not
+                    groups = _level1_runs(run)
+                    assert [ids for g in groups for ids in g] == want == one.level1_ids, (T, cuts)
+                    assert [len(g) for g in groups] == [batch] * (len(want) // batch) + [len(want) % batch] * (len(want) % batch > 0)
+                    assert run.emitted == one.emitted == CC.expected_stream(T, cuts, F)
+                    for level in range(2, F.bit_length()):
+                        assert _forwards(run, level) == _forwards(one, level)
+                    assert run.stats["windows_per_pass"] == one.stats["windows_per_pass"] and sum(run.flushes) == T - 1
+
+
+@pytest.mark.parametrize("F", CC.FACTORS)
+def test_with_batch_1_a_scene_is_announced_between_the_forwards_of_two_scenes(F):
+    """new_scene() drops the memos: it comes before the scene's first level-1 forward and after the last forward of every pass of the
+    scene before."""
+    for T, cuts in _short_streams():
+        for live in (False, True):
+            run = CC.StubRun(T, F, cuts=cuts, live=live)
+            begun = [(s, e) for s, e in CC.segments(T, cuts) if s < T - 1]
+            scene_no, per_scene = 0, {}
+            for entry in run.log:
+                if entry == ("scene",):
+                    scene_no += 1
+                elif entry[0] == "run":
+                    assert scene_no >= 1, "a forward before any scene was announced"
+                    per_scene.setdefault(scene_no - 1, []).append(("run", 1, entry[1][0]))
+                elif entry[0] == "forward":
+                    per_scene.setdefault(scene_no - 1, []).append(entry)
+            assert scene_no == len(begun) == len(per_scene)
+            # every forward logged after the n-th announcement and before the next belongs to the n-th scene
+            for n, (s, e) in enumerate(begun):
+                level1 = [entry[2] for entry in per_scene[n] if entry[0] == "run"]
+                assert level1 == ([[s] * 6] if e - s == 1 else [[s + f for f in CC.window_ids(j, e - s)] for j in range(e - s - 1)]), (T, cuts, n)
+                _, ids = CC.scene_levels(e - s, F.bit_length() - 1)
+                for p in ids:
+                    assert [entry[2] for entry in per_scene[n] if entry[0] == "forward" and entry[1] == p] == ids[p], (T, cuts, n, p)
 
 
 # ------------------------------------------------------------------------------------------------ the entry point and the header

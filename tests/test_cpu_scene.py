@@ -1,5 +1,6 @@
 """CPU: what can be pinned about the scene-cut path without a device — the ABI bookkeeping of libbinscene.so (include/binscene.h),
-every refusal that comes before a HIP call, the plan and the segments of bin_amd/scene.py exhaustively for short streams, the
+every refusal that comes before a HIP call, the segments of bin_amd/scene.py and the plan of the shipped window loop
+(bin_amd/chain.py) exhaustively for short streams, the
 decision on hand-made records, and the command line's conflicts.  GPU side: test_gpu_scene.py."""
 import ctypes as C
 import itertools
@@ -132,7 +133,12 @@ def _cut_sets(T):
 
 @pytest.mark.parametrize("T", range(2, 9))
 def test_plan_and_segments_over_every_cut_set(T):
-    from bin_amd import harness
+    """The plan as the shipped loop applies it: read off a factor-2 run of chain.run_stream on stub frames (chain_cases.StubRun), per
+    output position the Ft_p slot or the hold and the window it came from, per forward its six ids."""
+    import chain_cases as CC
+    import video_cases as VC
+    from bin_amd import chain, harness
+    HOLD = "hold"
     n_sets = 0
     for cuts in _cut_sets(T):
         n_sets += 1
@@ -140,54 +146,74 @@ def test_plan_and_segments_over_every_cut_set(T):
         # maximal runs: they tile 0 .. T, and a boundary lies exactly at every cut
         assert segs[0][0] == 0 and segs[-1][1] == T and all(a[1] == b[0] for a, b in zip(segs, segs[1:]))
         assert {s for s, _ in segs[1:]} == cuts and all(s < e for s, e in segs)
+        run = CC.StubRun(T, 2, cuts=sorted(cuts))
+        assert chain.HOLD is None and len(run.sources) == len(run.emitted)
+        by_window = {}                                          # window -> [(position, slot or HOLD)] in display order
+        for pos, src in enumerate(run.sources):
+            window, slot = (pos // 2, HOLD) if src is None else src
+            by_window.setdefault(window, []).append((pos, slot))
+        ids_of = {ids[2]: ids for ids in run.level1_ids}
+        assert len(ids_of) == len(run.level1_ids), "one forward per window at the most"
         positions, forwards = [], 0
         for s, e in segs:
             for i in range(s, min(e, T - 1)):
-                assert S.scene_of(i, cuts, T) == (s, e)
-                ids, outputs = S.plan(i, s, e, T)
+                ids, outputs = ids_of.get(i), by_window[i]
+                plan_ids, plan_slots, plan_last = chain.level1_plan(i, s, e)
+                assert plan_ids == ids and plan_last == (i + 1 == e)
                 last = None
                 for pos, slot in outputs:
-                    assert slot in (8, 13, 12, S.HOLD)
-                    if slot is S.HOLD:                       # a hold repeats D_i, which was emitted just before it
+                    assert slot in (8, 13, 12, HOLD)
+                    if slot is HOLD:                         # a hold repeats D_i, which was emitted just before it
                         assert pos == 2 * i + 1 and positions and positions[-1] == 2 * i and i + 1 == e
+                        assert run.emitted[pos] == CC.HOLD and run.emitted[pos - 1] == i
                     else:
                         assert ids is not None
                         assert pos == {8: 2 * i, 13: 2 * i + 1, 12: 2 * i + 2}[slot]
                     assert last is None or pos == last + 1
                     last = pos
                     positions.append(pos)
+                slots = tuple(slot for _, slot in outputs if slot is not HOLD)
                 if ids is None:
-                    assert i + 1 == e and i > s and [slot for _, slot in outputs] == [S.HOLD]
+                    assert i + 1 == e and i > s and [slot for _, slot in outputs] == [HOLD] and plan_slots == ()
                 else:
                     forwards += 1
                     assert len(ids) == 6 and all(s <= f < e for f in ids), "every id inside the window's scene"
                     assert ids == sorted(ids) and ids[2] == i
                     if i + 1 < e:
                         assert ids == [min(max(i + d, s), e - 1) for d in (-2, -1, 0, 1, 2, 3)] and ids[3] == i + 1
+                        assert plan_slots == ((8,) if i == s else ()) + (13, 12)
+                        # the stream's last window gives its slot 12 to the passes, never to the output
+                        assert slots == (plan_slots[:-1] if i == T - 2 else plan_slots)
                     else:
-                        assert ids == [i] * 6 and i == s
+                        assert ids == [i] * 6 and i == s, "a one-frame scene"
+                        assert plan_slots == slots == (8,) and [slot for _, slot in outputs] == [8, HOLD]
         assert positions == list(range(2 * T - 2)), (T, sorted(cuts), positions)
+        assert sorted(by_window) == [i for s, e in segs for i in range(s, min(e, T - 1))] == list(range(T - 1))
         # forwards: one per window that has a successor in its scene, one per one-frame scene that is not the last frame
+        assert forwards == len(run.level1_ids) == run.stats["windows_per_pass"][0]
         assert forwards == sum(max(e - s - 1, 0) for s, e in segs) + sum(1 for s, e in segs if e - s == 1 and s < T - 1)
     assert n_sets == 2 ** (T - 1)
     # no cuts: the sliding window and the ownership rule as they are
+    run = CC.StubRun(T, 2)
     for i in range(T - 1):
-        ids, outputs = S.plan(i, 0, T, T)
-        assert ids == harness.window_frame_ids(i, T)
-        assert tuple(slot for _, slot in outputs) == harness.video_slots(i, T - 1)
-    # a streaming caller that does not know the end yet (T = None, the scene end somewhere beyond i + 3) plans the same window
+        assert run.level1_ids[i] == harness.window_frame_ids(i, T)
+        assert tuple(slot for window, slot in run.sources if window == i) == VC.video_slots(i, T - 1)
+    # a streaming caller that does not know the end yet (the scene end somewhere beyond i + 3) plans the same window, and runs the same
     for i in range(T - 4):
-        assert S.plan(i, 0, i + 4, None) == S.plan(i, 0, T, T)
+        assert chain.level1_plan(i, 0, i + 4) == chain.level1_plan(i, 0, T)
+    live = CC.StubRun(T, 2, live=True)
+    assert live.sources == run.sources and live.level1_ids == run.level1_ids
 
 
 def test_plan_and_segments_refuse_what_is_not_a_window():
+    from bin_amd import chain
     for bad in ([0], [5], [-1], [2, 9]):
         with pytest.raises(ValueError):
             S.segments(5, bad)
     assert S.segments(5, [4, 2, 2]) == [(0, 2), (2, 4), (4, 5)] and S.segments(3, ()) == [(0, 3)]
-    for i, s, e, T in ((4, 0, 5, 5), (2, 3, 5, 5), (3, 0, 3, 5), (0, 0, 6, 5), (-1, 0, 2, 5)):
+    for i, s, e in ((2, 3, 5), (3, 0, 3), (-1, 0, 2), (5, 0, 5)):
         with pytest.raises(ValueError):
-            S.plan(i, s, e, T)
+            chain.level1_plan(i, s, e)
 
 
 # ------------------------------------------------------------------------------------------------ the decision

@@ -157,17 +157,16 @@ def test_resolve_format_auto_rules():
 
 
 def test_video_slots_are_the_folder_runners_ownership_rule():
-    from bin_amd import harness
     from bin_amd import test as T
-    assert [harness.video_slots(i, 4) for i in range(4)] == [(8, 13, 12), (13, 12), (13, 12), (13,)]
-    assert harness.video_slots(0, 1) == (8, 13)
+    assert [VC.video_slots(i, 4) for i in range(4)] == [(8, 13, 12), (13, 12), (13, 12), (13,)]
+    assert VC.video_slots(0, 1) == (8, 13)
     for n_frames in (2, 3, 5):
         frames = [f"{8 * k:05d}.png" for k in range(n_frames)]
         names = []
         for i in range(n_frames - 1):
             interp, d0, d1 = T.output_names(frames, i)
             by_slot = {13: interp, 8: d0, 12: d1}
-            names += [by_slot[k] for k in harness.video_slots(i, n_frames - 1)]
+            names += [by_slot[k] for k in VC.video_slots(i, n_frames - 1)]
         assert names == sorted(names) and len(set(names)) == 2 * (n_frames - 1) and None not in names, "display order = name order"
 
 

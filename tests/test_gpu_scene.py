@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import scene_cases as SC
+import video_cases as VC
 from conftest import REPO
 
 pytestmark = pytest.mark.gpu
@@ -215,7 +216,7 @@ def _one_clip(which, prec):
     out = []
     for i in range(T - 1):
         out += [_forward_by_hand(_net(prec), header, payloads, harness.window_frame_ids(i, T), k, None)
-                for k in harness.video_slots(i, T - 1)]
+                for k in VC.video_slots(i, T - 1)]
     return torch.stack(out)
 
 

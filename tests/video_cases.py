@@ -15,6 +15,12 @@ GUARD = 0xA5
 SAFE_POINT = (120, 110, 140)        # a code point in gamut under all four (matrix, range) pairs
 
 
+def video_slots(index, n_windows):
+    """The Ft_p slots window `index` of a clip contributes to the output video, in display order: the folder runner's ownership
+    rule (bin_amd/test.py) — the first window opens with its first deblurred frame, the last one has no second."""
+    return ((8,) if index == 0 else ()) + (13,) + ((12,) if index < n_windows - 1 else ())
+
+
 def pad_sizes(h, w):
     from bin_amd.utils import util
     return util.pad_sizes(h, w)
