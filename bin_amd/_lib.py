@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import CHAIN_LIB_PATH, EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, SCENE_LIB_PATH, YUV_LIB_PATH
+from .build import CHAIN_LIB_PATH, EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, RATE_LIB_PATH, SCENE_LIB_PATH, YUV_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -279,10 +279,19 @@ _CHAIN_SIGNATURES = {
     "binchain_reframe": (C.c_int, [C.POINTER(BinChainItem), C.c_int] + [C.c_int] * 11 + [C.c_void_p]),
 }
 
+# libbinrate.so (include/binrate.h): the rate library, loaded on first use
+RATE_VERSION = 100                     # BINRATE_VERSION
+RATE_E_ARG, RATE_E_SHAPE = -1, -2      # BINRATE_E_ARG, BINRATE_E_SHAPE
+_RATE_SIGNATURES = {
+    "binrate_version": (C.c_int, []),
+    "binrate_blend_to_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_int] * 6 + [C.POINTER(BinYuvFormat), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = _chainlib = None
+_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = _chainlib = _ratelib = None
 
 
 def _load(path, built_path, signatures, version=None):
@@ -404,6 +413,19 @@ def chainlib():
     if _chainlib is None:
         _chainlib = _load(CHAIN_LIB_PATH, CHAIN_LIB_PATH, _CHAIN_SIGNATURES, ("binchain_version", CHAIN_VERSION))
     return _chainlib
+
+
+def rate_exported_symbols():
+    """Names every include/binrate.h entry point must resolve to."""
+    return sorted(_RATE_SIGNATURES)
+
+
+def ratelib():
+    """Load libbinrate.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _ratelib
+    if _ratelib is None:
+        _ratelib = _load(RATE_LIB_PATH, RATE_LIB_PATH, _RATE_SIGNATURES, ("binrate_version", RATE_VERSION))
+    return _ratelib
 
 
 def check(rc, what):

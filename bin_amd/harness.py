@@ -140,8 +140,8 @@ class _MemoryFeed:
 
 
 @torch.no_grad()
-def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None, factor=2,
-                      scene_cut=None):
+def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None, rate=None,
+                      resample="blend", factor=2, scene_cut=None):
     """The window loop of the video runner (chain.run_stream) over the frames of a Y4M stream held in memory.  `payloads`:
     [T, frame_bytes] uint8 (host or device), the frames of `header` (bin_amd/video.py).  Returns the [factor (T-1), frame_bytes] uint8
     device tensor of the output payloads in display order; at factor 2 D0, I0, D1, I1, ..., D(T-2), I(T-2): exactly the frames the
@@ -154,8 +154,20 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
     scene comes out as if it ran alone, plus its last deblurred frame, and the frames up to the next scene are that frame, held.
     Same length, same layout.
     factor: 2, 4 or 8: above 2 the passes of bin_amd/chain.py on the fp32 outputs, which never leave the device; every second
-    payload is the output at factor / 2."""
+    payload is the output at factor / 2.
+    rate: None, or the absolute output frame rate as (N, D) or a Fraction (bin_amd/rate.py): the result is then the [M, frame_bytes]
+    stream at that rate, up to 8 times the header's, laid on the dense stream of the smallest factor F >= max(rate / input rate,
+    factor); an output frame between two dense frames is their mix in fp32, converted in the same launch (ops.blend_to_yuv), and never
+    a mix across a cut.  resample: "blend", or "nearest" for the nearer dense frame instead (ties go to the earlier one)."""
     from . import ops, scene, video
+    from . import rate as rate_
+    chain.levels(factor)
+    if resample not in rate_.MODES:
+        raise ValueError(f"resample must be one of {rate_.MODES} (got {resample!r})")
+    grid = None
+    if rate is not None:
+        grid = rate_.Grid(header.rate, rate, factor)
+        factor = grid.F
     k = chain.levels(factor)
     T = payloads.shape[0]
     if T < 2:
@@ -173,7 +185,8 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
         cuts = scene.check_cuts(scene_cut, T)
     pads = util.pad_sizes(h, w)
     l, r, t, b = pads
-    out = torch.empty((factor * (T - 1), header.frame_bytes), dtype=torch.uint8, device=dev)
+    n_out = factor * (T - 1) if grid is None else grid.frames(T)
+    out = torch.empty((n_out, header.frame_bytes), dtype=torch.uint8, device=dev)
     written = []
 
     def emit(pos, f):
@@ -183,13 +196,21 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
             ops.frame_to_yuv(f, t, l, h, w, fmt, out=out[pos])
         written.append(pos)
 
+    def emit_at_rate(m, left, right, weight):
+        if right is None:
+            ops.frame_to_yuv(left, t, l, h, w, fmt, out=out[m])
+        else:
+            ops.blend_to_yuv(left, right, weight, t, l, h, w, fmt, out=out[m])
+        written.append(m)
+
     def checked(flush):
         flush()
         ops.check_status(dev)             # (synchronises, as the image download of interpolate_clip does at this point)
 
     net = WindowRunner(netG, k, reuse_stage1, batch, ensemble, (h, w))
-    chain.run_stream(_MemoryFeed(payloads, header, fmt, pads, dev, cuts), net, emit, factor, net.batch, checked)
-    assert written == list(builtins_range(factor * (T - 1)))    # display order
+    sink = emit if grid is None else rate_.Resampler(grid, emit_at_rate, resample).push
+    chain.run_stream(_MemoryFeed(payloads, header, fmt, pads, dev, cuts), net, sink, factor, net.batch, checked)
+    assert written == list(builtins_range(n_out))               # display order
     return out
 
 

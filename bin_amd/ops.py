@@ -606,6 +606,34 @@ def frame_to_yuv(frame, top, left, h, w, fmt, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------------- rate glue (libbinrate.so)
+def blend_to_yuv(a, b, w, top, left, h, w_, fmt, out=None):
+    """Two fp32 [1,3,Hp,Wp] (or [3,Hp,Wp]) RGB frames of one shape -> the Y4M payload of the crop of a + w (b - a), 0 <= w < 1, on
+    clamped values (include/binrate.h): one launch, frame_to_yuv's conversion and its `out`.  w == 0 and `b is a` give
+    frame_to_yuv(a)'s bytes."""
+    f = yuv_format(fmt)
+    _need_cuda(a, b)
+    for x in (a, b):
+        if x.dim() not in (3, 4) or x.numel() != 3 * x.shape[-2] * x.shape[-1]:
+            raise ValueError(f"bin_amd: blend_to_yuv takes two [1,3,Hp,Wp] frames (got {tuple(x.shape)})")
+    if a.shape[-2:] != b.shape[-2:] or a.device != b.device:
+        raise ValueError(f"bin_amd: blend_to_yuv takes two frames of one shape on one device (got {tuple(a.shape)}, {tuple(b.shape)})")
+    a, b = (x.reshape(3, x.shape[-2], x.shape[-1]).contiguous().float() for x in (a, b))
+    w = float(w)
+    if not 0.0 <= w < 1.0:
+        raise ValueError(f"bin_amd: blend_to_yuv takes a weight in [0, 1) (got {w})")
+    hp, wp = a.shape[-2], a.shape[-1]
+    if h < 1 or w_ < 1 or top < 0 or left < 0 or top + h > hp or left + w_ > wp:
+        raise ValueError(f"bin_amd: crop ({top}, {left}, {h}, {w_}) leaves the {hp}x{wp} frame")
+    if out is None:
+        out = torch.empty(yuv_frame_bytes(h, w_, fmt[0])[0], dtype=torch.uint8, device=a.device)
+    y, u, v = _yuv_planes(out, h, w_, fmt[0])
+    with on_device(a):
+        L.check(L.ratelib().binrate_blend_to_yuv(_ptr(a), _ptr(b), w, hp, wp, top, left, h, w_, C.byref(f), y, u, v, _stream()),
+                "blend_to_yuv")
+    return out
+
+
 # --------------------------------------------------------------------------------------------- scene glue (libbinscene.so)
 LUMA_RECORD_BYTES = C.sizeof(L.BinSceneRecord)          # 264: a uint64 SAD, then 64 uint32 bins
 

@@ -9,7 +9,8 @@ interpolated and deblurred frames against the sharp ground truth) and demo.py (w
 With --input_video / --output_video the frames are those of one Y4M stream (bin_amd/video.py) instead of PNG files: same windows,
 same outputs, written in display order at twice the frame rate (run_video below; nothing is scored, one rank).  --factor 4 | 8
 chains passes on the fp32 outputs for four or eight times the frame rate (the same run_video: bin_amd/chain.py has the window loop
-of every factor).
+of every factor).  --output_rate N[:D] writes any frame rate up to eight times the input's: the frames of the factor's stream,
+resampled on the device (bin_amd/rate.py; --resample blend | nearest).
 
 What the reference does per input frame `index` of a clip (test.py:236-402) and this keeps:
   * the six blurry frames index + [-2..3], clamped to the clip (test.py:257-261, 333);
@@ -66,6 +67,12 @@ def parse_args(argv=None):
     p.add_argument("--factor", type=int, choices=[2, 4, 8], default=2,
                    help="--input_video: the output's frame rate over the input's; 4 and 8 chain passes on the fp32 outputs "
                         "(bin_amd/chain.py), every second frame of a factor's stream being the stream of half the factor")
+    p.add_argument("--output_rate", type=str, default=None, metavar="N[:D]",
+                   help="--input_video: the output's absolute frame rate, up to 8 times the input's (bin_amd/rate.py): the frames are "
+                        "laid on the stream of the smallest factor that reaches it (--factor is then a lower bound on that grid)")
+    p.add_argument("--resample", choices=["blend", "nearest"], default=None,
+                   help="--output_rate: an output frame between two frames of the dense stream is their fp32 mix (blend, the default) "
+                        "or the nearer one of them (nearest)")
     p.add_argument("--gpu_id", type=str, default=None)
     p.add_argument("--time_step", type=float, default=0.5)
     p.add_argument("--opt", type=str, required=True, help="Path to option YAML file.")
@@ -102,6 +109,19 @@ def check_args(args):
         raise ValueError("--scene_cut / --scene_cut_min_mad: scene cuts are looked for in a video only (--input_video)")
     if not video and getattr(args, "factor", 2) != 2:
         raise ValueError("--factor: passes are chained on a video only (--input_video)")
+    if not video and (getattr(args, "output_rate", None) is not None or getattr(args, "resample", None) is not None):
+        raise ValueError("--output_rate / --resample: a frame rate is resampled on a video only (--input_video)")
+    if getattr(args, "output_rate", None) is None and getattr(args, "resample", None) is not None:
+        raise ValueError("--resample goes with --output_rate")
+    if getattr(args, "output_rate", None) is not None:
+        from . import rate
+        n, d = rate.parse_rate(args.output_rate)        # (malformed: ValueError)
+        if n > 2 ** 31 - 1 or d > 2 ** 31 - 1:
+            raise ValueError(f"--output_rate: {args.output_rate} does not fit a Y4M header")
+        if args.input_video not in (None, "-") and os.path.isfile(args.input_video):
+            from . import video                             # a file's header can be looked at now (a pipe's: run_video, once it is read)
+            with open(args.input_video, "rb") as f:
+                rate.Grid(video.parse_header(f.readline(video.MAX_LINE)).rate, (n, d), getattr(args, "factor", 2))
     if getattr(args, "scene_cut", None) is None and getattr(args, "scene_cut_min_mad", 0.0):
         raise ValueError("--scene_cut_min_mad goes with --scene_cut")
     if video and folder:
@@ -521,6 +541,7 @@ class _VideoFeed:
         self.frames_dev = {}
         self.n_read, self.n_frames = 0, None           # frames uploaded so far; the stream's length once its end was read
         self.scene_on = args.scene_cut is not None
+        self.out_frame = lambda c: factor * c          # the output frame a cut at input frame c falls on (run_video: --output_rate)
         self.cuts, self.n_dup = [], 0                  # cut positions found so far; frames equal to the one before
         self.rec_pending, self.rec_free, self.rec_prev = {}, [], None   # frame -> (page-locked record, event); spare buffers; (sad, hist) of the frame before
         self.prev_payload, self.n_resolved = None, 0   # kept alive until the next frame's statistics are queued; frames decided so far
@@ -569,7 +590,7 @@ class _VideoFeed:
                 if scene.is_cut(self.rec_prev, rec, h, w, args.scene_cut, args.scene_cut_min_mad):
                     self.cuts.append(self.n_resolved)
                     self.log.info("scene cut at input frame %d (output frame %d): distance %.4f, mean |dY| %.3f", self.n_resolved,
-                                  self.factor * self.n_resolved, scene.distance(self.rec_prev[1], rec[1], h, w), rec[0] / float(h * w))
+                                  self.out_frame(self.n_resolved), scene.distance(self.rec_prev[1], rec[1], h, w), rec[0] / float(h * w))
             self.rec_prev = rec
             self.n_resolved += 1
 
@@ -591,7 +612,8 @@ class _VideoFeed:
 
 class _VideoWriter:
     """The output side of the video runner.  `emit` (chain.Chain's) packs each frame with ops.frame_to_yuv straight into a row of a
-    [3, frame_bytes] device staging tensor (a hold copies the row before it); `hand_over` sends what was staged to page-locked memory
+    [3, frame_bytes] device staging tensor (a hold copies the row before it), `emit_at_rate` (rate.Resampler's) likewise with
+    ops.blend_to_yuv where two frames are mixed; `hand_over` sends what was staged to page-locked memory
     on the copy stream and to the ONE writer thread: jobs (page-locked [3, frame_bytes] buffer, rows to write, event after which they
     are complete) are written first in, first out, which is display order; buffers come back through `free_out`.  An error of the
     thread is kept in `error` (it keeps draining, so that the main thread never blocks on a dead writer) and raised by hand_over."""
@@ -626,19 +648,33 @@ class _VideoWriter:
         self.thread = threading.Thread(target=write_frames, daemon=True)
         self.thread.start()
 
-    def emit(self, pos, frame):
-        from . import chain
+    def _next_row(self, pos):
         assert pos == self.n_written + sum(n for _, n in self.staged)          # display order
         if not self.staged or self.staged[-1][1] == 3:
             self.staged.append([torch.empty((3, self.header.frame_bytes), dtype=torch.uint8, device=self.dev), 0])
         outs, n = self.staged[-1]
+        self.staged[-1][1] = n + 1
+        return outs[n]
+
+    def emit(self, pos, frame):
+        from . import chain
+        row = self._next_row(pos)
         if frame is chain.HOLD:
-            outs[n].copy_(self.last_row)
+            row.copy_(self.last_row)
         else:
             l, r, t, b = self.pads
-            ops.frame_to_yuv(frame, t, l, self.header.height, self.header.width, self.fmt, out=outs[n])
-        self.last_row = outs[n]
-        self.staged[-1][1] = n + 1
+            ops.frame_to_yuv(frame, t, l, self.header.height, self.header.width, self.fmt, out=row)
+        self.last_row = row
+
+    def emit_at_rate(self, m, left, right, w):
+        """rate.Resampler's emit (--output_rate): `left` alone, or the mix left + w (right - left) packed in the same launch."""
+        row = self._next_row(m)
+        l, r, t, b = self.pads
+        if right is None:
+            ops.frame_to_yuv(left, t, l, self.header.height, self.header.width, self.fmt, out=row)
+        else:
+            ops.blend_to_yuv(left, right, w, t, l, self.header.height, self.header.width, self.fmt, out=row)
+        self.last_row = row
 
     def hand_over(self):
         for outs, n in self.staged:
@@ -669,11 +705,13 @@ def run_video(args, opt, stats=None):
     length of a piped stream is not known ahead), inside its scene with --scene_cut, through harness.WindowRunner; its fp32 outputs go
     to chain.Chain, which at --factor 4 | 8 runs the higher passes as their frames appear and emits in display order, so the frames
     resident on the device do not grow with the stream; _VideoWriter packs, copies and writes.  The bytes are
-    harness.interpolate_video's at the same factor.  Logging goes to stderr and the log file, never to stdout (--output_video -).
+    harness.interpolate_video's at the same factor.  --output_rate: rate.Resampler sits between the Chain and the writer and lays
+    the output frames on the dense stream; a frame between two of its frames is their fp32 mix, packed in the same launch
+    (ops.blend_to_yuv).  Logging goes to stderr and the log file, never to stdout (--output_video -).
     --scene_cut: ops.luma_stats runs on the upload stream right behind each frame's upload (its inputs are the payloads alone), its
     264-byte record comes back through a page-locked buffer and an event of that stream; the compute stream is never waited on for
     it.  Window i needs the cut flags up to the pair (i + 2, i + 3), frames read_to(i + 3) has taken already."""
-    from . import chain, video
+    from . import chain, rate, video
     factor = getattr(args, "factor", 2)
     log_root = os.getcwd() if args.output_video == "-" else os.path.dirname(os.path.abspath(args.output_video))
     os.makedirs(log_root, exist_ok=True)
@@ -681,10 +719,16 @@ def run_video(args, opt, stats=None):
     log = logging.getLogger("base")
     reader = video.Y4MReader(args.input_video)       # (the header is read and checked here: before the model is built)
     header = reader.header
+    grid, out_header = None, None
+    if getattr(args, "output_rate", None) is not None:   # (a pipe's header is known only now: still before the model is built)
+        grid = rate.Grid(header.rate, rate.parse_rate(args.output_rate), factor)
+        factor, out_header = grid.F, header.at_rate(grid.out_rate)
     fmt = video.resolve_format(header, args.yuv_matrix, args.yuv_range)
     h, w = header.height, header.width
     pads = util.pad_sizes(h, w)
     feed = _VideoFeed(args, reader, fmt, pads, factor, log)
+    if grid is not None:
+        feed.out_frame = lambda c: -(-c * grid.p // grid.q)         # the first output frame at or after the cut
 
     model = create_model(opt)
     netG = model.netG
@@ -696,8 +740,13 @@ def run_video(args, opt, stats=None):
     log.info("In video: %s %dx%d C%s F%d:%d -> %s at factor %d | YUV: %s %s | model: %s | stage-1 reuse: %s", args.input_video, w, h,
              header.colorspace or "420", header.rate[0], header.rate[1], args.output_video, factor, fmt[1], fmt[2],
              opt["path"]["pretrain_model_G"], net.reuse)
+    mode = getattr(args, "resample", None) or "blend"
+    if grid is not None:
+        log.info("output rate: F%d:%d, %s: the frames of the factor-%d stream, resample %s", grid.out_rate[0], grid.out_rate[1],
+                 grid.describe(), grid.F, mode)
     feed.attach(dev)
-    out = _VideoWriter(args.output_video, header.multiplied(factor), fmt, pads, dev)
+    out = _VideoWriter(args.output_video, out_header or header.multiplied(factor), fmt, pads, dev)
+    emit = out.emit if grid is None else rate.Resampler(grid, out.emit_at_rate, mode).push
     timer, stamps = AverageMeter(), []
 
     def timed(flush):
@@ -711,7 +760,7 @@ def run_video(args, opt, stats=None):
     t_all = time.time()
     try:
         with torch.no_grad():
-            run = chain.run_stream(feed, net, out.emit, factor, net.batch, timed)
+            run = chain.run_stream(feed, net, emit, factor, net.batch, timed)
             torch.cuda.current_stream(dev).synchronize()
     finally:
         out.finish()

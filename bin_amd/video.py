@@ -60,6 +60,12 @@ class Y4MHeader:
             raise ValueError(f"a frame rate is multiplied by a positive integer (got {f!r})")
         return replace(self, rate=(f * self.rate[0], self.rate[1]))
 
+    def at_rate(self, rate):
+        """The header of a stream resampled to the absolute frame rate `rate` (--output_rate; (N, D), N or a Fraction): F = N:D as
+        written, not reduced any further; everything else unchanged."""
+        from .rate import rate_pair
+        return replace(self, rate=rate_pair(rate, "output rate"))
+
     def line(self):
         tags = [f"W{self.width}", f"H{self.height}", f"F{self.rate[0]}:{self.rate[1]}"]
         if self.interlace is not None:
