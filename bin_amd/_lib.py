@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import CHAIN_LIB_PATH, EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, RATE_LIB_PATH, SCENE_LIB_PATH, YUV_LIB_PATH
+from .build import CHAIN_LIB_PATH, EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, RATE_LIB_PATH, SCENE_LIB_PATH, SCORE_LIB_PATH, YUV_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -134,6 +134,13 @@ CHAIN_MAX_ITEMS = 24                   # BINCHAIN_MAX_ITEMS (include/binchain.h,
 
 class BinChainItem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)]
+
+
+PLANE_SSIM_G11, PLANE_SSIM_U7 = 1, 2    # BINSCORE_SSIM_* (include/binscore.h, libbinscore.so)
+
+
+class BinPlaneScores(C.Structure):
+    _fields_ = [("sse", C.c_uint64 * 3), ("sad", C.c_uint64 * 3), ("ssim_g11", C.c_double), ("ssim_u7", C.c_double)]
 
 
 _SIGNATURES = {
@@ -288,10 +295,19 @@ _RATE_SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
 }
 
+# libbinscore.so (include/binscore.h): the score library, loaded on first use
+SCORE_VERSION = 100                    # BINSCORE_VERSION
+SCORE_E_ARG, SCORE_E_SHAPE, SCORE_E_WORKSPACE = -1, -2, -3   # BINSCORE_E_*
+_SCORE_SIGNATURES = {
+    "binscore_version": (C.c_int, []),
+    "binscore_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "binscore_planes": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = _chainlib = _ratelib = None
+_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = _chainlib = _ratelib = _scorelib = None
 
 
 def _load(path, built_path, signatures, version=None):
@@ -426,6 +442,19 @@ def ratelib():
     if _ratelib is None:
         _ratelib = _load(RATE_LIB_PATH, RATE_LIB_PATH, _RATE_SIGNATURES, ("binrate_version", RATE_VERSION))
     return _ratelib
+
+
+def score_exported_symbols():
+    """Names every include/binscore.h entry point must resolve to."""
+    return sorted(_SCORE_SIGNATURES)
+
+
+def scorelib():
+    """Load libbinscore.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _scorelib
+    if _scorelib is None:
+        _scorelib = _load(SCORE_LIB_PATH, SCORE_LIB_PATH, _SCORE_SIGNATURES, ("binscore_version", SCORE_VERSION))
+    return _scorelib
 
 
 def check(rc, what):

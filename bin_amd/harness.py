@@ -140,8 +140,8 @@ class _MemoryFeed:
 
 
 @torch.no_grad()
-def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, ensemble=None, rate=None,
-                      resample="blend", factor=2, scene_cut=None):
+def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse_stage1=True, batch=1, gt=None, gt_offset=0, gt_stride=1,
+                      ensemble=None, rate=None, resample="blend", factor=2, scene_cut=None):
     """The window loop of the video runner (chain.run_stream) over the frames of a Y4M stream held in memory.  `payloads`:
     [T, frame_bytes] uint8 (host or device), the frames of `header` (bin_amd/video.py).  Returns the [factor (T-1), frame_bytes] uint8
     device tensor of the output payloads in display order; at factor 2 D0, I0, D1, I1, ..., D(T-2), I(T-2): exactly the frames the
@@ -158,10 +158,19 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
     rate: None, or the absolute output frame rate as (N, D) or a Fraction (bin_amd/rate.py): the result is then the [M, frame_bytes]
     stream at that rate, up to 8 times the header's, laid on the dense stream of the smallest factor F >= max(rate / input rate,
     factor); an output frame between two dense frames is their mix in fp32, converted in the same launch (ops.blend_to_yuv), and never
-    a mix across a cut.  resample: "blend", or "nearest" for the nearer dense frame instead (ties go to the earlier one)."""
+    a mix across a cut.  resample: "blend", or "nearest" for the nearer dense frame instead (ties go to the earlier one).
+    gt: None, or the [Tg, frame_bytes] uint8 payloads (host or device) of a ground-truth stream of the same header whose frame
+    gt_stride m + gt_offset is the truth of output frame m (bin_amd/score.py).  Every output payload is then scored against it as the
+    bytes it was packed to, on the device, right after it is packed (ops.payload_scores), and the call returns (out, rows): one
+    score.py row per output frame that has a ground-truth frame, after one download of all records.  `out` is the same bytes."""
     from . import ops, scene, video
     from . import rate as rate_
+    from . import score as score_
     chain.levels(factor)
+    if gt is not None:
+        if gt.dim() != 2 or gt.dtype != torch.uint8 or gt.shape[1] != header.frame_bytes:
+            raise ValueError(f"gt must be uint8 [Tg, {header.frame_bytes}] for this header (got {gt.dtype} {tuple(gt.shape)})")
+        score_.check_offset(gt_offset)
     if resample not in rate_.MODES:
         raise ValueError(f"resample must be one of {rate_.MODES} (got {resample!r})")
     grid = None
@@ -188,6 +197,17 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
     n_out = factor * (T - 1) if grid is None else grid.frames(T)
     out = torch.empty((n_out, header.frame_bytes), dtype=torch.uint8, device=dev)
     written = []
+    plan = records = None
+    if gt is not None:
+        plan = score_.Plan(gt_stride, gt_offset, factor, grid is not None)
+        records = torch.empty((n_out, ops.PLANE_SCORES_BYTES), dtype=torch.uint8, device=dev)
+    scored = []                                        # (output frame, its class) of every frame that has a ground truth
+
+    def score(pos, is_hold):                           # (right after out[pos] is packed: the scored bytes are the returned bytes)
+        if plan is not None and plan.gt_index(pos) < gt.shape[0]:
+            truth = gt[plan.gt_index(pos)].to(dev).contiguous()
+            ops.payload_scores(out[pos], truth, h, w, header.chroma, ssim=min(h, w) >= 7, out=records[pos])
+            scored.append((pos, plan.frame_class(pos, is_hold)))
 
     def emit(pos, f):
         if f is chain.HOLD:
@@ -195,6 +215,7 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
         else:
             ops.frame_to_yuv(f, t, l, h, w, fmt, out=out[pos])
         written.append(pos)
+        score(pos, f is chain.HOLD)
 
     def emit_at_rate(m, left, right, weight):
         if right is None:
@@ -202,6 +223,7 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
         else:
             ops.blend_to_yuv(left, right, weight, t, l, h, w, fmt, out=out[m])
         written.append(m)
+        score(m, False)
 
     def checked(flush):
         flush()
@@ -211,7 +233,10 @@ def interpolate_video(netG, payloads, header, matrix="auto", range="auto", reuse
     sink = emit if grid is None else rate_.Resampler(grid, emit_at_rate, resample).push
     chain.run_stream(_MemoryFeed(payloads, header, fmt, pads, dev, cuts), net, sink, factor, net.batch, checked)
     assert written == list(builtins_range(n_out))               # display order
-    return out
+    if gt is None:
+        return out
+    host = records.cpu()
+    return out, [(m, plan.gt_index(m), cls) + ops.read_plane_scores(host[m]) for m, cls in scored]
 
 
 def luma_records(payloads, header, device=None):

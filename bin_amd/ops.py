@@ -676,6 +676,69 @@ def read_luma_record(record):
     return int(rec.sad), np.array(rec.hist, dtype=np.int64)
 
 
+# --------------------------------------------------------------------------------------------- score glue (libbinscore.so)
+PLANE_SCORES_BYTES = C.sizeof(L.BinPlaneScores)         # 64: uint64 sse[3], sad[3] (Y, U, V), then the two SSIMs of the Y plane
+_score_ws = {}                                          # (device, stream, h, w, chroma, flags) -> workspace
+
+
+def payload_scores(a, b, h, w, chroma, ssim=True, out=None):
+    """The scores of one Y4M payload against another on the device (include/binscore.h): `a`, `b` are uint8 device payloads of an
+    h x w frame of `chroma` (420 | 444), or (y, u, v) triples of plane tensors, views at any byte offset included; `a is b` is
+    legal.  Returns the device uint8 [64] record (`out` when given; it must be 8-byte aligned): per plane the exact sums of (a - b)^2
+    and |a - b|, and of the Y plane as a one-channel image util.calculate_ssim's SSIM and util.compare_ssim's.  Current stream, no
+    host sync; the workspace is cached per stream and shape, so calls on one stream may follow each other freely.  `ssim=False`
+    computes only the sums (both SSIMs NaN); an SSIM the plane is too small for is NaN (ssim_g11 below 11 x 11), and below 7 x 7
+    an SSIM request raises, as frame_scores does.  `read_plane_scores` reads a downloaded record."""
+    global _G11_TAPS
+    if chroma not in (420, 444) or h < 1 or w < 1:
+        raise ValueError(f"bin_amd: payload_scores needs a positive size and chroma 420 | 444 (got {h}x{w}, {chroma!r})")
+    pa, pb = _yuv_planes(a, h, w, chroma), _yuv_planes(b, h, w, chroma)
+    first = a[0] if isinstance(a, (tuple, list)) else a
+    other = b[0] if isinstance(b, (tuple, list)) else b
+    if first.device != other.device:
+        raise ValueError("bin_amd: payload_scores takes two payloads of one device")
+    _need_cuda(out)
+    flags = 0
+    if ssim:
+        flags = L.PLANE_SSIM_U7 | (L.PLANE_SSIM_G11 if min(h, w) >= 11 else 0)
+    if _G11_TAPS is None:
+        from .utils.util import _gauss_taps
+        _G11_TAPS = (C.c_double * 11)(*[float(v) for v in _gauss_taps()])
+    if out is None:
+        out = torch.empty(PLANE_SCORES_BYTES, dtype=torch.uint8, device=first.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() != PLANE_SCORES_BYTES or \
+            out.device != first.device:
+        raise ValueError(f"bin_amd: a score record is a contiguous uint8 tensor of [{PLANE_SCORES_BYTES}] bytes on the payloads' device "
+                         f"(got {out.dtype} {tuple(out.shape)})")
+    lib = L.scorelib()
+    with on_device(first):
+        nb = lib.binscore_workspace_bytes(h, w, chroma, flags)
+        if nb == 0:
+            raise RuntimeError(f"bin_amd: payload_scores: unsupported frame size {h} x {w} (SSIM needs 7 x 7 pixels)")
+        stream = _stream()
+        key = (_device_key(first.device), stream.value, h, w, chroma, flags)
+        ws = _score_ws.get(key)
+        if ws is None:
+            ws = _score_ws[key] = torch.empty(nb, dtype=torch.uint8, device=first.device)
+        L.check(lib.binscore_planes(*pa, *pb, h, w, chroma, flags, _G11_TAPS, _ptr(ws), nb, _ptr(out), stream), "payload_scores")
+    return out
+
+
+def read_plane_scores(record):
+    """(sse_y, sse_u, sse_v, sad_y, sad_u, sad_v, ssim_g11, ssim_u7) of a score record on the host, six ints and two floats: a
+    uint8 [64] tensor or array, or its bytes."""
+    import numpy as np
+    if isinstance(record, torch.Tensor):
+        if record.is_cuda:
+            raise ValueError("bin_amd: read_plane_scores reads a downloaded record (record.cpu())")
+        record = record.numpy()
+    raw = bytes(memoryview(np.ascontiguousarray(record)).cast("B"))
+    if len(raw) != PLANE_SCORES_BYTES:
+        raise ValueError(f"bin_amd: a score record has {PLANE_SCORES_BYTES} bytes (got {len(raw)})")
+    rec = L.BinPlaneScores.from_buffer_copy(raw)
+    return tuple(int(v) for v in rec.sse) + tuple(int(v) for v in rec.sad) + (float(rec.ssim_g11), float(rec.ssim_u7))
+
+
 def pixel_unshuffle(x, r=2):
     """Exact space-to-depth: out[b, c*r*r + i*r + j, y, x] = in[b, c, y*r+i, x*r+j] (reference RDN.py:107-132)."""
     _need_cuda(x)

@@ -7,10 +7,11 @@ interpolated and deblurred frames against the sharp ground truth) and demo.py (w
     DECODER ... -f yuv4mpegpipe - | python -m bin_amd.test --input_video - --output_video - --opt ... | ENCODER ...
 
 With --input_video / --output_video the frames are those of one Y4M stream (bin_amd/video.py) instead of PNG files: same windows,
-same outputs, written in display order at twice the frame rate (run_video below; nothing is scored, one rank).  --factor 4 | 8
+same outputs, written in display order at twice the frame rate (run_video below; one rank).  --factor 4 | 8
 chains passes on the fp32 outputs for four or eight times the frame rate (the same run_video: bin_amd/chain.py has the window loop
 of every factor).  --output_rate N[:D] writes any frame rate up to eight times the input's: the frames of the factor's stream,
-resampled on the device (bin_amd/rate.py; --resample blend | nearest).
+resampled on the device (bin_amd/rate.py; --resample blend | nearest).  --gt_video GT.y4m scores every written frame against the
+sharp stream at the output rate or a whole multiple of it, per plane, on the device (bin_amd/score.py; --gt_offset, --score_log).
 
 What the reference does per input frame `index` of a clip (test.py:236-402) and this keeps:
   * the six blurry frames index + [-2..3], clamped to the clip (test.py:257-261, 333);
@@ -73,6 +74,12 @@ def parse_args(argv=None):
     p.add_argument("--resample", choices=["blend", "nearest"], default=None,
                    help="--output_rate: an output frame between two frames of the dense stream is their fp32 mix (blend, the default) "
                         "or the nearer one of them (nearest)")
+    p.add_argument("--gt_video", type=str, default=None,
+                   help="--input_video: a Y4M ground truth at the output's frame rate or a whole multiple s of it; written frame m is "
+                        "scored against its frame s m + --gt_offset, per plane, on the device (bin_amd/score.py)")
+    p.add_argument("--gt_offset", type=int, default=0, metavar="K", help="--gt_video: the ground-truth frame of output frame 0")
+    p.add_argument("--score_log", type=str, default=None, metavar="FILE",
+                   help="--gt_video: one tab-separated row per scored output frame (indices, class, the six sums, the two SSIMs)")
     p.add_argument("--gpu_id", type=str, default=None)
     p.add_argument("--time_step", type=float, default=0.5)
     p.add_argument("--opt", type=str, required=True, help="Path to option YAML file.")
@@ -124,6 +131,26 @@ def check_args(args):
                 rate.Grid(video.parse_header(f.readline(video.MAX_LINE)).rate, (n, d), getattr(args, "factor", 2))
     if getattr(args, "scene_cut", None) is None and getattr(args, "scene_cut_min_mad", 0.0):
         raise ValueError("--scene_cut_min_mad goes with --scene_cut")
+    gt_video, score_log, gt_offset = getattr(args, "gt_video", None), getattr(args, "score_log", None), getattr(args, "gt_offset", 0)
+    if args.input_video is None and (gt_video is not None or score_log is not None):
+        raise ValueError("--gt_video / --score_log: a ground-truth stream scores a video only (--input_video)")
+    if score_log is not None and gt_video is None:
+        raise ValueError("--score_log goes with --gt_video")
+    if gt_video is None and gt_offset:
+        raise ValueError("--gt_offset goes with --gt_video")
+    if gt_video is not None:
+        from . import score
+        score.check_offset(gt_offset)
+        if gt_video == "-" and args.input_video == "-":
+            raise ValueError("--gt_video - together with --input_video -: stdin carries one stream")
+        if all(v not in (None, "-") and os.path.isfile(v) for v in (args.input_video, gt_video)):
+            from . import rate, video                       # two files: their headers can be compared now (a pipe's: run_video)
+            with open(args.input_video, "rb") as f, open(gt_video, "rb") as g:
+                header, gt_header = (video.parse_header(x.readline(video.MAX_LINE)) for x in (f, g))
+            written = header.multiplied(getattr(args, "factor", 2))
+            if getattr(args, "output_rate", None) is not None:
+                written = header.at_rate(rate.Grid(header.rate, rate.parse_rate(args.output_rate), getattr(args, "factor", 2)).out_rate)
+            score.align(written, gt_header, gt_offset)
     if video and folder:
         raise ValueError("give either --input_path / --output_path or --input_video / --output_video, not both kinds")
     if video:
@@ -610,17 +637,135 @@ class _VideoFeed:
                 self.n_read += 1
 
 
+class _GtFeed:
+    """The ground-truth side of a scored video run (--gt_video), modelled on _VideoFeed.  A reader thread reads the stream in order
+    and hands over the frames offset, offset + s, offset + 2 s, ...: the frames the stride skips are read into the same recycled
+    page-locked buffer and go nowhere, and the thread never reads past the frame it hands over next.  The buffers are few and the
+    queue is bounded, so the ground truth never runs ahead of the output by more than that.  `take()` (main thread) gives the next
+    wanted frame as a device payload, uploaded on the upload stream behind an event the compute stream waits on, or None once the
+    ground truth has ended; the page-locked buffer goes back to the reader when its upload has finished."""
+    BUFFERS = 6
+
+    def __init__(self, reader, stride, offset):
+        self.reader, self.stride, self.offset, self.nbytes = reader, stride, offset, reader.header.frame_bytes
+        self.free_in, self.filled = queue.Queue(), queue.Queue(maxsize=self.BUFFERS)
+        for _ in range(self.BUFFERS):
+            self.free_in.put(None)                     # allocated on first use by the reader thread
+        self.ended, self.n_taken = False, 0
+        threading.Thread(target=self._read_frames, daemon=True).start()
+
+    def _read_frames(self):                            # (reader thread)
+        try:
+            index, wanted, buf = 0, self.offset, None
+            while True:
+                if buf is None:
+                    buf = self.free_in.get()
+                    if buf is None:
+                        buf = torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=True)
+                if not self.reader.readinto(buf.numpy()):
+                    break
+                if index == wanted:
+                    self.filled.put(buf)
+                    buf, wanted = None, wanted + self.stride
+                index += 1                             # (a skipped frame: the next read overwrites it)
+            self.filled.put(None)
+        except BaseException as e:                     # handed to the main thread, which raises it
+            self.filled.put(e)
+
+    def attach(self, dev, upload_stream):
+        self.upload = _Uploader(dev, upload_stream, self.free_in.put)
+
+    def take(self):
+        if self.ended:
+            return None
+        while True:
+            try:
+                item = self.filled.get_nowait()
+                break
+            except queue.Empty:
+                if not self.upload.in_flight:          # the reader is at work: wait for it
+                    item = self.filled.get()
+                    break
+                ev, buf = self.upload.in_flight.pop(0)  # it may be waiting for a buffer: the oldest upload's (the upload stream only)
+                ev.synchronize()
+                self.free_in.put(buf)
+        if item is None:
+            self.ended = True
+            return None
+        if isinstance(item, BaseException):
+            raise item
+        self.n_taken += 1
+        return self.upload(item)
+
+
+class _VideoScorer:
+    """_VideoWriter's scorer (--gt_video): called with (pos, row, is_hold) right after output frame `pos` was packed into `row` of
+    the staging tensor, so the scored bytes are the bytes that get written.  ops.payload_scores runs on the compute stream against
+    the frame _GtFeed hands over, into a slot of a device ring of 64-byte records; `flush` (hand_over's, on the copy stream behind
+    the event it waits on anyway) copies the new slots to a page-locked ring allocated once, behind an event, and `collect` reads
+    the records whose event has completed (`wait=True`: all of them, at the end of the run).  The compute stream is never
+    synchronised for it and nothing is allocated while the stream runs."""
+    RING = 256
+
+    def __init__(self, gt, plan, header, dev):
+        from . import score
+        self.gt, self.plan, self.dev = gt, plan, dev
+        self.h, self.w, self.chroma = header.height, header.width, header.chroma
+        ch, cw = header.chroma_size
+        self.tally = score.Tally(self.h * self.w, ch * cw)
+        self.dev_recs = torch.empty((self.RING, ops.PLANE_SCORES_BYTES), dtype=torch.uint8, device=dev)
+        self.host_recs = torch.empty((self.RING, ops.PLANE_SCORES_BYTES), dtype=torch.uint8, pin_memory=True)
+        self.pending, self.n_scored = [], 0            # [pos, gt index, class, slot, event or None]; records made so far
+
+    def __call__(self, pos, row, is_hold):
+        truth = self.gt.take()
+        if truth is None:
+            self.tally.no_gt()
+            return
+        if len(self.pending) == self.RING:             # (more frames between two hand-overs than the ring has slots)
+            self.flush()
+            self.collect(wait=True)
+        slot = self.n_scored % self.RING
+        ops.payload_scores(row, truth, self.h, self.w, self.chroma, ssim=min(self.h, self.w) >= 7, out=self.dev_recs[slot])
+        self.pending.append([pos, self.plan.gt_index(pos), self.plan.frame_class(pos, is_hold), slot, None])
+        self.n_scored += 1
+
+    def flush(self):
+        """The records made since the last flush -> page-locked memory, on the current stream, which must be behind their kernels."""
+        new = [e for e in self.pending if e[4] is None]
+        if not new:
+            return
+        first, count = new[0][3], len(new)             # consecutive slots of the ring: one copy, or two where they wrap
+        for lo, hi in ((first, min(first + count, self.RING)), (0, first + count - self.RING)):
+            if hi > lo:
+                self.host_recs[lo:hi].copy_(self.dev_recs[lo:hi], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        for e in new:
+            e[4] = ev
+
+    def collect(self, wait=False):
+        if wait:
+            self.flush()
+        while self.pending and self.pending[0][4] is not None and (wait or self.pending[0][4].query()):
+            pos, index, cls, slot, ev = self.pending.pop(0)
+            ev.synchronize()
+            self.tally.add((pos, index, cls) + ops.read_plane_scores(self.host_recs[slot]))
+
+
 class _VideoWriter:
     """The output side of the video runner.  `emit` (chain.Chain's) packs each frame with ops.frame_to_yuv straight into a row of a
     [3, frame_bytes] device staging tensor (a hold copies the row before it), `emit_at_rate` (rate.Resampler's) likewise with
     ops.blend_to_yuv where two frames are mixed; `hand_over` sends what was staged to page-locked memory
     on the copy stream and to the ONE writer thread: jobs (page-locked [3, frame_bytes] buffer, rows to write, event after which they
     are complete) are written first in, first out, which is display order; buffers come back through `free_out`.  An error of the
-    thread is kept in `error` (it keeps draining, so that the main thread never blocks on a dead writer) and raised by hand_over."""
+    thread is kept in `error` (it keeps draining, so that the main thread never blocks on a dead writer) and raised by hand_over.
+    `scorer` (optional, --gt_video): called with (pos, row, is_hold) right after a row is packed; at every hand_over its new records
+    go to page-locked memory on the copy stream (`flush`) and it is asked to `collect` what has completed."""
 
-    def __init__(self, target, out_header, fmt, pads, dev):
+    def __init__(self, target, out_header, fmt, pads, dev, scorer=None):
         from . import video
-        self.header, self.fmt, self.pads, self.dev = out_header, fmt, pads, dev
+        self.header, self.fmt, self.pads, self.dev, self.scorer = out_header, fmt, pads, dev, scorer
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.staged, self.last_row, self.n_written = [], None, 0      # [device staging tensor, rows filled]; the row packed last
         self.to_write, self.free_out, self.error = queue.Queue(maxsize=10), [], []
@@ -665,6 +810,8 @@ class _VideoWriter:
             l, r, t, b = self.pads
             ops.frame_to_yuv(frame, t, l, self.header.height, self.header.width, self.fmt, out=row)
         self.last_row = row
+        if self.scorer is not None:
+            self.scorer(pos, row, frame is chain.HOLD)
 
     def emit_at_rate(self, m, left, right, w):
         """rate.Resampler's emit (--output_rate): `left` alone, or the mix left + w (right - left) packed in the same launch."""
@@ -675,6 +822,8 @@ class _VideoWriter:
         else:
             ops.blend_to_yuv(left, right, w, t, l, self.header.height, self.header.width, self.fmt, out=row)
         self.last_row = row
+        if self.scorer is not None:
+            self.scorer(m, row, False)
 
     def hand_over(self):
         for outs, n in self.staged:
@@ -689,6 +838,13 @@ class _VideoWriter:
                 done.record()
             self.to_write.put((host, n, done))
             self.n_written += n
+        if self.scorer is not None and self.staged:
+            ready = torch.cuda.Event()
+            ready.record()
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(ready)
+                self.scorer.flush()
+            self.scorer.collect()
         self.staged.clear()
         if self.error:
             raise self.error[0]
@@ -710,8 +866,12 @@ def run_video(args, opt, stats=None):
     (ops.blend_to_yuv).  Logging goes to stderr and the log file, never to stdout (--output_video -).
     --scene_cut: ops.luma_stats runs on the upload stream right behind each frame's upload (its inputs are the payloads alone), its
     264-byte record comes back through a page-locked buffer and an event of that stream; the compute stream is never waited on for
-    it.  Window i needs the cut flags up to the pair (i + 2, i + 3), frames read_to(i + 3) has taken already."""
-    from . import chain, rate, video
+    it.  Window i needs the cut flags up to the pair (i + 2, i + 3), frames read_to(i + 3) has taken already.
+    --gt_video: _GtFeed reads the ground truth beside the input, _VideoScorer scores every packed row against its frame
+    (ops.payload_scores on the compute stream, the upload on the upload stream behind an event); the 64-byte records come back
+    through page-locked memory and events and are tallied per class (bin_amd/score.py); the table goes to the log, the rows to
+    --score_log and to `stats["scores"]`.  The written bytes do not change with it."""
+    from . import chain, rate, score, video
     factor = getattr(args, "factor", 2)
     log_root = os.getcwd() if args.output_video == "-" else os.path.dirname(os.path.abspath(args.output_video))
     os.makedirs(log_root, exist_ok=True)
@@ -726,6 +886,17 @@ def run_video(args, opt, stats=None):
     fmt = video.resolve_format(header, args.yuv_matrix, args.yuv_range)
     h, w = header.height, header.width
     pads = util.pad_sizes(h, w)
+    written_header = out_header or header.multiplied(factor)
+    gt_reader = gt_feed = plan = None
+    if getattr(args, "gt_video", None) is not None:      # (refusals: still before the model is built)
+        gt_reader = video.Y4MReader(args.gt_video)
+        try:
+            plan = score.Plan(score.align(written_header, gt_reader.header, args.gt_offset), args.gt_offset, factor, grid is not None)
+        except BaseException:
+            gt_reader.close()
+            reader.close()
+            raise
+        gt_feed = _GtFeed(gt_reader, plan.stride, plan.offset)
     feed = _VideoFeed(args, reader, fmt, pads, factor, log)
     if grid is not None:
         feed.out_frame = lambda c: -(-c * grid.p // grid.q)         # the first output frame at or after the cut
@@ -745,7 +916,13 @@ def run_video(args, opt, stats=None):
         log.info("output rate: F%d:%d, %s: the frames of the factor-%d stream, resample %s", grid.out_rate[0], grid.out_rate[1],
                  grid.describe(), grid.F, mode)
     feed.attach(dev)
-    out = _VideoWriter(args.output_video, out_header or header.multiplied(factor), fmt, pads, dev)
+    scorer = None
+    if gt_feed is not None:
+        log.info("ground truth: %s F%d:%d, output frame m against its frame %d m + %d", args.gt_video, gt_reader.header.rate[0],
+                 gt_reader.header.rate[1], plan.stride, plan.offset)
+        gt_feed.attach(dev, feed.upload_stream)
+        scorer = _VideoScorer(gt_feed, plan, written_header, dev)
+    out = _VideoWriter(args.output_video, written_header, fmt, pads, dev, scorer)
     emit = out.emit if grid is None else rate.Resampler(grid, out.emit_at_rate, mode).push
     timer, stamps = AverageMeter(), []
 
@@ -765,6 +942,8 @@ def run_video(args, opt, stats=None):
     finally:
         out.finish()
         reader.close()
+        if gt_reader is not None:
+            gt_reader.close()
     if out.error:
         raise out.error[0]
     n_frames, cuts = feed.n_frames, feed.cuts
@@ -778,9 +957,19 @@ def run_video(args, opt, stats=None):
              out.n_written / max(wall, 1e-9), timer.avg, run["frames_resident_peak"])
     if feed.scene_on:
         log.info("scene cuts: %d at input frames %s; duplicates: %d", len(cuts), ", ".join(str(c) for c in cuts) or "-", feed.n_dup)
+    scores = None
+    if scorer is not None:
+        scorer.collect(wait=True)
+        scores = {"rows": sorted(scorer.tally.rows), "summary": scorer.tally.summary(), "stride": plan.stride, "offset": plan.offset}
+        for line in score.table(scores["summary"]):
+            log.info("%s", line)
+        if getattr(args, "score_log", None) is not None:
+            score.write_log(args.score_log, scores["rows"])
     if stats is not None:
         stats.update(run, wall=wall, net_s_per_window=timer.avg, stamps=[s - t_all for s in stamps], frames_out=out.n_written,
                      factor=factor)
+        if scores is not None:
+            stats.update(scores=scores)
         if feed.scene_on:
             stats.update(cuts=list(cuts))
     return 0
