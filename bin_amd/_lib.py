@@ -3,7 +3,7 @@ library is missing or a call fails this raises, it never routes to PyTorch/CPU c
 import ctypes as C
 import os
 
-from .build import CHAIN_LIB_PATH, EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, RATE_LIB_PATH, SCENE_LIB_PATH, SCORE_LIB_PATH, YUV_LIB_PATH
+from .build import CHAIN_LIB_PATH, CLIP_LIB_PATH, EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, RATE_LIB_PATH, SCENE_LIB_PATH, SCORE_LIB_PATH, YUV_LIB_PATH
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -304,10 +304,18 @@ _SCORE_SIGNATURES = {
     "binscore_planes": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
+# libbinclip.so (include/binclip.h): the clip library, loaded on first use
+CLIP_VERSION = 100                     # BINCLIP_VERSION
+CLIP_E_ARG, CLIP_E_SHAPE = -1, -2      # BINCLIP_E_ARG, BINCLIP_E_SHAPE
+_CLIP_SIGNATURES = {
+    "binclip_version": (C.c_int, []),
+    "binclip_yuv_to_bgr": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(BinYuvFormat), C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = _chainlib = _ratelib = _scorelib = None
+_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = _chainlib = _ratelib = _scorelib = _cliplib = None
 
 
 def _load(path, built_path, signatures, version=None):
@@ -455,6 +463,19 @@ def scorelib():
     if _scorelib is None:
         _scorelib = _load(SCORE_LIB_PATH, SCORE_LIB_PATH, _SCORE_SIGNATURES, ("binscore_version", SCORE_VERSION))
     return _scorelib
+
+
+def clip_exported_symbols():
+    """Names every include/binclip.h entry point must resolve to."""
+    return sorted(_CLIP_SIGNATURES)
+
+
+def cliplib():
+    """Load libbinclip.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
+    global _cliplib
+    if _cliplib is None:
+        _cliplib = _load(CLIP_LIB_PATH, CLIP_LIB_PATH, _CLIP_SIGNATURES, ("binclip_version", CLIP_VERSION))
+    return _cliplib
 
 
 def check(rc, what):

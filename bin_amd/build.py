@@ -63,6 +63,12 @@ SCORE_SOURCES = ["binscore.hip"]
 SCORE_LIB_PATH = os.path.join(CSRC, "libbinscore.so")
 SCORE_HEADER = os.path.join(os.path.dirname(HERE), "include", "binscore.h")
 
+# the clip library (include/binclip.h): the Y4M payloads of a clip -> the uint8 BGR frames of the device frame cache, the kernel of
+# bin_amd/data/video_dataset.py (dataset mode BIN_video); an eleventh shared object, for the same reason
+CLIP_SOURCES = ["binclip.hip"]
+CLIP_LIB_PATH = os.path.join(CSRC, "libbinclip.so")
+CLIP_HEADER = os.path.join(os.path.dirname(HERE), "include", "binclip.h")
+
 HEADER = os.path.join(os.path.dirname(HERE), "include", "binhip.h")
 # (name, sources, header, path) of every shared object: what drives the compile, the version script and the link
 LIBRARIES = (("binhip", SOURCES, HEADER, LIB_PATH), ("binopt", OPT_SOURCES, OPT_HEADER, OPT_LIB_PATH),
@@ -80,6 +86,8 @@ ALL_LIBRARIES = PRODUCT_LIBRARIES + CHAIN_LIBRARIES
 RATE_LIBRARIES = (("binrate", RATE_SOURCES, RATE_HEADER, RATE_LIB_PATH),)
 # the libraries that score a video run against its ground truth (same tuple layout), built and checked for staleness with them
 SCORE_LIBRARIES = (("binscore", SCORE_SOURCES, SCORE_HEADER, SCORE_LIB_PATH),)
+# the libraries that fill the training frame cache from video (same tuple layout), built and checked for staleness with them
+CLIP_LIBRARIES = (("binclip", CLIP_SOURCES, CLIP_HEADER, CLIP_LIB_PATH),)
 
 
 def _declared(header, macro, prefix):
@@ -139,13 +147,18 @@ def score_abi_symbols():
     return _declared(SCORE_HEADER, "BINSCORE_API", "binscore")
 
 
+def clip_abi_symbols():
+    """The entry points include/binclip.h declares (every BINCLIP_API declaration), in header order."""
+    return _declared(CLIP_HEADER, "BINCLIP_API", "binclip")
+
+
 def _stale():
-    libs = [path for _, _, _, path in ALL_LIBRARIES + RATE_LIBRARIES + SCORE_LIBRARIES]
+    libs = [path for _, _, _, path in ALL_LIBRARIES + RATE_LIBRARIES + SCORE_LIBRARIES + CLIP_LIBRARIES]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    deps += [header for _, _, header, _ in ALL_LIBRARIES + RATE_LIBRARIES + SCORE_LIBRARIES]
+    deps += [header for _, _, header, _ in ALL_LIBRARIES + RATE_LIBRARIES + SCORE_LIBRARIES + CLIP_LIBRARIES]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -154,7 +167,8 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     library bin_amd/csrc/libbinopt.so, the gradient-guard library bin_amd/csrc/libbingrad.so, the weight-average library
     bin_amd/csrc/libbinema.so, the self-ensemble library bin_amd/csrc/libbinens.so, the video library
     bin_amd/csrc/libbinyuv.so, the scene library bin_amd/csrc/libbinscene.so, the chain library bin_amd/csrc/libbinchain.so, the
-    rate library bin_amd/csrc/libbinrate.so and the score library bin_amd/csrc/libbinscore.so beside it).
+    rate library bin_amd/csrc/libbinrate.so, the score library bin_amd/csrc/libbinscore.so and the clip library
+    bin_amd/csrc/libbinclip.so beside it).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain): libbinhip.so alone, under another name.  The
@@ -165,7 +179,7 @@ def build_library(force=False, verbose=True, defines=(), out=None):
     objdir = CSRC if out is None else os.path.dirname(os.path.abspath(out))
     os.makedirs(objdir, exist_ok=True)
     tag = "" if out is None else "." + os.path.splitext(os.path.basename(out))[0]
-    libraries = ALL_LIBRARIES + RATE_LIBRARIES + SCORE_LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
+    libraries = ALL_LIBRARIES + RATE_LIBRARIES + SCORE_LIBRARIES + CLIP_LIBRARIES if out is None else (("binhip", SOURCES, HEADER, out),)
     procs, objs = [], {}
     for name, sources, _, _ in libraries:
         for src in sources:

@@ -159,14 +159,17 @@ def make_sharp_window_list(root, mode="train", split=100, shuffle=True, blur_win
     return windows[:keep], windows[keep:]
 
 
-def draw_window_aug(input_frame_size=(3, 128, 256), data_aug=True):
+def draw_window_aug(input_frame_size=(3, 128, 256), data_aug=True, src_size=(SRC_H, SRC_W)):
     """The reference loader's augmentation draws for one window, in its order: temporal order (randint: 1 keeps it, 0
     reverses; no aug => reversed, as in the reference), crop offsets (choice, choice), horizontal flip (randint).
-    Returns (reversed, y0, x0, flip).  load_window and the device-cache loader (device_cache.py) both draw through here."""
+    Returns (reversed, y0, x0, flip).  load_window and the device-cache loader (device_cache.py) both draw through here.
+    `src_size`: the (H, W) the offsets are drawn against; the prepared dataset's unless the frames come from a video clip
+    (video_dataset.py), which has its own."""
     reverse = not (data_aug and random.randint(0, 1))
     _, ch, cw = input_frame_size
-    y0 = random.choice(range(SRC_H - ch + 1))
-    x0 = random.choice(range(SRC_W - cw + 1))
+    src_h, src_w = src_size
+    y0 = random.choice(range(src_h - ch + 1))
+    x0 = random.choice(range(src_w - cw + 1))
     flip = bool(data_aug and random.randint(0, 1))
     return reverse, y0, x0, flip
 

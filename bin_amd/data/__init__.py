@@ -26,6 +26,14 @@ def create_dataloader(dataset, dataset_opt, opt=None, sampler=None, vscode_debug
     common = dict(shuffle=False, pin_memory=torch.cuda.is_available())
     train = dataset_opt["phase"] == "train"
     batch, workers = _train_loader_shape(dataset_opt, opt) if train else (1, 1)
+    if hasattr(dataset, "make_device_cache"):
+        # bin_amd extension, mode BIN_video: windows of sharp Y4M clips (data/video_dataset.py), served from the device frame cache in
+        # every phase
+        from .device_cache import create_device_loader
+        from .video_dataset import NO_HOST_LOADER
+        if not dataset_opt.get("device_cache"):
+            raise ValueError(NO_HOST_LOADER)
+        return create_device_loader(dataset, dataset_opt, batch, sampler if train else None)
     if dataset_opt.get("device_cache"):
         # bin_amd extension: batches cut out of a device-resident frame cache (data/device_cache.py); BIN windows only.  Any
         # other phase: single windows in order, nothing dropped; the loader (and with it the cache) is built once and
@@ -44,7 +52,9 @@ def create_dataloader(dataset, dataset_opt, opt=None, sampler=None, vscode_debug
 
 def create_dataset(dataset_opt):
     # "synthetic_texture" is a bin_amd extension: clips rendered on the fly with the structure of the reference's windows
-    kinds = {"BIN": ("BIN_dataset", "BINDataset"), "synthetic_texture": ("synthetic", "SyntheticTextureDataset")}
+    # and "BIN_video": windows of sharp high-frame-rate Y4M clips, their blurry inputs synthesised (data/video_dataset.py)
+    kinds = {"BIN": ("BIN_dataset", "BINDataset"), "synthetic_texture": ("synthetic", "SyntheticTextureDataset"),
+             "BIN_video": ("video_dataset", "VideoClipDataset")}
     mode = dataset_opt["mode"]
     if mode not in kinds:
         raise NotImplementedError("Dataset [{:s}] is not recognized.".format(mode))

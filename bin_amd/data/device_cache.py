@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .BIN_dataset import blur_half_max, draw_blur_half, draw_window_aug, frame_number
+from .BIN_dataset import SRC_H, SRC_W, blur_half_max, draw_blur_half, draw_window_aug, frame_number
 from .util import imread_u8
 
 N_SLOTS = 17                     # 6 blurry + 6 sharp + 5 in-between sharp frames per window
@@ -66,17 +66,7 @@ class DeviceFrameCache:
                         self.index[p] = len(self.paths)
                         self.paths.append(p)
         else:
-            spans = {}                                       # clip folder -> [first, last] blurry centre of any window
-            for win in window_list:
-                d, a, b = os.path.dirname(win[0][0]), frame_number(win[0][0]), frame_number(win[0][-1])
-                lo, hi = spans.get(d, (a, b))
-                spans[d] = (min(lo, a), max(hi, b))
-            self.clip_ranges = np.empty((len(spans), 2), dtype=np.int64)
-            for c, (d, (lo, hi)) in enumerate(spans.items()):
-                clip = [os.path.join(d, str(k).zfill(5) + ".png") for k in range(lo - blur_half, hi + blur_half + 1)]
-                self.clip_ranges[c] = (len(self.paths), len(self.paths) + len(clip))
-                self.index.update((p, len(self.paths) + j) for j, p in enumerate(clip))
-                self.paths += clip
+            self._index_spans(window_list, blur_half)
         if not self.paths:
             raise ValueError("DeviceFrameCache: the window list is empty")
         threads = threads or _default_threads()
@@ -96,6 +86,23 @@ class DeviceFrameCache:
         self.device = torch.device(device)
         self.frames = torch.empty(self.shape, dtype=torch.uint8, device=self.device)
         self._fill(threads)
+
+    def _index_spans(self, window_list, blur_half):
+        """`paths`, `index` and `clip_ranges` of make_sharp_window_list's windows: per clip every file from its first blurry centre
+        - blur_half to its last + blur_half.  Returns {clip folder: (first, last) blurry centre of any window}, in arena order."""
+        self.paths, self.index = [], {}
+        spans = {}
+        for win in window_list:
+            d, a, b = os.path.dirname(win[0][0]), frame_number(win[0][0]), frame_number(win[0][-1])
+            lo, hi = spans.get(d, (a, b))
+            spans[d] = (min(lo, a), max(hi, b))
+        self.clip_ranges = np.empty((len(spans), 2), dtype=np.int64)
+        for c, (d, (lo, hi)) in enumerate(spans.items()):
+            clip = [os.path.join(d, str(k).zfill(5) + ".png") for k in range(lo - blur_half, hi + blur_half + 1)]
+            self.clip_ranges[c] = (len(self.paths), len(self.paths) + len(clip))
+            self.index.update((p, len(self.paths) + j) for j, p in enumerate(clip))
+            self.paths += clip
+        return spans
 
     def _fill(self, threads):
         """Decode into two pinned buffers in turn; each chunk's copy to the arena overlaps the next chunk's decoding."""
@@ -152,7 +159,12 @@ class DeviceWindowLoader:
         self.crop = tuple(dataset.input_frame_size)
         self.blur_window = getattr(dataset, "blur_window", None)
         blur_half = None if self.blur_window is None else blur_half_max(self.blur_window)
-        self.cache = cache or DeviceFrameCache(dataset.all_paths, device, max_gb, blur_half=blur_half)
+        from_clips = getattr(dataset, "make_device_cache", None)   # mode BIN_video (video_dataset.py): the frames come from its clips
+        if cache is None:
+            cache = from_clips(device, max_gb) if from_clips else DeviceFrameCache(dataset.all_paths, device, max_gb, blur_half=blur_half)
+        self.cache = cache
+        # crop offsets are drawn against the prepared dataset's frame size, as the host loader draws them; a clip's own for BIN_video
+        self.src_size = tuple(self.cache.shape[1:3]) if from_clips else (SRC_H, SRC_W)
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else len(self.dataset)
@@ -172,10 +184,10 @@ class DeviceWindowLoader:
         for idx in self.index_batches():
             windows = [self.dataset.all_paths[i] for i in idx]
             if self.blur_window is None:
-                draws = [draw_window_aug(self.crop) for _ in windows]
+                draws = [draw_window_aug(self.crop, src_size=self.src_size) for _ in windows]
                 out = ops.gather_windows(self.cache.frames, self.cache.table(windows, draws), (ch, cw))
             else:                                            # per sample: the four draws, then the exposure's (load_window's order)
-                both = [(draw_window_aug(self.crop), draw_blur_half(self.blur_window)) for _ in windows]
+                both = [(draw_window_aug(self.crop, src_size=self.src_size), draw_blur_half(self.blur_window)) for _ in windows]
                 table = self.cache.table(windows, [d for d, _ in both], [h for _, h in both])
                 out = ops.gather_windows_blur(self.cache.frames, table, (ch, cw), N_BLUR, self.cache.clip_ranges)
             yield {"LQs": out[0:6].transpose(0, 1), "GTenh": out[6:12].transpose(0, 1), "GTinp": out[12:17].transpose(0, 1),

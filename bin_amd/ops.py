@@ -606,6 +606,33 @@ def frame_to_yuv(frame, top, left, h, w, fmt, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------------- clip glue (libbinclip.so)
+def yuv_to_bgr(payloads, h, w, fmt, out=None):
+    """The Y4M payloads of n frames (device uint8 [n, stride], stride >= frame_bytes, each row contiguous: frame i is the first
+    frame_bytes bytes of row i, the rest of a row is never read) -> uint8 [n, h, w, 3] HWC BGR, the frames of the device frame cache
+    (into `out` when given: a contiguous uint8 [n, h, w, 3], e.g. arena[i:j]).  One launch; per frame the bytes of
+    frame_to_u8(yuv_to_frame(payload, pads 0)) (include/binclip.h).  fmt: (chroma, matrix, range)."""
+    f = yuv_format(fmt)
+    if h < 1 or w < 1:
+        raise ValueError(f"bin_amd: yuv_to_bgr needs a positive size (got {h}x{w})")
+    need = yuv_frame_bytes(h, w, fmt[0])[0]
+    if payloads.dtype != torch.uint8 or payloads.dim() != 2 or payloads.shape[0] < 1 or payloads.shape[1] < need or \
+            (payloads.shape[1] > 1 and payloads.stride(1) != 1) or (payloads.shape[0] > 1 and payloads.stride(0) < payloads.shape[1]):
+        raise ValueError(f"bin_amd: the payloads of {w}x{h} {fmt[0]} frames are a uint8 tensor [n, stride >= {need}] with contiguous rows "
+                         f"(got {payloads.dtype} {tuple(payloads.shape)}, strides {tuple(payloads.stride())})")
+    n = payloads.shape[0]
+    stride = payloads.stride(0) if n > 1 else payloads.shape[1]
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous() or out.device != payloads.device):
+        raise ValueError(f"bin_amd: yuv_to_bgr fills a contiguous uint8 [{n}, {h}, {w}, 3] on the payloads' device "
+                         f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+    _need_cuda(payloads, out)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=payloads.device)
+    with on_device(payloads):
+        L.check(L.cliplib().binclip_yuv_to_bgr(_ptr(payloads), n, stride, h, w, C.byref(f), _ptr(out), _stream()), "yuv_to_bgr")
+    return out
+
+
 # --------------------------------------------------------------------------------------------- rate glue (libbinrate.so)
 def blend_to_yuv(a, b, w, top, left, h, w_, fmt, out=None):
     """Two fp32 [1,3,Hp,Wp] (or [3,Hp,Wp]) RGB frames of one shape -> the Y4M payload of the crop of a + w (b - a), 0 <= w < 1, on

@@ -230,6 +230,47 @@ class Y4MWriter:
         self.close()
 
 
+def clip_info(path):
+    """(Y4MHeader, number of frames) of a clip in a seekable file (a path or a seekable binary file object), without reading a payload.
+    From the file size when every frame is a bare `FRAME` line and its payload (the size fits and FRAME stands at the first and at the
+    last computed offset); otherwise by walking the FRAME lines with seeks.  ValueError names a trailing partial frame; `-` and
+    objects that cannot seek are refused."""
+    if isinstance(path, (str, bytes)) and path in ("-", b"-"):
+        raise ValueError("clip_info needs a seekable file: `-` (a pipe) cannot be measured without reading it")
+    f, mine = _open(path, "rb")
+    try:
+        if not (hasattr(f, "seekable") and f.seekable()):
+            raise ValueError(f"clip_info needs a seekable file (got {f!r})")
+        f.seek(0)
+        rd = Y4MReader(f)
+        header, start, size = rd.header, f.tell(), f.seek(0, 2)
+        step = len(FRAME) + 1 + header.frame_bytes
+
+        def bare(at):
+            f.seek(at)
+            return f.read(len(FRAME) + 1) == FRAME + b"\n"
+        n, rest = divmod(size - start, step)
+        if rest == 0 and (n == 0 or (bare(start) and bare(start + (n - 1) * step))):
+            return header, n
+        n, at = 0, start
+        while at < size:
+            f.seek(at)
+            try:
+                line = rd._line()
+            except ValueError as e:
+                raise ValueError(f"Y4M frame {n} is truncated: {e}") from None
+            if line != FRAME and not line.startswith(FRAME + b" "):
+                raise ValueError(f"Y4M frame {n}: expected a FRAME line, found {line[:16]!r}")
+            at = f.tell() + header.frame_bytes
+            if at > size:
+                raise ValueError(f"Y4M frame {n} is truncated: {size - f.tell()} of {header.frame_bytes} bytes")
+            n += 1
+        return header, n
+    finally:
+        if mine:
+            f.close()
+
+
 def resolve_format(header, matrix="auto", range="auto"):
     """(chroma, matrix, range) of a stream for ops.yuv_to_frame / ops.frame_to_yuv.  matrix "auto": bt709 when W >= 1280 or H > 576,
     else bt601; range "auto": the header's XCOLORRANGE, else limited."""
