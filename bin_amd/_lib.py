@@ -1,9 +1,11 @@
-"""ctypes binding of libbinhip.so (include/binhip.h).  The product path has NO fallback: if the
-library is missing or a call fails this raises, it never routes to PyTorch/CPU code."""
+"""ctypes binding of the eleven shared objects of bin_amd/build.py's table (libbinhip.so and the ten small libraries beside it,
+include/<name>.h), each loaded on first use.  The product path has NO fallback: if a library is missing, of another version or a
+call fails this raises, it never routes to PyTorch/CPU code."""
 import ctypes as C
 import os
+from functools import partial
 
-from .build import CHAIN_LIB_PATH, CLIP_LIB_PATH, EMA_LIB_PATH, ENS_LIB_PATH, GRAD_LIB_PATH, LIB_PATH, OPT_LIB_PATH, RATE_LIB_PATH, SCENE_LIB_PATH, SCORE_LIB_PATH, YUV_LIB_PATH
+from .build import BY_NAME, LIB_PATH  # noqa: F401  (LIB_PATH: callers read libbinhip.so's path as _lib.LIB_PATH)
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
@@ -315,167 +317,58 @@ _CLIP_SIGNATURES = {
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
-_lib = _optlib = _gradlib = _emalib = _enslib = _yuvlib = _scenelib = _chainlib = _ratelib = _scorelib = _cliplib = None
+# name (a row of build.LIBRARIES) -> (signatures, the value <name>_version() must return; None: no gate, binders check binhip_version())
+_LIBRARIES = {"binhip": (_SIGNATURES, None), "binopt": (_OPT_SIGNATURES, OPT_VERSION), "bingrad": (_GRAD_SIGNATURES, GRAD_VERSION),
+              "binema": (_EMA_SIGNATURES, EMA_VERSION), "binens": (_ENS_SIGNATURES, ENS_VERSION), "binyuv": (_YUV_SIGNATURES, YUV_VERSION),
+              "binscene": (_SCENE_SIGNATURES, SCENE_VERSION), "binchain": (_CHAIN_SIGNATURES, CHAIN_VERSION),
+              "binrate": (_RATE_SIGNATURES, RATE_VERSION), "binscore": (_SCORE_SIGNATURES, SCORE_VERSION),
+              "binclip": (_CLIP_SIGNATURES, CLIP_VERSION)}
+_loaded = {}                    # name -> the CDLL, once library(name) has loaded it
 
 
-def _load(path, built_path, signatures, version=None):
-    """dlopen `path` and type its entry points.  Raises RuntimeError with the build hint when it is absent, and when `version`
-    (the version entry point's name, the value this binding is for) does not match."""
-    if not os.path.exists(path):
-        raise RuntimeError(
-            f"bin_amd: HIP library {built_path} not built. Run `python -c 'import __graft_entry__ as g; "
-            f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
-    h = C.CDLL(path)
-    for name, (res, args) in signatures.items():
-        fn = getattr(h, name)
-        fn.restype = res
-        fn.argtypes = args
-    if version is not None and getattr(h, version[0])() != version[1]:
-        raise RuntimeError(f"bin_amd: {path} is version {getattr(h, version[0])()}, this binding is for {version[1]}")
-    return h
+def exported_symbols(name="binhip"):
+    """Names every include/<name>.h entry point must resolve to (checked by the CPU test-suite)."""
+    return sorted(_LIBRARIES[name][0])
 
 
-def exported_symbols():
-    """Names every include/binhip.h entry point must resolve to (checked by the CPU test-suite)."""
-    return sorted(_SIGNATURES)
+def library(name):
+    """Load lib<name>.so (once) and type its entry points.  Raises RuntimeError with the build hint when it is absent, and when
+    its <name>_version() is not the value this binding is for."""
+    if name not in _loaded:
+        signatures, version = _LIBRARIES[name]
+        built = path = BY_NAME[name].path
+        if name == "binhip":        # BIN_AMD_LIB: developer knob: the timeline side build, another commit's library
+            path = os.environ.get("BIN_AMD_LIB", built)
+        if not os.path.exists(path):
+            raise RuntimeError(
+                f"bin_amd: HIP library {built} not built. Run `python -c 'import __graft_entry__ as g; "
+                f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback by design.")
+        h = C.CDLL(path)
+        for sym, (res, args) in signatures.items():
+            fn = getattr(h, sym)
+            fn.restype = res
+            fn.argtypes = args
+        if version is not None and getattr(h, name + "_version")() != version:
+            raise RuntimeError(f"bin_amd: {path} is version {getattr(h, name + '_version')()}, this binding is for {version}")
+        _loaded[name] = h
+    return _loaded[name]
 
 
 def lib():
     """Load libbinhip.so (once).  Raises RuntimeError with the build hint when it is absent."""
-    global _lib
-    if _lib is None:                # BIN_AMD_LIB: developer knob: the timeline side build, another commit's library
-        _lib = _load(os.environ.get("BIN_AMD_LIB", LIB_PATH), LIB_PATH, _SIGNATURES)
-    return _lib
+    return library("binhip")
 
 
-def opt_exported_symbols():
-    """Names every include/binopt.h entry point must resolve to."""
-    return sorted(_OPT_SIGNATURES)
-
-
-def optlib():
-    """Load libbinopt.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _optlib
-    if _optlib is None:
-        _optlib = _load(OPT_LIB_PATH, OPT_LIB_PATH, _OPT_SIGNATURES, ("binopt_version", OPT_VERSION))
-    return _optlib
-
-
-def grad_exported_symbols():
-    """Names every include/bingrad.h entry point must resolve to."""
-    return sorted(_GRAD_SIGNATURES)
-
-
-def gradlib():
-    """Load libbingrad.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _gradlib
-    if _gradlib is None:
-        _gradlib = _load(GRAD_LIB_PATH, GRAD_LIB_PATH, _GRAD_SIGNATURES, ("bingrad_version", GRAD_VERSION))
-    return _gradlib
-
-
-def ema_exported_symbols():
-    """Names every include/binema.h entry point must resolve to."""
-    return sorted(_EMA_SIGNATURES)
-
-
-def emalib():
-    """Load libbinema.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _emalib
-    if _emalib is None:
-        _emalib = _load(EMA_LIB_PATH, EMA_LIB_PATH, _EMA_SIGNATURES, ("binema_version", EMA_VERSION))
-    return _emalib
-
-
-def ens_exported_symbols():
-    """Names every include/binens.h entry point must resolve to."""
-    return sorted(_ENS_SIGNATURES)
-
-
-def enslib():
-    """Load libbinens.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _enslib
-    if _enslib is None:
-        _enslib = _load(ENS_LIB_PATH, ENS_LIB_PATH, _ENS_SIGNATURES, ("binens_version", ENS_VERSION))
-    return _enslib
-
-
-def yuv_exported_symbols():
-    """Names every include/binyuv.h entry point must resolve to."""
-    return sorted(_YUV_SIGNATURES)
-
-
-def yuvlib():
-    """Load libbinyuv.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _yuvlib
-    if _yuvlib is None:
-        _yuvlib = _load(YUV_LIB_PATH, YUV_LIB_PATH, _YUV_SIGNATURES, ("binyuv_version", YUV_VERSION))
-    return _yuvlib
-
-
-def scene_exported_symbols():
-    """Names every include/binscene.h entry point must resolve to."""
-    return sorted(_SCENE_SIGNATURES)
-
-
-def scenelib():
-    """Load libbinscene.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _scenelib
-    if _scenelib is None:
-        _scenelib = _load(SCENE_LIB_PATH, SCENE_LIB_PATH, _SCENE_SIGNATURES, ("binscene_version", SCENE_VERSION))
-    return _scenelib
-
-
-def chain_exported_symbols():
-    """Names every include/binchain.h entry point must resolve to."""
-    return sorted(_CHAIN_SIGNATURES)
-
-
-def chainlib():
-    """Load libbinchain.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _chainlib
-    if _chainlib is None:
-        _chainlib = _load(CHAIN_LIB_PATH, CHAIN_LIB_PATH, _CHAIN_SIGNATURES, ("binchain_version", CHAIN_VERSION))
-    return _chainlib
-
-
-def rate_exported_symbols():
-    """Names every include/binrate.h entry point must resolve to."""
-    return sorted(_RATE_SIGNATURES)
-
-
-def ratelib():
-    """Load libbinrate.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _ratelib
-    if _ratelib is None:
-        _ratelib = _load(RATE_LIB_PATH, RATE_LIB_PATH, _RATE_SIGNATURES, ("binrate_version", RATE_VERSION))
-    return _ratelib
-
-
-def score_exported_symbols():
-    """Names every include/binscore.h entry point must resolve to."""
-    return sorted(_SCORE_SIGNATURES)
-
-
-def scorelib():
-    """Load libbinscore.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _scorelib
-    if _scorelib is None:
-        _scorelib = _load(SCORE_LIB_PATH, SCORE_LIB_PATH, _SCORE_SIGNATURES, ("binscore_version", SCORE_VERSION))
-    return _scorelib
-
-
-def clip_exported_symbols():
-    """Names every include/binclip.h entry point must resolve to."""
-    return sorted(_CLIP_SIGNATURES)
-
-
-def cliplib():
-    """Load libbinclip.so (once).  Raises RuntimeError with the build hint when it is absent or of another version."""
-    global _cliplib
-    if _cliplib is None:
-        _cliplib = _load(CLIP_LIB_PATH, CLIP_LIB_PATH, _CLIP_SIGNATURES, ("binclip_version", CLIP_VERSION))
-    return _cliplib
+optlib = partial(library, "binopt")
+gradlib = partial(library, "bingrad")
+emalib = partial(library, "binema")
+enslib = partial(library, "binens")
+yuvlib = partial(library, "binyuv")
+scenelib = partial(library, "binscene")
+chainlib = partial(library, "binchain")
+ratelib = partial(library, "binrate")
+scorelib = partial(library, "binscore")
+cliplib = partial(library, "binclip")
 
 
 def check(rc, what):

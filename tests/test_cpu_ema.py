@@ -130,34 +130,13 @@ def test_walk_reference_bars_hold_a_plain_float32_run_and_refuse_a_lagging_one()
 
 # ------------------------------------------------------------------------------------------------ ABI bookkeeping
 def test_ema_library_header_and_binding_agree():
-    """libbinema.so is a library of its own beside the other three, whose interfaces do not change with it: its dynamic symbols are
-    exactly include/binema.h's declarations, the binding's and nothing else."""
-    from bin_amd import _lib, build
+    """What is binema's own beside the bookkeeping of test_cpu_libraries.py: the row, the codes and the limit, and what the header
+    says of inf / NaN and of the decay."""
+    from bin_amd import _lib
     hdr = _header()
-    want = ["binema_version", "binema_step"]
-    assert build.ema_abi_symbols() == want and build.EMA_SOURCES == ["binema_step.hip"]
-    assert set(_lib.ema_exported_symbols()) == set(want)
-    assert set(re.findall(r"\b(binema_[a-z0-9_]+)\s*\(", hdr)) == set(want)
-    assert os.path.basename(build.EMA_LIB_PATH) == "libbinema.so" and os.path.basename(build.EMA_HEADER) == "binema.h"
-    out = subprocess.run(["nm", "-D", "--defined-only", build.EMA_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()} == set(want)
-    assert not set(build.EMA_SOURCES) & (set(build.SOURCES) | set(build.OPT_SOURCES) | set(build.GRAD_SOURCES))
-    # none of the other three gains or loses anything
-    assert not any("binema" in n for n in build.abi_symbols() + build.opt_abi_symbols() + build.grad_abi_symbols())
-    assert not any("binema" in n for n in _lib.exported_symbols() + _lib.opt_exported_symbols() + _lib.grad_exported_symbols())
-    for other in ("binhip.h", "binopt.h", "bingrad.h"):
-        assert "binema" not in open(os.path.join(REPO, "include", other)).read().lower(), other
-    for path in (build.LIB_PATH, build.OPT_LIB_PATH, build.GRAD_LIB_PATH):
-        syms = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        assert "binema" not in syms, path
-    # every macro of the header carries the BINEMA_ prefix
-    assert all(m.startswith("BINEMA_") for m in re.findall(r"#\s*define\s+(\w+)", hdr))
     assert re.search(r"typedef struct BinEmaTensor \{\s*float\* e;\s*const float\* p;\s*int64_t numel;\s*\} BinEmaTensor;", hdr)
     assert C.sizeof(_lib.BinEmaTensor) == 24 and [f[0] for f in _lib.BinEmaTensor._fields_] == ["e", "p", "numel"]
     assert _lib.BinEmaTensor.p.offset == 8 and _lib.BinEmaTensor.numel.offset == 16
-    lib = _lib.emalib()
-    ver = int(re.search(r"#define\s+BINEMA_VERSION\s+(\d+)", hdr).group(1))
-    assert lib.binema_version() == ver == _lib.EMA_VERSION == 100
     for name, value in (("BINEMA_E_ARG", -1), ("BINEMA_E_SHAPE", -2)):
         assert int(re.search(rf"#define\s+{name}\s+\((-?\d+)\)", hdr).group(1)) == value
     assert int(re.search(r"#define\s+BINEMA_MAX_TENSORS\s+(\d+)", hdr).group(1)) == _lib.EMA_MAX_TENSORS == EC.EMA_MAX_TENSORS
@@ -262,7 +241,7 @@ def test_with_the_option_off_nothing_of_it_is_imported_or_loaded():
             "assert option.weight_ema({'train': {'lr_G': 1e-4}}, []) is None\n"
             "assert option.weight_ema({'train': {'ema_decay': 0}}, []) is None\n"
             "assert 'bin_amd.optim' not in sys.modules, 'bin_amd.optim imported'\n"
-            "assert _lib._emalib is None, 'libbinema.so loaded'\n"
+            "assert 'binema' not in _lib._loaded, 'libbinema.so loaded'\n"
             "print('clean')\n")
     out = subprocess.run([sys.executable, "-c", code], cwd=REPO, capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip() == "clean", out.stderr[-2000:]

@@ -106,26 +106,17 @@ def test_numpy_float32_restatement_stays_within_the_bar(tag):
 
 # ------------------------------------------------------------------------------------------------ ABI bookkeeping
 def test_optimizer_library_header_and_binding_agree():
-    """libbinopt.so is a library of its own beside libbinhip.so, whose interface (include/binhip.h: version, entry-point count) does
-    not change with it: its dynamic symbols are exactly include/binopt.h's declarations, the binding's and nothing else."""
-    import subprocess
-    from bin_amd import _lib, build
+    """What is binopt's own beside the bookkeeping of test_cpu_libraries.py: libbinhip.so's header knows nothing of Adam, the row
+    struct, the error code and the refusals."""
+    from bin_amd import _lib
     hdr = _header()
-    assert build.opt_abi_symbols() == ["binopt_version", "binopt_adam_step"] and build.OPT_SOURCES == ["binopt_adam.hip"]
-    assert set(_lib.opt_exported_symbols()) == set(build.opt_abi_symbols())
-    assert set(re.findall(r"\b(binopt_[a-z0-9_]+)\s*\(", hdr)) == set(build.opt_abi_symbols())
-    out = subprocess.run(["nm", "-D", "--defined-only", build.OPT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()} == set(build.opt_abi_symbols())
     assert "adam" not in open(os.path.join(REPO, "include", "binhip.h")).read().lower()
-    assert not set(build.OPT_SOURCES) & set(build.SOURCES) and not any("binopt" in n for n in build.abi_symbols())
     assert re.search(r"typedef struct BinAdamTensor \{\s*float\* p;\s*const float\* g;\s*float\* m;\s*float\* v;\s*int64_t numel;\s*"
                      r"float step_size;\s*float inv_sqrt_bc2;\s*\} BinAdamTensor;", hdr)
     assert C.sizeof(_lib.BinAdamTensor) == 48
     assert [f[0] for f in _lib.BinAdamTensor._fields_] == ["p", "g", "m", "v", "numel", "step_size", "inv_sqrt_bc2"]
     lib = _lib.optlib()
     assert lib.binopt_adam_step.restype is C.c_int and len(lib.binopt_adam_step.argtypes) == 7
-    ver = int(re.search(r"#define\s+BINOPT_VERSION\s+(\d+)", hdr).group(1))
-    assert lib.binopt_version() == ver == _lib.OPT_VERSION
     assert int(re.search(r"#define\s+BINOPT_E_ARG\s+\((-?\d+)\)", hdr).group(1)) == -1
     # the refusals come before any HIP call, so they run without a device
     table = (_lib.BinAdamTensor * 2)()
