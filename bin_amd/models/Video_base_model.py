@@ -22,7 +22,7 @@ from . import lr_scheduler, networks
 from .base_model import BaseModel, _direct_param_grads
 from .bin_model import FlatGradAllReduce, SingleProcessParallel, _get
 from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class, grad_guard, weight_ema
+from ..options.options import adam_class, grad_guard, micro_batch, weight_ema
 from ..utils import util
 
 logger = logging.getLogger("base")
@@ -34,6 +34,7 @@ class _CbPair(nn.Module):
     def __init__(self):
         super().__init__()
         self.cb = CharbonnierLoss()
+        self.reduction = self.cb.reduction
 
     def forward(self, x, y):
         return self.cb(x, y), None
@@ -87,6 +88,8 @@ class VideoBaseModel(BaseModel):
         self.grad_guard = grad_guard(opt, [p for _, p in trainable])
         # train.ema_decay (bin_amd extension): the average of every generator weight, started from the loaded ones; None when off
         self.weight_ema = weight_ema(opt, self.netG.module.parameters())
+        # train.micro_batch (bin_amd extension): samples per forward / backward inside optimize_parameters; None = the fed batch
+        self.micro_batch = micro_batch(opt)
         scheme = train_opt["lr_scheme"]
         if scheme == "MultiStepLR":
             sched = lr_scheduler.MultiStepLR_Restart(
@@ -132,14 +135,18 @@ class VideoBaseModel(BaseModel):
         ft = _get(self.opt["train"], "ft_tsa_only")
         if ft and step < ft:
             self.set_params_lr_zero()
+        chunks = self._micro_batch_chunks(self.var_L.size(0))
         self.optimizer_G.zero_grad()
         if self.grad_sync is not None:
             self.grad_sync.attach()
-        self.fake_H = self._net(self.var_L)
-        loss, parts = self._pix_loss()
-        l_pix = self.l_pix_w * loss
-        with _direct_param_grads(self.netG):       # weight gradients land in .grad straight from the kernels
-            l_pix.backward()
+        if len(chunks) > 1:                        # train.micro_batch: the same gradients from several smaller passes
+            l_pix, parts = self._accumulate_micro_batches(chunks)
+        else:
+            self.fake_H = self._net(self.var_L)
+            loss, parts = self._pix_loss()
+            l_pix = self.l_pix_w * loss
+            with _direct_param_grads(self.netG):   # weight gradients land in .grad straight from the kernels
+                l_pix.backward()
         if self.grad_sync is not None:
             self.grad_sync()
         if self.grad_guard is None or self.grad_guard.apply():     # a skipped step still counts as an iteration
@@ -153,6 +160,26 @@ class VideoBaseModel(BaseModel):
             self.log_dict["l_pix"], self.log_dict["ssim_loss"] = parts[0].item(), parts[1].item()
 
     optimize_parameters_without_schudlue = optimize_parameters      # the reference's second spelling of the same step
+
+    def _accumulate_micro_batches(self, chunks):
+        """bin_model._accumulate_micro_batches for the single-tensor surface: forward, loss and backward per chunk of `var_L` /
+        `real_H`, gradients accumulating; leaves `fake_H` as the whole batch's detached outputs and returns the whole batch's
+        `l_pix` and parts: the criterion over them and `real_H`, evaluated once without a graph."""
+        outs = []
+
+        def one(weight):
+            fake_H = self.fake_H = self._net(self.var_L)
+            l_pix = (self.l_pix_w * weight) * self._pix_loss()[0]
+            with _direct_param_grads(self.netG):
+                l_pix.backward()
+            outs.append(fake_H.detach())
+            self.fake_H = None
+
+        self._for_each_micro_batch(("var_L", "real_H"), chunks, one)
+        self.fake_H = torch.cat(outs, 0)
+        with torch.no_grad():
+            loss, parts = self._pix_loss()
+            return self.l_pix_w * loss, parts
 
     def get_loss(self):
         return self.l_pix_w * self._pix_loss()[0]

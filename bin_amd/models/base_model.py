@@ -76,6 +76,7 @@ class BaseModel:
         self.optimizers = []
         self.schedulers = []
         self.weight_ema = None       # train.ema_decay: the wrapper builds a bin_amd.optim.WeightEMA after load()
+        self.micro_batch = None      # train.micro_batch: samples per forward / backward of a training step; None = the whole batch
 
     # ---- interface stubs the concrete wrapper overrides (kept for API parity) ----------------------
     def feed_data(self, data):
@@ -98,6 +99,34 @@ class BaseModel:
 
     def load(self):
         pass
+
+    # ---- train.micro_batch (bin_amd extension): one optimizer step as several forward / backward passes -------------------
+    def _micro_batch_chunks(self, batch):
+        """The (start, n) chunks this step cuts its `batch` fed samples into: one, unless `train.micro_batch` is below the batch."""
+        from ..options.options import micro_batches
+        return micro_batches(batch, getattr(self, "micro_batch", None))
+
+    def _for_each_micro_batch(self, names, chunks, body):
+        """Run `body(weight)` once per chunk with the batch tensors `names` (attributes of self) narrowed to the chunk along N —
+        views, nothing is copied — and the data-parallel reducer held for every chunk but the last; `weight` is what the chunk's
+        loss is multiplied by so that the accumulated gradient is the whole batch's.  The whole-batch tensors are put back on
+        every exit."""
+        from ..options.options import micro_batch_weights
+        weights = micro_batch_weights(chunks, getattr(self.cri_pix, "reduction", None))
+        whole = {nm: getattr(self, nm) for nm in names}
+        sync = getattr(self, "grad_sync", None)
+        try:
+            for k, ((start, n), weight) in enumerate(zip(chunks, weights)):
+                if sync is not None:
+                    sync.hold(k + 1 < len(chunks))
+                for nm, t in whole.items():
+                    setattr(self, nm, t.narrow(0, start, n))
+                body(weight)
+        finally:
+            for nm, t in whole.items():
+                setattr(self, nm, t)
+            if sync is not None:
+                sync.hold(False)
 
     # ---- learning rate -----------------------------------------------------------------------------
     def _set_lr(self, lr_groups_l):

@@ -20,7 +20,7 @@ from . import lr_scheduler
 from . import networks
 from .base_model import BaseModel, unwrap, _direct_param_grads
 from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class, grad_guard, weight_ema
+from ..options.options import adam_class, grad_guard, micro_batch, weight_ema
 from ..utils import dist_util, util
 from ..utils.util import AverageMeter
 
@@ -59,7 +59,13 @@ class FlatGradAllReduce:
     the set's contiguous slice of the flat buffer is all-reduced on a SIDE stream, behind an event recorded on the
     compute stream, while the remaining backward kernels keep running.  `__call__` (after backward) reduces whatever
     is left (ConvLSTM cells; everything, if nothing was watched), joins the side stream and divides by the world size.
-    On CPU tensors (gloo tests) there are no streams: the same slices are reduced synchronously."""
+    On CPU tensors (gloo tests) there are no streams: the same slices are reduced synchronously.
+
+    Gradient accumulation (`train.micro_batch`): a weight set's count of owed backwards returns to zero at the end of EVERY
+    micro-batch's backward, but its slice is complete only in the last one.  The step says which one is running with `hold()`:
+    while held, a finished bucket is left alone (its slice still takes local gradients); `hold(False)` ahead of the last
+    micro-batch lets that backward start the early all-reduces as an unsplit step does.  Every slice is reduced once per step
+    and divided by the world size once, in `__call__`.  `attach()` starts every step not held."""
 
     def __init__(self, params):
         self.params = [p for p in params if p.requires_grad]
@@ -68,6 +74,7 @@ class FlatGradAllReduce:
         self.force_collective = False      # run the collectives even at world size 1 (tests of the RCCL path)
         self._buckets = []                 # (module, start, end) slices whose completion is signalled during backward
         self._reduced = []                 # slices already all-reduced in this step
+        self._held = False                 # hold(): more micro-batches of this step will still add into the buffer
         self._stream = None
 
     def _offsets(self):
@@ -113,8 +120,15 @@ class FlatGradAllReduce:
             p.grad = self.flat[o:o + p.numel()].view_as(p)
             o += p.numel()
         self._reduced = []
+        self._held = False
         for mod, _, _ in self._buckets:
             mod._bwd_pending = 0
+
+    def hold(self, on=True):
+        """`hold(True)`: the backward passes that follow belong to a micro-batch that is not the step's last, so a bucket that
+        signals completion is not reduced.  `hold(False)`: the next backward is the last one and reduces its buckets as they finish."""
+        self._held = bool(on)
+        return self
 
     def _active(self):
         import torch.distributed as dist
@@ -142,7 +156,7 @@ class FlatGradAllReduce:
 
     def _bucket_ready(self, idx):
         """Called from the backward pass when weight set `idx` has received its last contribution."""
-        if not self._active() or not self._views_intact():
+        if self._held or not self._active() or not self._views_intact():
             return
         _, start, end = self._buckets[idx]
         if (start, end) not in self._reduced:
@@ -155,6 +169,9 @@ class FlatGradAllReduce:
 
     def __call__(self):
         import torch.distributed as dist
+        if self._held:
+            raise RuntimeError("bin_amd: FlatGradAllReduce was called while held: hold(False) goes ahead of the step's last "
+                               "backward, and the reduce after it")
         if not self._active():
             return
         world = dist.get_world_size()
@@ -277,6 +294,8 @@ class bin_model(BaseModel):
             self.grad_guard = grad_guard(opt, [v for _, v in trainable])
             # train.ema_decay (bin_amd extension): the average of every generator weight, started from the loaded ones; None when off
             self.weight_ema = weight_ema(opt, unwrap(self.netG).parameters())
+            # train.micro_batch (bin_amd extension): samples per forward / backward inside optimize_parameters; None = the fed batch
+            self.micro_batch = micro_batch(opt)
 
             scheme = train_opt["lr_scheme"]
             if scheme == "MultiStepLR":
@@ -326,14 +345,18 @@ class bin_model(BaseModel):
         ft = _get(self.opt["train"], "ft_tsa_only")
         if ft and step < ft:
             self.set_params_lr_zero()
+        chunks = self._micro_batch_chunks(self.B1.size(0))
         self.optimizer_G.zero_grad()
         if self.grad_sync is not None:
             self.grad_sync.attach()
-        self.Ft_p = self.forward()
-        self.loss, self.loss_list = self.get_loss(ret=1)
-        l_pix = self.l_pix_w * self.loss
-        with _direct_param_grads(self.netG):       # weight gradients land in .grad straight from the kernels
-            l_pix.backward()
+        if len(chunks) > 1:                        # train.micro_batch: the same gradients from several smaller passes
+            self._accumulate_micro_batches(chunks)
+        else:
+            self.Ft_p = self.forward()
+            self.loss, self.loss_list = self.get_loss(ret=1)
+            l_pix = self.l_pix_w * self.loss
+            with _direct_param_grads(self.netG):   # weight gradients land in .grad straight from the kernels
+                l_pix.backward()
         if self.grad_sync is not None:
             self.grad_sync()
         # a skipped step (the guard found non-finite gradients or fp16 saturation) leaves the weights and the optimizer state as they
@@ -342,6 +365,30 @@ class bin_model(BaseModel):
             self.optimizer_G.step()
             if self.weight_ema is not None:        # only a step that was taken moves the average
                 self.weight_ema.update()
+
+    _BATCH_TENSORS = ("B1", "B3", "B5", "B7", "B9", "B11", "I1", "I2", "I3", "I4", "I5", "I6", "I7", "I8", "I9", "I10", "I11")
+
+    def _accumulate_micro_batches(self, chunks):
+        """Forward, loss and backward of each chunk in turn; every .grad accumulates (the RDN kernels add into it, the ConvLSTM
+        cells through autograd).  A chunk's graph and saved workspaces die with the locals of `one` before the next forward; what
+        is kept of it is its 14 outputs, detached.  Leaves `Ft_p`, `loss` and `loss_list` with the unsplit step's meaning: the whole
+        batch's outputs, and the criterion over them and the whole batch's targets, evaluated once without a graph — the numbers the
+        unsplit step reports, not sums of per-chunk roundings (a sum-reduced loss near 6e3 has an fp32 ulp of 5e-4)."""
+        outs = []
+
+        def one(weight):
+            Ft_p = self.forward()
+            loss, _ = self.get_loss(ret=1)
+            l_pix = (self.l_pix_w * weight) * loss
+            with _direct_param_grads(self.netG):
+                l_pix.backward()
+            outs.append([t.detach() for t in Ft_p])
+            self.Ft_p = None
+
+        self._for_each_micro_batch(self._BATCH_TENSORS, chunks, one)
+        self.Ft_p = tuple(torch.cat(ts, 0) for ts in zip(*outs))
+        with torch.no_grad():
+            self.loss, self.loss_list = self.get_loss(ret=1)
 
     def set_params_lr_zero(self):
         self.optimizers[0].param_groups[0]["lr"] = 0

@@ -95,6 +95,7 @@ class CharbonnierLoss(nn.Module):
     """mean(sqrt((x-y)^2 + eps)); eps is NOT squared, as in the reference."""
 
     kind = L.LOSS_CHARBONNIER
+    reduction = "mean"             # over the elements, so over the batch: what train.micro_batch weighs a chunk's loss by
 
     def __init__(self, eps=1e-6):
         super().__init__()
@@ -107,6 +108,7 @@ class CharbonnierLoss(nn.Module):
 class L1SumLoss(nn.Module):
     """sum |x - y|  (= nn.L1Loss(reduction='sum'), bin_model.py:55)."""
     kind, eps = L.LOSS_L1_SUM, 0.0
+    reduction = "sum"
 
     def forward(self, x, y):
         return _PixelLossFn.apply(x, y, L.LOSS_L1_SUM, 0.0)
@@ -115,6 +117,7 @@ class L1SumLoss(nn.Module):
 class L2SumLoss(nn.Module):
     """sum (x - y)^2  (= nn.MSELoss(reduction='sum'), bin_model.py:57)."""
     kind, eps = L.LOSS_L2_SUM, 0.0
+    reduction = "sum"
 
     def forward(self, x, y):
         return _PixelLossFn.apply(x, y, L.LOSS_L2_SUM, 0.0)

@@ -127,6 +127,47 @@ def weight_ema(opt, params):
     return WeightEMA(params, decay)
 
 
+def micro_batch(opt):
+    """`train.micro_batch` (bin_amd extension): how many samples of the fed batch run through one forward / backward inside an
+    optimizer step; the step accumulates the gradients of ceil(B / m) such passes and updates the weights once, so the activations
+    that are alive at a time are those of m samples, not of B.  Absent or null: off -> None (the whole batch in one pass); a positive
+    int.  Anything else raises."""
+    value = _train_value(opt, "micro_batch")
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f"train.micro_batch: {value!r} is not an integer")
+    if value < 1:
+        raise ValueError(f"train.micro_batch: {value!r} is not a positive integer")
+    return value
+
+
+def micro_batches(batch, m):
+    """The consecutive (start, n) chunks along N that a batch of `batch` samples is cut into with `train.micro_batch: m`:
+    ceil(batch / m) chunks of m, the last one smaller when m does not divide the batch; one chunk when m is None or >= batch."""
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"micro_batches: a batch of {batch} samples")
+    if m is None or m >= batch:
+        return [(0, batch)]
+    if m < 1:
+        raise ValueError(f"micro_batches: micro_batch {m!r} is not a positive integer")
+    return [(start, min(m, batch - start)) for start in range(0, batch, m)]
+
+
+REDUCTIONS = ("mean", "sum")
+
+
+def micro_batch_weights(chunks, reduction):
+    """What each chunk's loss is multiplied by so that the accumulated loss and gradient are the whole batch's: n_k / B under a
+    criterion that takes the mean over its elements, 1 under one that sums them."""
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"train.micro_batch: the criterion's reduction is {reduction!r}, not one of {', '.join(REDUCTIONS)}: "
+                         "how a chunk's loss adds up to the whole batch's is not known")
+    total = sum(n for _, n in chunks)
+    return [n / total if reduction == "mean" else 1.0 for _, n in chunks]
+
+
 def val_self_ensemble(opt):
     """`train.val_self_ensemble` (bin_amd extension): the self-ensemble group validation runs the generator under
     (bin_amd/ensemble.py: letters of `hvt`, `flipx4`, `x8`).  Absent, null, "" or `none`: off -> ""; otherwise the group's canonical
@@ -147,6 +188,7 @@ def parse(opt_path, is_train=True):
         grad_clip(opt)
         skip_bad_steps(opt)
         ema_decay(opt)
+        micro_batch(opt)
         val_self_ensemble(opt)
     if is_train and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the reference exports CUDA_VISIBLE_DEVICES from gpu_ids (torch on ROCm honours the same variable); under

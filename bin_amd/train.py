@@ -163,6 +163,9 @@ def main(argv=None, model_factory=None, probe=None):
     val_freq = int(opt["train"]["val_freq"] or 0)
     limit = min(total_iters, args.max_iter) if args.max_iter else total_iters
     per_rank_batch = opt["datasets"]["train"]["batch_size"] // world
+    micro = option.micro_batch(opt)                          # train.micro_batch: named once, the step itself reads the model's copy
+    if micro is not None and rank <= 0:
+        log.info("micro_batch %d: %d forward/backward passes per step", micro, len(option.micro_batches(max(per_rank_batch, 1), micro)))
     t_print = time.time()
     done = step >= limit
     for epoch in range(start_epoch, total_epochs + 1):

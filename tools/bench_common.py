@@ -48,9 +48,9 @@ def medians(ms):
     return {k: statistics.median(v) for k, v in ms.items()}
 
 
-def train_model(**train):
+def train_model(batch=8, size=256, **train):
     """The training model of bench.py's training leg (8 x 256^2, f16x3, `train.optimizer: hip`) with the given train options on top,
-    one synthetic batch fed."""
+    one synthetic batch fed (`batch` x `size`^2 where another shape is asked for)."""
     import tempfile
     import torch
     from bin_amd.models import create_model
@@ -66,7 +66,7 @@ def train_model(**train):
     m = create_model(opt)
     m.netG.module.load_state_dict(reference_state_dict(0), strict=True)
     g = torch.Generator().manual_seed(7)
-    B, S = 8, 256
+    B, S = batch, size
     m.feed_data({"LQs": torch.rand(B, 6, 3, S, S, generator=g), "GTenh": torch.rand(B, 6, 3, S, S, generator=g),
                  "GTinp": torch.rand(B, 5, 3, S, S, generator=g)})
     return m
