@@ -2,11 +2,10 @@
 // (bin_amd/data/video_dataset.py):
 //   yuv_to_bgr_kernel : the 8-bit planar YUV payloads of n frames (4:2:0 / 4:4:4, BT.601 / BT.709, limited / full) -> uint8 HWC BGR.
 // An HBM-bound element-wise kernel of binyuv.hip's shape: no LDS, no reuse beyond a lane's own registers.  A lane owns 4 consecutive
-// pixels of a row, of two rows at 4:2:0 (a chroma pair is loaded once); blockIdx.x grid-strides over (frame, row or row pair, column
-// group) items with 64-bit indices.  Data paths (binclip.h): VEC moves dwords / 16-bit chroma pairs in and one 12-byte store per row
-// out, the other path bytes; both fill the same registers and call the same per-pixel function (binyuv_common.h, shared with
-// binyuv.hip and binrate.hip), so they agree bit for bit with each other and with binyuv_to_frame.  All of a lane's loads come
-// before its first store.
+// pixels of a row, of two rows at 4:2:0; blockIdx.x grid-strides over (frame, row or row pair, column group) items with 64-bit
+// indices.  The load stage and the per-pixel function are binyuv_common.h's (load_yuv4_vec / load_yuv4_bytes, yuv_pixel:
+// yuv_to_frame_kernel's, so the bytes are those of binyuv_to_frame's values); what is written here is the three-level item split and
+// the store: VEC (binclip.h) one 12-byte store per row, the other path bytes.  All of a lane's loads come before its first store.
 #include "binyuv_common.h"
 #include "../../include/binclip.h"
 
@@ -52,33 +51,12 @@ yuv_to_bgr_kernel(const uint8_t* __restrict__ payloads, const int64_t payload_st
         const int64_t crow = (int64_t)j * cw;
         uint32_t yv[R][4], uv[4], vv[4];
         if (VEC) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const uint32_t w = *reinterpret_cast<const uint32_t*>(Yp + (int64_t)sy[r] * W + x0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) yv[r][i] = (w >> (8 * i)) & 255u;
-            }
-            if (C420) {
-                const uint32_t wu = *reinterpret_cast<const uint16_t*>(Up + crow + (x0 >> 1));
-                const uint32_t wv = *reinterpret_cast<const uint16_t*>(Vp + crow + (x0 >> 1));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { uv[i] = (wu >> (8 * (i >> 1))) & 255u; vv[i] = (wv >> (8 * (i >> 1))) & 255u; }
-            } else {
-                const uint32_t wu = *reinterpret_cast<const uint32_t*>(Up + crow + x0);
-                const uint32_t wv = *reinterpret_cast<const uint32_t*>(Vp + crow + x0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { uv[i] = (wu >> (8 * i)) & 255u; vv[i] = (wv >> (8 * i)) & 255u; }
-            }
+            load_yuv4_vec<C420, R>(Yp, Up, Vp, W, sy, crow, x0, yv, uv, vv);
         } else {
+            int sx[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int sx = x0 + i < W ? x0 + i : W - 1;
-#pragma unroll
-                for (int r = 0; r < R; ++r) yv[r][i] = Yp[(int64_t)sy[r] * W + sx];
-                const int cx = C420 ? sx >> 1 : sx;
-                uv[i] = Up[crow + cx];
-                vv[i] = Vp[crow + cx];
-            }
+            for (int i = 0; i < 4; ++i) sx[i] = x0 + i < W ? x0 + i : W - 1;
+            load_yuv4_bytes<C420, R>(Yp, Up, Vp, W, sy, crow, sx, yv, uv, vv);
         }
         uint32_t qb[R][4], qg[R][4], qr[R][4];
 #pragma unroll
@@ -116,7 +94,8 @@ int binclip_yuv_to_bgr(const uint8_t* payloads, int n, int64_t payload_stride, i
     if (int rc = coefficients(format, &k, nullptr)) return rc;
     if (!payloads || !bgr_hwc || n < 1 || H < 1 || W < 1 || payload_stride < 1) return BINCLIP_E_ARG;
     const bool c420 = format->chroma == BINYUV_CHROMA_420;
-    const int ch = c420 ? (int)(((int64_t)H + 1) / 2) : H, cw = c420 ? (int)(((int64_t)W + 1) / 2) : W;
+    int ch, cw;
+    chroma_size(c420, H, W, ch, cw);
     const uint64_t pixels = (uint64_t)H * W, c_bytes = (uint64_t)ch * cw, frame_bytes = pixels + 2 * c_bytes;   // below 2^64
     if ((uint64_t)payload_stride < frame_bytes) return BINCLIP_E_ARG;
     const uint64_t limit = (uint64_t)YUV_MAX_ELEMS;
@@ -128,10 +107,7 @@ int binclip_yuv_to_bgr(const uint8_t* payloads, int n, int64_t payload_stride, i
     const bool vec = W % 4 == 0 && payload_stride % 4 == 0 && aligned(payloads, 4) && aligned(bgr_hwc, 4);
     const int ng = (int)(((int64_t)W + 3) / 4);
     const int64_t items = (int64_t)n * ch * ng;
-    const dim3 grid = grid_for(items), block(YUV_THREADS);
-    hipStream_t s = (hipStream_t)stream;
     const auto kernel = vec ? (c420 ? yuv_to_bgr_kernel<true, true> : yuv_to_bgr_kernel<true, false>)
                             : (c420 ? yuv_to_bgr_kernel<false, true> : yuv_to_bgr_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, payloads, payload_stride, H, W, cw, (int64_t)c_bytes, ch, ng, items, k, bgr_hwc);
-    return (int)hipGetLastError();
+    return launch(kernel, grid_for(items), stream, payloads, payload_stride, H, W, cw, (int64_t)c_bytes, ch, ng, items, k, bgr_hwc);
 }

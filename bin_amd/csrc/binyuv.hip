@@ -3,10 +3,8 @@
 //   yuv_from_frame_kernel : the crop of an fp32 planar RGB frame -> 8-bit planar YUV, 4:2:0 chroma as the box mean of its block.
 // Both are HBM-bound element-wise kernels: no LDS, no reuse beyond a lane's own registers.  A lane owns 4 consecutive pixels of a
 // row, of two rows at 4:2:0 (a chroma pair is loaded once); blockIdx.x grid-strides over (row or row pair, column group) items with
-// 64-bit indices.  Data paths (binyuv.h): VEC moves dwords / 16-bit chroma pairs / float4s, the other path bytes and single floats;
-// both fill the same registers and call the same per-pixel functions (binyuv_common.h, shared with binrate.hip), so they agree bit
-// for bit.  The arithmetic is written with fmaf and the rounding intrinsics: nothing is left to contraction.  All of a lane's loads
-// come before its first store.
+// 64-bit indices.  The load and store stages, the per-pixel functions and the two data paths (binyuv.h) are binyuv_common.h's; what
+// is written here is each kernel's item geometry and the padded float4 store.  All of a lane's loads come before its first store.
 #include "binyuv_common.h"
 
 static_assert(sizeof(BinYuvFormat) == 12, "BinYuvFormat layout");
@@ -31,35 +29,14 @@ yuv_to_frame_kernel(const uint8_t* __restrict__ Yp, const uint8_t* __restrict__ 
         for (int r = 0; r < R; ++r) sy[r] = clampi(oy0 + r - pt, H - 1);
         const int64_t crow = (int64_t)(C420 ? sy[0] >> 1 : sy[0]) * cw;
         uint32_t yv[R][4], uv[4], vv[4];
-        if (VEC && ox0 >= pl && ox0 - pl < W) {                  // an interior group: pl, W multiples of 4, so all of it is
-            const int sx0 = ox0 - pl;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const uint32_t w = *reinterpret_cast<const uint32_t*>(Yp + (int64_t)sy[r] * W + sx0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) yv[r][i] = (w >> (8 * i)) & 255u;
-            }
-            if (C420) {
-                const uint32_t wu = *reinterpret_cast<const uint16_t*>(Up + crow + (sx0 >> 1));
-                const uint32_t wv = *reinterpret_cast<const uint16_t*>(Vp + crow + (sx0 >> 1));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { uv[i] = (wu >> (8 * (i >> 1))) & 255u; vv[i] = (wv >> (8 * (i >> 1))) & 255u; }
-            } else {
-                const uint32_t wu = *reinterpret_cast<const uint32_t*>(Up + crow + sx0);
-                const uint32_t wv = *reinterpret_cast<const uint32_t*>(Vp + crow + sx0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { uv[i] = (wu >> (8 * i)) & 255u; vv[i] = (wv >> (8 * i)) & 255u; }
-            }
+        // an interior group: pl, W multiples of 4, so all of it is
+        if (VEC && ox0 >= pl && ox0 - pl < W) {
+            load_yuv4_vec<C420, R>(Yp, Up, Vp, W, sy, crow, ox0 - pl, yv, uv, vv);
         } else {
+            int sx[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int sx = clampi(ox0 + i - pl, W - 1);
-#pragma unroll
-                for (int r = 0; r < R; ++r) yv[r][i] = Yp[(int64_t)sy[r] * W + sx];
-                const int cx = C420 ? sx >> 1 : sx;
-                uv[i] = Up[crow + cx];
-                vv[i] = Vp[crow + cx];
-            }
+            for (int i = 0; i < 4; ++i) sx[i] = clampi(ox0 + i - pl, W - 1);
+            load_yuv4_bytes<C420, R>(Yp, Up, Vp, W, sy, crow, sx, yv, uv, vv);
         }
         float cr[R][4], cg[R][4], cb[R][4];
 #pragma unroll
@@ -99,81 +76,13 @@ yuv_from_frame_kernel(const float* __restrict__ x, const int Hp, const int Wp, c
         split(item, ng, small, j, g);
         const int x0 = 4 * g, y0 = R * j;
         float cr[R][4], cg[R][4], cb[R][4];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int yy = y0 + r < H ? y0 + r : H - 1;
-            const float* p = x + (int64_t)(top + yy) * Wp + left;
-            if (VEC) {
-                const float4 a = *reinterpret_cast<const float4*>(p + x0);
-                const float4 b = *reinterpret_cast<const float4*>(p + plane + x0);
-                const float4 c = *reinterpret_cast<const float4*>(p + 2 * plane + x0);
-                cr[r][0] = a.x; cr[r][1] = a.y; cr[r][2] = a.z; cr[r][3] = a.w;
-                cg[r][0] = b.x; cg[r][1] = b.y; cg[r][2] = b.z; cg[r][3] = b.w;
-                cb[r][0] = c.x; cb[r][1] = c.y; cb[r][2] = c.z; cb[r][3] = c.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int xx = x0 + i < W ? x0 + i : W - 1;
-                    cr[r][i] = p[xx]; cg[r][i] = p[plane + xx]; cb[r][i] = p[2 * plane + xx];
-                }
-            }
-        }
+        load_rgb4<VEC, R>(x, plane, Wp, top, left, H, W, x0, y0, cr, cg, cb);
         float ly[R][4], pb[R][4], pr[R][4];
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int i = 0; i < 4; ++i) rgb_pixel(cr[r][i], cg[r][i], cb[r][i], k, ly[r][i], pb[r][i], pr[r][i]);
-        uint32_t qy[R][4], qu[4], qv[4];
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) qy[r][i] = quantise(ly[r][i], k.y_scale, k.y_off);
-        if (C420) {
-            const bool row1 = y0 + 1 < H;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const bool col1 = x0 + 2 * c + 1 < W;
-                qu[c] = quantise(block_mean(pb[0][2 * c], pb[0][2 * c + 1], pb[R - 1][2 * c], pb[R - 1][2 * c + 1], col1, row1), k.c_scale, 128.f);
-                qv[c] = quantise(block_mean(pr[0][2 * c], pr[0][2 * c + 1], pr[R - 1][2 * c], pr[R - 1][2 * c + 1], col1, row1), k.c_scale, 128.f);
-            }
-            qu[2] = qu[3] = qv[2] = qv[3] = 0;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { qu[i] = quantise(pb[0][i], k.c_scale, 128.f); qv[i] = quantise(pr[0][i], k.c_scale, 128.f); }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (y0 + r >= H) continue;
-            uint8_t* o = Yp + (int64_t)(y0 + r) * W + x0;
-            if (VEC) {
-                *reinterpret_cast<uint32_t*>(o) = pack4(qy[r]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (x0 + i < W) o[i] = (uint8_t)qy[r][i];
-            }
-        }
-        if (C420) {
-            const int64_t at = (int64_t)j * cw + 2 * g;
-            if (VEC) {
-                *reinterpret_cast<uint16_t*>(Up + at) = (uint16_t)(qu[0] | (qu[1] << 8));
-                *reinterpret_cast<uint16_t*>(Vp + at) = (uint16_t)(qv[0] | (qv[1] << 8));
-            } else {
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-                    if (x0 + 2 * c < W) { Up[at + c] = (uint8_t)qu[c]; Vp[at + c] = (uint8_t)qv[c]; }
-            }
-        } else {
-            const int64_t at = (int64_t)j * cw + x0;
-            if (VEC) {
-                *reinterpret_cast<uint32_t*>(Up + at) = pack4(qu);
-                *reinterpret_cast<uint32_t*>(Vp + at) = pack4(qv);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (x0 + i < W) { Up[at + i] = (uint8_t)qu[i]; Vp[at + i] = (uint8_t)qv[i]; }
-            }
-        }
+        store_yuv<VEC, C420, R>(ly, pb, pr, k, x0, y0, j, g, H, W, cw, Yp, Up, Vp);
     }
 }
 
@@ -188,42 +97,29 @@ int binyuv_to_frame(const uint8_t* y, const uint8_t* u, const uint8_t* v, int H,
     const int64_t Hp = (int64_t)H + pad_top + pad_bottom, Wp = (int64_t)W + pad_left + pad_right;
     if (Hp > INT32_MAX || Wp > INT32_MAX || 3 * Hp > YUV_MAX_ELEMS / Wp) return BINYUV_E_SHAPE;
     const bool c420 = format->chroma == BINYUV_CHROMA_420;
-    const int ch = c420 ? (H + 1) / 2 : H, cw = c420 ? (W + 1) / 2 : W;
+    int ch, cw;
+    chroma_size(c420, H, W, ch, cw);
     const uint64_t out_bytes = (uint64_t)(3 * Hp * Wp) * 4, c_bytes = (uint64_t)ch * cw;
     if (overlap(out_chw, out_bytes, y, (uint64_t)H * W) || overlap(out_chw, out_bytes, u, c_bytes) || overlap(out_chw, out_bytes, v, c_bytes))
         return BINYUV_E_ARG;
     const bool vec = W % 4 == 0 && pad_left % 4 == 0 && Wp % 4 == 0 && aligned(out_chw, 16) && aligned(y, 4) && aligned(u, 4) && aligned(v, 4);
     const int ng = (int)((Wp + 3) / 4);
-    const int64_t rows = c420 ? (Hp + (pad_top & 1) + 1) / 2 : Hp, items = rows * ng;
-    const dim3 grid = grid_for(items), block(YUV_THREADS);
-    hipStream_t s = (hipStream_t)stream;
+    const int64_t rows = c420 ? (Hp + (pad_top & 1) + 1) / 2 : Hp;
     const auto kernel = vec ? (c420 ? yuv_to_frame_kernel<true, true> : yuv_to_frame_kernel<true, false>)
                             : (c420 ? yuv_to_frame_kernel<false, true> : yuv_to_frame_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, y, u, v, H, W, cw, pad_left, pad_top, (int)Hp, (int)Wp, ng, items, k, out_chw);
-    return (int)hipGetLastError();
+    return launch(kernel, grid_for(rows * ng), stream, y, u, v, H, W, cw, pad_left, pad_top, (int)Hp, (int)Wp, ng, rows * ng, k, out_chw);
 }
 
 int binyuv_from_frame(const float* chw, int Hp, int Wp, int top, int left, int H, int W, const BinYuvFormat* format, uint8_t* y,
                       uint8_t* u, uint8_t* v, void* stream) {
     FromCoef k;
+    YuvOutGeometry q;
     if (int rc = coefficients(format, nullptr, &k)) return rc;
-    if (!chw || !y || !u || !v || !aligned(chw, 4)) return BINYUV_E_ARG;
-    if (Hp < 1 || Wp < 1 || H < 1 || W < 1 || top < 0 || left < 0) return BINYUV_E_ARG;
-    if ((int64_t)top + H > Hp || (int64_t)left + W > Wp) return BINYUV_E_ARG;
-    if (3 * (int64_t)Hp > YUV_MAX_ELEMS / Wp) return BINYUV_E_SHAPE;
-    const bool c420 = format->chroma == BINYUV_CHROMA_420;
-    const int ch = c420 ? (H + 1) / 2 : H, cw = c420 ? (W + 1) / 2 : W;
-    const uint64_t in_bytes = (uint64_t)3 * Hp * Wp * 4, y_bytes = (uint64_t)H * W, c_bytes = (uint64_t)ch * cw;
-    if (overlap(chw, in_bytes, y, y_bytes) || overlap(chw, in_bytes, u, c_bytes) || overlap(chw, in_bytes, v, c_bytes) ||
-        overlap(y, y_bytes, u, c_bytes) || overlap(y, y_bytes, v, c_bytes) || overlap(u, c_bytes, v, c_bytes))
-        return BINYUV_E_ARG;
-    const bool vec = W % 4 == 0 && Wp % 4 == 0 && left % 4 == 0 && aligned(chw, 16) && aligned(y, 4) && aligned(u, 4) && aligned(v, 4);
-    const int ng = (W + 3) / 4;
-    const int64_t items = (int64_t)ch * ng;
-    const dim3 grid = grid_for(items), block(YUV_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    const auto kernel = vec ? (c420 ? yuv_from_frame_kernel<true, true> : yuv_from_frame_kernel<true, false>)
-                            : (c420 ? yuv_from_frame_kernel<false, true> : yuv_from_frame_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, chw, Hp, Wp, top, left, H, W, cw, ng, items, k, y, u, v);
-    return (int)hipGetLastError();
+    if (!chw || !aligned(chw, 4)) return BINYUV_E_ARG;
+    if (int rc = yuv_out_geometry(Hp, Wp, top, left, H, W, format, y, u, v, &q)) return rc;
+    if (overlaps_planes(chw, q, y, u, v)) return BINYUV_E_ARG;
+    const bool vec = q.vec && aligned(chw, 16);
+    const auto kernel = vec ? (q.c420 ? yuv_from_frame_kernel<true, true> : yuv_from_frame_kernel<true, false>)
+                            : (q.c420 ? yuv_from_frame_kernel<false, true> : yuv_from_frame_kernel<false, false>);
+    return launch(kernel, grid_for(q.items), stream, chw, Hp, Wp, top, left, H, W, q.cw, q.ng, q.items, k, y, u, v);
 }

@@ -587,20 +587,31 @@ def yuv_to_frame(payload_u8, h, w, fmt, pads):
     return out
 
 
+def _crop_to_payload(name, frames, top, left, h, w, chroma, out):
+    """What frame_to_yuv and blend_to_yuv check and prepare alike: `frames` ([1,3,Hp,Wp] or [3,Hp,Wp], of one shape on one device) as
+    contiguous fp32 [3,Hp,Wp] tensors, the crop checked against them, and the payload (`out`, or a fresh one) with its plane addresses.
+    Returns (frames, Hp, Wp, out, (y, u, v))."""
+    _need_cuda(*frames)
+    count = "one [1,3,Hp,Wp] frame" if len(frames) == 1 else "two [1,3,Hp,Wp] frames"
+    for x in frames:
+        if x.dim() not in (3, 4) or x.numel() != 3 * x.shape[-2] * x.shape[-1]:
+            raise ValueError(f"bin_amd: {name} takes {count} (got {tuple(x.shape)})")
+    if any(x.shape[-2:] != frames[0].shape[-2:] or x.device != frames[0].device for x in frames):
+        raise ValueError(f"bin_amd: {name} takes {count} of one shape on one device (got {', '.join(str(tuple(x.shape)) for x in frames)})")
+    frames = [x.reshape(3, x.shape[-2], x.shape[-1]).contiguous().float() for x in frames]
+    hp, wp = frames[0].shape[1], frames[0].shape[2]
+    if h < 1 or w < 1 or top < 0 or left < 0 or top + h > hp or left + w > wp:
+        raise ValueError(f"bin_amd: crop ({top}, {left}, {h}, {w}) leaves the {hp}x{wp} frame")
+    if out is None:
+        out = torch.empty(yuv_frame_bytes(h, w, chroma)[0], dtype=torch.uint8, device=frames[0].device)
+    return frames, hp, wp, out, _yuv_planes(out, h, w, chroma)
+
+
 def frame_to_yuv(frame, top, left, h, w, fmt, out=None):
     """fp32 [1,3,Hp,Wp] (or [3,Hp,Wp]) RGB -> the Y4M payload of its crop (uint8 [frame_bytes], into `out` when given; `out` may
     also be a (y, u, v) triple of plane tensors).  Float all the way: one rounding, so yuv_to_frame -> frame_to_yuv is exact."""
     f = yuv_format(fmt)
-    _need_cuda(frame)
-    if frame.dim() not in (3, 4) or frame.numel() != 3 * frame.shape[-2] * frame.shape[-1]:
-        raise ValueError(f"bin_amd: frame_to_yuv takes one [1,3,Hp,Wp] frame (got {tuple(frame.shape)})")
-    x = frame.reshape(3, frame.shape[-2], frame.shape[-1]).contiguous().float()
-    hp, wp = x.shape[1], x.shape[2]
-    if h < 1 or w < 1 or top < 0 or left < 0 or top + h > hp or left + w > wp:
-        raise ValueError(f"bin_amd: crop ({top}, {left}, {h}, {w}) leaves the {hp}x{wp} frame")
-    if out is None:
-        out = torch.empty(yuv_frame_bytes(h, w, fmt[0])[0], dtype=torch.uint8, device=x.device)
-    y, u, v = _yuv_planes(out, h, w, fmt[0])
+    (x,), hp, wp, out, (y, u, v) = _crop_to_payload("frame_to_yuv", [frame], top, left, h, w, fmt[0], out)
     with on_device(x):
         L.check(L.yuvlib().binyuv_from_frame(_ptr(x), hp, wp, top, left, h, w, C.byref(f), y, u, v, _stream()), "frame_to_yuv")
     return out
@@ -639,26 +650,38 @@ def blend_to_yuv(a, b, w, top, left, h, w_, fmt, out=None):
     clamped values (include/binrate.h): one launch, frame_to_yuv's conversion and its `out`.  w == 0 and `b is a` give
     frame_to_yuv(a)'s bytes."""
     f = yuv_format(fmt)
-    _need_cuda(a, b)
-    for x in (a, b):
-        if x.dim() not in (3, 4) or x.numel() != 3 * x.shape[-2] * x.shape[-1]:
-            raise ValueError(f"bin_amd: blend_to_yuv takes two [1,3,Hp,Wp] frames (got {tuple(x.shape)})")
-    if a.shape[-2:] != b.shape[-2:] or a.device != b.device:
-        raise ValueError(f"bin_amd: blend_to_yuv takes two frames of one shape on one device (got {tuple(a.shape)}, {tuple(b.shape)})")
-    a, b = (x.reshape(3, x.shape[-2], x.shape[-1]).contiguous().float() for x in (a, b))
+    (a, b), hp, wp, out, (y, u, v) = _crop_to_payload("blend_to_yuv", [a, b], top, left, h, w_, fmt[0], out)
     w = float(w)
     if not 0.0 <= w < 1.0:
         raise ValueError(f"bin_amd: blend_to_yuv takes a weight in [0, 1) (got {w})")
-    hp, wp = a.shape[-2], a.shape[-1]
-    if h < 1 or w_ < 1 or top < 0 or left < 0 or top + h > hp or left + w_ > wp:
-        raise ValueError(f"bin_amd: crop ({top}, {left}, {h}, {w_}) leaves the {hp}x{wp} frame")
-    if out is None:
-        out = torch.empty(yuv_frame_bytes(h, w_, fmt[0])[0], dtype=torch.uint8, device=a.device)
-    y, u, v = _yuv_planes(out, h, w_, fmt[0])
     with on_device(a):
         L.check(L.ratelib().binrate_blend_to_yuv(_ptr(a), _ptr(b), w, hp, wp, top, left, h, w_, C.byref(f), y, u, v, _stream()),
                 "blend_to_yuv")
     return out
+
+
+# --------------------------------------------------------------------------------------------- records (scene and score glue)
+def _record_out(out, nbytes, what, inputs, device):
+    """The device record a kernel fills: `out` when it is one (a contiguous uint8 [nbytes] on `device`), a fresh one when None."""
+    if out is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() != nbytes or out.device != device:
+        raise ValueError(f"bin_amd: a {what} record is a contiguous uint8 tensor of [{nbytes}] bytes on the {inputs}' device "
+                         f"(got {out.dtype} {tuple(out.shape)})")
+    return out
+
+
+def _read_record(record, struct, what, reader):
+    """A downloaded record (a uint8 tensor or array of the struct's size, or its bytes) as the ctypes `struct`."""
+    import numpy as np
+    if isinstance(record, torch.Tensor):
+        if record.is_cuda:
+            raise ValueError(f"bin_amd: {reader} reads a downloaded record (record.cpu())")
+        record = record.numpy()
+    raw = bytes(memoryview(np.ascontiguousarray(record)).cast("B"))
+    if len(raw) != C.sizeof(struct):
+        raise ValueError(f"bin_amd: a {what} record has {C.sizeof(struct)} bytes (got {len(raw)})")
+    return struct.from_buffer_copy(raw)
 
 
 # --------------------------------------------------------------------------------------------- scene glue (libbinscene.so)
@@ -678,12 +701,7 @@ def luma_stats(cur_y, prev_y, h, w, out=None):
                              f"(got {t.dtype} {tuple(t.shape)})")
     if prev_y is not None and prev_y.device != cur_y.device:
         raise ValueError("bin_amd: luma_stats takes two planes of one device")
-    if out is None:
-        out = torch.empty(LUMA_RECORD_BYTES, dtype=torch.uint8, device=cur_y.device)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() != LUMA_RECORD_BYTES or \
-            out.device != cur_y.device:
-        raise ValueError(f"bin_amd: a luma record is a contiguous uint8 tensor of [{LUMA_RECORD_BYTES}] bytes on the planes' device "
-                         f"(got {out.dtype} {tuple(out.shape)})")
+    out = _record_out(out, LUMA_RECORD_BYTES, "luma", "planes", cur_y.device)
     with on_device(cur_y):
         L.check(L.scenelib().binscene_luma_stats(_ptr(cur_y), _ptr(prev_y), h, w, _ptr(out), _stream()), "luma_stats")
     return out
@@ -692,14 +710,7 @@ def luma_stats(cur_y, prev_y, h, w, out=None):
 def read_luma_record(record):
     """(sad: int, hist: np.ndarray[64] of int64) of a luma record on the host: a uint8 [264] tensor or array, or its bytes."""
     import numpy as np
-    if isinstance(record, torch.Tensor):
-        if record.is_cuda:
-            raise ValueError("bin_amd: read_luma_record reads a downloaded record (record.cpu())")
-        record = record.numpy()
-    raw = bytes(memoryview(np.ascontiguousarray(record)).cast("B"))
-    if len(raw) != LUMA_RECORD_BYTES:
-        raise ValueError(f"bin_amd: a luma record has {LUMA_RECORD_BYTES} bytes (got {len(raw)})")
-    rec = L.BinSceneRecord.from_buffer_copy(raw)
+    rec = _read_record(record, L.BinSceneRecord, "luma", "read_luma_record")
     return int(rec.sad), np.array(rec.hist, dtype=np.int64)
 
 
@@ -731,12 +742,7 @@ def payload_scores(a, b, h, w, chroma, ssim=True, out=None):
     if _G11_TAPS is None:
         from .utils.util import _gauss_taps
         _G11_TAPS = (C.c_double * 11)(*[float(v) for v in _gauss_taps()])
-    if out is None:
-        out = torch.empty(PLANE_SCORES_BYTES, dtype=torch.uint8, device=first.device)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() != PLANE_SCORES_BYTES or \
-            out.device != first.device:
-        raise ValueError(f"bin_amd: a score record is a contiguous uint8 tensor of [{PLANE_SCORES_BYTES}] bytes on the payloads' device "
-                         f"(got {out.dtype} {tuple(out.shape)})")
+    out = _record_out(out, PLANE_SCORES_BYTES, "score", "payloads", first.device)
     lib = L.scorelib()
     with on_device(first):
         nb = lib.binscore_workspace_bytes(h, w, chroma, flags)
@@ -754,15 +760,7 @@ def payload_scores(a, b, h, w, chroma, ssim=True, out=None):
 def read_plane_scores(record):
     """(sse_y, sse_u, sse_v, sad_y, sad_u, sad_v, ssim_g11, ssim_u7) of a score record on the host, six ints and two floats: a
     uint8 [64] tensor or array, or its bytes."""
-    import numpy as np
-    if isinstance(record, torch.Tensor):
-        if record.is_cuda:
-            raise ValueError("bin_amd: read_plane_scores reads a downloaded record (record.cpu())")
-        record = record.numpy()
-    raw = bytes(memoryview(np.ascontiguousarray(record)).cast("B"))
-    if len(raw) != PLANE_SCORES_BYTES:
-        raise ValueError(f"bin_amd: a score record has {PLANE_SCORES_BYTES} bytes (got {len(raw)})")
-    rec = L.BinPlaneScores.from_buffer_copy(raw)
+    rec = _read_record(record, L.BinPlaneScores, "score", "read_plane_scores")
     return tuple(int(v) for v in rec.sse) + tuple(int(v) for v in rec.sad) + (float(rec.ssim_g11), float(rec.ssim_u7))
 
 
