@@ -410,9 +410,14 @@ def rdb_tail(blk, cw3, cwl, out=None, store_o3=False):
     return out
 
 
-def conv2d_bwd_data(gy, dw, res=None, res_chunks=0, acc=None, mask=None, mask_from=0, out=None, y_unshuf=0):
+def conv2d_bwd_data(gy, dw, res=None, res_chunks=0, acc=None, mask=None, mask_from=0, out=None, y_unshuf=0, y_cpg=0,
+                    y_group_stride=0):
     """gx = [mask](conv_{W'}(gy) [+ res] [+ acc]) on chunk planes (binhip_conv2d_bwd_data).  `y_unshuf` > 0: the result leaves
-    through an inverse PixelShuffle(2) — 4 * y_unshuf planes at half resolution (BinConvDesc.reserved)."""
+    through an inverse PixelShuffle(2) — 4 * y_unshuf planes at half resolution (BinConvDesc.reserved).  `y_cpg` /
+    `y_group_stride` (fp16 elements): output chunk i goes to group i // y_cpg of `out`, which the caller then supplies (as are res,
+    acc and mask, which are indexed like the output)."""
+    if y_cpg > 0 and out is None:
+        raise ValueError("bin_amd: conv2d_bwd_data with y_cpg needs the grouped `out` buffer")
     _, n, h, w, _ = gy.hi.shape
     d = L.BinConvDesc()
     d.N, d.H, d.W, d.ksize = n, h, w, dw.ks
@@ -428,7 +433,7 @@ def conv2d_bwd_data(gy, dw, res=None, res_chunks=0, acc=None, mask=None, mask_fr
         C.byref(d), _ptr(gy.hi), _ptr(gy.lo), _ptr(dw.w_hi), _ptr(dw.w_lo), _ptr(dw.bias),
         _ptr(res.hi) if res is not None else z, _ptr(res.lo) if res is not None else z, res_chunks,
         _ptr(acc.hi) if acc is not None else z, _ptr(acc.lo) if acc is not None else z,
-        _ptr(mask.hi) if mask is not None else z, mask_from, 0, 0, _ptr(out.hi), _ptr(out.lo), _stream())
+        _ptr(mask.hi) if mask is not None else z, mask_from, int(y_cpg), int(y_group_stride), _ptr(out.hi), _ptr(out.lo), _stream())
     L.check(rc, "conv2d_bwd_data")
     return out
 

@@ -14,6 +14,9 @@ the next even sizes, 2 x 2 and 18 x 34, which keep the same properties.
 
 Operands are white noise from a seeded CPU generator, weights scaled by 1 / sqrt(fan in) so that outputs stay of order one.  Output
 buffers are zero-filled before the call, so padding the kernels leave alone cannot change a digest.
+
+white_noise_bits is two halves: white_noise_operands() draws the operands, call_library() makes the call on any operands of that
+form.  tests/conv_ref_cases.py holds the same calls — on these operands and on two exact families — to float64.
 """
 import hashlib
 from collections import namedtuple
@@ -110,14 +113,57 @@ def _plane_digests(cp, prefix=""):
     return d
 
 
-def white_noise_bits(case, nterms, shape):
-    """{buffer name: sha256} of every output buffer of one call of the library on the case's white noise (needs a GPU)."""
-    from bin_amd import _lib as L, ops
+def white_noise_operands(case, shape):
+    """The case's white noise as fp32 CPU tensors, drawn in the order the fixture was recorded with.  tail: blk, w3, b3, wl, bl;
+    bwd: w, gy, res, acc, mask (None where the case has none; each of chunks(cin) * 16 channels, as the planes are indexed like
+    the output); fwd: w, b, x (with its gap planes when x_cpg is set), imgs (a list), res."""
     n, h, w = shape
     o = case.opts
     g = _gen(case, shape)
     randn = lambda *s: torch.randn(*s, generator=g)
-    planes = lambda t: ops.nchw_to_planes(t.cuda(), nterms)
+    if case.kind == "tail":
+        return {"blk": randn(n, 224, h, w), "w3": randn(32, 192, 3, 3) / (192 * 9) ** 0.5, "b3": randn(32),
+                "wl": randn(96, 224, 1, 1) / 224 ** 0.5, "bl": randn(96)}
+    wt = randn(case.cout, case.cin, case.ks, case.ks) / (case.cin * case.ks * case.ks) ** 0.5
+    if case.kind == "bwd":
+        gy = randn(n, case.cout, h, w)
+        extra = lambda: randn(n, chunks(case.cin) * 16, h, w)
+        res = extra() if o.get("res") else None
+        acc = extra() if o.get("acc") else None
+        mask = extra() if "mask_from" in o else None
+        return {"w": wt, "gy": gy, "res": res, "acc": acc, "mask": mask}
+    b = randn(case.cout)
+    x = randn(n, x_buffer_channels(case), h, w)
+    epi = o.get("epilogue", "planes")
+    imgs, res = [], None
+    if epi in ("final", "subpix"):
+        up = 2 if epi == "subpix" else 1
+        imgs = [randn(n, case.cout // (up * up), up * h, up * w) for _ in range(o.get("nimg", 0))]
+    elif o.get("res"):
+        res = randn(n, case.cout, h, w)
+    return {"w": wt, "b": b, "x": x, "imgs": imgs, "res": res}
+
+
+def chunks(c):
+    return (c + 15) // 16
+
+
+def x_buffer_channels(case):
+    """Channels of a forward case's input buffer: cin, or with x_cpg groups of x_cpg planes with one unused plane between them —
+    chunk c is plane (c / x_cpg) * (x_cpg + 1) + c % x_cpg of the buffer."""
+    cpg = case.opts.get("x_cpg")
+    return (chunks(case.cin) // cpg) * (cpg + 1) * 16 if cpg else case.cin
+
+
+def call_library(case, nterms, shape, opnd, out=None, **bwd_args):
+    """One call of the library on the operands `opnd` (the dict white_noise_operands describes; needs a GPU).  Returns
+    (outputs, inputs): outputs {"y": CP} for plane stores, {"f32": tensor} for the FINAL epilogues, {"y": CP, "o3": CP} for the
+    tail that keeps o3; inputs the activation planes as uploaded, by operand name.  `out`: the output planes (default: zero-filled,
+    so that padding the kernels leave alone cannot change a digest); `bwd_args`: further arguments of ops.conv2d_bwd_data."""
+    from bin_amd import _lib as L, ops
+    n, h, w = shape
+    o = case.opts
+    planes = lambda t: None if t is None else ops.nchw_to_planes(t.cuda(), nterms)
     dev = torch.device("cuda")
 
     def zeros(nch, hh, ww, channels=None):
@@ -128,50 +174,57 @@ def white_noise_bits(case, nterms, shape):
         return cp
 
     if case.kind == "tail":
-        blk = planes(randn(n, 224, h, w))
-        cw3 = ops.ConvWeights((randn(32, 192, 3, 3) / (192 * 9) ** 0.5).cuda(), randn(32).cuda(), nterms=nterms)
-        cwl = ops.ConvWeights((randn(96, 224, 1, 1) / 224 ** 0.5).cuda(), randn(96).cuda(), nterms=nterms)
-        y = ops.rdb_tail(blk, cw3, cwl, out=zeros(6, h, w), store_o3=bool(o.get("store_o3")))
-        d = _plane_digests(y)
+        blk = planes(opnd["blk"])
+        cw3 = ops.ConvWeights(opnd["w3"].cuda(), opnd["b3"].cuda(), nterms=nterms)
+        cwl = ops.ConvWeights(opnd["wl"].cuda(), opnd["bl"].cuda(), nterms=nterms)
+        read = ops.CP(blk.hi.clone(), None if blk.lo is None else blk.lo.clone(), 224)      # (store_o3 writes planes 12, 13 of blk)
+        y = ops.rdb_tail(blk, cw3, cwl, out=out if out is not None else zeros(6, h, w), store_o3=bool(o.get("store_o3")))
+        outs = {"y": y}
         if o.get("store_o3"):
-            d.update(_plane_digests(blk.sub(12, 2), "o3_"))
-        return d
+            outs["o3"] = blk.sub(12, 2)
+        return outs, {"blk": read}
 
-    wt = randn(case.cout, case.cin, case.ks, case.ks) / (case.cin * case.ks * case.ks) ** 0.5
     if case.kind == "bwd":
-        gy = planes(randn(n, case.cout, h, w))
-        dw = ops.DgradWeights(wt.cuda(), nterms=nterms)
+        gy = planes(opnd["gy"])
+        dw = ops.DgradWeights(opnd["w"].cuda(), nterms=nterms)
         nch = ops.chunks(case.cin)
-        extra = lambda: planes(randn(n, nch * 16, h, w))
-        res = extra() if o.get("res") else None
-        acc = extra() if o.get("acc") else None
-        mask = extra() if "mask_from" in o else None
+        res, acc, mask = planes(opnd["res"]), planes(opnd["acc"]), planes(opnd["mask"])
         yu = o.get("y_unshuf", 0)
-        out = zeros(4 * yu, h // 2, w // 2) if yu else zeros(nch, h, w, case.cin)
+        if out is None:
+            out = zeros(4 * yu, h // 2, w // 2) if yu else zeros(nch, h, w, case.cin)
         y = ops.conv2d_bwd_data(gy, dw, res=res, res_chunks=o.get("res_chunks", 0), acc=acc, mask=mask, mask_from=o.get("mask_from", 0),
-                                out=out, y_unshuf=yu)
-        return _plane_digests(y)
+                                out=out, y_unshuf=yu, **bwd_args)
+        return {"y": y}, {"gy": gy, "res": res, "acc": acc, "mask": mask}
 
-    b = randn(case.cout)
     epi = o.get("epilogue", "planes")
-    cw = ops.ConvWeights(wt.cuda(), b.cuda(), nterms=nterms, shuffle=epi == "shuffle")
+    cw = ops.ConvWeights(opnd["w"].cuda(), opnd["b"].cuda(), nterms=nterms, shuffle=epi == "shuffle")
     kw = {}
     if o.get("x_cpg"):
-        # groups of x_cpg planes, one unused plane between them: chunk c is plane (c / x_cpg) * (x_cpg + 1) + c % x_cpg of the buffer
         cpg = o["x_cpg"]
-        ngroups = ops.chunks(case.cin) // cpg
-        x = planes(randn(n, ngroups * (cpg + 1) * 16, h, w))
         kw = dict(x_cpg=cpg, x_group_stride=(cpg + 1) * n * h * w * 16)
-    else:
-        x = planes(randn(n, case.cin, h, w))
+    x = planes(opnd["x"])
     if epi in ("final", "subpix"):
-        up = 2 if epi == "subpix" else 1
-        imgs = [randn(n, case.cout // (up * up), up * h, up * w).cuda() for _ in range(o.get("nimg", 0))]
+        imgs = [t.cuda() for t in opnd["imgs"]]
         y = ops.conv2d(x, cw, epilogue=L.EPI_FINAL if epi == "final" else L.EPI_FINAL_SUBPIX, images=imgs, **kw)
-        return {"f32": _sha(y.view(torch.int32))}
-    res = planes(randn(n, case.cout, h, w)) if o.get("res") else None
+        if epi == "subpix":                  # the same buffer as the kernel fills it: fp32 NCHW [N, cout / 4, 2 H, 2 W]
+            y = y.view(n, case.cout // 4, 2 * h, 2 * w)
+        return {"f32": y}, {"x": x}
+    res = planes(opnd["res"])
     if epi == "shuffle":
-        y = ops.conv2d(x, cw, epilogue=L.EPI_SHUFFLE, out=zeros(ops.chunks(case.cout // 4), 2 * h, 2 * w, case.cout // 4), **kw)
+        y = ops.conv2d(x, cw, epilogue=L.EPI_SHUFFLE,
+                       out=out if out is not None else zeros(ops.chunks(case.cout // 4), 2 * h, 2 * w, case.cout // 4), **kw)
     else:
-        y = ops.conv2d(x, cw, relu=bool(o.get("relu")), residual=res, out=zeros(ops.chunks(case.cout), h, w, case.cout), **kw)
-    return _plane_digests(y)
+        y = ops.conv2d(x, cw, relu=bool(o.get("relu")), residual=res,
+                       out=out if out is not None else zeros(ops.chunks(case.cout), h, w, case.cout), **kw)
+    return {"y": y}, {"x": x, "res": res}
+
+
+def white_noise_bits(case, nterms, shape):
+    """{buffer name: sha256} of every output buffer of one call of the library on the case's white noise (needs a GPU)."""
+    outs, _ = call_library(case, nterms, shape, white_noise_operands(case, shape))
+    if "f32" in outs:
+        return {"f32": _sha(outs["f32"].view(torch.int32))}
+    d = _plane_digests(outs["y"])
+    if "o3" in outs:
+        d.update(_plane_digests(outs["o3"], "o3_"))
+    return d
