@@ -155,11 +155,12 @@ def x_buffer_channels(case):
     return (chunks(case.cin) // cpg) * (cpg + 1) * 16 if cpg else case.cin
 
 
-def call_library(case, nterms, shape, opnd, out=None, **bwd_args):
+def call_library(case, nterms, shape, opnd, out=None, zero_fill=True, **bwd_args):
     """One call of the library on the operands `opnd` (the dict white_noise_operands describes; needs a GPU).  Returns
     (outputs, inputs): outputs {"y": CP} for plane stores, {"f32": tensor} for the FINAL epilogues, {"y": CP, "o3": CP} for the
     tail that keeps o3; inputs the activation planes as uploaded, by operand name.  `out`: the output planes (default: zero-filled,
-    so that padding the kernels leave alone cannot change a digest); `bwd_args`: further arguments of ops.conv2d_bwd_data."""
+    so that padding the kernels leave alone cannot change a digest; `zero_fill=False`: left to the wrapper, which allocates them
+    uninitialised — tests/test_gpu_poison.py); `bwd_args`: further arguments of ops.conv2d_bwd_data."""
     from bin_amd import _lib as L, ops
     n, h, w = shape
     o = case.opts
@@ -167,6 +168,8 @@ def call_library(case, nterms, shape, opnd, out=None, **bwd_args):
     dev = torch.device("cuda")
 
     def zeros(nch, hh, ww, channels=None):
+        if not zero_fill:
+            return None
         cp = ops.CP.empty(nch, n, hh, ww, nterms, dev, channels)
         cp.hi.zero_()
         if cp.lo is not None:
