@@ -281,6 +281,10 @@ int bh_prepare_conv(const BhConvCall& c, ConvKArgs* out) {
     if (d.nterms == 3 && (!c.x_lo || !c.w_lo)) return BINHIP_E_ARG;
     if (d.N <= 0 || d.H <= 0 || d.W <= 0 || d.cin_chunks <= 0) return BINHIP_E_SHAPE;
     if ((long long)d.N * d.H * d.W >= (1ll << 26)) return BINHIP_E_SHAPE;   // plane < 2 GiB (DMA OOB sentinel)
+    // the weights have cout_pad rows and och_limit below comes from cout: rows beyond the weights would be read and stored
+    if (d.cout <= 0 || d.cout > d.cout_pad) return BINHIP_E_SHAPE;
+    // a grouped tensor (cpg > 0) steps FORWARD from its base pointer; cpg <= 0 is one group and ignores the stride
+    if ((d.x_cpg > 0 && d.x_group_stride < 0) || (c.y_cpg > 0 && c.y_group_stride < 0)) return BINHIP_E_SHAPE;
     ConvKArgs a;
     a.x_hi = (const _Float16*)c.x_hi; a.x_lo = (const _Float16*)c.x_lo;
     a.w_hi = (const _Float16*)c.w_hi; a.w_lo = (const _Float16*)c.w_lo;
@@ -332,6 +336,8 @@ int bh_prepare_conv(const BhConvCall& c, ConvKArgs* out) {
     } else {
         return BINHIP_E_ARG;
     }
+    if (d.epilogue == F || d.epilogue == BINHIP_EPI_FINAL_SUBPIX)       // both FINAL epilogues read img[t][idx] for every t < n_images
+        for (int i = 0; i < d.n_images; ++i) if (!c.images[i]) return BINHIP_E_ARG;
     {   // 32-bit buffer offsets: write-through stores only while the whole output tensor stays below 4 GiB
         const int e = d.epilogue, cp = d.cout_pad;
         const long long out_chunks = (e == BINHIP_EPI_SHUFFLE) ? (a.cout / 4 + 15) / 16 : (cp + 15) / 16;
@@ -520,7 +526,7 @@ int binhip_conv2d_fwd(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
     c.r_hi = res_hi; c.r_lo = res_lo; c.y_hi = y_hi; c.y_lo = y_lo; c.y_f32 = y_f32;
     c.status = d->status;
     for (int i = 0; images && i < d->n_images && i < 5; ++i) c.images[i] = images[i];
-    if (d->epilogue == BINHIP_EPI_FINAL && d->n_images > 0 && !images) return BINHIP_E_ARG;
+    // (a FINAL epilogue without `images`, or with a null entry below n_images, is refused in bh_prepare_conv: c.images stays null)
     return bh_launch_conv(c, (hipStream_t)stream);
 }
 

@@ -199,6 +199,8 @@ int binhip_multi_loss_bwd(int kind, const BinLossTerms* t, int64_t numel, float 
                           void* stream) {
     if (!t || !g || !gloss || !kind_ok(kind)) return BINHIP_E_ARG;
     if (t->n_terms <= 0 || t->n_terms > BINHIP_LOSS_MAX_TERMS || g->n_out <= 0 || g->n_out > BINHIP_LOSS_MAX_TERMS) return BINHIP_E_ARG;
+    for (int i = 0; i < t->n_terms; ++i)                   // the kernel reads x[term] and y[term] of the terms the outputs name
+        if (!t->x[i] || !t->y[i]) return BINHIP_E_ARG;
     for (int k = 0; k < g->n_out; ++k)
         if (!g->out[k] || g->term_a[k] < 0 || g->term_a[k] >= t->n_terms || g->term_b[k] >= t->n_terms) return BINHIP_E_ARG;
     return loss_bwd(kind, *t, *g, numel, eps, gloss, (hipStream_t)stream);

@@ -46,7 +46,10 @@ inline int layer_conv(const Shp& sh, int d, int c) { return 2 + d * (sh.C + 1) +
 
 // the frame arguments every entry point takes: N, H, W positive, H and W even, 2 / 3 / 5 input frames
 bool frames_ok(int N, int H, int W, int n_inputs) {
-    return N > 0 && H > 0 && W > 0 && !(H & 1) && !(W & 1) && (n_inputs == 2 || n_inputs == 3 || n_inputs == 5);
+    // (N H W < 2^26: the limit of the full-resolution convolutions, checked here so that a frame they would refuse in the middle of
+    //  the launch sequence is refused before the first launch, and by the workspace queries)
+    return N > 0 && H > 0 && W > 0 && !(H & 1) && !(W & 1) && (n_inputs == 2 || n_inputs == 3 || n_inputs == 5) &&
+           (long long)N * H * W < (1ll << 26);
 }
 
 // A tensor of a workspace, in fp16 elements from the 256-byte aligned base: hi planes at `off`, lo planes (nterms == 3) at
@@ -133,6 +136,8 @@ int binhip_rdn_forward(const BinRdnPlan* p, const float* const* inputs, float* o
     const int N = p->N, H = p->H, W = p->W, nin = p->n_inputs, nt = p->nterms;
     if (!frames_ok(N, H, W, nin)) return BINHIP_E_SHAPE;
     if (nt != 1 && nt != 3) return BINHIP_E_ARG;
+    if (p->reserved & ~(BINHIP_PLAN_KEEP_ACTS | BINHIP_PLAN_NO_FUSE | BINHIP_PLAN_RDB3 | BINHIP_PLAN_FUSED_UPNET | BINHIP_PLAN_FUSED_UPNET_TRAIN |
+                        BINHIP_PLAN_UPNET_FOLD)) return BINHIP_E_ARG;      // an undefined flag bit
     if ((p->reserved & BINHIP_PLAN_UPNET_FOLD) && (nt != 3 || (p->reserved & BINHIP_PLAN_KEEP_ACTS) || !(p->reserved & BINHIP_PLAN_FUSED_UPNET)))
         return BINHIP_E_ARG;              // the folded slab exists for the fused UPNet of fp32-class inference only
     Shp sh;
@@ -353,12 +358,17 @@ int binhip_rdn_backward(const BinRdnBwdPlan* p, const void* saved, size_t saved_
     // sign of hi, which is the sign of hi + lo) at the offsets of the 3-term layout
     const int nt_saved = (p->reserved & BINHIP_BWD_SAVED_X3) ? 3 : nt;
     if (nt == 3 && (p->reserved & BINHIP_BWD_SAVED_X3)) return BINHIP_E_ARG;
+    if (p->reserved & ~(BINHIP_BWD_ACCUMULATE | BINHIP_BWD_SAVED_X3 | BINHIP_BWD_FUSED_UPNET)) return BINHIP_E_ARG;   // an undefined flag bit
     Shp sh;
     if (!resolve_shape(&p->shape, &sh)) return BINHIP_E_SHAPE;
     if (saved_bytes < binhip_rdn_workspace_bytes(N, H, W, nin, nt_saved, &p->shape)) return BINHIP_E_WORKSPACE;
     const Bws b = make_bws(N, H, W, nin, nt, sh);
     if (workspace_bytes < b.total_bytes) return BINHIP_E_WORKSPACE;
     for (int i = 0; i < sh.L; ++i) if (!p->wt_hi[i] || (nt == 3 && !p->wt_lo[i]) || !p->dw[i] || !p->db[i]) return BINHIP_E_ARG;
+    // BINHIP_BWD_FUSED_UPNET: slots L and L + 1 (checked with the rest, before the first launch)
+    if ((p->reserved & BINHIP_BWD_FUSED_UPNET) &&
+        (sh.L + 1 >= BINHIP_RDN_MAX_LAYERS || !p->wt_hi[sh.L] || (nt == 3 && !p->wt_lo[sh.L]) || !p->wt_hi[sh.L + 1] || !p->dw[sh.L] ||
+         !p->db[sh.L] || !p->dw[sh.L + 1] || !p->db[sh.L + 1])) return BINHIP_E_ARG;
     const int G0 = sh.G0, G = sh.G, C = sh.C, D = sh.D, c0 = sh.c0, cg = sh.cg, cb = sh.cb, LG = sh.L - 4;
 
     hipStream_t s = (hipStream_t)stream;
@@ -400,8 +410,6 @@ int binhip_rdn_backward(const BinRdnBwdPlan* p, const void* saved, size_t saved_
     // gsub: the pixel-unshuffled, scaled gradient with the ring zeroed — ONE half-resolution chunk where gout would be, lo one plane further
     const Planes gsub = {b.gout.off, P};
     if (fused_up) {
-        if (sh.L + 1 >= BINHIP_RDN_MAX_LAYERS || !p->wt_hi[sh.L] || (nt == 3 && !p->wt_lo[sh.L]) || !p->wt_hi[sh.L + 1] || !p->dw[sh.L] ||
-            !p->db[sh.L] || !p->dw[sh.L + 1] || !p->db[sh.L + 1]) return BINHIP_E_ARG;
         if ((rc = bh_upnet_gsub(gout, N, h, ww, sc, Gw.hi(gsub), Gw.lo(gsub), p->status, s))) return rc;
     } else if ((rc = binhip_nchw_to_planes_scaled(gout, N, 3, H, W, sc, Gw.hi(b.gout), Gw.lo(b.gout), p->status, stream))) return rc;
 

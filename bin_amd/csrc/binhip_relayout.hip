@@ -103,6 +103,7 @@ static int relayout_check(BinRelayoutItem& L) {
     const bool blocks_ok = L.cout_block > 0 && L.rows_pad % L.cout_block == 0 && L.cout_block % 32 == 0;
     if (L.kind == BINHIP_RELAYOUT_FWD || L.kind == BINHIP_RELAYOUT_DGRAD) {
         if (L.rows_pad % 32 || !blocks_ok) return BINHIP_E_SHAPE;
+        if ((L.ksize != 1 && L.ksize != 3 && L.ksize != 5) || L.cout <= 0 || L.cin <= 0) return BINHIP_E_SHAPE;
         // rows and K entries of the operator: (cout, cin) of a forward layer, swapped for its backward-data
         const bool fwd = L.kind == BINHIP_RELAYOUT_FWD;
         const int rows = fwd ? L.cout : L.cin, kdim = fwd ? L.cin : L.cout;
@@ -128,12 +129,14 @@ static int relayout_check(BinRelayoutItem& L) {
 extern "C" {
 
 size_t binhip_weights_bytes(int cout_pad, int cin_chunks, int ksize) {
+    if (cout_pad <= 0 || cin_chunks <= 0 || ksize <= 0) return 0;      // no such layout (a negative product would wrap to a huge size)
     return (size_t)cout_pad * cin_chunks * ksize * ksize * 32;
 }
 
 int binhip_dgrad_rows_pad(int ksize, int cin) {
     // rows of the backward-data conv = original input channels, padded to the kernel's cout granularity (the LFF
     // dgrad's 224 rows form ONE 224-row workgroup column, so its input — the 96-channel output gradient — is read once)
+    if (cin <= 0) return 0;
     return ((cin + 31) / 32) * 32;
 }
 

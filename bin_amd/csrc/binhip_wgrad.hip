@@ -911,6 +911,7 @@ int bh_wgrad_partials(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
     if ((long long)d->N * d->H * d->W >= (1ll << 26)) return BINHIP_E_SHAPE;
     if (cin <= 0 || cin > d->cin_chunks * 16) return BINHIP_E_SHAPE;
     if (shuffle_perm && d->cout % 4) return BINHIP_E_SHAPE;
+    if (d->x_cpg > 0 && d->x_group_stride < 0) return BINHIP_E_SHAPE;      // groups step forward from x (x_cpg <= 0: one group)
     const WgGeom g = wg_geom(d->ksize, d->N, d->H, d->W, d->cin_chunks, d->cout, cus());
     if (workspace_bytes < wg_workspace_bytes(g)) return BINHIP_E_WORKSPACE;
     float* part = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);

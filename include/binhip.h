@@ -97,7 +97,7 @@ typedef struct BinConvDesc {
     int32_t N, H, W;          /* input batch / height / width (output same, 2x for SHUFFLE)      */
     int32_t ksize;            /* 1, 3 or 5                                                       */
     int32_t cin_chunks;       /* number of 16-channel input chunks (zero-padded channels allowed) */
-    int32_t cout;             /* real output channels                                            */
+    int32_t cout;             /* real output channels, 1 .. cout_pad (else BINHIP_E_SHAPE)       */
     int32_t cout_pad;         /* weight rows, multiple of 32: bin_stage4 32 / 96 / 224 / 256 / 1152; other RDN shapes any */
                               /* multiple of 32 up to 256 (forward) / 5120 (backward-data rows, D G0)                 */
     int32_t nterms;           /* 1 or 3                                                          */
@@ -105,8 +105,12 @@ typedef struct BinConvDesc {
     int32_t relu;             /* apply ReLU (PLANES only)                                        */
     int32_t x_cpg;            /* input chunks per group; chunk i lives at                        */
     int64_t x_group_stride;   /*   x + (i / x_cpg) * x_group_stride + (i % x_cpg) * N*H*W*16     */
-                              /*   (elements). x_cpg <= 0: one group.                             */
-    int32_t n_images;         /* FINAL: number of fp32 NCHW images averaged into the output      */
+                              /*   (elements). x_cpg <= 0: one group (ungrouped), x_group_stride  */
+                              /*   is then ignored; x_cpg > 0 needs x_group_stride >= 0 (else     */
+                              /*   BINHIP_E_SHAPE): groups step forward from x                    */
+    int32_t n_images;         /* FINAL / FINAL_SUBPIX: number of fp32 NCHW images averaged into the output, 0 .. 5; `images` */
+                              /*   and each of its first n_images entries must then be non-null (else BINHIP_E_ARG); FINAL   */
+                              /*   takes cout <= 4; ignored by the other epilogues                                          */
     int32_t reserved;         /* binhip_conv2d_bwd_data only: y_unshuf > 0 = store the result through an  */
                               /*   inverse PixelShuffle(2): full-resolution pixel (Y, X), chunk c goes to    */
                               /*   plane (2 (Y & 1) + (X & 1)) * y_unshuf + c at (Y / 2, X / 2) of a tensor  */
@@ -135,7 +139,10 @@ BINHIP_API int binhip_conv_cout_block(int ksize, int cout_pad, int nterms);
 /* OIHW fp32 -> kernel layout fp16 [cout_pad/cb][cin_chunks][k*k][cb][16] (+lo), 16-byte slots
  * XOR-swizzled for conflict-free ds_read_b128; input channels >= cin and rows >= cout are zero.
  * shuffle_perm != 0 reorders output rows co' = (co%4)*(cout/4) + co/4 so PixelShuffle becomes a
- * plain plane store.  bias_out: fp32 [cout_pad] (same row order, zero padded).  w_lo may be NULL. */
+ * plain plane store.  bias_out: fp32 [cout_pad] (same row order, zero padded).  w_lo may be NULL.
+ * Domain (both relayouts and their batch items; else BINHIP_E_SHAPE): ksize 1, 3 or 5; cout, cin >= 1; the operator's rows <= the
+ * plane's rows and its K <= 16 cin_chunks; cout_block a multiple of 32 that divides the rows.  binhip_weights_bytes is 0 when an
+ * argument is not positive, binhip_dgrad_rows_pad is 0 for cin <= 0.                                  */
 BINHIP_API int binhip_weights_relayout(const float* w_oihw, const float* bias, int cout, int cin, int ksize,
                             int cout_pad, int cin_chunks, int cout_block, int shuffle_perm,
                             void* w_hi, void* w_lo, float* bias_out, void* stream);
@@ -178,7 +185,12 @@ BINHIP_API int binhip_conv2d_fwd(const BinConvDesc* d,
  *   acc   — running gradient of the dense block input being accumulated; may alias gx (in place)
  *   mask  — saved forward activation planes: output chunks >= mask_from are zeroed where it is <= 0
  *           (ReLU backward, RDN.py:142), applied when the last contribution to that chunk lands
- *   y_cpg / y_group_stride — output chunk grouping (GFF.0 dgrad scatters to the 12 block buffers)     */
+ *   y_cpg / y_group_stride — output chunk grouping (GFF.0 dgrad scatters to the 12 block buffers)
+ * Domain: d->epilogue must be BINHIP_EPI_PLANES; cout <= cout_pad as for the forward.  res_chunks <= 0, or beyond the output's
+ * chunk count, = the residual applies to every chunk; mask_from <= 0 = the mask applies to every chunk, beyond the chunk count = to
+ * none (only the ceil(cout / 16) chunks that exist are ever loaded or stored).  y_cpg <= 0: one group, y_group_stride ignored;
+ * 1 <= y_cpg <= 128 with y_group_stride >= 0 (elements; else BINHIP_E_SHAPE): output chunk c goes to
+ * gx + (c / y_cpg) * y_group_stride + (c % y_cpg) * N*H*W*16, and acc is read at the same offsets.                     */
 BINHIP_API int binhip_dgrad_rows_pad(int ksize, int cin);   /* rows_pad the library expects for a layer's dgrad weights */
 BINHIP_API int binhip_weights_relayout_dgrad(const float* w_oihw, int cout, int cin, int ksize, int rows_pad,
                                   int cin_chunks, int cout_block, int shuffle_perm, void* w_hi, void* w_lo,
@@ -225,7 +237,8 @@ BINHIP_API int binhip_frame_to_u8(const float* chw, int Hp, int Wp, int top, int
 
 /* ---- ConvLSTM cell (RDN.py:50-95): gates = conv3x3(cat(x,h)) 6->12, i,j,f,o = chunk(4);
  * c' = c*sigmoid(f+forget_bias) + sigmoid(i)*tanh(j); h' = tanh(c')*sigmoid(o).  fp32 NCHW.
- * c_prev/h_prev may both be NULL (zero state, RDN.py:57-68).                                      */
+ * c_prev/h_prev may both be NULL (zero state, RDN.py:57-68); one without the other is BINHIP_E_ARG.
+ * c_new may be NULL (not stored).                                                                */
 BINHIP_API int binhip_convlstm_fwd(const float* x, const float* c_prev, const float* h_prev,
                         const float* w /*[12,6,3,3]*/, const float* b /*[12]*/, float forget_bias,
                         int N, int H, int W, float* c_new, float* h_new, void* stream);
@@ -274,7 +287,8 @@ BINHIP_API int binhip_multi_loss_fwd(int kind, const BinLossTerms* t, int64_t nu
                           float* loss, void* stream);
 /* d loss / d tensor for up to BINHIP_LOSS_MAX_TERMS distinct tensors in one launch: out[k] = gloss / T * sum over the (at most
  * two) terms that contain tensor k of sign * criterion'(x[term] - y[term]) (sign +1 where the tensor is the term's x, -1 where
- * it is its y; term_b[k] = -1: one term only).                                                                           */
+ * it is its y; term_b[k] = -1, or any negative value: one term only).  x and y of EVERY term below n_terms must be non-null, as
+ * in the forward, and 0 <= term_a[k] < n_terms, term_b[k] < n_terms, out[k] non-null for k < n_out (else BINHIP_E_ARG).            */
 typedef struct {
     float* out[BINHIP_LOSS_MAX_TERMS];
     int32_t term_a[BINHIP_LOSS_MAX_TERMS], term_b[BINHIP_LOSS_MAX_TERMS];
@@ -310,6 +324,8 @@ BINHIP_API int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* 
                                   /* where UPNet.2's zero padding of the INTERMEDIATE differs from padding the input, is           */
                                   /* recomputed exactly by a second small launch.  Same function as the two-layer form up to fp32  */
                                   /* summation order; bin_amd/rdn_plan.py builds the operands (RdnWeights.ensure_fused_upnet).     */
+                                  /* With the flag set and one of these slot pointers NULL the call is still valid: it runs the    */
+                                  /* two-layer form from the UPNet.0 / UPNet.2 slots, which are required in every case.            */
 #define BINHIP_PLAN_FUSED_UPNET_TRAIN 16 /* with KEEP_ACTS: the fused UPNet in the TRAINING forward too (needs the slots of          */
                                         /* BINHIP_PLAN_FUSED_UPNET); its backward is BINHIP_BWD_FUSED_UPNET                          */
 #define BINHIP_PLAN_UPNET_FOLD 32 /* with _FUSED_UPNET, nterms 3, without KEEP_ACTS (any other combination: BINHIP_E_ARG): the main  */
@@ -337,7 +353,10 @@ typedef struct BinRdnPlan {
     struct BinhipProfiler* profiler;       /* optional live kernel timing (below) or NULL         */
 } BinRdnPlan;
 /* The fused dense-block tail and the three-phase launch exist for the bin_stage4 shape only; other shapes run conv C-1 and
- * the LFF as two launches (what BINHIP_PLAN_NO_FUSE does for bin_stage4) — same values.                                 */
+ * the LFF as two launches (what BINHIP_PLAN_NO_FUSE does for bin_stage4) — same values.
+ * Domain of both plans, checked before the first launch: N, H, W >= 1 with H, W even and N H W < 2^26 (else BINHIP_E_SHAPE, and
+ * the workspace queries return 0); a `reserved` bit that is not a BINHIP_PLAN_* (BINHIP_BWD_*) flag is BINHIP_E_ARG; every
+ * pointer of every layer the shape has, and of slots L, L + 1 where a flag asks for them in the backward, non-null.    */
 
 BINHIP_API size_t binhip_rdn_workspace_bytes(int N, int H, int W, int n_inputs, int nterms, const BinRdnShape* shape /* NULL = bin_stage4 */);
 /* Where the activations of a call live inside its workspace (the caller owns it, and with BINHIP_PLAN_KEEP_ACTS it is
@@ -360,7 +379,9 @@ BINHIP_API int binhip_rdn_forward(const BinRdnPlan* plan, const float* const* in
  * pixel index with LDS transpose reads; deterministic two-stage reduction.  d describes the FORWARD conv
  * (N,H,W, ksize, cin_chunks, cout, nterms, x_cpg/x_group_stride).  The result is multiplied by
  * inv_scale[0] (device scalar, may be NULL) and written (or added, accumulate != 0) to OIHW fp32.
- * shuffle_perm != 0: gY's channels are in UPNet.0's PixelShuffle-permuted order.                      */
+ * shuffle_perm != 0: gY's channels are in UPNet.0's PixelShuffle-permuted order (cout % 4 == 0).
+ * 1 <= cin <= 16 cin_chunks; x_cpg / x_group_stride as in BinConvDesc (x_cpg <= 0: ungrouped; a grouped x needs
+ * x_group_stride >= 0, else BINHIP_E_SHAPE); dbias and inv_scale may be NULL.                         */
 BINHIP_API size_t binhip_wgrad_workspace_bytes(int ksize, int N, int H, int W, int cin_chunks, int cout);
 BINHIP_API int binhip_conv2d_bwd_weight(const BinConvDesc* d, const void* x_hi, const void* x_lo,
                              const void* gy_hi, const void* gy_lo, const float* inv_scale,
