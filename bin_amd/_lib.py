@@ -1,10 +1,11 @@
 """ctypes binding of the eleven shared objects of bin_amd/build.py's table (libbinhip.so and the ten small libraries beside it,
-include/<name>.h), each loaded on first use.  The product path has NO fallback: if a library is missing, of another version or a
+include/<name>.h) and of those of its EXTRA_LIBRARIES (libbinexpose.so), each loaded on first use.  The product path has NO fallback: if a library is missing, of another version or a
 call fails this raises, it never routes to PyTorch/CPU code."""
 import ctypes as C
 import os
 from functools import partial
 
+from . import build as _build
 from .build import BY_NAME, LIB_PATH  # noqa: F401  (LIB_PATH: callers read libbinhip.so's path as _lib.LIB_PATH)
 
 RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold RDN_MAX_LAYERS
@@ -314,6 +315,16 @@ _CLIP_SIGNATURES = {
     "binclip_yuv_to_bgr": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(BinYuvFormat), C.c_void_p, C.c_void_p]),
 }
 
+# libbinexpose.so (include/binexpose.h): the exposure library, loaded on first use
+EXPOSE_VERSION = 100                   # BINEXPOSE_VERSION
+EXPOSE_E_ARG, EXPOSE_E_SHAPE = -1, -2  # BINEXPOSE_E_ARG, BINEXPOSE_E_SHAPE
+EXPOSE_ONE, EXPOSE_TABLE = (1 << 24) - 1, 256   # BINEXPOSE_ONE, BINEXPOSE_TABLE
+_EXPOSE_SIGNATURES = {
+    "binexpose_version": (C.c_int, []),
+    "binexpose_check_curve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "binexpose_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
@@ -323,20 +334,26 @@ _LIBRARIES = {"binhip": (_SIGNATURES, None), "binopt": (_OPT_SIGNATURES, OPT_VER
               "binscene": (_SCENE_SIGNATURES, SCENE_VERSION), "binchain": (_CHAIN_SIGNATURES, CHAIN_VERSION),
               "binrate": (_RATE_SIGNATURES, RATE_VERSION), "binscore": (_SCORE_SIGNATURES, SCORE_VERSION),
               "binclip": (_CLIP_SIGNATURES, CLIP_VERSION)}
+# the same for the rows of build.EXTRA_LIBRARIES
+_EXTRA_LIBRARIES = {"binexpose": (_EXPOSE_SIGNATURES, EXPOSE_VERSION)}
 _loaded = {}                    # name -> the CDLL, once library(name) has loaded it
+
+
+def _entry(name):
+    return _LIBRARIES[name] if name in _LIBRARIES else _EXTRA_LIBRARIES[name]
 
 
 def exported_symbols(name="binhip"):
     """Names every include/<name>.h entry point must resolve to (checked by the CPU test-suite)."""
-    return sorted(_LIBRARIES[name][0])
+    return sorted(_entry(name)[0])
 
 
 def library(name):
     """Load lib<name>.so (once) and type its entry points.  Raises RuntimeError with the build hint when it is absent, and when
     its <name>_version() is not the value this binding is for."""
     if name not in _loaded:
-        signatures, version = _LIBRARIES[name]
-        built = path = BY_NAME[name].path
+        signatures, version = _entry(name)
+        built = path = _build.row(name).path
         if name == "binhip":        # BIN_AMD_LIB: developer knob: the timeline side build, another commit's library
             path = os.environ.get("BIN_AMD_LIB", built)
         if not os.path.exists(path):
@@ -369,6 +386,7 @@ chainlib = partial(library, "binchain")
 ratelib = partial(library, "binrate")
 scorelib = partial(library, "binscore")
 cliplib = partial(library, "binclip")
+exposelib = partial(library, "binexpose")
 
 
 def check(rc, what):

@@ -14,10 +14,12 @@ CSRC = os.path.join(HERE, "csrc")
 
 class Library(NamedTuple):
     """One shared object: bin_amd/csrc/lib<name>.so, made from `sources`, exporting exactly what include/<name>.h declares
-    <NAME>_API.  Each is a library of its own, so that no other library's interface changes with it."""
+    <NAME>_API.  Each is a library of its own, so that no other library's interface changes with it.  `subdir`: the folder under
+    bin_amd/csrc/ that holds its sources and receives what is built from them (the core table's rows have none)."""
     name: str
     sources: list
     purpose: str
+    subdir: str = ""
 
     @property
     def header(self):
@@ -25,7 +27,7 @@ class Library(NamedTuple):
 
     @property
     def path(self):
-        return os.path.join(CSRC, f"lib{self.name}.so")
+        return os.path.join(CSRC, self.subdir, f"lib{self.name}.so")
 
 
 # every shared object, in build order: what drives the compile, the version script, the link and the binding (bin_amd/_lib.py)
@@ -50,6 +52,13 @@ LIBRARIES = (
             "clips: the Y4M payloads of a clip -> the uint8 BGR frames of the device frame cache (dataset mode BIN_video)"),
 )
 BY_NAME = {lib.name: lib for lib in LIBRARIES}
+# the libraries beside the core table: the same rows, built, linked and bound by the same machinery, their sources one folder down
+EXTRA_LIBRARIES = (
+    Library("binexpose", ["binexpose.hip"],
+            "exposures: the training batches with blurry inputs averaged in linear light, with sensor noise (blur_gamma, blur_noise)",
+            "extra"),
+)
+EXTRA_BY_NAME = {lib.name: lib for lib in EXTRA_LIBRARIES}
 SOURCES, HEADER, LIB_PATH = BY_NAME["binhip"].sources, BY_NAME["binhip"].header, BY_NAME["binhip"].path
 
 
@@ -62,35 +71,42 @@ def _declared(header, macro, prefix):
 
 def abi_symbols(name="binhip"):
     """The entry points include/<name>.h declares (every <NAME>_API declaration), in header order."""
-    return _declared(BY_NAME[name].header, name.upper() + "_API", name)
+    return _declared(row(name).header, name.upper() + "_API", name)
+
+
+def row(name):
+    """The Library row of `name`, of either table."""
+    return BY_NAME[name] if name in BY_NAME else EXTRA_BY_NAME[name]
 
 
 def _stale():
-    libs = [lib.path for lib in LIBRARIES]
+    rows = LIBRARIES + EXTRA_LIBRARIES
+    libs = [lib.path for lib in rows]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    deps += [lib.header for lib in LIBRARIES]
+    dirs = [CSRC] + sorted({os.path.join(CSRC, lib.subdir) for lib in rows if lib.subdir})
+    deps = [os.path.join(d, f) for d in dirs for f in os.listdir(d) if f.endswith((".hip", ".h"))]
+    deps += [lib.header for lib in rows]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_plan(defines=(), out=None):
-    """What build_library(defines=, out=) runs, without running it: the compile commands (one hipcc per source), and per library
-    to link its (version-script path, exported names, link command)."""
+def build_plan(defines=(), out=None, table=LIBRARIES):
+    """What build_library(defines=, out=) runs for the rows of `table`, without running it: the compile commands (one hipcc per
+    source), and per library to link its (version-script path, exported names, link command)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = CSRC if out is None else os.path.dirname(os.path.abspath(out))
     tag = "" if out is None else "." + os.path.splitext(os.path.basename(out))[0]
-    libraries = [(lib, lib.path) for lib in LIBRARIES] if out is None else [(BY_NAME["binhip"], out)]
+    libraries = [(lib, lib.path) for lib in table] if out is None else [(BY_NAME["binhip"], out)]
     compiles, links = [], []
     for lib, path in libraries:
-        objs = [os.path.join(objdir, src.replace(".hip", tag + ".o")) for src in lib.sources]
+        objs = [os.path.join(objdir, lib.subdir, src.replace(".hip", tag + ".o")) for src in lib.sources]
         for src, obj in zip(lib.sources, objs):
             compiles.append([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"] +
-                            [f"-D{d}" for d in defines] + ["-c", os.path.join(CSRC, src), "-o", obj])
+                            [f"-D{d}" for d in defines] + ["-c", os.path.join(CSRC, lib.subdir, src), "-o", obj])
         # Dynamic symbols = exactly the entry points the library's header declares (sources are compiled -fvisibility=hidden; the
         # version script also makes the host-side kernel handles hipcc emits with default visibility local).
-        vmap = os.path.join(objdir, "binhip_exports" + tag + ".map" if lib.name == "binhip" else f"binhip_exports.{lib.name}.map")
+        vmap = os.path.join(objdir, lib.subdir, "binhip_exports" + tag + ".map" if lib.name == "binhip" else f"binhip_exports.{lib.name}.map")
         names = abi_symbols(lib.name)
         if lib.name == "binhip" and any(d.startswith("BINHIP_TIMELINE") for d in defines):
             names.append("binhip_set_timeline")
@@ -100,15 +116,21 @@ def build_plan(defines=(), out=None):
     return compiles, links
 
 
-def build_library(force=False, verbose=True, defines=(), out=None):
-    """Compile every HIP source for gfx950 into every library in the table (bin_amd/csrc/lib<name>.so).
+def build_library(force=False, verbose=True, defines=(), out=None, table=None):
+    """Compile every HIP source for gfx950 into every library of `table`: of both tables, LIBRARIES and EXTRA_LIBRARIES, when none
+    is given (bin_amd/csrc/lib<name>.so, bin_amd/csrc/extra/lib<name>.so).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain): libbinhip.so alone, under another name.  The
     sources are compiled in parallel (one hipcc per file)."""
     if out is None and not force and not _stale():
         return LIB_PATH
-    compiles, links = build_plan(defines, out)
+    tables = [table] if table is not None else [LIBRARIES] if out is not None else [LIBRARIES, EXTRA_LIBRARIES]
+    compiles, links = [], []
+    for rows in tables:
+        c, l = build_plan(defines, out, rows)
+        compiles += c
+        links += l
     os.makedirs(CSRC if out is None else os.path.dirname(os.path.abspath(out)), exist_ok=True)
     procs = []
     for cmd in compiles:

@@ -11,7 +11,8 @@ bin_amd extension, option `blur_window` (an odd exposure 1 .. 33 in sharp frames
 the window list is built from <root>/<mode>/ alone by that script's rule (make_sharp_window_list) and every blurry frame is
 synthesised when it is loaded, as the script's truncated mean of the sharp frames around it (blur_average) — no <mode>_blur,
 no <mode>_list.  On the host that costs 6 x L extra PNG decodes per sample; the device cache (device_cache.py), which averages
-inside its gather launch, is the intended way to train with it.
+inside its gather launch, is the intended way to train with it.  With `blur_gamma` (and `blur_noise`) beside it the frames of an
+exposure are averaged in linear light, with sensor noise, instead (exposure.py; ops.gather_windows_exposed on the device).
 
 NOTE the reference's `_make_dataset_deep_long_` falls off its end without returning (BIN_dataset.py:283-287), so
 `BINDataset(opt)` raises there; this class implements what that code computes up to that point (the window list,
@@ -103,6 +104,14 @@ def blur_average(frames_u8):
     return (a.sum(axis=0, dtype=np.uint32) // np.uint32(a.shape[0])).astype(np.uint8)
 
 
+def exposure_options(opt, blur_window):
+    """exposure.parse_options of a dataset's options; None, without importing that module, when both are absent."""
+    if opt.get("blur_gamma") is None and opt.get("blur_noise") is None:
+        return None
+    from . import exposure
+    return exposure.parse_options(opt, blur_window)
+
+
 def frame_number(path):
     return int(os.path.basename(path)[:-4])
 
@@ -174,20 +183,36 @@ def draw_window_aug(input_frame_size=(3, 128, 256), data_aug=True, src_size=(SRC
     return reverse, y0, x0, flip
 
 
-def load_window(window, input_frame_size=(3, 128, 256), data_aug=True, blur_window=None):
+def load_window(window, input_frame_size=(3, 128, 256), data_aug=True, blur_window=None, exposure=None, train=True, index=0):
     """Read the 17 frames of one window with the draws of draw_window_aug.  Returns ([B1..B11], [I1..I11], [I2..I10], key)
     as float32 HWC BGR crops.  With `blur_window` (parse_blur_window) the window is one of make_sharp_window_list and its
-    blurry frames are averaged from the sharp files, after draw_blur_half's draw."""
+    blurry frames are averaged from the sharp files, after draw_blur_half's draw.  With `exposure` (exposure.parse_options)
+    beside it they are exposures in linear light: the sample's key is drawn next (exposure.sample_key; `train` and the
+    window's `index` decide it), and each exposure is made from the cropped and flipped frames, because its noise is tied to
+    output coordinates."""
     blurry, sharp, mid, key = window
     reverse, y0, x0, flip = draw_window_aug(input_frame_size, data_aug)
     if reverse:
         blurry, sharp, mid = blurry[::-1], sharp[::-1], mid[::-1]
+    _, ch, cw = input_frame_size
+
+    def cut(f):
+        f = f[y0:y0 + ch, x0:x0 + cw, :]
+        return np.fliplr(f) if flip else f
+
     if blur_window is None:
         frames = [util.read_img(p) for p in list(blurry) + list(sharp) + list(mid)]
-    else:
+    elif exposure is None:
         h = draw_blur_half(blur_window)
         frames = [read_blurry(p, h) for p in blurry] + [util.read_img(p) for p in list(sharp) + list(mid)]
-    _, ch, cw = input_frame_size
+    else:
+        from . import exposure as X
+        h = draw_blur_half(blur_window)
+        k = X.sample_key(exposure, train, index)
+        exposed = [X.expose_average([cut(util.imread_u8(q)[:, :, :3]) for q in exposure_paths(p, h)], exposure.tables, k, slot)
+                   for slot, p in enumerate(blurry)]
+        frames = [e.astype(np.float32) / 255. for e in exposed] + [cut(util.read_img(p)) for p in list(sharp) + list(mid)]
+        return frames[:6], frames[6:12], frames[12:], key
     frames = [f[y0:y0 + ch, x0:x0 + cw, :] for f in frames]
     if flip:
         frames = [np.fliplr(f) for f in frames]
@@ -206,6 +231,8 @@ class BINDataset(data.Dataset):
             self.all_paths, _ = make_window_list(self.LQ_root, mode=opt["name"])
         else:
             self.all_paths, _ = make_sharp_window_list(self.LQ_root, mode=opt["name"], blur_window=self.blur_window)
+        self.exposure = exposure_options(opt, self.blur_window)
+        self.train = opt.get("phase", "train") == "train"
 
     def __len__(self):
         return len(self.all_paths)
@@ -220,6 +247,7 @@ class BINDataset(data.Dataset):
         return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2))).float()
 
     def __getitem__(self, index):
-        LQs, GTenh, GTinp, key = load_window(self.all_paths[index], self.input_frame_size, blur_window=self.blur_window)
+        LQs, GTenh, GTinp, key = load_window(self.all_paths[index], self.input_frame_size, blur_window=self.blur_window,
+                                             exposure=self.exposure, train=self.train, index=index)
         return {"LQs": self._to_tensor(LQs), "GTenh": self._to_tensor(GTenh), "GTinp": self._to_tensor(GTinp),
                 "key": key}

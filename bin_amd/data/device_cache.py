@@ -11,7 +11,8 @@ bit.
 
 With the dataset option `blur_window` the arena holds sharp frames only, each clip's consecutively in file order, and the six
 blurry inputs of a window are averaged from them inside the launch (ops.gather_windows_blur), with the exposure of each
-sample in the table."""
+sample in the table.  With `blur_gamma` / `blur_noise` beside it (exposure.py) the launch is ops.gather_windows_exposed: the frames
+of an exposure are averaged in linear light, with sensor noise, and the table also carries each sample's key."""
 import concurrent.futures as cf
 import logging
 import os
@@ -127,23 +128,26 @@ class DeviceFrameCache:
                 done[k % 2].record()
             torch.cuda.current_stream().synchronize()
 
-    def table(self, windows, draws, halves=None):
+    def table(self, windows, draws, halves=None, keys=None):
         """window_table of these windows against this arena."""
-        return window_table(windows, draws, self.index, halves)
+        return window_table(windows, draws, self.index, halves, keys)
 
 
-def window_table(windows, draws, index, halves=None):
+def window_table(windows, draws, index, halves=None, keys=None):
     """int32 [len(windows), 17 + 3] rows of binhip_gather_windows: the arena ids (`index`: path -> id) of each window's frames
     in slot order, a reversed window's in reverse order, then y0, x0, flip.  `draws`: one (reverse, y0, x0, flip) per window
     (draw_window_aug).  With `halves` (one half range h per window, draw_blur_half) the rows are binhip_gather_windows_blur's:
-    [len(windows), 17 + 4], h last, the blurry ids being those of the centre sharp frames."""
-    extra = 3 if halves is None else 4
+    [len(windows), 17 + 4], h last, the blurry ids being those of the centre sharp frames.  With `keys` as well (one (k0, k1) per
+    window, exposure.sample_key) they are binexpose_gather's: [len(windows), 17 + 6], the 32 bits of k0 and k1 last."""
+    extra = 3 if halves is None else 4 if keys is None else 6
     rows = np.empty((len(windows), N_SLOTS + extra), dtype=np.int32)
     for r, (win, (reverse, y0, x0, flip)) in enumerate(zip(windows, draws)):
         rows[r, :N_SLOTS] = [index[p] for p in window_slots(win, reverse)]
         rows[r, N_SLOTS:N_SLOTS + 3] = (y0, x0, int(flip))
     if halves is not None:
         rows[:, N_SLOTS + 3] = halves
+    if keys is not None:
+        rows[:, N_SLOTS + 4:] = np.array(keys, dtype=np.uint32).reshape(-1, 2).view(np.int32)
     return rows
 
 
@@ -158,6 +162,7 @@ class DeviceWindowLoader:
         self.dataset, self.batch, self.sampler = dataset, int(batch), sampler
         self.crop = tuple(dataset.input_frame_size)
         self.blur_window = getattr(dataset, "blur_window", None)
+        self.exposure, self.train = getattr(dataset, "exposure", None), getattr(dataset, "train", True)
         blur_half = None if self.blur_window is None else blur_half_max(self.blur_window)
         from_clips = getattr(dataset, "make_device_cache", None)   # mode BIN_video (video_dataset.py): the frames come from its clips
         if cache is None:
@@ -186,10 +191,17 @@ class DeviceWindowLoader:
             if self.blur_window is None:
                 draws = [draw_window_aug(self.crop, src_size=self.src_size) for _ in windows]
                 out = ops.gather_windows(self.cache.frames, self.cache.table(windows, draws), (ch, cw))
-            else:                                            # per sample: the four draws, then the exposure's (load_window's order)
+            elif self.exposure is None:                      # per sample: the four draws, then the exposure's (load_window's order)
                 both = [(draw_window_aug(self.crop, src_size=self.src_size), draw_blur_half(self.blur_window)) for _ in windows]
                 table = self.cache.table(windows, [d for d, _ in both], [h for _, h in both])
                 out = ops.gather_windows_blur(self.cache.frames, table, (ch, cw), N_BLUR, self.cache.clip_ranges)
+            else:                                            # ... then the key's, when there is noise (exposure.sample_key)
+                from .exposure import sample_key
+                three = [(draw_window_aug(self.crop, src_size=self.src_size), draw_blur_half(self.blur_window),
+                          sample_key(self.exposure, self.train, i)) for i in idx]
+                table = self.cache.table(windows, [d for d, _, _ in three], [h for _, h, _ in three], [k for _, _, k in three])
+                out = ops.gather_windows_exposed(self.cache.frames, table, (ch, cw), N_BLUR, ops.exposure_curve(*self.exposure),
+                                                 self.cache.clip_ranges)
             yield {"LQs": out[0:6].transpose(0, 1), "GTenh": out[6:12].transpose(0, 1), "GTinp": out[12:17].transpose(0, 1),
                    "key": [w[3] for w in windows]}
 

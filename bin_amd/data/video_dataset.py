@@ -6,7 +6,7 @@ stream of n frames gives the windows and keys a folder of 00001.png .. n.png giv
 `<clip.y4m>/<NNNNN>.png`, which keeps window_slots, frame_number and the cache's index as they are.  The blurry inputs are
 synthesised from the sharp frames (`blur_window`, required), so the only loader is the device one (device_cache.py): the arena
 (VideoFrameCache) is filled from the payloads by ops.yuv_to_bgr (libbinclip.so), nothing of a frame is converted on the host, and
-every batch is the one ops.gather_windows_blur launch of the folder path."""
+every batch is the one ops.gather_windows_blur launch of the folder path (ops.gather_windows_exposed with `blur_gamma`)."""
 import math
 import os
 import queue
@@ -17,7 +17,7 @@ import torch
 import torch.utils.data as data
 
 from .. import ops, video
-from .BIN_dataset import BLUR_FIRST_CENTRE, BLUR_STEP, NUM_WIN_PER_BUNCH, blur_half_max, parse_blur_window
+from .BIN_dataset import BLUR_FIRST_CENTRE, BLUR_STEP, NUM_WIN_PER_BUNCH, blur_half_max, exposure_options, parse_blur_window
 from .device_cache import CHUNK_BYTES, DeviceFrameCache
 
 NO_HOST_LOADER = ("mode BIN_video: there is no host loader for video clips; the batches are cut out of the device frame cache: "
@@ -80,6 +80,8 @@ class VideoClipDataset(data.Dataset):
         if self.blur_window is None:
             raise ValueError("mode BIN_video: `blur_window` is required: the clips hold sharp frames only, the blurry inputs are "
                              "averaged from them")
+        self.exposure = exposure_options(opt, self.blur_window)   # blur_gamma, blur_noise: exposures in linear light (exposure.py)
+        self.train = opt.get("phase", "train") == "train"
         if opt.get("dataroot_video") is None:
             raise ValueError("mode BIN_video: `dataroot_video` (a folder of *.y4m clips, or a list of files) is required")
         matrix, rng = opt.get("yuv_matrix") or "auto", opt.get("yuv_range") or "auto"

@@ -974,6 +974,94 @@ def gather_windows_blur(frames_u8, table_host, crop, n_blur, clip_ranges=None):
     return out
 
 
+_curve_dev = {}                                          # (the 768 words as bytes, device) -> their device copy
+
+
+def exposure_curve(gamma, noise=None):
+    """The curve of the dataset options `blur_gamma` and `blur_noise` (bin_amd/data/exposure.py): uint32 [3, 256] on the HOST,
+    LIN, MID and SIG of include/binexpose.h, built once per (gamma, noise) and accepted by binexpose_check_curve.  `gamma`: a
+    number 1.0 .. 2.4 or "srgb"; `noise`: None or (read, shot).  gather_windows_exposed uploads it once per device."""
+    from .data import exposure as X
+    gamma, noise = X.parse_blur_gamma(gamma), X.parse_blur_noise(noise)
+    if gamma is None:
+        raise ValueError("exposure_curve: a gamma (a number 1.0 .. 2.4 or \"srgb\") is required")
+    return _exposure_curve(gamma, noise)
+
+
+@functools.lru_cache(maxsize=None)
+def _exposure_curve(gamma, noise):
+    from .data import exposure as X
+    tab = _checked_curve(X.curve_tables(gamma, noise))
+    tab.setflags(write=False)
+    return tab
+
+
+def _checked_curve(curve):
+    import numpy as np
+    tab = np.ascontiguousarray(curve, dtype=np.uint32)
+    if tab.shape != (3, L.EXPOSE_TABLE):
+        raise ValueError(f"exposure curve: uint32 [3, {L.EXPOSE_TABLE}] tables (LIN, MID, SIG), got {tab.shape}")
+    if L.exposelib().binexpose_check_curve(*(tab[i].ctypes.data for i in range(3))) != 0:
+        raise ValueError("exposure curve: the tables break a validity rule of include/binexpose.h (binexpose_check_curve)")
+    return tab
+
+
+def gather_windows_exposed(frames_u8, table_host, crop, n_blur, curve, clip_ranges=None):
+    """gather_windows_blur with the first `n_blur` slots synthesised as a camera exposure (binexpose_gather, libbinexpose.so): the
+    mean of the 2h + 1 arena frames around the slot's id in linear light, sensor noise added there, re-encoded to a code; the
+    arithmetic is specified in include/binexpose.h.  `table_host`: int32 [n, n_slots + 6] on the HOST, a gather_windows_blur row
+    followed by the sample's key words k0, k1 (their 32 bits); `curve`: exposure_curve's tables.  Checked here (the kernel only
+    clamps): everything gather_windows_blur checks, and a curve not seen before by binexpose_check_curve.  Returns fp32
+    [n_slots, n, 3, ch, cw]."""
+    import numpy as np
+    _need_cuda(frames_u8)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise ValueError(f"gather_windows_exposed: frames must be a contiguous uint8 [n_frames, H, W, 3] tensor, got "
+                         f"{frames_u8.dtype} {tuple(frames_u8.shape)}")
+    nf, h, w, _ = frames_u8.shape
+    ch, cw = (int(v) for v in crop)
+    tab = np.ascontiguousarray(table_host.numpy() if torch.is_tensor(table_host) else table_host, dtype=np.int32)
+    if tab.ndim != 2 or tab.shape[0] < 1 or not 1 <= tab.shape[1] - 6 <= GATHER_MAX_SLOTS:
+        raise ValueError(f"gather_windows_exposed: table must be [n, n_slots + 6] with 1 <= n_slots <= {GATHER_MAX_SLOTS}, "
+                         f"got {tab.shape}")
+    n, n_slots, n_blur = tab.shape[0], tab.shape[1] - 6, int(n_blur)
+    if not 0 <= n_blur <= n_slots:
+        raise ValueError(f"gather_windows_exposed: n_blur {n_blur} outside [0, {n_slots}]")
+    if not (0 < ch <= h and 0 < cw <= w):
+        raise ValueError(f"gather_windows_exposed: crop {ch}x{cw} does not fit {h}x{w} frames")
+    ids, y0, x0, flip, half = (tab[:, :n_slots], tab[:, n_slots], tab[:, n_slots + 1], tab[:, n_slots + 2],
+                               tab[:, n_slots + 3])
+    if ids.min() < 0 or ids.max() >= nf:
+        raise ValueError(f"gather_windows_exposed: frame id outside [0, {nf})")
+    if y0.min() < 0 or y0.max() > h - ch or x0.min() < 0 or x0.max() > w - cw:
+        raise ValueError(f"gather_windows_exposed: crop offset outside the {h}x{w} frame for a {ch}x{cw} crop")
+    if ((flip != 0) & (flip != 1)).any():
+        raise ValueError("gather_windows_exposed: flip must be 0 or 1")
+    if half.min() < 0 or half.max() > GATHER_MAX_HALF:
+        raise ValueError(f"gather_windows_exposed: h outside [0, {GATHER_MAX_HALF}]")
+    if n_blur:
+        lo, hi = ids[:, :n_blur] - half[:, None], ids[:, :n_blur] + half[:, None]
+        if lo.min() < 0 or hi.max() >= nf:
+            raise ValueError(f"gather_windows_exposed: a blurry centre's id - h .. id + h leaves the arena [0, {nf})")
+        if clip_ranges is not None:
+            cr = np.asarray(clip_ranges, dtype=np.int64).reshape(-1, 2)
+            cr = cr[np.argsort(cr[:, 0])]
+            clip = np.searchsorted(cr[:, 0], lo, side="right") - 1         # the clip that holds the first frame of the range
+            if (clip < 0).any() or (hi >= cr[np.maximum(clip, 0), 1]).any():
+                raise ValueError("gather_windows_exposed: a blurry centre's id - h .. id + h crosses a clip boundary")
+    dev = frames_u8.device
+    words = np.ascontiguousarray(curve, dtype=np.uint32)
+    key = (words.tobytes(), dev)
+    with on_device(frames_u8):
+        if key not in _curve_dev:
+            _curve_dev[key] = torch.from_numpy(_checked_curve(words).reshape(-1).copy()).to(dev)
+        table = torch.from_numpy(tab).pin_memory().to(dev, non_blocking=True)
+        out = torch.empty((n_slots, n, 3, ch, cw), dtype=torch.float32, device=dev)
+        L.check(L.exposelib().binexpose_gather(_ptr(frames_u8), nf, h, w, _ptr(table), n, n_slots, n_blur, ch, cw,
+                                               _ptr(_curve_dev[key]), _ptr(out), _stream()), "gather_windows_exposed")
+    return out
+
+
 # --------------------------------------------------------------------------------------------- optimizer
 def _check_row_tensors(what, named_tensors):
     """One row of a by-value table (adam_row, ema_row, grad_rows): float32 contiguous device tensors of one size on one device, not

@@ -23,6 +23,12 @@ reports, as one JSON line:
 
     python tools/bench_train_data.py --blur_window 11
     python tools/bench_train_data.py --blur_window 11 --only kernel --kernel-windows 33    # for rocprofv3, one exposure per run
+
+--blur_window N --blur_gamma G [--blur_noise READ,SHOT] compares the exposure path (libbinexpose.so, `blur_gamma` / `blur_noise`)
+with the `blur_window: N` path instead: no blurry folders are written, gather_kernel also times binexpose_gather without and
+with noise at each exposure, and train_step alternates the `blur_window: N` loader with the one that has the options on top.
+
+    python tools/bench_train_data.py --blur_window 11 --blur_gamma 2.2 --blur_noise 0.004,0.0004
 """
 import argparse
 import json
@@ -119,11 +125,17 @@ def blur_leg(args):
     tool = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(tool)
 
-    def blur_dataset(root, window):
+    def blur_dataset(root, window, **exposure):
         random.seed(0)
         opt = {"mode": "BIN", "name": "train", "dataroot_GT": root, "dataroot_LQ": root, "LQ_size": [3, CROP, CROP],
                "data_type": "img", "phase": "train", "blur_window": window}
-        return create_dataset(opt)
+        return create_dataset(dict(opt, **exposure))
+
+    exposure = {}
+    if args.blur_gamma is not None:
+        exposure["blur_gamma"] = tool.parse_gamma_flag(args.blur_gamma)
+        if args.blur_noise is not None:
+            exposure["blur_noise"] = tool.parse_noise_flag(args.blur_noise)
 
     N = args.blur_window
     dev = torch.device("cuda", 0)
@@ -134,7 +146,8 @@ def blur_leg(args):
         t = time.perf_counter()
         root = make_sharp_tree(os.path.join(tmp, "adobe"), clips=tuple((f"clip{c:02d}", 1 + 8 * c, args.sharp_files)
                                                                        for c in range(args.clips)))
-        tool.make_blur_folder(root, "train", N)
+        if not exposure:
+            tool.make_blur_folder(root, "train", N)
         res["tree_s"] = round(time.perf_counter() - t, 2)
         print(f"tree: {args.clips} clips of {args.sharp_files} sharp frames in {res['tree_s']} s", file=sys.stderr, flush=True)
 
@@ -158,6 +171,21 @@ def blur_leg(args):
             rows.append({"L": L, "us_per_launch_events": round(e0.elapsed_time(e1) * 1e3 / args.kernel_launches, 2),
                          "bytes_no_reuse": nbytes, "hbm_bound_us": round(nbytes / HBM_BYTES_PER_S * 1e6, 2)})
             print(f"gather_windows_blur {rows[-1]}", file=sys.stderr, flush=True)
+            for noise in ([None] + ([exposure.get("blur_noise")] if exposure.get("blur_noise") else []) if exposure else []):
+                import numpy as np
+                curve = ops.exposure_curve(exposure["blur_gamma"], noise)
+                keyed = np.concatenate([tab, np.arange(2 * len(wins), dtype=np.int32).reshape(-1, 2) * 2654435 + 1], axis=1)
+                for _ in range(10):
+                    ops.gather_windows_exposed(cache.frames, keyed, (CROP, CROP), N_BLUR, curve, cache.clip_ranges)
+                e0.record()
+                for _ in range(args.kernel_launches):
+                    ops.gather_windows_exposed(cache.frames, keyed, (CROP, CROP), N_BLUR, curve, cache.clip_ranges)
+                e1.record()
+                torch.cuda.synchronize()
+                rows.append({"L": L, "kernel": "binexpose_gather", "noise": noise,
+                             "us_per_launch_events": round(e0.elapsed_time(e1) * 1e3 / args.kernel_launches, 2),
+                             "bytes_no_reuse": nbytes, "hbm_bound_us": round(nbytes / HBM_BYTES_PER_S * 1e6, 2)})
+                print(f"gather_windows_exposed {rows[-1]}", file=sys.stderr, flush=True)
         res["gather_kernel"] = {"arena_bytes": cache.nbytes, "rows": rows,
                                 "note": "event-timed launches include the pinned table upload and launch gaps; "
                                         "rocprofv3 gives the kernel alone"}
@@ -167,7 +195,9 @@ def blur_leg(args):
             return
 
         loaders, res["cache"] = {}, {}
-        for name, ds in (("device_cache", dataset(root)), ("device_cache_blur_window", blur_dataset(root, N))):
+        pair = ((("device_cache_blur_window", blur_dataset(root, N)), ("device_cache_exposed", blur_dataset(root, N, **exposure)))
+                if exposure else (("device_cache", dataset(root)), ("device_cache_blur_window", blur_dataset(root, N))))
+        for name, ds in pair:
             torch.cuda.synchronize()
             t = time.perf_counter()
             loaders[name] = DeviceWindowLoader(ds, args.batch, None, dev)
@@ -188,7 +218,11 @@ def blur_leg(args):
                 print(f"round {r}: step fed by {k}: {ts[k][-1]} ms", file=sys.stderr, flush=True)
         med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
         res["train_step_ms"] = {"rounds": ts, "median": med}
-        res["blur_vs_device_cache"] = round(med["device_cache_blur_window"] / med["device_cache"], 4)
+        if exposure:
+            res["exposure"] = exposure
+            res["exposed_vs_blur_window"] = round(med["device_cache_exposed"] / med["device_cache_blur_window"], 4)
+        else:
+            res["blur_vs_device_cache"] = round(med["device_cache_blur_window"] / med["device_cache"], 4)
         print(json.dumps(res))
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
@@ -209,6 +243,8 @@ def main():
     ap.add_argument("--sharp-files", type=int, default=120, help="blur_window leg: consecutive sharp frames per clip")
     ap.add_argument("--kernel-windows", type=int, nargs="+", default=None, help="blur_window leg: exposures of the kernel launches")
     ap.add_argument("--rounds", type=int, default=3, help="blur_window leg: alternations of the two device-fed steps")
+    ap.add_argument("--blur_gamma", default=None, help="blur_window leg: compare the exposure path (a number 1.0 .. 2.4 or srgb) with it")
+    ap.add_argument("--blur_noise", default=None, help="blur_window leg, with --blur_gamma: READ,SHOT")
     args = ap.parse_args()
     if args.blur_window is not None:
         return blur_leg(args)

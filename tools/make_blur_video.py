@@ -9,6 +9,14 @@ functions training from clips uses (dataset mode BIN_video): ops.yuv_to_bgr, ops
 ops.frame_to_yuv.  Centres whose exposure leaves the clip are dropped from the front and the back; the tool says how many, and
 prints the `python -m bin_amd.test` arguments that score a run on OUT.y4m against IN.y4m.
 
+With --gamma G (a number 1.0 .. 2.4 or srgb) a blurry frame is an exposure in linear light instead, and with --noise READ,SHOT
+[--noise_seed N] it carries sensor noise: ops.gather_windows_exposed, the launch the `blur_gamma` / `blur_noise` training options
+use (bin_amd.data.exposure.expose_average gives the same bytes on the host).  The planes are treated as training from clips treats
+them: the Y plane and the chroma of every sharp frame are converted to 8-bit BGR first (ops.yuv_to_bgr), the exposure is made on
+those B, G and R codes, noise per colour channel, and the result is converted back to Y and chroma by ops.frame_to_yuv; neither
+the curve nor the noise is applied to a YUV plane directly.  The key of output frame i is (N, i).  Without the flags the bytes
+are those of the truncated mean.
+
 Refuses to overwrite: OUT.y4m must not exist."""
 import argparse
 import collections
@@ -28,8 +36,9 @@ def blur_centres(n, h):
     return centres, [c for c in centres if c - h >= 0 and c + h <= n - 1]
 
 
-def make_blur_video(src, dst, window, matrix="auto", range_="auto", device="cuda"):
-    """Returns (the sharp frame index of every blurry frame written, centres dropped at the front, at the back)."""
+def make_blur_video(src, dst, window, matrix="auto", range_="auto", device="cuda", gamma=None, noise=None, noise_seed=0):
+    """Returns (the sharp frame index of every blurry frame written, centres dropped at the front, at the back).  `gamma`, `noise`:
+    the values of the dataset options `blur_gamma` and `blur_noise`; None (both): the reference's truncated mean."""
     import torch
     from bin_amd import ops, video
     from bin_amd.data.BIN_dataset import blur_half_max, parse_blur_window
@@ -37,6 +46,10 @@ def make_blur_video(src, dst, window, matrix="auto", range_="auto", device="cuda
     if not isinstance(window, int):
         raise ValueError(f"make_blur_video: one window size, got {window!r}")
     h = blur_half_max(window)
+    curve = None
+    if gamma is not None or noise is not None:
+        from bin_amd.data import exposure as X
+        curve = ops.exposure_curve(*X.parse_options({"blur_gamma": gamma, "blur_noise": noise}, window))
     if os.path.exists(dst):
         raise FileExistsError(f"make_blur_video: {dst} exists; remove it or choose another name")
     header, n = video.clip_info(src)
@@ -50,7 +63,7 @@ def make_blur_video(src, dst, window, matrix="auto", range_="auto", device="cuda
     stage = torch.empty((L, stride), dtype=torch.uint8, pin_memory=True)
     row = np.array([[h, 0, 0, 0, h]], dtype=np.int32)         # one slot: the centre's id in the exposure's arena, y0, x0, flip, h
     recent = collections.deque(maxlen=L)
-    want = set(kept)
+    want, written = set(kept), 0
     out_header = video.Y4MHeader(W, H, (header.rate[0], 8 * header.rate[1]), header.interlace, header.aspect, header.colorspace, header.extra)
     with video.Y4MReader(src) as rd, video.Y4MWriter(dst, out_header) as wr, torch.cuda.device(device):
         for k in range(kept[-1] + h + 1):
@@ -63,7 +76,12 @@ def make_blur_video(src, dst, window, matrix="auto", range_="auto", device="cuda
             for j, p in enumerate(recent):
                 stage[j, :header.frame_bytes] = torch.from_numpy(p)
             arena = ops.yuv_to_bgr(stage.to(device, non_blocking=True), H, W, fmt)
-            blurry = ops.gather_windows_blur(arena, row, (H, W), 1)
+            if curve is None:
+                blurry = ops.gather_windows_blur(arena, row, (H, W), 1)
+            else:                                            # the same row, then the key (seed, output frame index)
+                keyed = np.concatenate([row, np.array([[int(noise_seed) & 0xFFFFFFFF, written]], np.uint32).view(np.int32)], axis=1)
+                blurry = ops.gather_windows_exposed(arena, keyed, (H, W), 1, curve)
+            written += 1
             wr.write(ops.frame_to_yuv(blurry[0], 0, 0, H, W, fmt).cpu().numpy())
     return kept, front, back
 
@@ -75,9 +93,17 @@ def main():
     ap.add_argument("--window", type=int, default=11, help="odd exposure in sharp frames, 1 .. 33")
     ap.add_argument("--yuv_matrix", default="auto", help="auto | bt601 | bt709")
     ap.add_argument("--yuv_range", default="auto", help="auto | limited | full")
+    ap.add_argument("--gamma", default=None, help="average in linear light: a number 1.0 .. 2.4 (code e -> e^G) or srgb; applied to the "
+                    "B, G, R codes the YUV planes convert to, not to the planes")
+    ap.add_argument("--noise", default=None, help="READ,SHOT: sensor noise of variance READ^2 + SHOT * lin in linear light, per colour "
+                    "channel (needs --gamma)")
+    ap.add_argument("--noise_seed", type=int, default=0, help="first key word of the noise; the second is the output frame index")
     args = ap.parse_args()
     try:
-        kept, front, back = make_blur_video(args.input, args.output, args.window, args.yuv_matrix, args.yuv_range)
+        from make_blur_folder import parse_gamma_flag, parse_noise_flag
+        kept, front, back = make_blur_video(args.input, args.output, args.window, args.yuv_matrix, args.yuv_range,
+                                            gamma=None if args.gamma is None else parse_gamma_flag(args.gamma),
+                                            noise=None if args.noise is None else parse_noise_flag(args.noise), noise_seed=args.noise_seed)
     except (FileExistsError, FileNotFoundError, ValueError) as e:
         sys.exit(str(e))
     print(f"{len(kept)} blurry frames in {args.output}; {front} centre(s) dropped at the front and {back} at the back (their exposure "
