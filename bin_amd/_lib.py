@@ -1,6 +1,7 @@
 """ctypes binding of the eleven shared objects of bin_amd/build.py's table (libbinhip.so and the ten small libraries beside it,
-include/<name>.h) and of those of its EXTRA_LIBRARIES (libbinexpose.so), each loaded on first use.  The product path has NO fallback: if a library is missing, of another version or a
-call fails this raises, it never routes to PyTorch/CPU code."""
+include/<name>.h) and of those of its EXTRA_LIBRARIES (libbinexpose.so) and ADDON_LIBRARIES (libbinssim.so), each loaded on first
+use.  The product path has NO fallback: if a library is missing, of another version or a call fails this raises, it never routes
+to PyTorch/CPU code."""
 import ctypes as C
 import os
 from functools import partial
@@ -325,6 +326,27 @@ _EXPOSE_SIGNATURES = {
     "binexpose_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# libbinssim.so (include/binssim.h): the SSIM-criterion library, loaded on first use
+SSIM_VERSION = 100                     # BINSSIM_VERSION
+SSIM_E_ARG, SSIM_E_SHAPE, SSIM_E_WORKSPACE = -1, -2, -3   # BINSSIM_E_*
+SSIM_MAX_TERMS = 24                    # BINSSIM_MAX_TERMS
+SSIM_FWD_TILE = (16, 118)              # BINSSIM_FWD_TILE_H, BINSSIM_FWD_TILE_W: windows per workgroup of the forward
+SSIM_BWD_TILE = (32, 32)               # BINSSIM_BWD_TILE_H, BINSSIM_BWD_TILE_W: pixels per workgroup of the backward
+
+
+class BinSsimTerms(C.Structure):
+    _fields_ = [("x", C.c_void_p * SSIM_MAX_TERMS), ("y", C.c_void_p * SSIM_MAX_TERMS), ("gx", C.c_void_p * SSIM_MAX_TERMS),
+                ("gy", C.c_void_p * SSIM_MAX_TERMS), ("n_terms", C.c_int32)]
+
+
+_SSIM_SIGNATURES = {
+    "binssim_version": (C.c_int, []),
+    "binssim_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "binssim_forward": (C.c_int, [C.POINTER(BinSsimTerms), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_void_p]),
+    "binssim_backward": (C.c_int, [C.POINTER(BinSsimTerms), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
@@ -336,11 +358,16 @@ _LIBRARIES = {"binhip": (_SIGNATURES, None), "binopt": (_OPT_SIGNATURES, OPT_VER
               "binclip": (_CLIP_SIGNATURES, CLIP_VERSION)}
 # the same for the rows of build.EXTRA_LIBRARIES
 _EXTRA_LIBRARIES = {"binexpose": (_EXPOSE_SIGNATURES, EXPOSE_VERSION)}
+# the same for the rows of build.ADDON_LIBRARIES, the open-ended table
+_ADDON_LIBRARIES = {"binssim": (_SSIM_SIGNATURES, SSIM_VERSION)}
 _loaded = {}                    # name -> the CDLL, once library(name) has loaded it
 
 
 def _entry(name):
-    return _LIBRARIES[name] if name in _LIBRARIES else _EXTRA_LIBRARIES[name]
+    for table in (_LIBRARIES, _EXTRA_LIBRARIES):
+        if name in table:
+            return table[name]
+    return _ADDON_LIBRARIES[name]
 
 
 def exported_symbols(name="binhip"):
@@ -387,6 +414,7 @@ ratelib = partial(library, "binrate")
 scorelib = partial(library, "binscore")
 cliplib = partial(library, "binclip")
 exposelib = partial(library, "binexpose")
+ssimlib = partial(library, "binssim")
 
 
 def check(rc, what):

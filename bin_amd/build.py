@@ -59,6 +59,13 @@ EXTRA_LIBRARIES = (
             "extra"),
 )
 EXTRA_BY_NAME = {lib.name: lib for lib in EXTRA_LIBRARIES}
+# the open-ended table: a library added after those two joins it here (the same rows and machinery again), so neither of them moves
+ADDON_LIBRARIES = (
+    Library("binssim", ["binssim.hip"],
+            "the structural term of the training criterion: SSIM of fp32 frames and its gradient, in double (pixel_criterion: cb+ssim)",
+            "extra"),
+)
+ADDON_BY_NAME = {lib.name: lib for lib in ADDON_LIBRARIES}
 SOURCES, HEADER, LIB_PATH = BY_NAME["binhip"].sources, BY_NAME["binhip"].header, BY_NAME["binhip"].path
 
 
@@ -75,12 +82,15 @@ def abi_symbols(name="binhip"):
 
 
 def row(name):
-    """The Library row of `name`, of either table."""
-    return BY_NAME[name] if name in BY_NAME else EXTRA_BY_NAME[name]
+    """The Library row of `name`, of any of the three tables."""
+    for table in (BY_NAME, EXTRA_BY_NAME):
+        if name in table:
+            return table[name]
+    return ADDON_BY_NAME[name]
 
 
 def _stale():
-    rows = LIBRARIES + EXTRA_LIBRARIES
+    rows = LIBRARIES + EXTRA_LIBRARIES + ADDON_LIBRARIES
     libs = [lib.path for lib in rows]
     if not all(os.path.exists(p) for p in libs):
         return True
@@ -117,15 +127,15 @@ def build_plan(defines=(), out=None, table=LIBRARIES):
 
 
 def build_library(force=False, verbose=True, defines=(), out=None, table=None):
-    """Compile every HIP source for gfx950 into every library of `table`: of both tables, LIBRARIES and EXTRA_LIBRARIES, when none
-    is given (bin_amd/csrc/lib<name>.so, bin_amd/csrc/extra/lib<name>.so).
+    """Compile every HIP source for gfx950 into every library of `table`: of all three tables, LIBRARIES, EXTRA_LIBRARIES and
+    ADDON_LIBRARIES, when none is given (bin_amd/csrc/lib<name>.so, bin_amd/csrc/extra/lib<name>.so).
 
     `defines` / `out`: the instrumentation side build of tools/wg_timeline.py (defines=("BINHIP_TIMELINE=1",), out=<path>:
     per-workgroup time stamps, which the product library does not contain): libbinhip.so alone, under another name.  The
     sources are compiled in parallel (one hipcc per file)."""
     if out is None and not force and not _stale():
         return LIB_PATH
-    tables = [table] if table is not None else [LIBRARIES] if out is not None else [LIBRARIES, EXTRA_LIBRARIES]
+    tables = [table] if table is not None else [LIBRARIES] if out is not None else [LIBRARIES, EXTRA_LIBRARIES, ADDON_LIBRARIES]
     compiles, links = [], []
     for rows in tables:
         c, l = build_plan(defines, out, rows)

@@ -1,7 +1,7 @@
 """Single-tensor wrapper API over the same generator (reference Video_base_model.py:22-335).
 
-The reference class cannot be imported (it needs `CharbonnierLossPlusSSIM`, which models/loss.py does not define),
-so no reference outputs exist for its training step: PARITY UNPINNED there.  What is kept is its surface — `feed_data({'LQs', 'GT'})`,
+The reference class cannot be imported (it needs `CharbonnierLossPlusSSIM`, which models/loss.py does not define; ours is
+models/loss.py::CharbonnierSsimLoss, `pixel_criterion: cb+ssim`), so no reference outputs exist for its training step: PARITY UNPINNED there.  What is kept is its surface — `feed_data({'LQs', 'GT'})`,
 `optimize_parameters`, `test`, `test_stitch`, `get_current_log`, `get_loss`, `get_current_visuals`, `load`, `save` —
 over a `var_L [B,N,C,H,W]` tensor.  The frames along N are handed to bin_stage4 as its six inputs and the 14
 outputs come back stacked as `fake_H [B,14,C,H,W]`; `GT` is the matching [B,14,C,H,W] stack.
@@ -21,8 +21,8 @@ import torch.nn as nn
 from . import lr_scheduler, networks
 from .base_model import BaseModel, _direct_param_grads
 from .bin_model import FlatGradAllReduce, SingleProcessParallel, _get
-from .loss import CharbonnierLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class, grad_guard, micro_batch, weight_ema
+from .loss import CharbonnierLoss, CharbonnierSsimLoss, L1SumLoss, L2SumLoss
+from ..options.options import adam_class, grad_guard, micro_batch, ssim_weight, weight_ema
 from ..utils import util
 
 logger = logging.getLogger("base")
@@ -38,6 +38,20 @@ class _CbPair(nn.Module):
 
     def forward(self, x, y):
         return self.cb(x, y), None
+
+
+class _CbSsimPair(nn.Module):
+    """`cb+ssim` with that return shape: (cb + ssim_weight * (1 - ssim), (cb, 1 - ssim)), the parts detached, over the whole
+    [B,14,C,H,W] stack as B * 14 * C planes."""
+
+    def __init__(self, ssim_weight):
+        super().__init__()
+        self.both = CharbonnierSsimLoss(ssim_weight)
+        self.reduction, self.ssim_weight = self.both.reduction, self.both.ssim_weight
+
+    def forward(self, x, y):
+        loss = self.both(x, y)
+        return loss, self.both.last_parts
 
 
 class VideoBaseModel(BaseModel):
@@ -57,6 +71,7 @@ class VideoBaseModel(BaseModel):
 
         self.netG.train()
         kind = train_opt["pixel_criterion"]
+        lam = ssim_weight(opt)                                    # train.ssim_weight: with cb+ssim only, refused elsewhere
         if cri_pix is not None:
             self.cri_pix = cri_pix
         elif kind == "l1":
@@ -65,6 +80,8 @@ class VideoBaseModel(BaseModel):
             self.cri_pix = L2SumLoss().to(self.device)
         elif kind == "cb":
             self.cri_pix = _CbPair().to(self.device)
+        elif kind == "cb+ssim":
+            self.cri_pix = _CbSsimPair(lam).to(self.device)
         else:
             raise NotImplementedError("Loss type [{:s}] is not recognized.".format(kind))
         self.l_pix_w = train_opt["pixel_weight"]

@@ -1,6 +1,7 @@
 """Pixel criteria of bin_model (reference models/bin_model.py:52-60) on the HIP reduction kernels, with backward:
 CharbonnierLoss (reference models/loss.py:130-141), and the sum-reduced L1 / L2 losses the option 'pixel_criterion'
-can select instead (`nn.L1Loss(reduction='sum')`, `nn.MSELoss(reduction='sum')` in the reference)."""
+can select instead (`nn.L1Loss(reduction='sum')`, `nn.MSELoss(reduction='sum')` in the reference), and CharbonnierSsimLoss
+(`cb+ssim`, which the reference names but does not define) on libbinssim.so."""
 import torch
 import torch.nn as nn
 
@@ -62,21 +63,38 @@ class _MultiPixelLossFn(torch.autograd.Function):
         return (None, None, None, *grads)
 
 
-def multi_term_loss(criterion, pairs):
-    """(loss, [terms]) of `criterion` over the (x, y) `pairs`, loss = sum(terms) / len(terms): fused when `criterion` is one of this
-    module's (they carry `.kind`), the plain per-term loop otherwise (an injected criterion; tensors of different sizes)."""
-    import os
-    kind = getattr(criterion, "kind", None)
-    if os.environ.get("BIN_AMD_FUSED_LOSS", "1") == "0":          # diagnostics / A-B only: the per-term path it replaced
-        kind = None
-    # fused only when it means what the per-term path means: every pair of ONE shape (equal numel with different shapes, or two
-    # devices, raised there and must not be summed silently here — advisor r05)
-    x0 = pairs[0][0]
-    fusable = (kind is not None and len(pairs) <= L.LOSS_MAX_TERMS
-               and all(t.is_cuda and t.device == x0.device and t.shape == x0.shape for p in pairs for t in p))
-    if not fusable:
-        terms = [criterion(x, y) for x, y in pairs]
-        return sum(terms) / len(terms), terms
+class _MultiSsimFn(torch.autograd.Function):
+    """ssim(x_t, y_t) of T pairs as ONE autograd node: an fp32 [T] from one forward call (two launches), every gradient from one
+    backward call (one launch) whichever sides need one.  A tensor that sits in two terms gets the sum of its two buffers."""
+
+    @staticmethod
+    def forward(ctx, index_pairs, *tensors):
+        ts = [t.contiguous().float() for t in tensors]
+        ctx.save_for_backward(*ts)
+        ctx.index_pairs = list(index_pairs)
+        return ops.ssim_terms([(ts[i], ts[j]) for i, j in index_pairs])
+
+    @staticmethod
+    def backward(ctx, gs):
+        ts = ctx.saved_tensors
+        wants = ctx.needs_input_grad[1:]
+        terms = [t for t, (i, j) in enumerate(ctx.index_pairs) if wants[i] or wants[j]]
+        grads = [None] * len(ts)
+        if terms:
+            gs = gs.contiguous().float()
+            if len(terms) != len(ctx.index_pairs):
+                gs = gs[torch.tensor(terms, device=gs.device)]
+            chosen = [ctx.index_pairs[t] for t in terms]
+            outs = ops.ssim_terms_grad([(ts[i], ts[j]) for i, j in chosen], gs, [(wants[i], wants[j]) for i, j in chosen])
+            for (i, j), (gx, gy) in zip(chosen, outs):
+                for k, o in ((i, gx), (j, gy)):
+                    if o is not None:
+                        grads[k] = o if grads[k] is None else grads[k] + o
+        return (None, *grads)
+
+
+def _index_pairs(pairs):
+    """(the distinct tensors of `pairs`, per pair the two positions in that list)."""
     uniq, index = [], {}
     idx_pairs = []
     for x, y in pairs:
@@ -87,8 +105,45 @@ def multi_term_loss(criterion, pairs):
                 uniq.append(t)
             ij.append(index[id(t)])
         idx_pairs.append(tuple(ij))
-    loss, terms = _MultiPixelLossFn.apply(kind, getattr(criterion, "eps", 0.0), tuple(idx_pairs), *uniq)
-    return loss, list(terms.unbind(0))
+    return uniq, tuple(idx_pairs)
+
+
+def _one_shape_on_device(pairs):
+    """Whether the fused nodes mean what the per-term path means: every pair of ONE shape on one device (equal numel with different
+    shapes, or two devices, raised there and must not be summed silently here — advisor r05)."""
+    x0 = pairs[0][0]
+    return all(t.is_cuda and t.device == x0.device and t.shape == x0.shape for p in pairs for t in p)
+
+
+def multi_term_loss(criterion, pairs):
+    """(loss, [terms]) of `criterion` over the (x, y) `pairs`, loss = sum(terms) / len(terms): fused when `criterion` is one of this
+    module's (they carry `.kind`, or `.ssim_weight` for cb+ssim), the plain per-term loop otherwise (an injected criterion; tensors
+    of different sizes).  A criterion with `.ssim_weight` leaves the two unweighted summands of the loss, detached, in its
+    `last_parts`: (the mean Charbonnier term, the mean of 1 - ssim)."""
+    import os
+    kind = getattr(criterion, "kind", None)
+    lam = getattr(criterion, "ssim_weight", None)
+    if os.environ.get("BIN_AMD_FUSED_LOSS", "1") == "0":          # diagnostics / A-B only: the per-term path it replaced
+        kind = lam = None
+    fusable = (kind is not None or lam is not None) and len(pairs) <= L.LOSS_MAX_TERMS and _one_shape_on_device(pairs)
+    if not fusable:
+        terms, parts = [], []
+        for x, y in pairs:
+            terms.append(criterion(x, y))
+            parts.append(getattr(criterion, "last_parts", None))
+        if getattr(criterion, "ssim_weight", None) is not None and all(p is not None for p in parts):
+            criterion.last_parts = (sum(p[0] for p in parts) / len(parts), sum(p[1] for p in parts) / len(parts))
+        return sum(terms) / len(terms), terms
+    uniq, idx_pairs = _index_pairs(pairs)
+    if lam is None:
+        loss, terms = _MultiPixelLossFn.apply(kind, getattr(criterion, "eps", 0.0), idx_pairs, *uniq)
+        return loss, list(terms.unbind(0))
+    # cb+ssim: the Charbonnier part through the node above, the SSIM part one forward and one backward call for all pairs
+    loss_cb, cb_terms = _MultiPixelLossFn.apply(L.LOSS_CHARBONNIER, criterion.eps, idx_pairs, *uniq)
+    d = 1.0 - _MultiSsimFn.apply(idx_pairs, *uniq)
+    d_mean = d.sum() / len(pairs)
+    criterion.last_parts = (loss_cb.detach(), d_mean.detach())
+    return loss_cb + lam * d_mean, list((cb_terms + lam * d).unbind(0))
 
 
 class CharbonnierLoss(nn.Module):
@@ -121,3 +176,27 @@ class L2SumLoss(nn.Module):
 
     def forward(self, x, y):
         return _PixelLossFn.apply(x, y, L.LOSS_L2_SUM, 0.0)
+
+
+class CharbonnierSsimLoss(nn.Module):
+    """cb(x, y) + ssim_weight * (1 - ssim(x, y)) (`pixel_criterion: cb+ssim`; the reference names a CharbonnierLossPlusSSIM that its
+    models/loss.py does not define): cb the Charbonnier mean above, ssim the mean over all planes and all valid 11 x 11 Gaussian
+    windows of the unquantised fp32 frames with data range 1 (include/binssim.h) — the SSIM the validation log prints.  x, y: at
+    least 3-D, the last two dimensions H, W.  `last_parts`: the last call's (cb, 1 - ssim), detached."""
+
+    reduction = "mean"             # both summands are means over the batch's elements / windows
+
+    def __init__(self, ssim_weight, eps=1e-6):
+        super().__init__()
+        if isinstance(ssim_weight, bool) or not isinstance(ssim_weight, (int, float)) or not 0.0 < float(ssim_weight) < float("inf"):
+            raise ValueError(f"CharbonnierSsimLoss: ssim_weight {ssim_weight!r} is not a finite number > 0")
+        self.ssim_weight = float(ssim_weight)
+        self.eps = eps
+        self.last_parts = None
+
+    def forward(self, x, y):
+        cb = _PixelLossFn.apply(x, y, L.LOSS_CHARBONNIER, self.eps)
+        uniq, idx_pairs = _index_pairs([(x, y)])
+        d = 1.0 - _MultiSsimFn.apply(idx_pairs, *uniq)[0]
+        self.last_parts = (cb.detach(), d.detach())
+        return cb + self.ssim_weight * d

@@ -369,6 +369,93 @@ def charbonnier_grad(x, y, gloss, eps=1e-6):
     return pixel_loss_grad(L.LOSS_CHARBONNIER, x, y, gloss, eps)
 
 
+_SSIM_TAPS = None
+
+
+def _ssim_taps():
+    global _SSIM_TAPS
+    if _SSIM_TAPS is None:
+        from .utils.util import _gauss_taps
+        _SSIM_TAPS = (C.c_double * 11)(*[float(v) for v in _gauss_taps()])
+    return _SSIM_TAPS
+
+
+def _ssim_geometry(what, pairs):
+    """(planes, H, W) of the pairs of ssim_terms / ssim_terms_grad, which are checked here: tensors of one shape, at least 3-D with
+    the last two dimensions H, W, contiguous fp32 on one device."""
+    pairs = list(pairs)
+    if not pairs or any(len(p) != 2 for p in pairs):
+        raise ValueError(f"{what}: a non-empty sequence of (x, y) pairs")
+    first = pairs[0][0]
+    _need_cuda(*[t for p in pairs for t in p])
+    for t in (t for p in pairs for t in p):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: float32 tensors, got {t.dtype}")
+        if t.dim() < 3:
+            raise ValueError(f"{what}: tensors of at least 3 dimensions [..., H, W], got {tuple(t.shape)}")
+        if t.shape != first.shape or t.device != first.device:
+            raise ValueError(f"{what}: tensors of one shape on one device, got {tuple(t.shape)} on {t.device} next to "
+                             f"{tuple(first.shape)} on {first.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: contiguous tensors, got strides {t.stride()} for shape {tuple(t.shape)}")
+    h, w = first.shape[-2:]
+    planes = first.numel() // (h * w) if h * w else 0
+    if h < 11 or w < 11 or planes < 1 or first.numel() > 2 ** 31 - 1:
+        raise ValueError(f"{what}: planes of at least 11 x 11 pixels and at most 2^31 - 1 elements per tensor, got {tuple(first.shape)}")
+    return pairs, planes, h, w
+
+
+def ssim_terms(pairs):
+    """ssim(x, y) of every (x, y) of `pairs` as an fp32 device tensor [T] (binssim_forward, include/binssim.h): the mean over all
+    planes and all valid 11 x 11 Gaussian windows (sigma 1.5, C1 = 0.01^2, C2 = 0.03^2, data range 1), in double, rounded once.
+    One call of two launches per SSIM_MAX_TERMS pairs, on the current stream, no host sync."""
+    pairs, planes, h, w = _ssim_geometry("ssim_terms", pairs)
+    lib = L.ssimlib()
+    dev = pairs[0][0].device
+    out = torch.empty(len(pairs), dtype=torch.float32, device=dev)
+    with on_device(pairs[0][0]):
+        for i0 in range(0, len(pairs), L.SSIM_MAX_TERMS):
+            part = pairs[i0:i0 + L.SSIM_MAX_TERMS]
+            t = L.BinSsimTerms()
+            t.n_terms = len(part)
+            for i, (x, y) in enumerate(part):
+                t.x[i], t.y[i] = x.data_ptr(), y.data_ptr()
+            nb = lib.binssim_workspace_bytes(len(part), planes, h, w)
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            L.check(lib.binssim_forward(C.byref(t), planes, h, w, _ssim_taps(), _ptr(ws), nb, _ptr(out[i0:i0 + len(part)]), _stream()),
+                    "ssim_forward")
+    return out
+
+
+def ssim_terms_grad(pairs, g, need):
+    """The gradients of `sum_t g[t] * ssim(x_t, y_t)` (binssim_backward): `g` an fp32 device tensor [T], `need` per term
+    (want_gx, want_gy), at least one of them.  Returns per term (gx | None, gy | None), fresh tensors shaped like the inputs.  One
+    launch per SSIM_MAX_TERMS pairs, on the current stream, no host sync."""
+    pairs, planes, h, w = _ssim_geometry("ssim_terms_grad", pairs)
+    need = [(bool(a), bool(b)) for a, b in need]
+    if len(need) != len(pairs) or not all(a or b for a, b in need):
+        raise ValueError(f"ssim_terms_grad: `need` names at least one side of each of the {len(pairs)} terms, got {need}")
+    dev = pairs[0][0].device
+    if g.dtype != torch.float32 or g.shape != (len(pairs),) or g.device != dev:
+        raise ValueError(f"ssim_terms_grad: g is a float32 tensor [{len(pairs)}] on {dev}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+    g = g.contiguous()
+    lib = L.ssimlib()
+    outs = []
+    with on_device(pairs[0][0]):
+        for i0 in range(0, len(pairs), L.SSIM_MAX_TERMS):
+            part = pairs[i0:i0 + L.SSIM_MAX_TERMS]
+            t = L.BinSsimTerms()
+            t.n_terms = len(part)
+            for i, ((x, y), (wx, wy)) in enumerate(zip(part, need[i0:i0 + len(part)])):
+                gx = torch.empty_like(x) if wx else None
+                gy = torch.empty_like(y) if wy else None
+                t.x[i], t.y[i] = x.data_ptr(), y.data_ptr()
+                t.gx[i], t.gy[i] = gx.data_ptr() if wx else None, gy.data_ptr() if wy else None
+                outs.append((gx, gy))
+            L.check(lib.binssim_backward(C.byref(t), planes, h, w, _ssim_taps(), _ptr(g[i0:i0 + len(part)]), _stream()), "ssim_backward")
+    return outs
+
+
 # --------------------------------------------------------------------------------------------- backward ops
 class DgradWeights(_KernelWeights):
     """Backward-data weights of one convolution (binhip_weights_relayout_dgrad)."""

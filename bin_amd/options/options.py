@@ -142,6 +142,27 @@ def micro_batch(opt):
     return value
 
 
+def ssim_weight(opt):
+    """`train.ssim_weight` (bin_amd extension): the weight of the structural term of `pixel_criterion: cb+ssim`, whose loss is
+    cb(x, y) + ssim_weight * (1 - ssim(x, y)) (bin_amd.models.loss.CharbonnierSsimLoss).  Required, a finite number > 0, with that
+    criterion; refused beside any other criterion, where it would silently do nothing.  Returns the weight, or None without the
+    criterion."""
+    value = _train_value(opt, "ssim_weight")
+    criterion = _train_value(opt, "pixel_criterion")
+    if criterion != "cb+ssim":
+        if value is not None:
+            raise ValueError(f"train.ssim_weight: {value!r} is set, but train.pixel_criterion is {criterion!r}: the weight belongs to "
+                             "pixel_criterion: cb+ssim")
+        return None
+    if value is None:
+        raise ValueError("train.ssim_weight: pixel_criterion: cb+ssim needs it (a finite number > 0)")
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise ValueError(f"train.ssim_weight: {value!r} is not a number (in YAML write 1.0e-1 or !!float 1e-1, not 1e-1)")
+    if not 0.0 < float(value) < float("inf"):                 # NaN fails both comparisons
+        raise ValueError(f"train.ssim_weight: {value!r} is not a finite number > 0")
+    return float(value)
+
+
 def micro_batches(batch, m):
     """The consecutive (start, n) chunks along N that a batch of `batch` samples is cut into with `train.micro_batch: m`:
     ceil(batch / m) chunks of m, the last one smaller when m does not divide the batch; one chunk when m is None or >= batch."""
@@ -189,6 +210,7 @@ def parse(opt_path, is_train=True):
         skip_bad_steps(opt)
         ema_decay(opt)
         micro_batch(opt)
+        ssim_weight(opt)
         val_self_ensemble(opt)
     if is_train and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the reference exports CUDA_VISIBLE_DEVICES from gpu_ids (torch on ROCm honours the same variable); under

@@ -193,6 +193,9 @@ def main(argv=None, model_factory=None, probe=None):
                     extra = "  gnorm %.3e" % guard.last.norm
                     if guard.skip_bad_steps:
                         extra += "  skipped %d" % guard.skipped_total
+                parts = getattr(model, "loss_parts", None)   # pixel_criterion: cb+ssim: the last step's two summands, unweighted
+                if parts is not None:
+                    extra += "  l_cb %.4e  l_ssim %.4e" % (float(parts[0]), float(parts[1]))
                 log.info("<epoch:%3d, iter:%8d, lr:%.3e> loss %.4e (I7''' %.4e)  %.1f samples/s%s", epoch, step,
                          model.get_current_learning_rate()[0], avg["Al"], avg["13"],
                          print_freq * per_rank_batch * world / max(dt, 1e-9), extra)
