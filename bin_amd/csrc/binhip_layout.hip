@@ -6,6 +6,7 @@
 //   * the harness's u8 image <-> padded fp32 frame glue (u8_to_frame, frame_to_u8)
 //   * binhip_version, binhip_device_cus
 #include "binhip_internal.h"
+#include <initializer_list>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
@@ -186,6 +187,20 @@ __global__ void unpack_input_grads_kernel(UnpackArgs a, const _Float16* __restri
 }
 
 
+// Every launch below is one thread per 16-byte slot or per element, 256 to a block, and the runtime refuses a launch of 2^32 threads
+// or more: `nb` = the blocks of f0 * f1 * .. threads (factors >= 1), or false when the launch would not fit (BINHIP_E_SHAPE; nothing
+// a plan issues comes near it: include/binhip.h, "Launch limit of the layout entry points").
+static bool bh_layout_blocks(unsigned* nb, std::initializer_list<long long> factors) {
+    const long long limit = (1LL << 32) - 256;          // the largest thread count whose round-up to whole blocks stays below 2^32
+    long long total = 1;
+    for (long long f : factors) {
+        if (f < 1 || total > limit / f) return false;   // (total * f > limit, without forming the product)
+        total *= f;
+    }
+    *nb = (unsigned)((total + 255) / 256);
+    return true;
+}
+
 extern "C" {
 
 int binhip_version(void) { return BINHIP_VERSION; }
@@ -201,8 +216,9 @@ int binhip_device_cus(void) {
 int binhip_nchw_to_planes(const float* x, int N, int C, int H, int W, void* y_hi, void* y_lo, void* status, void* stream) {
     if (!x || !y_hi) return BINHIP_E_ARG;
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return BINHIP_E_SHAPE;
-    const long long total = (long long)bh_chunks(C) * N * H * W * 2;
-    hipLaunchKernelGGL(nchw_to_planes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    unsigned nb;
+    if (!bh_layout_blocks(&nb, {bh_chunks(C), N, H, W, 2})) return BINHIP_E_SHAPE;
+    hipLaunchKernelGGL(nchw_to_planes_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream,
                        x, N, C, H, W, (_Float16*)y_hi, (_Float16*)y_lo, (const float*)nullptr, (unsigned*)status);
     BH_CHECK_LAUNCH();
     return 0;
@@ -212,8 +228,9 @@ int binhip_nchw_to_planes_scaled(const float* x, int N, int C, int H, int W, con
                                  void* y_lo, void* status, void* stream) {
     if (!x || !y_hi || !scale) return BINHIP_E_ARG;
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return BINHIP_E_SHAPE;
-    const long long total = (long long)bh_chunks(C) * N * H * W * 2;
-    hipLaunchKernelGGL(nchw_to_planes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    unsigned nb;
+    if (!bh_layout_blocks(&nb, {bh_chunks(C), N, H, W, 2})) return BINHIP_E_SHAPE;
+    hipLaunchKernelGGL(nchw_to_planes_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream,
                        x, N, C, H, W, (_Float16*)y_hi, (_Float16*)y_lo, scale, (unsigned*)status);
     BH_CHECK_LAUNCH();
     return 0;
@@ -222,8 +239,9 @@ int binhip_nchw_to_planes_scaled(const float* x, int N, int C, int H, int W, con
 int binhip_planes_to_nchw(const void* x_hi, const void* x_lo, int N, int C, int H, int W, float* y, void* stream) {
     if (!x_hi || !y) return BINHIP_E_ARG;
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return BINHIP_E_SHAPE;
-    const long long total = (long long)N * C * H * W;
-    hipLaunchKernelGGL(planes_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    unsigned nb;
+    if (!bh_layout_blocks(&nb, {N, C, H, W})) return BINHIP_E_SHAPE;
+    hipLaunchKernelGGL(planes_to_nchw_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream,
                        (const _Float16*)x_hi, (const _Float16*)x_lo, N, C, H, W, y);
     BH_CHECK_LAUNCH();
     return 0;
@@ -232,8 +250,9 @@ int binhip_planes_to_nchw(const void* x_hi, const void* x_lo, int N, int C, int 
 int binhip_pixel_unshuffle_f32(const float* x, int N, int C, int H, int W, int r, float* y, void* stream) {
     if (!x || !y) return BINHIP_E_ARG;
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || r < 1 || H % r || W % r) return BINHIP_E_SHAPE;
-    const long long total = (long long)N * C * H * W;
-    hipLaunchKernelGGL(pixel_unshuffle_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
+    unsigned nb;
+    if (!bh_layout_blocks(&nb, {N, C, H, W})) return BINHIP_E_SHAPE;
+    hipLaunchKernelGGL(pixel_unshuffle_f32_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x,
                        N, C, H, W, r, y);
     BH_CHECK_LAUNCH();
     return 0;
@@ -247,8 +266,9 @@ int binhip_pack_inputs(const float* const* images, int n_images, int N, int H, i
     for (int i = 0; i < 5; ++i) a.img[i] = (i < n_images) ? images[i] : nullptr;
     for (int i = 0; i < n_images; ++i) if (!images[i]) return BINHIP_E_ARG;
     a.nimg = n_images; a.N = N; a.H = H; a.W = W;
-    const long long total = (long long)bh_chunks(12 * n_images) * N * (H / 2) * (W / 2) * 2;
-    hipLaunchKernelGGL(pack_inputs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    unsigned nb;
+    if (!bh_layout_blocks(&nb, {bh_chunks(12 * n_images), N, H / 2, W / 2, 2})) return BINHIP_E_SHAPE;
+    hipLaunchKernelGGL(pack_inputs_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream,
                        a, (_Float16*)y_hi, (_Float16*)y_lo, (unsigned*)status);
     BH_CHECK_LAUNCH();
     return 0;
@@ -281,8 +301,8 @@ int binhip_unshuffle_planes(const void* x_hi, const void* x_lo, int N, int H, in
                             void* stream) {
     if (!x_hi || !y_hi || ((x_lo == nullptr) != (y_lo == nullptr))) return BINHIP_E_ARG;
     if (N <= 0 || H <= 0 || W <= 0 || nchunks <= 0) return BINHIP_E_SHAPE;
-    const long long total = (long long)4 * nchunks * N * H * W * 2;
-    const unsigned nb = (unsigned)((total + 255) / 256);
+    unsigned nb;
+    if (!bh_layout_blocks(&nb, {4, nchunks, N, H, W, 2})) return BINHIP_E_SHAPE;
     hipLaunchKernelGGL(unshuffle_planes_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x_hi, N, H, W,
                        nchunks, (_Float16*)y_hi);
     if (x_lo)
@@ -299,8 +319,9 @@ int binhip_unpack_input_grads(const void* gx0_hi, const void* gx0_lo, const floa
     UnpackArgs a;
     for (int i = 0; i < 5; ++i) a.out[i] = (i < n_images) ? outs[i] : nullptr;
     a.nimg = n_images; a.N = N; a.H = H; a.W = W;
-    const long long total = (long long)N * 3 * H * W;
-    hipLaunchKernelGGL(unpack_input_grads_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    unsigned nb;
+    if (!bh_layout_blocks(&nb, {N, 3, H, W})) return BINHIP_E_SHAPE;
+    hipLaunchKernelGGL(unpack_input_grads_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream,
                        a, (const _Float16*)gx0_hi, (const _Float16*)gx0_lo, gout, scale);
     BH_CHECK_LAUNCH();
     return 0;

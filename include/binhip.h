@@ -213,6 +213,12 @@ BINHIP_API int binhip_conv2d_bwd_data(const BinConvDesc* d, const void* gy_hi, c
                            void* gx_hi, void* gx_lo, void* stream);
 
 /* ---- layout glue ------------------------------------------------------------------------------ */
+/* Launch limit of the layout entry points.  binhip_nchw_to_planes(_scaled), binhip_pack_inputs and binhip_unshuffle_planes run one
+ * thread per 16-byte slot of their OUTPUT planes (chunks * N * H * W * 2 slots at the output's resolution); binhip_planes_to_nchw,
+ * binhip_pixel_unshuffle_f32 and binhip_unpack_input_grads one thread per fp32 element of one output tensor (N * C * H * W, C = 3
+ * for the last).  That count may be at most 2^32 - 256: a larger one is BINHIP_E_SHAPE before anything launches (the runtime
+ * refuses a grid of 2^32 threads).  At N H W = 2^26 - 1 that admits 31 chunks into planes and 63 channels out of them; the plans
+ * stay below a sixteenth of it.  These entry points place no other upper limit on N H W: their indices are 64-bit.          */
 /* fp32 NCHW [N,C,H,W] -> chunk planes (C padded with zeros to 16).                              */
 BINHIP_API int binhip_nchw_to_planes(const float* x, int N, int C, int H, int W, void* y_hi, void* y_lo,
                           void* status, void* stream);

@@ -25,6 +25,8 @@ E_ARG, E_SHAPE, E_WS = -1, -2, -3
 EXEMPT = ("binhip_version", "binhip_device_cus", "binhip_charbonnier_partials", "binhip_profiler_destroy")
 
 NHW_LIMIT = 1 << 26            # N H W of a convolution stays below it (plane < 2 GiB, include/binhip.h BinConvDesc)
+LAYOUT_MAX_THREADS = (1 << 32) - 256     # layout entry points: one thread per output slot / element (include/binhip.h, "Launch limit")
+TOP = {"N": 3, "H": 2731, "W": 8191}     # N H W = 2^26 - 1
 MAX_IMAGES = 5                 # frames averaged by a FINAL epilogue / packed by binhip_pack_inputs
 MAX_Y_CPG = 128                # binhip_conv2d_bwd_data: chunks per output group
 SCORE_MAX_HW = 65535           # binhip_image_score / binhip_frame_score: H, W and (image score) n
@@ -571,6 +573,8 @@ nulls("nchw_to_planes/hi", ("x", "y_hi"), "binhip_layout.hip: x and y_hi (y_lo, 
 nulls("nchw_to_planes_scaled/hi", ("x", "y_hi", "scale"), "binhip_layout.hip: x, y_hi and scale")
 dims("nchw_to_planes/hi", ("N", "C", "H", "W"), "every dimension is positive")
 dims("nchw_to_planes_scaled/hi", ("N", "C", "H", "W"), "every dimension is positive")
+for _b in ("nchw_to_planes/hi", "nchw_to_planes_scaled/hi-lo"):      # chunks * (2^26 - 1) * 2 slots: 31 chunks fit, 32 make 2^32 - 64
+    limit(_b, dict(TOP, C=31 * 16), dict(TOP, C=31 * 16 + 1), E_SHAPE, "one thread per 16-byte slot: at most 2^32 - 256 (launch limit)")
 
 
 def _planes_to_nchw(lo):
@@ -585,6 +589,7 @@ baseline("binhip_planes_to_nchw", "hi")(_planes_to_nchw(False))
 baseline("binhip_planes_to_nchw", "hi-lo")(_planes_to_nchw(True))
 nulls("planes_to_nchw/hi", ("x_hi", "y"), "x_hi and y")
 dims("planes_to_nchw/hi", ("N", "C", "H", "W"), "every dimension is positive")
+limit("planes_to_nchw/hi-lo", dict(TOP, C=63), dict(TOP, C=64), E_SHAPE, "one thread per element: 64 * (2^26 - 1) = 2^32 - 64 > 2^32 - 256")
 
 
 @baseline("binhip_pixel_unshuffle_f32")
@@ -598,6 +603,7 @@ dims("pixel_unshuffle_f32", ("N", "C", "H", "W", "r"), "every dimension and r ar
 mut("pixel_unshuffle_f32", {"H": 5}, E_SHAPE, "H % r")
 mut("pixel_unshuffle_f32", {"W": 7}, E_SHAPE, "W % r")
 mut("pixel_unshuffle_f32", {"r": 4}, E_SHAPE, "H % r (4 % 4 == 0 but 6 % 4 != 0)")
+limit("pixel_unshuffle_f32", dict(TOP, C=63, r=1), dict(TOP, C=64, r=1), E_SHAPE, "one thread per element: at most 2^32 - 256 (launch limit)")
 
 
 def _pack(n, lo):
@@ -617,6 +623,9 @@ dims("pack_inputs/2-hi", ("n_images", "N", "H", "W"), "every dimension is positi
 mut("pack_inputs/2-hi", {"H": 3}, E_SHAPE, "pixel_reshuffle(2): H even")
 mut("pack_inputs/2-hi", {"W": 5}, E_SHAPE, "pixel_reshuffle(2): W even")
 limit("pack_inputs/5-hi-lo", {"n_images": MAX_IMAGES}, {"n_images": MAX_IMAGES + 1}, E_SHAPE, "PackArgs.img holds 5 frames")
+# 4 chunks * N * H/2 * W/2 * 2 slots = 2 N H W: the limit sits at N H W = 2^31 - 128, far above the 2^26 of the convolutions behind it
+limit("pack_inputs/5-hi-lo", {"N": 1, "H": 65536, "W": 32766}, {"N": 1, "H": 65536, "W": 32768}, E_SHAPE,
+      "one thread per 16-byte slot: at most 2^32 - 256 (launch limit)")
 
 
 @baseline("binhip_u8_to_frame")
@@ -659,6 +668,7 @@ baseline("binhip_unshuffle_planes", "hi-lo")(_unshuffle(True))
 nulls("unshuffle_planes/hi", ("x_hi", "y_hi"), "x_hi and y_hi")
 nulls("unshuffle_planes/hi-lo", ("x_lo", "y_lo"), "x_lo and y_lo come together")
 dims("unshuffle_planes/hi", ("N", "H", "W", "nchunks"), "every dimension is positive")
+limit("unshuffle_planes/hi-lo", dict(TOP, nchunks=7), dict(TOP, nchunks=8), E_SHAPE, "4 nchunks N H W 2 slots: 64 * (2^26 - 1) > 2^32 - 256 (launch limit)")
 
 
 def _unpack(n, full):
@@ -678,6 +688,8 @@ dims("unpack_input_grads/3-full", ("n_images", "N", "H", "W"), "every dimension 
 mut("unpack_input_grads/3-full", {"H": 3}, E_SHAPE, "H even")
 mut("unpack_input_grads/3-full", {"W": 5}, E_SHAPE, "W even")
 limit("unpack_input_grads/3-full", {"n_images": MAX_IMAGES}, {"n_images": MAX_IMAGES + 1}, E_SHAPE, "UnpackArgs.out holds 5 frames")
+limit("unpack_input_grads/3-full", {"N": 1, "H": 32768, "W": 43690}, {"N": 1, "H": 32768, "W": 43692}, E_SHAPE,
+      "one thread per element of one frame, 3 N H W: at most 2^32 - 256 (launch limit)")
 
 
 # ================================================================================================== ConvLSTM
