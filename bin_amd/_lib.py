@@ -1,6 +1,6 @@
 """ctypes binding of the eleven shared objects of bin_amd/build.py's table (libbinhip.so and the ten small libraries beside it,
-include/<name>.h) and of those of its EXTRA_LIBRARIES (libbinexpose.so) and ADDON_LIBRARIES (libbinssim.so), each loaded on first
-use.  The product path has NO fallback: if a library is missing, of another version or a call fails this raises, it never routes
+include/<name>.h) and of those of its EXTRA_LIBRARIES (libbinexpose.so) and ADDON_LIBRARIES (libbinssim.so, libbinlap.so), each loaded
+on first use.  The product path has NO fallback: if a library is missing, of another version or a call fails this raises, it never routes
 to PyTorch/CPU code."""
 import ctypes as C
 import os
@@ -347,6 +347,29 @@ _SSIM_SIGNATURES = {
     "binssim_backward": (C.c_int, [C.POINTER(BinSsimTerms), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
 }
 
+# libbinlap.so (include/binlap.h): the pyramid-criterion library, loaded on first use
+LAP_VERSION = 100                      # BINLAP_VERSION
+LAP_E_ARG, LAP_E_SHAPE, LAP_E_WORKSPACE = -1, -2, -3   # BINLAP_E_*
+LAP_MAX_TERMS, LAP_MAX_LEVELS = 24, 8  # BINLAP_MAX_TERMS, BINLAP_MAX_LEVELS
+LAP_DOWN_TILE = (16, 32)               # BINLAP_DOWN_TILE_H, BINLAP_DOWN_TILE_W: coarse pixels per workgroup of the reduce / E^T kernels
+LAP_UP_TILE = (32, 64)                 # BINLAP_UP_TILE_H, BINLAP_UP_TILE_W: fine pixels per workgroup of the band / R^T kernels
+
+
+class BinLapTerms(C.Structure):
+    _fields_ = [("x", C.c_void_p * LAP_MAX_TERMS), ("y", C.c_void_p * LAP_MAX_TERMS), ("gx", C.c_void_p * LAP_MAX_TERMS),
+                ("gy", C.c_void_p * LAP_MAX_TERMS), ("n_terms", C.c_int32)]
+
+
+_LAP_SIGNATURES = {
+    "binlap_version": (C.c_int, []),
+    "binlap_forward_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "binlap_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "binlap_forward": (C.c_int, [C.POINTER(BinLapTerms), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t,
+                                 C.c_void_p, C.c_void_p]),
+    "binlap_backward": (C.c_int, [C.POINTER(BinLapTerms), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
@@ -359,7 +382,7 @@ _LIBRARIES = {"binhip": (_SIGNATURES, None), "binopt": (_OPT_SIGNATURES, OPT_VER
 # the same for the rows of build.EXTRA_LIBRARIES
 _EXTRA_LIBRARIES = {"binexpose": (_EXPOSE_SIGNATURES, EXPOSE_VERSION)}
 # the same for the rows of build.ADDON_LIBRARIES, the open-ended table
-_ADDON_LIBRARIES = {"binssim": (_SSIM_SIGNATURES, SSIM_VERSION)}
+_ADDON_LIBRARIES = {"binssim": (_SSIM_SIGNATURES, SSIM_VERSION), "binlap": (_LAP_SIGNATURES, LAP_VERSION)}
 _loaded = {}                    # name -> the CDLL, once library(name) has loaded it
 
 
@@ -415,6 +438,7 @@ scorelib = partial(library, "binscore")
 cliplib = partial(library, "binclip")
 exposelib = partial(library, "binexpose")
 ssimlib = partial(library, "binssim")
+laplib = partial(library, "binlap")
 
 
 def check(rc, what):

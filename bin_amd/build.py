@@ -64,6 +64,10 @@ ADDON_LIBRARIES = (
     Library("binssim", ["binssim.hip"],
             "the structural term of the training criterion: SSIM of fp32 frames and its gradient, in double (pixel_criterion: cb+ssim)",
             "extra"),
+    Library("binlap", ["binlap.hip"],
+            "the multi-scale term of the training criterion: the Laplacian-pyramid loss of fp32 frames and its gradient, in double "
+            "(pixel_criterion: cb+lap)",
+            "extra"),
 )
 ADDON_BY_NAME = {lib.name: lib for lib in ADDON_LIBRARIES}
 SOURCES, HEADER, LIB_PATH = BY_NAME["binhip"].sources, BY_NAME["binhip"].header, BY_NAME["binhip"].path

@@ -21,8 +21,8 @@ import torch.nn as nn
 from . import lr_scheduler, networks
 from .base_model import BaseModel, _direct_param_grads
 from .bin_model import FlatGradAllReduce, SingleProcessParallel, _get
-from .loss import CharbonnierLoss, CharbonnierSsimLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class, grad_guard, micro_batch, ssim_weight, weight_ema
+from .loss import CharbonnierLapLoss, CharbonnierLoss, CharbonnierSsimLoss, L1SumLoss, L2SumLoss
+from ..options.options import adam_class, grad_guard, lap_levels, lap_weight, micro_batch, ssim_weight, weight_ema
 from ..utils import util
 
 logger = logging.getLogger("base")
@@ -54,6 +54,20 @@ class _CbSsimPair(nn.Module):
         return loss, self.both.last_parts
 
 
+class _CbLapPair(nn.Module):
+    """`cb+lap` with that return shape: (cb + lap_weight * lap, (cb, lap)), the parts detached, over the whole [B,14,C,H,W] stack
+    as B * 14 * C planes."""
+
+    def __init__(self, lap_weight, levels):
+        super().__init__()
+        self.both = CharbonnierLapLoss(lap_weight, levels)
+        self.reduction, self.lap_weight, self.levels = self.both.reduction, self.both.lap_weight, self.both.levels
+
+    def forward(self, x, y):
+        loss = self.both(x, y)
+        return loss, self.both.last_parts
+
+
 class VideoBaseModel(BaseModel):
     def __init__(self, opt, netG=None, cri_pix=None):
         super().__init__(opt)
@@ -72,6 +86,8 @@ class VideoBaseModel(BaseModel):
         self.netG.train()
         kind = train_opt["pixel_criterion"]
         lam = ssim_weight(opt)                                    # train.ssim_weight: with cb+ssim only, refused elsewhere
+        mu, levels = lap_weight(opt), lap_levels(opt)             # train.lap_weight, train.lap_levels: with cb+lap only
+        self.part_key = "lap_loss" if kind == "cb+lap" else "ssim_loss"   # the log's name of the criterion's second part
         if cri_pix is not None:
             self.cri_pix = cri_pix
         elif kind == "l1":
@@ -82,6 +98,8 @@ class VideoBaseModel(BaseModel):
             self.cri_pix = _CbPair().to(self.device)
         elif kind == "cb+ssim":
             self.cri_pix = _CbSsimPair(lam).to(self.device)
+        elif kind == "cb+lap":
+            self.cri_pix = _CbLapPair(mu, levels).to(self.device)
         else:
             raise NotImplementedError("Loss type [{:s}] is not recognized.".format(kind))
         self.l_pix_w = train_opt["pixel_weight"]
@@ -174,7 +192,7 @@ class VideoBaseModel(BaseModel):
             self.log_dict["l_pix"] = l_pix.item()
         else:
             self.log_dict["total_loss"] = l_pix.item()
-            self.log_dict["l_pix"], self.log_dict["ssim_loss"] = parts[0].item(), parts[1].item()
+            self.log_dict["l_pix"], self.log_dict[self.part_key] = parts[0].item(), parts[1].item()
 
     optimize_parameters_without_schudlue = optimize_parameters      # the reference's second spelling of the same step
 

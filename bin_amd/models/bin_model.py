@@ -19,8 +19,8 @@ import torch.nn as nn
 from . import lr_scheduler
 from . import networks
 from .base_model import BaseModel, unwrap, _direct_param_grads
-from .loss import CharbonnierLoss, CharbonnierSsimLoss, L1SumLoss, L2SumLoss
-from ..options.options import adam_class, grad_guard, micro_batch, ssim_weight, weight_ema
+from .loss import CharbonnierLapLoss, CharbonnierLoss, CharbonnierSsimLoss, L1SumLoss, L2SumLoss
+from ..options.options import adam_class, grad_guard, lap_levels, lap_weight, micro_batch, ssim_weight, weight_ema
 from ..utils import dist_util, util
 from ..utils.util import AverageMeter
 
@@ -257,11 +257,13 @@ class bin_model(BaseModel):
         self.load()
         self.grad_guard = None
         self.loss_parts = None                     # cb+ssim: the last loss's detached (mean cb term, mean 1 - ssim); None otherwise
+        self.loss_part_names = None                # what loss_parts holds: ("l_cb", "l_ssim") under cb+ssim, ("l_cb", "l_lap") under cb+lap
 
         if self.is_train:
             self.netG.train()
             self.loss_type = loss_type = train_opt["pixel_criterion"]
             lam = ssim_weight(opt)                                # train.ssim_weight: with cb+ssim only, refused elsewhere
+            mu, levels = lap_weight(opt), lap_levels(opt)         # train.lap_weight, train.lap_levels: with cb+lap only
             if loss_type == "l1":
                 self.cri_pix = L1SumLoss().to(self.device)        # nn.L1Loss(reduction='sum') in the reference
             elif loss_type == "l2":
@@ -270,6 +272,10 @@ class bin_model(BaseModel):
                 self.cri_pix = CharbonnierLoss().to(self.device)
             elif loss_type == "cb+ssim":
                 self.cri_pix = CharbonnierSsimLoss(lam).to(self.device)
+                self.loss_part_names = ("l_cb", "l_ssim")
+            elif loss_type == "cb+lap":
+                self.cri_pix = CharbonnierLapLoss(mu, levels).to(self.device)
+                self.loss_part_names = ("l_cb", "l_lap")
             else:
                 raise NotImplementedError("Loss type [{:s}] is not recognized.".format(loss_type))
             if cri_pix is not None:
@@ -468,7 +474,7 @@ class bin_model(BaseModel):
         if self.nframes == 6 and self.version == 2:
             pairs += [(self.Ft_p[1], self.Ft_p[7]), (self.Ft_p[5], self.Ft_p[9]), (self.Ft_p[2], self.Ft_p[8])]
         loss, loss_list = multi_term_loss(self.cri_pix, pairs)
-        if getattr(self.cri_pix, "ssim_weight", None) is not None:
+        if getattr(self.cri_pix, "ssim_weight", None) is not None or getattr(self.cri_pix, "lap_weight", None) is not None:
             self.loss_parts = getattr(self.cri_pix, "last_parts", None)
         loss_list = loss_list[:num]
         if ret == 1:

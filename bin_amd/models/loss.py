@@ -1,7 +1,8 @@
 """Pixel criteria of bin_model (reference models/bin_model.py:52-60) on the HIP reduction kernels, with backward:
 CharbonnierLoss (reference models/loss.py:130-141), and the sum-reduced L1 / L2 losses the option 'pixel_criterion'
 can select instead (`nn.L1Loss(reduction='sum')`, `nn.MSELoss(reduction='sum')` in the reference), and CharbonnierSsimLoss
-(`cb+ssim`, which the reference names but does not define) on libbinssim.so."""
+(`cb+ssim`, which the reference names but does not define) on libbinssim.so, and CharbonnierLapLoss (`cb+lap`, the
+Laplacian-pyramid criterion of frame interpolation) on libbinlap.so."""
 import torch
 import torch.nn as nn
 
@@ -93,6 +94,37 @@ class _MultiSsimFn(torch.autograd.Function):
         return (None, *grads)
 
 
+class _MultiLapFn(torch.autograd.Function):
+    """lap(x_t, y_t) of T pairs as ONE autograd node: an fp32 [T] from one forward call, every gradient from one backward call
+    whichever sides need one.  A tensor that sits in two terms gets the sum of its two buffers."""
+
+    @staticmethod
+    def forward(ctx, levels, eps, index_pairs, *tensors):
+        ts = [t.contiguous().float() for t in tensors]
+        ctx.save_for_backward(*ts)
+        ctx.levels, ctx.eps, ctx.index_pairs = levels, eps, list(index_pairs)
+        return ops.lap_terms([(ts[i], ts[j]) for i, j in index_pairs], levels, eps)
+
+    @staticmethod
+    def backward(ctx, gs):
+        ts = ctx.saved_tensors
+        wants = ctx.needs_input_grad[3:]
+        terms = [t for t, (i, j) in enumerate(ctx.index_pairs) if wants[i] or wants[j]]
+        grads = [None] * len(ts)
+        if terms:
+            gs = gs.contiguous().float()
+            if len(terms) != len(ctx.index_pairs):
+                gs = gs[torch.tensor(terms, device=gs.device)]
+            chosen = [ctx.index_pairs[t] for t in terms]
+            outs = ops.lap_terms_grad([(ts[i], ts[j]) for i, j in chosen], gs, [(wants[i], wants[j]) for i, j in chosen],
+                                      ctx.levels, ctx.eps)
+            for (i, j), (gx, gy) in zip(chosen, outs):
+                for k, o in ((i, gx), (j, gy)):
+                    if o is not None:
+                        grads[k] = o if grads[k] is None else grads[k] + o
+        return (None, None, None, *grads)
+
+
 def _index_pairs(pairs):
     """(the distinct tensors of `pairs`, per pair the two positions in that list)."""
     uniq, index = [], {}
@@ -117,24 +149,33 @@ def _one_shape_on_device(pairs):
 
 def multi_term_loss(criterion, pairs):
     """(loss, [terms]) of `criterion` over the (x, y) `pairs`, loss = sum(terms) / len(terms): fused when `criterion` is one of this
-    module's (they carry `.kind`, or `.ssim_weight` for cb+ssim), the plain per-term loop otherwise (an injected criterion; tensors
-    of different sizes).  A criterion with `.ssim_weight` leaves the two unweighted summands of the loss, detached, in its
-    `last_parts`: (the mean Charbonnier term, the mean of 1 - ssim)."""
+    module's (they carry `.kind`, `.ssim_weight` for cb+ssim or `.lap_weight` for cb+lap), the plain per-term loop otherwise (an
+    injected criterion; tensors of different sizes).  A criterion with `.ssim_weight` or `.lap_weight` leaves the two unweighted
+    summands of the loss, detached, in its `last_parts`: (the mean Charbonnier term, the mean of 1 - ssim or of lap)."""
     import os
     kind = getattr(criterion, "kind", None)
     lam = getattr(criterion, "ssim_weight", None)
+    mu = getattr(criterion, "lap_weight", None)
     if os.environ.get("BIN_AMD_FUSED_LOSS", "1") == "0":          # diagnostics / A-B only: the per-term path it replaced
-        kind = lam = None
-    fusable = (kind is not None or lam is not None) and len(pairs) <= L.LOSS_MAX_TERMS and _one_shape_on_device(pairs)
+        kind = lam = mu = None
+    fusable = (kind is not None or lam is not None or mu is not None) and len(pairs) <= L.LOSS_MAX_TERMS and _one_shape_on_device(pairs)
     if not fusable:
         terms, parts = [], []
         for x, y in pairs:
             terms.append(criterion(x, y))
             parts.append(getattr(criterion, "last_parts", None))
-        if getattr(criterion, "ssim_weight", None) is not None and all(p is not None for p in parts):
+        two_parts = getattr(criterion, "ssim_weight", None) is not None or getattr(criterion, "lap_weight", None) is not None
+        if two_parts and all(p is not None for p in parts):
             criterion.last_parts = (sum(p[0] for p in parts) / len(parts), sum(p[1] for p in parts) / len(parts))
         return sum(terms) / len(terms), terms
     uniq, idx_pairs = _index_pairs(pairs)
+    if mu is not None:
+        # cb+lap: the Charbonnier part through the node above, the pyramid part one forward and one backward call for all pairs
+        loss_cb, cb_terms = _MultiPixelLossFn.apply(L.LOSS_CHARBONNIER, criterion.eps, idx_pairs, *uniq)
+        lap = _MultiLapFn.apply(criterion.levels, criterion.eps, idx_pairs, *uniq)
+        lap_mean = lap.sum() / len(pairs)
+        criterion.last_parts = (loss_cb.detach(), lap_mean.detach())
+        return loss_cb + mu * lap_mean, list((cb_terms + mu * lap).unbind(0))
     if lam is None:
         loss, terms = _MultiPixelLossFn.apply(kind, getattr(criterion, "eps", 0.0), idx_pairs, *uniq)
         return loss, list(terms.unbind(0))
@@ -200,3 +241,30 @@ class CharbonnierSsimLoss(nn.Module):
         d = 1.0 - _MultiSsimFn.apply(idx_pairs, *uniq)[0]
         self.last_parts = (cb.detach(), d.detach())
         return cb + self.ssim_weight * d
+
+
+class CharbonnierLapLoss(nn.Module):
+    """cb(x, y) + lap_weight * lap(x, y) (`pixel_criterion: cb+lap`): cb the Charbonnier mean above, lap the Laplacian-pyramid loss
+    of include/binlap.h over `levels` octave bands of x - y, each band's Charbonnier mean with the same eps, on the unquantised fp32
+    frames (the reference's models/loss.py carries a multi_scale_loss that nothing calls).  x, y: at least 3-D, the last two
+    dimensions H, W of at least 2^(levels - 1) pixels.  `last_parts`: the last call's (cb, lap), detached."""
+
+    reduction = "mean"             # both summands are means over the batch's elements
+
+    def __init__(self, lap_weight, levels=5, eps=1e-6):
+        super().__init__()
+        if isinstance(lap_weight, bool) or not isinstance(lap_weight, (int, float)) or not 0.0 < float(lap_weight) < float("inf"):
+            raise ValueError(f"CharbonnierLapLoss: lap_weight {lap_weight!r} is not a finite number > 0")
+        if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= L.LAP_MAX_LEVELS:
+            raise ValueError(f"CharbonnierLapLoss: levels {levels!r} is not an integer 1 .. {L.LAP_MAX_LEVELS}")
+        self.lap_weight = float(lap_weight)
+        self.levels = levels
+        self.eps = eps
+        self.last_parts = None
+
+    def forward(self, x, y):
+        cb = _PixelLossFn.apply(x, y, L.LOSS_CHARBONNIER, self.eps)
+        uniq, idx_pairs = _index_pairs([(x, y)])
+        lap = _MultiLapFn.apply(self.levels, self.eps, idx_pairs, *uniq)[0]
+        self.last_parts = (cb.detach(), lap.detach())
+        return cb + self.lap_weight * lap

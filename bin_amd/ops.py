@@ -456,6 +456,92 @@ def ssim_terms_grad(pairs, g, need):
     return outs
 
 
+def _lap_geometry(what, pairs, levels, eps):
+    """(pairs, planes, H, W, levels, eps) of lap_terms / lap_terms_grad, which are checked here: tensors of one shape, at least 3-D
+    with the last two dimensions H, W of at least 2^(levels - 1) pixels, contiguous fp32 on one device; levels an int 1 .. 8, eps a
+    finite number > 0."""
+    pairs = list(pairs)
+    if not pairs or any(len(p) != 2 for p in pairs):
+        raise ValueError(f"{what}: a non-empty sequence of (x, y) pairs")
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= L.LAP_MAX_LEVELS:
+        raise ValueError(f"{what}: levels {levels!r} is not an integer 1 .. {L.LAP_MAX_LEVELS}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 < float(eps) < float("inf"):
+        raise ValueError(f"{what}: eps {eps!r} is not a finite number > 0")
+    first = pairs[0][0]
+    _need_cuda(*[t for p in pairs for t in p])
+    for t in (t for p in pairs for t in p):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: float32 tensors, got {t.dtype}")
+        if t.dim() < 3:
+            raise ValueError(f"{what}: tensors of at least 3 dimensions [..., H, W], got {tuple(t.shape)}")
+        if t.shape != first.shape or t.device != first.device:
+            raise ValueError(f"{what}: tensors of one shape on one device, got {tuple(t.shape)} on {t.device} next to "
+                             f"{tuple(first.shape)} on {first.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: contiguous tensors, got strides {t.stride()} for shape {tuple(t.shape)}")
+    h, w = first.shape[-2:]
+    planes = first.numel() // (h * w) if h * w else 0
+    least = 1 << (levels - 1)
+    if h < least or w < least or planes < 1 or first.numel() > 2 ** 31 - 1:
+        raise ValueError(f"{what}: planes of at least {least} x {least} pixels for {levels} levels and at most 2^31 - 1 elements per "
+                         f"tensor, got {tuple(first.shape)}")
+    return pairs, planes, h, w, levels, float(eps)
+
+
+def lap_terms(pairs, levels=5, eps=1e-6):
+    """lap(x, y) of every (x, y) of `pairs` as an fp32 device tensor [T] (binlap_forward, include/binlap.h): the sum over `levels`
+    Laplacian-pyramid bands of x - y of the mean of sqrt(b^2 + eps), in double, rounded once.  One call of 2 * levels launches per
+    LAP_MAX_TERMS pairs, on the current stream, no host sync."""
+    pairs, planes, h, w, levels, eps = _lap_geometry("lap_terms", pairs, levels, eps)
+    lib = L.laplib()
+    dev = pairs[0][0].device
+    out = torch.empty(len(pairs), dtype=torch.float32, device=dev)
+    with on_device(pairs[0][0]):
+        for i0 in range(0, len(pairs), L.LAP_MAX_TERMS):
+            part = pairs[i0:i0 + L.LAP_MAX_TERMS]
+            t = L.BinLapTerms()
+            t.n_terms = len(part)
+            for i, (x, y) in enumerate(part):
+                t.x[i], t.y[i] = x.data_ptr(), y.data_ptr()
+            nb = lib.binlap_forward_workspace_bytes(len(part), planes, h, w, levels)
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            L.check(lib.binlap_forward(C.byref(t), planes, h, w, levels, eps, _ptr(ws), nb, _ptr(out[i0:i0 + len(part)]), _stream()),
+                    "lap_forward")
+    return out
+
+
+def lap_terms_grad(pairs, g, wants, levels=5, eps=1e-6):
+    """The gradients of `sum_t g[t] * lap(x_t, y_t)` (binlap_backward): `g` an fp32 device tensor [T], `wants` per term
+    (want_gx, want_gy), at least one of them.  Returns per term (gx | None, gy | None), fresh tensors shaped like the inputs.  One
+    call of 3 * levels - 2 launches per LAP_MAX_TERMS pairs, on the current stream, no host sync."""
+    pairs, planes, h, w, levels, eps = _lap_geometry("lap_terms_grad", pairs, levels, eps)
+    wants = [(bool(a), bool(b)) for a, b in wants]
+    if len(wants) != len(pairs) or not all(a or b for a, b in wants):
+        raise ValueError(f"lap_terms_grad: `wants` names at least one side of each of the {len(pairs)} terms, got {wants}")
+    dev = pairs[0][0].device
+    if g.dtype != torch.float32 or g.shape != (len(pairs),) or g.device != dev:
+        raise ValueError(f"lap_terms_grad: g is a float32 tensor [{len(pairs)}] on {dev}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+    g = g.contiguous()
+    lib = L.laplib()
+    outs = []
+    with on_device(pairs[0][0]):
+        for i0 in range(0, len(pairs), L.LAP_MAX_TERMS):
+            part = pairs[i0:i0 + L.LAP_MAX_TERMS]
+            t = L.BinLapTerms()
+            t.n_terms = len(part)
+            for i, ((x, y), (wx, wy)) in enumerate(zip(part, wants[i0:i0 + len(part)])):
+                gx = torch.empty_like(x) if wx else None
+                gy = torch.empty_like(y) if wy else None
+                t.x[i], t.y[i] = x.data_ptr(), y.data_ptr()
+                t.gx[i], t.gy[i] = gx.data_ptr() if wx else None, gy.data_ptr() if wy else None
+                outs.append((gx, gy))
+            nb = lib.binlap_backward_workspace_bytes(len(part), planes, h, w, levels)
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            L.check(lib.binlap_backward(C.byref(t), planes, h, w, levels, eps, _ptr(g[i0:i0 + len(part)]), _ptr(ws), nb, _stream()),
+                    "lap_backward")
+    return outs
+
+
 # --------------------------------------------------------------------------------------------- backward ops
 class DgradWeights(_KernelWeights):
     """Backward-data weights of one convolution (binhip_weights_relayout_dgrad)."""

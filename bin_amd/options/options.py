@@ -163,6 +163,49 @@ def ssim_weight(opt):
     return float(value)
 
 
+def lap_weight(opt):
+    """`train.lap_weight` (bin_amd extension): the weight of the multi-scale term of `pixel_criterion: cb+lap`, whose loss is
+    cb(x, y) + lap_weight * lap(x, y) (bin_amd.models.loss.CharbonnierLapLoss).  Required, a finite number > 0, with that criterion;
+    refused beside any other criterion, where it would silently do nothing.  Returns the weight, or None without the criterion."""
+    value = _train_value(opt, "lap_weight")
+    criterion = _train_value(opt, "pixel_criterion")
+    if criterion != "cb+lap":
+        if value is not None:
+            raise ValueError(f"train.lap_weight: {value!r} is set, but train.pixel_criterion is {criterion!r}: the weight belongs to "
+                             "pixel_criterion: cb+lap")
+        return None
+    if value is None:
+        raise ValueError("train.lap_weight: pixel_criterion: cb+lap needs it (a finite number > 0)")
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise ValueError(f"train.lap_weight: {value!r} is not a number (in YAML write 1.0e-1 or !!float 1e-1, not 1e-1)")
+    if not 0.0 < float(value) < float("inf"):                  # NaN fails both comparisons
+        raise ValueError(f"train.lap_weight: {value!r} is not a finite number > 0")
+    return float(value)
+
+
+LAP_LEVELS_DEFAULT, LAP_LEVELS_MAX = 5, 8
+
+
+def lap_levels(opt):
+    """`train.lap_levels` (bin_amd extension): the number of pyramid levels of `pixel_criterion: cb+lap`, an integer 1 .. 8; the
+    training crop must be at least 2^(levels - 1) pixels high and wide.  Absent or null: 5.  Refused beside any other criterion.
+    Returns the count, or None without the criterion."""
+    value = _train_value(opt, "lap_levels")
+    criterion = _train_value(opt, "pixel_criterion")
+    if criterion != "cb+lap":
+        if value is not None:
+            raise ValueError(f"train.lap_levels: {value!r} is set, but train.pixel_criterion is {criterion!r}: the level count belongs "
+                             "to pixel_criterion: cb+lap")
+        return None
+    if value is None:
+        return LAP_LEVELS_DEFAULT
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f"train.lap_levels: {value!r} is not an integer")
+    if not 1 <= value <= LAP_LEVELS_MAX:
+        raise ValueError(f"train.lap_levels: {value!r} is not an integer 1 .. {LAP_LEVELS_MAX}")
+    return value
+
+
 def micro_batches(batch, m):
     """The consecutive (start, n) chunks along N that a batch of `batch` samples is cut into with `train.micro_batch: m`:
     ceil(batch / m) chunks of m, the last one smaller when m does not divide the batch; one chunk when m is None or >= batch."""
@@ -211,6 +254,8 @@ def parse(opt_path, is_train=True):
         ema_decay(opt)
         micro_batch(opt)
         ssim_weight(opt)
+        lap_weight(opt)
+        lap_levels(opt)
         val_self_ensemble(opt)
     if is_train and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the reference exports CUDA_VISIBLE_DEVICES from gpu_ids (torch on ROCm honours the same variable); under

@@ -194,7 +194,10 @@ def main(argv=None, model_factory=None, probe=None):
                     if guard.skip_bad_steps:
                         extra += "  skipped %d" % guard.skipped_total
                 parts = getattr(model, "loss_parts", None)   # pixel_criterion: cb+ssim: the last step's two summands, unweighted
-                if parts is not None:
+                names = getattr(model, "loss_part_names", None)   # which two: pixel_criterion: cb+lap holds ("l_cb", "l_lap")
+                if parts is not None and names == ("l_cb", "l_lap"):
+                    extra += "  l_cb %.4e  l_lap %.4e" % (float(parts[0]), float(parts[1]))
+                elif parts is not None:
                     extra += "  l_cb %.4e  l_ssim %.4e" % (float(parts[0]), float(parts[1]))
                 log.info("<epoch:%3d, iter:%8d, lr:%.3e> loss %.4e (I7''' %.4e)  %.1f samples/s%s", epoch, step,
                          model.get_current_learning_rate()[0], avg["Al"], avg["13"],
