@@ -13,6 +13,7 @@ RDN_LAYERS = 66              # bin_stage4's layer count; BinRdnPlan arrays hold 
 RDN_MAX_LAYERS, RDN_MAX_CONVS = 192, 7
 PLAN_KEEP_ACTS, PLAN_NO_FUSE, PLAN_RDB3, PLAN_FUSED_UPNET, PLAN_FUSED_UPNET_TRAIN = 1, 2, 4, 8, 16
 PLAN_UPNET_FOLD = 32         # BINHIP_PLAN_UPNET_FOLD
+PLAN_HOLD_WEIGHTS = 64       # BINHIP_PLAN_HOLD_WEIGHTS
 BWD_ACCUMULATE = 1          # BinRdnBwdPlan.reserved flag (BINHIP_BWD_ACCUMULATE)
 BWD_SAVED_X3 = 2            # BINHIP_BWD_SAVED_X3
 BWD_FUSED_UPNET = 4         # BINHIP_BWD_FUSED_UPNET
@@ -33,6 +34,8 @@ class BinConvDesc(C.Structure):
 LOSS_MAX_TERMS = 24          # BINHIP_LOSS_MAX_TERMS
 CONV_HALF_LAST_CHUNK = 1     # BinConvDesc.reserved flag of binhip_conv2d_fwd (BINHIP_CONV_HALF_LAST_CHUNK)
 CONV_UPNET_FOLD = 2          # BINHIP_CONV_UPNET_FOLD
+CONV_HOLD_WEIGHTS = 4        # BINHIP_CONV_HOLD_WEIGHTS
+TAIL_STORE_O3, TAIL_HOLD_WEIGHTS = 1, 2      # binhip_rdb_tail_fwd's store_o3 bits (BINHIP_TAIL_*)
 
 
 class BinLossTerms(C.Structure):

@@ -302,6 +302,8 @@ int bh_prepare_conv(const BhConvCall& c, ConvKArgs* out) {
     a.half_last = (d.reserved & BINHIP_CONV_HALF_LAST_CHUNK) ? 1 : 0;
     a.upnet_fold = (d.reserved & BINHIP_CONV_UPNET_FOLD) ? 1 : 0;
     if (a.upnet_fold && (d.epilogue != BINHIP_EPI_FINAL_SUBPIX || d.nterms != 3)) return BINHIP_E_ARG;
+    a.hold_w = (d.reserved & BINHIP_CONV_HOLD_WEIGHTS) ? 1 : 0;
+    if (a.hold_w && (d.epilogue != BINHIP_EPI_PLANES || d.ksize != 3 || d.nterms != 3)) return BINHIP_E_ARG;
     a.y_unshuf = c.y_unshuf;
     if (c.y_unshuf && (d.epilogue != BINHIP_EPI_PLANES || c.y_cpg > 0 || (d.H & 1) || (d.W & 1) || c.y_unshuf * 16 < d.cout))
         return BINHIP_E_SHAPE;
@@ -516,9 +518,9 @@ int binhip_conv2d_fwd(const BinConvDesc* d, const void* x_hi, const void* x_lo, 
                       void* y_hi, void* y_lo, float* y_f32, const float* const* images, void* stream) {
     if (!d) return BINHIP_E_ARG;
     // `reserved`: the defined bits, each only where it is legal (the 5x5 bit's promise concerns that layer's last chunk; a wrong promise
-    // would give wrong sums silently because the real cin is not in the descriptor — advisor r05; BINHIP_CONV_UPNET_FOLD is checked in
-    // bh_prepare_conv)
-    if (d->reserved & ~(BINHIP_CONV_HALF_LAST_CHUNK | BINHIP_CONV_UPNET_FOLD)) return BINHIP_E_ARG;
+    // would give wrong sums silently because the real cin is not in the descriptor — advisor r05; BINHIP_CONV_UPNET_FOLD and
+    // BINHIP_CONV_HOLD_WEIGHTS are checked in bh_prepare_conv)
+    if (d->reserved & ~(BINHIP_CONV_HALF_LAST_CHUNK | BINHIP_CONV_UPNET_FOLD | BINHIP_CONV_HOLD_WEIGHTS)) return BINHIP_E_ARG;
     if ((d->reserved & BINHIP_CONV_HALF_LAST_CHUNK) && d->ksize != 5) return BINHIP_E_ARG;
     BhConvCall c;
     c.d = *d;

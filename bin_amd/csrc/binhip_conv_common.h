@@ -63,6 +63,7 @@ struct ConvKArgs {
     unsigned tl_base;         // first record of this launch (records are pre-assigned: base + tile index, no atomics)
 #endif
     int upnet_fold;           // FINAL_SUBPIX in the fp32-class mode: w_hi / w_lo are the folded slab (BINHIP_CONV_UPNET_FOLD)
+    int hold_w;               // 3x3 plane-split kernel: hold the hi weight fragments across a chunk's sub-stages (BINHIP_CONV_HOLD_WEIGHTS)
     int y_unshuf;             // XTRA kernels only: > 0 = the output goes out through an inverse PixelShuffle(2) — full-resolution
                               // pixel (Y, X), chunk c -> plane (2 (Y & 1) + (X & 1)) * y_unshuf + c at (Y / 2, X / 2) of the half-
                               // resolution tensor (the channel order UPNet.0's permuted rows use); y_unshuf = chunks per sub-position

@@ -84,11 +84,19 @@ __device__ __forceinline__ void x3_issue_weights(const ConvKArgs& a, char* smem,
 // One sub-stage out of LDS.  HI: both weight planes against the hi patch (2 products); !HI: hi weights against the lo
 // patch.  Tap order dx-major: the R+KS-1 patch-row fragments of a tap column are fetched once and serve its KS taps;
 // weight fragments are fetched one tap ahead, the next column's patch rows at the column's first tap.
-template <class C, int KS, int R, bool HI>
-__device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a_lane_off, int b_lane_off, floatx16 (&acc)[R]) {
+// HOLD (BINHIP_CONV_HOLD_WEIGHTS, 3x3): the hi sub-stage fetches the hi-plane fragment of tap s into keep[s] and leaves all
+// KS * KS of them there; the lo sub-stage of the same chunk multiplies from keep[] and reads no weight fragment at all
+// (51 -> 42 ds_read_b128 per wave and chunk).  Same operands in the same order per accumulator: the same bits.
+template <class C, int KS, int R, bool HI, bool HOLD = false>
+__device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a_lane_off, int b_lane_off, floatx16 (&acc)[R],
+                                           half8* keep = nullptr) {
     constexpr int NTAP = KS * KS;
     half8 B[2][R + KS - 1];
     half8 Ah[2], Al[2];
+    auto ah = [&](int s) -> half8& {
+        if constexpr (HOLD) return keep[s];
+        else return Ah[s & 1];
+    };
     auto load_b = [&](int dx, half8 (&dst)[R + KS - 1]) {
 #pragma unroll
         for (int rr = 0; rr < R + KS - 1; ++rr) dst[rr] = ld8(pb + b_lane_off + (rr * C::PW + dx) * 16);
@@ -96,15 +104,15 @@ __device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a
     auto load_a = [&](int s, half8& h, half8& l) {
         const int dx = s / KS, dy = s % KS;
         const int off = ((dy * KS + dx) * 32) * 32 + a_lane_off;
-        h = ld8(wb + off);
+        if constexpr (HI || !HOLD) h = ld8(wb + off);
         if constexpr (HI) l = ld8(wb + C::WP * 1024 + off);
     };
     load_b(0, B[0]);
-    load_a(0, Ah[0], Al[0]);
+    load_a(0, ah(0), Al[0]);
 #pragma unroll
     for (int s = 0; s < NTAP; ++s) {
         const int dx = s / KS, dy = s % KS;
-        if (s + 1 < NTAP) load_a(s + 1, Ah[(s + 1) & 1], Al[(s + 1) & 1]);
+        if (s + 1 < NTAP) load_a(s + 1, ah(s + 1), Al[(s + 1) & 1]);
         if (dy == 0 && dx + 1 < KS) load_b(dx + 1, B[(dx + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (HI) {
@@ -114,7 +122,7 @@ __device__ __forceinline__ void x3_compute(const char* pb, const char* wb, int a
         }
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            acc[r] = mfma_32x32x16(Ah[s & 1], B[dx & 1][r + dy], acc[r]);
+            acc[r] = mfma_32x32x16(ah(s), B[dx & 1][r + dy], acc[r]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -220,11 +228,13 @@ constexpr unsigned RDB3_SPIN_LIMIT = 1u << 22;
 
 // One output tile (TH x 32 pixels, 32 output channels of column z) from prologue DMA to epilogue stores.  Every wave of
 // the workgroup calls it with the same arguments; LDS must be free of readers on entry.
-template <int KS, int R, int WN, int EPI, bool XTRA, bool GATED = false>
+// HOLD: the lo sub-stage of a chunk takes its hi-plane weight fragments from the hi sub-stage's registers (x3_compute)
+template <int KS, int R, int WN, int EPI, bool XTRA, bool GATED = false, bool HOLD = false>
 __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restrict__ bias, char* smem, const ConvTile& t,
                                         const X3Gate gate = X3Gate{nullptr, 0u, 1 << 30, nullptr}) {
     constexpr bool FOLD = EPI == BINHIP_EPI_SUBPIX_FOLD;       // the folded fused UPNet: one accumulator tile for the wave's row pair
     static_assert(!FOLD || (KS == 5 && R == 2 && !XTRA && !GATED), "the folded walk is the 5x5 FINAL_SUBPIX layer's");
+    static_assert(!HOLD || (KS == 3 && EPI == BINHIP_EPI_PLANES && !XTRA && !GATED), "held weight fragments: the 3x3 forward layers' form");
     constexpr int RA = FOLD ? 1 : R;
     using C = X3CfgOf<KS, R, WN, EPI>;
     BH_TL_DECL;
@@ -311,13 +321,14 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
         }
         // (5x5 only: the last chunk of a 24- / 36-channel layer on tap pairs, see x3_compute_pair)
         const bool pair = (KS == 5) && !XTRA && !FOLD && a.half_last && (c + 1 == nchunks);
+        half8 keep[HOLD ? KS * KS : 1];                   // HOLD: this chunk's hi-plane weight fragments, hi sub-stage -> lo sub-stage
         if constexpr (FOLD) {
             x3_compute_fold<C, true>(smem, wb, a_lane_off, b_lane_off, acc[0][0]);
         } else if constexpr (KS == 5 && !XTRA) {
             if (pair) x3_compute_pair<C, KS, R, true>(smem, wb, n, kg, wave, acc[0]);
             else x3_compute<C, KS, R, true>(smem, wb, a_lane_off, b_lane_off, acc[0]);
         } else {
-            x3_compute<C, KS, R, true>(smem, wb, a_lane_off, b_lane_off, acc[0]);
+            x3_compute<C, KS, R, true, HOLD>(smem, wb, a_lane_off, b_lane_off, acc[0], keep);
         }
         // ---- lo sub-stage: meanwhile the next chunk's hi patch plane lands
         wait_vmcnt<0>();
@@ -347,7 +358,7 @@ __device__ __forceinline__ void x3_tile(const ConvKArgs& a, const float* __restr
             if (pair) x3_compute_pair<C, KS, R, false>(smem + C::PATCH_BYTES, wb, n, kg, wave, acc[0]);
             else x3_compute<C, KS, R, false>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0]);
         } else {
-            x3_compute<C, KS, R, false>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0]);
+            x3_compute<C, KS, R, false, HOLD>(smem + C::PATCH_BYTES, wb, a_lane_off, b_lane_off, acc[0], keep);
         }
     }
     BH_TL_STAMP(2);
@@ -369,6 +380,15 @@ __global__ void __launch_bounds__(64 * WN)
 conv_x3_kernel(const ConvKArgs a, const float* __restrict__ bias) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     x3_tile<KS, R, WN, EPI, XTRA>(a, bias, smem, tile_decode<X3CfgOf<KS, R, WN, EPI>::TH>(a, a.ncol));
+}
+
+// The same 3x3 forward layer (EPI_PLANES, no extras) with the hi-plane weight fragments held across a chunk's two sub-stages
+// (BINHIP_CONV_HOLD_WEIGHTS).  A kernel of its own, so conv_x3_kernel keeps its symbols and per-kernel profiles tell the forms apart.
+template <int R, int WN, int WIDE>
+__global__ void __launch_bounds__(64 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2, WN / 2)))
+conv_x3_hold_kernel(const ConvKArgs a, const float* __restrict__ bias) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    x3_tile<3, R, WN, BINHIP_EPI_PLANES, false, false, true>(a, bias, smem, tile_decode<X3Cfg<3, R, WN>::TH>(a, a.ncol));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -435,8 +455,16 @@ conv_x3_rdbs_kernel(const Rdb3Args a, const float* __restrict__ bias0, const flo
 template <int KS, int R, int WN, int EPI, int WIDE, bool XTRA>
 static int launch_x3_x(const ConvKArgs& ka, int cout_pad, hipStream_t s) {
     using C = X3CfgOf<KS, R, WN, EPI>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&conv_x3_kernel<KS, R, WN, EPI, WIDE, XTRA>, C::LDS_BYTES, lds_set)) return rc;
+    // a.hold_w (BINHIP_CONV_HOLD_WEIGHTS): the 3x3 plane-epilogue layers without extras have the held form; every other
+    // instantiation (residual / backward-data extras, SHUFFLE, FINAL, 5x5) runs the reloading one whatever the bit says
+    constexpr bool CAN_HOLD = KS == 3 && EPI == BINHIP_EPI_PLANES && !XTRA;
+    static std::atomic<unsigned long long> lds_set{0}, lds_set_hold{0};
+    void (*kernel)(const ConvKArgs, const float*) = &conv_x3_kernel<KS, R, WN, EPI, WIDE, XTRA>;
+    std::atomic<unsigned long long>* set = &lds_set;
+    if constexpr (CAN_HOLD) {
+        if (ka.hold_w) { kernel = &conv_x3_hold_kernel<R, WN, WIDE>; set = &lds_set_hold; }
+    }
+    if (int rc = bh_set_max_lds(kernel, C::LDS_BYTES, *set)) return rc;
     ConvKArgs a = ka;
     const dim3 grid(set_tiles<C>(a, cout_pad / 32));
     // progress-ordered wave priority: only for launches whose workgroups are all resident at once (two per CU), forward layers only
@@ -446,7 +474,7 @@ static int launch_x3_x(const ConvKArgs& ka, int cout_pad, hipStream_t s) {
     a.tl = bh_tl_reserve(grid.x, &a.tl_base);
     a.tl_launch = ((KS == 3 && EPI == BINHIP_EPI_PLANES && WIDE == 0 && !XTRA ? 1u : 3u) << 24) | (g_bh_tl_serial.fetch_add(1) & 0xFFFFFFu);
 #endif
-    conv_x3_kernel<KS, R, WN, EPI, WIDE, XTRA><<<grid, dim3(64 * C::NW), C::LDS_BYTES, s>>>(a, a.bias);
+    kernel<<<grid, dim3(64 * C::NW), C::LDS_BYTES, s>>>(a, a.bias);
     BH_CHECK_LAUNCH();
     return 0;
 }

@@ -11,6 +11,7 @@ struct TailKArgs {
     _Float16 *o3_hi, *o3_lo;           // optional: where to keep o3 (2 chunks) for the backward pass
     unsigned* flags;                   // device status word (BINHIP_STATUS_*), may be null
     int N, H, W, tiles_x, tiles_y, wt;
+    int hold_w;                        // nterms = 3: hold the hi weight fragments across a chunk's sub-stages (BINHIP_TAIL_HOLD_WEIGHTS)
 #if BINHIP_TIMELINE
     void* tl;                          // side builds: see BhTl (binhip_conv_common.h)
     unsigned tl_launch, tl_base;

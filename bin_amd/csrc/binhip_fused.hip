@@ -351,6 +351,11 @@ int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* blk_hi, con
     if (nterms == 3 && (!blk_lo || !wc_lo || !wl_lo || !y_lo)) return BINHIP_E_ARG;
     if (N <= 0 || H <= 0 || W <= 0) return BINHIP_E_SHAPE;
     if ((long long)N * H * W >= (1ll << 26)) return BINHIP_E_SHAPE;
+    // `store_o3`: BINHIP_TAIL_* bits; the held form exists in the fp32-class kernel only
+    if (store_o3 & ~(BINHIP_TAIL_STORE_O3 | BINHIP_TAIL_HOLD_WEIGHTS)) return BINHIP_E_ARG;
+    const bool hold = (store_o3 & BINHIP_TAIL_HOLD_WEIGHTS) != 0;
+    if (hold && nterms != 3) return BINHIP_E_ARG;
+    store_o3 &= BINHIP_TAIL_STORE_O3;
     TailKArgs a;
     a.x_hi = (const _Float16*)blk_hi; a.x_lo = (const _Float16*)blk_lo;
     a.wc_hi = (const _Float16*)wc_hi; a.wc_lo = (const _Float16*)wc_lo;
@@ -363,6 +368,7 @@ int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* blk_hi, con
     a.flags = (unsigned*)status;
     a.N = N; a.H = H; a.W = W; a.tiles_x = a.tiles_y = 0;
     a.wt = (6 * plane * 2 < (1ll << 32) - 64) ? 1 : 0;
+    a.hold_w = hold ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     if (nterms == 1) return launch_tail<1, 2>(a, s);             // ring depth 2: measured best on MI355X (56.7 vs 63 us at 384x672)
     return bh_launch_tail_x3(a, s);                              // plane-split stages, half-CU footprint (binhip_fused_x3.hip)

@@ -114,13 +114,20 @@ __device__ __forceinline__ void tx_add_residual_row(const half8& bc, floatx16 (&
 // else -1 — a compile-time constant (it names accumulator registers): the kernel peels chunks 0-6.  The ~16 VALU
 // instructions per row go between the issue of this sub-stage's first fragment reads and its first MFMA, i.e. under the
 // LDS latency the wave would otherwise sit out; every sub-stage leaves its own centre column in `carry`.
-template <bool HI, int RES>
+// HOLD (BINHIP_TAIL_HOLD_WEIGHTS; x3_compute in binhip_conv_x3.hip has the same form): the hi sub-stage fetches the hi-plane
+// fragment of step s into keep[s] and leaves all twelve there, the lo sub-stage of the same chunk multiplies from keep[] and
+// reads no weight fragment: 60 -> 48 ds_read_b128 per wave and chunk, same operands in the same order.
+template <bool HI, int RES, bool HOLD>
 __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a_lane_off, int b_lane_off,
-                                           floatx16 (&accc)[TX::R], floatx16 (&accl)[3][TX::R], half8 (&carry)[TX::R]) {
+                                           floatx16 (&accc)[TX::R], floatx16 (&accl)[3][TX::R], half8 (&carry)[TX::R], half8* keep) {
     constexpr int R = TX::R;
     constexpr int NSTEP = 12;
     half8 B[2][R + 2];
     half8 Ah[2], Al[2];
+    auto ah = [&](int s) -> half8& {
+        if constexpr (HOLD) return keep[s];
+        else return Ah[s & 1];
+    };
     auto load_b = [&](int dx, half8 (&dst)[R + 2]) {
 #pragma unroll
         for (int rr = 0; rr < R + 2; ++rr) dst[rr] = ld8(pb + b_lane_off + (rr * TX::PW + dx) * 16);
@@ -136,16 +143,16 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
         bool lff; int dx, k;
         step_kind(s, lff, dx, k);
         const int off = (lff ? TX::CWP * 1024 + (k * 32) * 32 : ((k * 3 + dx) * 32) * 32) + a_lane_off;
-        h = ld8(wb + off);
+        if constexpr (HI || !HOLD) h = ld8(wb + off);
         if constexpr (HI) l = ld8(wb + TX::WPL + off);
     };
     load_b(0, B[0]);
-    load_a(0, Ah[0], Al[0]);
+    load_a(0, ah(0), Al[0]);
 #pragma unroll
     for (int s = 0; s < NSTEP; ++s) {
         bool lff; int dx, k;
         step_kind(s, lff, dx, k);
-        if (s + 1 < NSTEP) load_a(s + 1, Ah[(s + 1) & 1], Al[(s + 1) & 1]);
+        if (s + 1 < NSTEP) load_a(s + 1, ah(s + 1), Al[(s + 1) & 1]);
         if (s == 0) load_b(1, B[1]);
         if (s == 3) load_b(2, B[0]);                           // column 0's rows are dead after step 2
         __builtin_amdgcn_sched_barrier(0);
@@ -165,7 +172,7 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
             }
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                accc[r] = mfma_32x32x16(Ah[s & 1], B[set][r + k], accc[r]);
+                accc[r] = mfma_32x32x16(ah(s), B[set][r + k], accc[r]);
         } else {
             if constexpr (HI) {
 #pragma unroll
@@ -174,7 +181,7 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
             }
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                accl[k][r] = mfma_32x32x16(Ah[s & 1], B[1][r + 1], accl[k][r]);
+                accl[k][r] = mfma_32x32x16(ah(s), B[1][r + 1], accl[k][r]);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -182,6 +189,8 @@ __device__ __forceinline__ void tx_compute(const char* pb, const char* wb, int a
     for (int r = 0; r < R; ++r) carry[r] = B[1][r + 1];
 }
 
+// HOLD: the hi-plane weight fragments held across a chunk's two sub-stages (TailKArgs.hold_w, tx_compute)
+template <bool HOLD>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const float* __restrict__ bias_l) {
     // (the two biases again as the kernel's own restrict parameters: scalar loads in the epilogues, binhip_conv_common.h)
@@ -231,13 +240,14 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
         tx_issue_patch(a, smem, c, 1, wave, voff, t);
         if (c + 1 < TX::NCHUNK) tx_issue_weights(a, smem, c + 1, (c + 1) & 1, wave, lane);
         else tx_issue_tailw(a, smem, wave, lane);                // weight buffer 0: chunk 10's, read for the last time in lo(10)
-        tx_compute<true, RH>(smem, wb, a_lane_off, b_lane_off, accc, accl, carry);
+        half8 keep[HOLD ? 12 : 1];                               // HOLD: this chunk's hi-plane weight fragments, hi -> lo sub-stage
+        tx_compute<true, RH, HOLD>(smem, wb, a_lane_off, b_lane_off, accc, accl, carry, keep);
         // ---- lo sub-stage; meanwhile the next chunk's hi plane lands
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         if (c + 1 < TX::NCHUNK) tx_issue_patch(a, smem, c + 1, 0, wave, voff, t);
-        tx_compute<false, RL>(smem + TX::PATCH_BYTES, wb, a_lane_off, b_lane_off, accc, accl, carry);
+        tx_compute<false, RL, HOLD>(smem + TX::PATCH_BYTES, wb, a_lane_off, b_lane_off, accc, accl, carry, keep);
     };
     using std::integral_constant;
     // hi(c) adds the lo plane of chunk c - 1, lo(c) the hi plane of chunk c: each one sub-stage after it was read
@@ -339,15 +349,16 @@ rdb_tail_x3_kernel(const TailKArgs a, const float* __restrict__ bias_c, const fl
 }  // namespace
 
 int bh_launch_tail_x3(const TailKArgs& a0, hipStream_t s) {
-    static std::atomic<unsigned long long> lds_set{0};
-    if (int rc = bh_set_max_lds(&rdb_tail_x3_kernel, TX::LDS_BYTES, lds_set)) return rc;
+    static std::atomic<unsigned long long> lds_set{0}, lds_set_hold{0};
+    auto* kernel = a0.hold_w ? &rdb_tail_x3_kernel<true> : &rdb_tail_x3_kernel<false>;
+    if (int rc = bh_set_max_lds(kernel, TX::LDS_BYTES, a0.hold_w ? lds_set_hold : lds_set)) return rc;
     TailKArgs a = a0;
     const unsigned grid = set_tiles<TX>(a);
 #if BINHIP_TIMELINE
     a.tl = bh_tl_reserve(grid, &a.tl_base);
     a.tl_launch = (2u << 24) | (g_bh_tl_serial.fetch_add(1) & 0xFFFFFFu);      // kind 2 = the fused tail
 #endif
-    rdb_tail_x3_kernel<<<dim3(grid), dim3(256), TX::LDS_BYTES, s>>>(a, a.bc, a.bl);
+    kernel<<<dim3(grid), dim3(256), TX::LDS_BYTES, s>>>(a, a.bc, a.bl);
     BH_CHECK_LAUNCH();
     return 0;
 }

@@ -137,9 +137,12 @@ int binhip_rdn_forward(const BinRdnPlan* p, const float* const* inputs, float* o
     if (!frames_ok(N, H, W, nin)) return BINHIP_E_SHAPE;
     if (nt != 1 && nt != 3) return BINHIP_E_ARG;
     if (p->reserved & ~(BINHIP_PLAN_KEEP_ACTS | BINHIP_PLAN_NO_FUSE | BINHIP_PLAN_RDB3 | BINHIP_PLAN_FUSED_UPNET | BINHIP_PLAN_FUSED_UPNET_TRAIN |
-                        BINHIP_PLAN_UPNET_FOLD)) return BINHIP_E_ARG;      // an undefined flag bit
+                        BINHIP_PLAN_UPNET_FOLD | BINHIP_PLAN_HOLD_WEIGHTS)) return BINHIP_E_ARG;      // an undefined flag bit
     if ((p->reserved & BINHIP_PLAN_UPNET_FOLD) && (nt != 3 || (p->reserved & BINHIP_PLAN_KEEP_ACTS) || !(p->reserved & BINHIP_PLAN_FUSED_UPNET)))
         return BINHIP_E_ARG;              // the folded slab exists for the fused UPNet of fp32-class inference only
+    // held weight fragments: the per-conv launches of fp32-class inference (the three-phase launch has the reloading form only)
+    const bool hold = (p->reserved & BINHIP_PLAN_HOLD_WEIGHTS) != 0;
+    if (hold && (nt != 3 || (p->reserved & (BINHIP_PLAN_KEEP_ACTS | BINHIP_PLAN_RDB3)))) return BINHIP_E_ARG;
     Shp sh;
     if (!resolve_shape(&p->shape, &sh)) return BINHIP_E_SHAPE;
     const size_t need = binhip_rdn_workspace_bytes(N, H, W, nin, nt, &p->shape);
@@ -166,6 +169,7 @@ int binhip_rdn_forward(const BinRdnPlan* p, const float* const* inputs, float* o
         if (l.ks == 1 && l.epi == BINHIP_EPI_PLANES && c.d.W > 32 && c.d.W % 32 == 0) { c.d.H *= c.d.W / 32; c.d.W = 32; }
         // SFENet1 on 2 / 3 input frames: 24 / 36 channels = the last chunk's upper half is zero padding (packer and relayout)
         if (l.layer == 0 && l.ks == 5 && (12 * nin) % 16 >= 1 && (12 * nin) % 16 <= 8) c.d.reserved = BINHIP_CONV_HALF_LAST_CHUNK;
+        if (hold && l.ks == 3 && l.epi == BINHIP_EPI_PLANES) c.d.reserved |= BINHIP_CONV_HOLD_WEIGHTS;
         c.x_hi = A.hi(l.x); c.x_lo = A.lo(l.x);
         c.w_hi = p->w_hi[l.layer]; c.w_lo = p->w_lo[l.layer]; c.bias = p->bias[l.layer];
         c.r_hi = A.hi(l.res); c.r_lo = A.lo(l.res);
@@ -219,7 +223,9 @@ int binhip_rdn_forward(const BinRdnPlan* p, const float* const* inputs, float* o
             // conv #3 + LFF + residual in one kernel (binhip_fused.hip); o3 is only written out for training
             const int L3 = layer_conv(sh, d, 3), LF = layer_conv(sh, d, 4);
             if ((rc = binhip_rdb_tail_fwd(N, h, ww, nt, A.hi(b), A.lo(b), p->w_hi[L3], p->w_lo[L3], p->bias[L3], p->w_hi[LF], p->w_lo[LF], p->bias[LF],
-                                          A.hi(b_next), A.lo(b_next), (p->reserved & BINHIP_PLAN_KEEP_ACTS) ? 1 : 0, p->status, stream)))
+                                          A.hi(b_next), A.lo(b_next),
+                                          ((p->reserved & BINHIP_PLAN_KEEP_ACTS) ? BINHIP_TAIL_STORE_O3 : 0) | (hold ? BINHIP_TAIL_HOLD_WEIGHTS : 0),
+                                          p->status, stream)))
                 return rc;
         } else if ((rc = conv({.layer = layer_conv(sh, d, C), .ks = 1, .cin_chunks = cb, .cout = G0, .x = b, .y = b_next, .res = b})))
             return rc;

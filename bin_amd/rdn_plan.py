@@ -418,6 +418,11 @@ def default_plan_flags():
         # other call).  BIN_AMD_UPNET_FOLD=0: the 5x5 kernel and layout
         if _os.environ.get("BIN_AMD_UPNET_FOLD", "1") != "0":
             flags |= L.PLAN_UPNET_FOLD
+    # the 3x3 forward layers with a chunk's hi weight fragments held in registers between its two sub-stages (fp32-class inference on
+    # per-conv launches only: `_rdn_forward` clears the bit for every other call): 720p window -1.2 %, profiles/weight_hold.md.
+    # BIN_AMD_WEIGHT_HOLD=0: the reloading form
+    if _os.environ.get("BIN_AMD_WEIGHT_HOLD", "1") != "0":
+        flags |= L.PLAN_HOLD_WEIGHTS
     return flags
 
 
@@ -450,6 +455,9 @@ def _rdn_forward(weights, inputs, out, ws, flags, profiler):
             fold = bool(plan.reserved & L.PLAN_UPNET_FOLD) and fused is not None and weights.fused_fold is not None
     if not fold:
         plan.reserved &= ~L.PLAN_UPNET_FOLD
+    # held weight fragments: the per-conv launches of fp32-class inference have the form, nothing else does
+    if weights.nterms != 3 or plan.reserved & (L.PLAN_KEEP_ACTS | L.PLAN_RDB3):
+        plan.reserved &= ~L.PLAN_HOLD_WEIGHTS
     weights.fill_plan(plan, fused, fold)
     nbytes = lib.binhip_rdn_workspace_bytes(n, h, w, weights.n_inputs, weights.nterms, C.byref(plan.shape))
     if nbytes == 0:

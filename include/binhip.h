@@ -127,11 +127,17 @@ typedef struct BinConvDesc {
                               /*   BINHIP_E_ARG): w_hi / w_lo are the FOLDED slab of the fused UPNet's operator    */
                               /*   (BINHIP_PLAN_UPNET_FOLD below) and the launch leaves the full-resolution border */
                               /*   ring unwritten.                                                                 */
-    void*   status;           /* device uint32 status word (BINHIP_STATUS_*), OR-ed into; or NULL */
+                              /*   BINHIP_CONV_HOLD_WEIGHTS (BINHIP_EPI_PLANES, ksize 3, nterms 3 only, else        */
+                              /*   BINHIP_E_ARG): a 16-channel chunk's hi-plane weight fragments stay in registers */
+                              /*   from its hi sub-stage to its lo sub-stage instead of being read from LDS twice  */
+                              /*   (BINHIP_PLAN_HOLD_WEIGHTS below).  Same bits; a call with a residual runs the   */
+                              /*   reloading form whatever the bit says.                                           */
+    void*   status;          /* device uint32 status word (BINHIP_STATUS_*), OR-ed into; or NULL */
 } BinConvDesc;
 
 #define BINHIP_CONV_HALF_LAST_CHUNK 1
 #define BINHIP_CONV_UPNET_FOLD 2
+#define BINHIP_CONV_HOLD_WEIGHTS 4
 
 /* Rows per weight block for a (ksize, cout_pad, nterms) configuration (relayout needs it). */
 BINHIP_API int binhip_conv_cout_block(int ksize, int cout_pad, int nterms);
@@ -307,7 +313,11 @@ BINHIP_API int binhip_multi_loss_bwd(int kind, const BinLossTerms* t, int64_t nu
 /* ---- fused tail of a residual dense block: o3 = relu(conv3x3(blk[0:192])), y = LFF(cat(blk[0:192], o3)) + blk[0:96]
  * (RDN.py:141-147 for conv #3, :162-165 for LFF + residual) in one kernel; blk = 14-chunk dense-block buffer,
  * wc/wl = binhip_weights_relayout outputs of conv #3 (cout_block 32) and LFF (cout_block 96); y = 6 planes.
- * store_o3 != 0 also writes o3 to blk planes 12, 13 (needed by the backward pass only).               */
+ * store_o3 = BINHIP_TAIL_* bits (any other bit: BINHIP_E_ARG): BINHIP_TAIL_STORE_O3 also writes o3 to blk planes 12, 13 (needed by
+ * the backward pass only); BINHIP_TAIL_HOLD_WEIGHTS (nterms 3 only, else BINHIP_E_ARG) keeps a 16-channel chunk's hi-plane weight
+ * fragments of conv #3 and the LFF in registers from its hi to its lo sub-stage, as BINHIP_CONV_HOLD_WEIGHTS does: the same bits. */
+#define BINHIP_TAIL_STORE_O3 1
+#define BINHIP_TAIL_HOLD_WEIGHTS 2
 BINHIP_API int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* blk_hi, const void* blk_lo,
                         const void* wc_hi, const void* wc_lo, const float* bias_c,
                         const void* wl_hi, const void* wl_lo, const float* bias_l,
@@ -346,6 +356,13 @@ BINHIP_API int binhip_rdb_tail_fwd(int N, int H, int W, int nterms, const void* 
                                   /* swizzled as binhip_weights_relayout does), bias as before; bin_amd/rdn_plan.py                 */
                                   /* folded_upnet_weights builds it.  The main launch then writes full-resolution rows 1 .. H - 2   */
                                   /* and columns 1 .. W - 2; the ring launch (unchanged) writes the rest.                           */
+#define BINHIP_PLAN_HOLD_WEIGHTS 64 /* nterms 3, without KEEP_ACTS and without _RDB3 (any other combination: BINHIP_E_ARG): the 3x3   */
+                                  /* forward layers with a plane epilogue and no residual (SFENet2, the dense-block convs) run with  */
+                                  /* BINHIP_CONV_HOLD_WEIGHTS and the fused dense-block tail with BINHIP_TAIL_HOLD_WEIGHTS: the lo    */
+                                  /* sub-stage of a 16-channel chunk multiplies with the hi-plane weight fragments its hi sub-stage  */
+                                  /* fetched, 42 instead of 51 (tail: 48 instead of 60) LDS fragment reads per wave and chunk.  Same */
+                                  /* operands in the same order: the same bits.  The three-phase launch, layers with a residual,     */
+                                  /* the training forward and every backward kernel keep the reloading form.                         */
 typedef struct BinRdnPlan {
     int32_t N, H, W;          /* full-resolution frame size (H, W even)                          */
     int32_t n_inputs;         /* 2, 3 or 5 input frames                                          */
