@@ -1,5 +1,5 @@
 """ctypes binding of the eleven shared objects of bin_amd/build.py's table (libbinhip.so and the ten small libraries beside it,
-include/<name>.h) and of those of its EXTRA_LIBRARIES (libbinexpose.so) and ADDON_LIBRARIES (libbinssim.so, libbinlap.so), each loaded
+include/<name>.h) and of those of its EXTRA_LIBRARIES (libbinexpose.so) and ADDON_LIBRARIES (libbinssim.so, libbinlap.so, libbincrop.so), each loaded
 on first use.  The product path has NO fallback: if a library is missing, of another version or a call fails this raises, it never routes
 to PyTorch/CPU code."""
 import ctypes as C
@@ -373,6 +373,22 @@ _LAP_SIGNATURES = {
                                   C.c_size_t, C.c_void_p]),
 }
 
+# libbincrop.so (include/bincrop.h): the crop-decode library, loaded on first use
+CROP_VERSION = 100                     # BINCROP_VERSION
+CROP_E_ARG, CROP_E_SHAPE = -1, -2      # BINCROP_E_ARG, BINCROP_E_SHAPE
+CROP_FORMATS = 4                       # BINCROP_FORMATS: format index = 2 * matrix + range
+
+
+class BinCropRow(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32), ("format", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+_CROP_SIGNATURES = {
+    "bincrop_version": (C.c_int, []),
+    "bincrop_yuv_crops_to_bgr": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
 STATUS_SATURATED = 1            # BINHIP_STATUS_SATURATED
 STATUS_SYNC_TIMEOUT = 2         # BINHIP_STATUS_SYNC_TIMEOUT
 
@@ -385,7 +401,8 @@ _LIBRARIES = {"binhip": (_SIGNATURES, None), "binopt": (_OPT_SIGNATURES, OPT_VER
 # the same for the rows of build.EXTRA_LIBRARIES
 _EXTRA_LIBRARIES = {"binexpose": (_EXPOSE_SIGNATURES, EXPOSE_VERSION)}
 # the same for the rows of build.ADDON_LIBRARIES, the open-ended table
-_ADDON_LIBRARIES = {"binssim": (_SSIM_SIGNATURES, SSIM_VERSION), "binlap": (_LAP_SIGNATURES, LAP_VERSION)}
+_ADDON_LIBRARIES = {"binssim": (_SSIM_SIGNATURES, SSIM_VERSION), "binlap": (_LAP_SIGNATURES, LAP_VERSION),
+                    "bincrop": (_CROP_SIGNATURES, CROP_VERSION)}
 _loaded = {}                    # name -> the CDLL, once library(name) has loaded it
 
 
@@ -442,6 +459,7 @@ cliplib = partial(library, "binclip")
 exposelib = partial(library, "binexpose")
 ssimlib = partial(library, "binssim")
 laplib = partial(library, "binlap")
+croplib = partial(library, "bincrop")
 
 
 def check(rc, what):

@@ -68,6 +68,10 @@ ADDON_LIBRARIES = (
             "the multi-scale term of the training criterion: the Laplacian-pyramid loss of fp32 frames and its gradient, in double "
             "(pixel_criterion: cb+lap)",
             "extra"),
+    Library("bincrop", ["bincrop.hip"],
+            "crops: a batch's crops of the YUV payloads of a byte arena -> uint8 BGR, the per-batch decode of a device frame cache kept "
+            "in YUV (device_cache_format: yuv)",
+            "extra"),
 )
 ADDON_BY_NAME = {lib.name: lib for lib in ADDON_LIBRARIES}
 SOURCES, HEADER, LIB_PATH = BY_NAME["binhip"].sources, BY_NAME["binhip"].header, BY_NAME["binhip"].path

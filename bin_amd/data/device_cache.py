@@ -169,7 +169,17 @@ class DeviceWindowLoader:
             cache = from_clips(device, max_gb) if from_clips else DeviceFrameCache(dataset.all_paths, device, max_gb, blur_half=blur_half)
         self.cache = cache
         # crop offsets are drawn against the prepared dataset's frame size, as the host loader draws them; a clip's own for BIN_video
-        self.src_size = tuple(self.cache.shape[1:3]) if from_clips else (SRC_H, SRC_W)
+        # (None: each window's own clip's, from a cache that holds clips of different sizes: YuvFrameCache.src_size)
+        self.src_size = (SRC_H, SRC_W) if not from_clips else None if hasattr(self.cache, "src_size") else tuple(self.cache.shape[1:3])
+
+    def _src_size(self, window):
+        return self.src_size or self.cache.src_size(window)
+
+    def _gather(self, table, launch):
+        """`launch(frames, table, clip_ranges)` on the arena, or on the batch's decoded crops when the cache keeps YUV (crop_batch)."""
+        if hasattr(self.cache, "crop_batch"):
+            return launch(*self.cache.crop_batch(table, self.crop[1:]))
+        return launch(self.cache.frames, table, self.cache.clip_ranges)
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else len(self.dataset)
@@ -189,19 +199,19 @@ class DeviceWindowLoader:
         for idx in self.index_batches():
             windows = [self.dataset.all_paths[i] for i in idx]
             if self.blur_window is None:
-                draws = [draw_window_aug(self.crop, src_size=self.src_size) for _ in windows]
+                draws = [draw_window_aug(self.crop, src_size=self._src_size(w)) for w in windows]
                 out = ops.gather_windows(self.cache.frames, self.cache.table(windows, draws), (ch, cw))
             elif self.exposure is None:                      # per sample: the four draws, then the exposure's (load_window's order)
-                both = [(draw_window_aug(self.crop, src_size=self.src_size), draw_blur_half(self.blur_window)) for _ in windows]
+                both = [(draw_window_aug(self.crop, src_size=self._src_size(w)), draw_blur_half(self.blur_window)) for w in windows]
                 table = self.cache.table(windows, [d for d, _ in both], [h for _, h in both])
-                out = ops.gather_windows_blur(self.cache.frames, table, (ch, cw), N_BLUR, self.cache.clip_ranges)
+                out = self._gather(table, lambda frames, tab, ranges: ops.gather_windows_blur(frames, tab, (ch, cw), N_BLUR, ranges))
             else:                                            # ... then the key's, when there is noise (exposure.sample_key)
                 from .exposure import sample_key
-                three = [(draw_window_aug(self.crop, src_size=self.src_size), draw_blur_half(self.blur_window),
-                          sample_key(self.exposure, self.train, i)) for i in idx]
+                three = [(draw_window_aug(self.crop, src_size=self._src_size(w)), draw_blur_half(self.blur_window),
+                          sample_key(self.exposure, self.train, i)) for w, i in zip(windows, idx)]
                 table = self.cache.table(windows, [d for d, _, _ in three], [h for _, h, _ in three], [k for _, _, k in three])
-                out = ops.gather_windows_exposed(self.cache.frames, table, (ch, cw), N_BLUR, ops.exposure_curve(*self.exposure),
-                                                 self.cache.clip_ranges)
+                curve = ops.exposure_curve(*self.exposure)
+                out = self._gather(table, lambda frames, tab, ranges: ops.gather_windows_exposed(frames, tab, (ch, cw), N_BLUR, curve, ranges))
             yield {"LQs": out[0:6].transpose(0, 1), "GTenh": out[6:12].transpose(0, 1), "GTinp": out[12:17].transpose(0, 1),
                    "key": [w[3] for w in windows]}
 
@@ -211,6 +221,6 @@ def create_device_loader(dataset, dataset_opt, batch, sampler=None):
     device = torch.device("cuda", torch.cuda.current_device())
     max_gb = dataset_opt.get("device_cache_max_gb") or 64
     loader = DeviceWindowLoader(dataset, batch, sampler, device, max_gb)
-    logging.getLogger("base").info("Device frame cache: %d frames, %.2f GB on %s", loader.cache.shape[0],
-                                   loader.cache.nbytes / 1e9, device)
+    logging.getLogger("base").info("Device frame cache: %d frames, %.2f GB on %s, format %s", len(loader.cache.paths),
+                                   loader.cache.nbytes / 1e9, device, "yuv" if hasattr(loader.cache, "crop_batch") else "bgr")
     return loader

@@ -822,6 +822,70 @@ def yuv_to_bgr(payloads, h, w, fmt, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------------- crop glue (libbincrop.so)
+CROP_ROW_FIELDS = ("offset", "H", "W", "y0", "x0", "format")
+
+
+def yuv_format_index(fmt):
+    """The format index of a crop row: 2 * matrix + range of (chroma, matrix, range) (include/bincrop.h)."""
+    f = yuv_format(fmt)
+    return 2 * f.matrix + f.range
+
+
+def yuv_crops_to_bgr(arena_u8, rows_host, crop, chroma, out=None):
+    """Crops of YUV frames that lie in a byte arena -> uint8 [n_rows, ch, cw, 3] HWC BGR in one launch (bincrop_yuv_crops_to_bgr,
+    libbincrop.so): per row the bytes yuv_to_bgr gives the crop of that frame.  `arena_u8`: contiguous uint8 [bytes] device tensor;
+    `rows_host`: integer [n_rows, 6] on the HOST, per decoded frame (payload offset, H, W, y0, x0, format index: yuv_format_index);
+    `crop`: (ch, cw); `chroma`: 420 | 444, of every row.  The table is checked here (the kernel only clamps): every payload inside the
+    arena, every crop inside its frame, every format index known; a ValueError names the row and what is wrong with it.  It is
+    uploaded through pinned memory without a host sync and the kernel launched on the current stream.  `out`: a contiguous uint8
+    [n_rows, ch, cw, 3] on the arena's device to fill."""
+    import numpy as np
+    if arena_u8.dtype != torch.uint8 or arena_u8.dim() != 1 or arena_u8.numel() < 1 or not arena_u8.is_contiguous():
+        raise ValueError(f"yuv_crops_to_bgr: the arena must be a contiguous uint8 [bytes] tensor, got {arena_u8.dtype} {tuple(arena_u8.shape)}")
+    if chroma not in (420, 444):
+        raise ValueError(f"yuv_crops_to_bgr: unknown chroma {chroma!r}: 420 | 444")
+    ch, cw = (int(v) for v in crop)
+    if ch < 1 or cw < 1:
+        raise ValueError(f"yuv_crops_to_bgr: a crop of {ch}x{cw}")
+    tab = np.asarray(rows_host.numpy() if torch.is_tensor(rows_host) else rows_host)
+    if tab.ndim != 2 or tab.shape[0] < 1 or tab.shape[1] != len(CROP_ROW_FIELDS) or tab.dtype.kind not in "iu":
+        raise ValueError(f"yuv_crops_to_bgr: rows must be an integer [n_rows, {len(CROP_ROW_FIELDS)}] table "
+                         f"({', '.join(CROP_ROW_FIELDS)}), got {tab.dtype} {tab.shape}")
+    tab = tab.astype(np.int64)
+    off, h, w, y0, x0, fmt = (tab[:, i] for i in range(6))
+    nbytes = arena_u8.numel()
+
+    def refuse(bad, what):
+        if bad.any():
+            r = int(np.argmax(bad))
+            raise ValueError(f"yuv_crops_to_bgr: row {r}: {what} (offset {off[r]}, {w[r]}x{h[r]} frame, crop {cw}x{ch} at "
+                             f"({y0[r]}, {x0[r]}), format {fmt[r]})")
+    refuse((h < 1) | (w < 1) | (h > 2 ** 31 - 1) | (w > 2 ** 31 - 1), "the frame size is not positive")
+    c_h, c_w = (h, w) if chroma == 444 else ((h + 1) // 2, (w + 1) // 2)
+    frame_bytes = h * w + 2 * c_h * c_w
+    refuse((off < 0) | (off > nbytes - frame_bytes), f"the payload leaves the arena of {nbytes} bytes")
+    refuse((y0 < 0) | (x0 < 0) | (y0 > h - ch) | (x0 > w - cw), "the crop leaves the frame")
+    refuse((fmt < 0) | (fmt >= L.CROP_FORMATS), f"the format index is outside [0, {L.CROP_FORMATS})")
+    n = tab.shape[0]
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (n, ch, cw, 3) or not out.is_contiguous() or
+                            out.device != arena_u8.device):
+        raise ValueError(f"yuv_crops_to_bgr: fills a contiguous uint8 [{n}, {ch}, {cw}, 3] on the arena's device "
+                         f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+    _need_cuda(arena_u8, out)
+    words = np.zeros((n, 8), dtype=np.int32)                 # BinCropRow: int64 offset, then H, W, y0, x0, format, reserved
+    words[:, :2] = off.astype("<i8").view(np.int32).reshape(n, 2)
+    words[:, 2:7] = tab[:, 1:6]
+    dev = arena_u8.device
+    with on_device(arena_u8):
+        table = torch.from_numpy(words).pin_memory().to(dev, non_blocking=True)
+        if out is None:
+            out = torch.empty((n, ch, cw, 3), dtype=torch.uint8, device=dev)
+        L.check(L.croplib().bincrop_yuv_crops_to_bgr(_ptr(arena_u8), nbytes, _ptr(table), n, ch, cw, int(chroma), _ptr(out), _stream()),
+                "yuv_crops_to_bgr")
+    return out
+
+
 # --------------------------------------------------------------------------------------------- rate glue (libbinrate.so)
 def blend_to_yuv(a, b, w, top, left, h, w_, fmt, out=None):
     """Two fp32 [1,3,Hp,Wp] (or [3,Hp,Wp]) RGB frames of one shape -> the Y4M payload of the crop of a + w (b - a), 0 <= w < 1, on

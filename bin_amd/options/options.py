@@ -206,6 +206,25 @@ def lap_levels(opt):
     return value
 
 
+CACHE_FORMATS = ("bgr", "yuv")
+
+
+def device_cache_format(dataset_opt, phase=None):
+    """`datasets.<phase>.device_cache_format` (bin_amd extension): what the device frame cache of a `BIN_video` dataset holds.  Absent,
+    null or `bgr`: uint8 BGR frames, converted once while the arena fills; `yuv`: the Y4M payloads as they are (half the bytes at
+    4:2:0, clips of different sizes allowed), each batch's crops decoded by one HIP launch (bin_amd/data/video_dataset.py).  Anything
+    else raises, and so does `yuv` on a dataset of another mode, where it would silently do nothing."""
+    key = f"datasets.{phase or dataset_opt.get('phase') or '<phase>'}.device_cache_format"
+    value = dataset_opt.get("device_cache_format")
+    if value is None:
+        return "bgr"
+    if value not in CACHE_FORMATS:
+        raise ValueError(f"{key}: {value!r} is not one of {', '.join(CACHE_FORMATS)}")
+    if value == "yuv" and dataset_opt.get("mode") != "BIN_video":
+        raise ValueError(f"{key}: yuv keeps the payloads of Y4M clips, so it needs mode BIN_video, not mode {dataset_opt.get('mode')!r}")
+    return value
+
+
 def micro_batches(batch, m):
     """The consecutive (start, n) chunks along N that a batch of `batch` samples is cut into with `train.micro_batch: m`:
     ceil(batch / m) chunks of m, the last one smaller when m does not divide the batch; one chunk when m is None or >= batch."""
@@ -267,6 +286,7 @@ def parse(opt_path, is_train=True):
 
     for phase, ds in opt["datasets"].items():
         ds["phase"] = phase
+        device_cache_format(ds, phase)       # a misspelt value, or yuv on a mode without payloads, stops the run here
         if sr:
             ds["scale"] = scale
         lmdb = False
